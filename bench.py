@@ -6,9 +6,11 @@ One "step" = DenseCapModel:forward_test on ONE synthetic 720x600 image with 1000
 heads -> greedy LSTM decode (T=15, V=10497) -> final NMS.  Images are resident in HBM before
 the timed region; results (boxes, scores, tokens) come back to the host inside it.
 
-Timed region = exactly K steps between barrier + device sync on both sides, max over ranks.  It is
-repeated `--repeats` times inside one invocation (0.12 s is too short to stand alone) and the MEDIAN
-repeat is reported; every repeat's rate is in the line.
+Timed region = exactly K steps between barrier + device sync on both sides, max over ranks.  A plain run
+(`--steps K --warmup W`) sets up, picks the schedule by an untimed trial, warms up with W steps, times ONE
+region of K steps, writes the last step's outputs if `--dump-outputs DIR` is given and prints the line.
+`--full` adds everything else: the region is repeated `--repeats` times (7) and the MEDIAN repeat is
+reported, plus the sustained leg, the secondary legs, the roofline passes and the CPU baseline.
 
 N GPUs: one process per GPU (torch.distributed), images sharded contiguously, weak scaling (K images
 per GPU), ONE gather of the typed (boxes,scores,tokens) records on rank 0 at the end of each timed
@@ -30,6 +32,7 @@ HBM_PEAK_GBPS = 8000.0
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA (v_mfma_f32_32x32x16_bf16)
 PMC_PROFILE = os.path.join("profiles", "r06_pmc_summary.json")
 PARITY_REPORT = os.path.join("profiles", "r06_parity_report.json")
+DISTINCT_IMAGES = 64          # synthetic images made per rank (BASELINE configs[3]: 64 per GPU); larger --steps repeat them
 
 VGG = [(3, 64, 0), (64, 64, 1), (64, 128, 0), (128, 128, 1), (128, 256, 0), (256, 256, 0), (256, 256, 1),
        (256, 512, 0), (512, 512, 0), (512, 512, 1), (512, 512, 0), (512, 512, 0), (512, 512, 0)]
@@ -251,6 +254,20 @@ class StubComm:
         pass
 
 
+def dump_outputs(path, records):
+    """Writes what the timed path handed back for its last step -- the (boxes, scores, token ids) record of every rank's last
+    image of the last timed region, in rank order -- as float32 .npy files (token ids < 2^24 are exact).  Rows of all ranks
+    are concatenated; boxes_per_image[r] is rank r's row count."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"boxes": np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for b, _, _ in records]),
+              "scores": np.concatenate([np.asarray(s, np.float32).reshape(-1) for _, s, _ in records]),
+              "tokens": np.concatenate([np.asarray(t) for _, _, t in records]).astype(np.float32),
+              "boxes_per_image": np.array([len(b) for b, _, _ in records], np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def git_head():
     try:
         return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
@@ -349,9 +366,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64, help="images per timed region and GPU (BASELINE configs[3] shards 64 per GPU)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=7, help="timed regions of --steps steps each; the median is reported")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0,
-                    help="length of the sustained leg (back-to-back timed regions with clock/power sampling); 0 = skip")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1; 7 with --full)")
+    ap.add_argument("--sustain-seconds", type=float, default=None,
+                    help="length of the sustained leg (back-to-back timed regions with clock/power sampling); 0 = skip "
+                         "(default 0; 10 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: warm-up until stable, 7 repeats, the sustained leg, the H2D-inclusive "
+                         "legs, the caption-order and split-bf16 legs, the serial roofline pass, the other BASELINE configs, the "
+                         "live counter passes, the CPU baseline and the in-run parity check.  Without it a run sets up, warms up, "
+                         "times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (boxes, scores, token ids of every "
+                         "rank's last image) to DIR/<name>.npy in float32")
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=720)
     ap.add_argument("--proposals", type=int, default=1000)
@@ -393,6 +420,14 @@ def main():
     ap.add_argument("--stub-rank0-leg-seconds", type=float, default=0.0, help=argparse.SUPPRESS)   # a stand-in for rank 0's own legs (teardown test)
     ap.add_argument("--stub-comm-fail", default="never:-1", help=argparse.SUPPRESS)   # "create:R": StubComm cannot be created on rank R
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 10.0 if args.full else 0.0
+    if not args.full:
+        # a plain run does only what `value` needs: every secondary leg stays off
+        args.no_settle = args.no_cpu_baseline = args.no_alt_pass = args.no_host_input_leg = True
+        args.no_split_leg = args.no_traffic_leg = args.no_config_legs = True
 
     if args.dry_run:
         world = int(os.environ.get("WORLD_SIZE", args.gpus))
@@ -451,6 +486,7 @@ def main():
     H, W, P, K, Wm = args.height, args.width, args.proposals, args.steps, args.warmup
     T, V = 15, 10497
     n_img = max(K, Wm, args.lanes, 8, 1)                      # (>= dc_set_group's maximum: a whole group is resident even for --steps 4)
+    n_distinct = min(n_img, DISTINCT_IMAGES)
     if on_gpu:
         from densecap_amd import DenseCapModel
         from densecap_amd._lib import check
@@ -467,9 +503,14 @@ def main():
         ctx = model.ctx
         if args.plan_mode >= 0:
             check(ctx.h, ctx.lib.dc_debug_set(ctx.h, b"plan_mode", args.plan_mode), "dc_debug_set")
-        # K distinct images per rank (global image id = rank*n_img + i), resident in HBM
-        host = np.stack([make_synthetic_image(H, W, rank * n_img + i) for i in range(n_img)])
-        dev = ctx.to_device(host)
+        # n_img images per rank resident in HBM: up to DISTINCT_IMAGES distinct ones (global image id = rank*n_img + i), repeated
+        # in order beyond that, so that setup time does not grow with --steps
+        host = np.stack([make_synthetic_image(H, W, rank * n_img + i) for i in range(n_distinct)])
+        dev = ctx.empty((n_img,) + host.shape[1:])
+        for i0 in range(0, n_img, n_distinct):
+            nb_ = min(n_distinct, n_img - i0) * host[0].nbytes
+            check(ctx.h, ctx.lib.dc_memcpy_h2d(ctx.h, ctypes.c_void_p(dev.ptr.value + i0 * host[0].nbytes), host.ctypes.data, nb_),
+                  "dc_memcpy_h2d")
         imgs = dev.ptr
 
         def sync():
@@ -582,8 +623,9 @@ def main():
     if args.lanes <= 0 and args.group < 0 and on_gpu:
         # both scheduling knobs together (results are bit-identical for every pair): the best lane count depends on the group size
         # (the trial runs regions of exactly K images, the size of a timed region: with few images per region the best pair
-        # depends on how the groups fall on the lanes -- 20 images are five groups of four on two lanes, three against two)
-        sched_trials = model.autotuneSchedule(imgs, min(n_img, K), H, W)
+        # depends on how the groups fall on the lanes -- 20 images are five groups of four on two lanes, three against two);
+        # at most DISTINCT_IMAGES images, so that the trial's 24 regions stay a few seconds at any --steps
+        sched_trials = model.autotuneSchedule(imgs, min(n_distinct, K), H, W)
         args.lanes, args.group = max(sched_trials, key=sched_trials.get)
         if dist is not None:
             lt = torch.tensor([args.lanes, args.group], dtype=torch.int32, device=coll_device)
@@ -690,6 +732,8 @@ def main():
             all(np.array_equal(x, y) for x, y in zip(gathered[r][i], ref.forward_batch_device([r * n_img + i], 1, H, W)[0]))
             for r in range(world) for i in range(K))
         assert gather_order_verified, "gather delivered records in a wrong order"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [shard[-1] for shard in gathered])
     host_enqueue_us = None
     if on_gpu:
         try:       # host time spent enqueueing one image of the last timed region (the N-GPU ceiling is 1 / this per rank)
@@ -713,8 +757,8 @@ def main():
         dist.all_gather(allr, tt)
         per_rank_rates = [float(t.item()) for t in allr]
 
-    # ---- H2D-inclusive legs ("include H2D of the image"): the same K images in HOST memory, pageable and
-    # pinned, through dc_forward_batch(imgs_on_device = 0).  `value` keeps inputs resident in HBM (the tier's rule); these
+    # ---- H2D-inclusive legs ("include H2D of the image"): the same K images (at most DISTINCT_IMAGES) in HOST
+    # memory, pageable and pinned, through dc_forward_batch(imgs_on_device = 0).  `value` keeps inputs resident in HBM (the tier's rule); these
     # two figures say what the boundary delivers when it is handed host buffers.
     host_legs = None
     if on_gpu and dist is None and not args.no_host_input_leg:
@@ -726,7 +770,7 @@ def main():
             h0 = time.perf_counter()
             model.forward_batch(arr)
             sync()
-            host_legs[kind] = K / (time.perf_counter() - h0)
+            host_legs[kind] = len(arr) / (time.perf_counter() - h0)
         del pinned_t
 
     # ---- sustained leg: the same timed region back to back for >= --sustain-seconds, clocks and power sampled ---------
@@ -794,7 +838,7 @@ def main():
         # runs ~900 rows a launch where a single image has ~225, so the pair the reference order picked is not this order's best
         alt_sched, alt_trial = (args.lanes, args.group), None
         if args.lanes != 1 and not group_fixed:
-            alt_trial = model.autotuneSchedule(imgs, min(n_img, K), H, W)
+            alt_trial = model.autotuneSchedule(imgs, min(n_distinct, K), H, W)
             alt_sched = max(alt_trial, key=alt_trial.get)
         model.setLanes(alt_sched[0]); model.setGroup(alt_sched[1])
         model.forward_batch_device(imgs, K, H, W)            # warm
@@ -871,7 +915,7 @@ def main():
     serial_pass = False
     stage_live, single_image_latency_ms, stage_group = None, None, None
     nprof = K * nrep
-    if on_gpu and rank == 0 and args.lanes != 1:
+    if on_gpu and rank == 0 and args.lanes != 1 and args.full:
         # Per-kernel durations are only meaningful when kernels do not overlap: with >1 lanes the MFMA launches of
         # different images run concurrently.  Roofline pass: the same workload on ONE lane, HIP events around every
         # MFMA launch (on the stream it is launched on).  It describes the serial schedule, not the timed one.
@@ -987,7 +1031,8 @@ def main():
 
     if rank == 0:
         burst = world * K / elapsed
-        value, value_source = burst, "median of %d timed regions of %d steps" % (nrep, K)
+        value, value_source = burst, ("median of %d timed regions of %d steps" % (nrep, K) if nrep > 1
+                                      else "one timed region of %d steps" % K)
         if sustained is not None:
             sustained["vs_timed_regions"] = sustained["images_per_s"] / burst
             if abs(sustained["vs_timed_regions"] - 1.0) > 0.03:
@@ -1025,11 +1070,21 @@ def main():
                                         "vs_value": {k: v / burst for k, v in host_legs.items()},
                                         "note": "one region of %d images handed over in host memory (dc_forward_batch, "
                                                 "imgs_on_device = 0): the 5.2 MB H2D copy of an image rides the lane's stream "
-                                                "ahead of its kernels; `value` is measured with inputs resident in HBM" % K}
+                                                "ahead of its kernels; `value` is measured with inputs resident in HBM" % min(K, n_distinct)}
         if not on_gpu:
             out["lanes"] = args.lanes
             out["config"]["gather_order_verified"] = gather_order_verified
         if on_gpu:
+            out["lanes"] = args.lanes
+            out["host_enqueue_us_per_image"] = host_enqueue_us
+            out["group"] = args.group
+            if lane_trials is not None:
+                out["lanes_trial_images_per_s"] = {str(k): v for k, v in lane_trials.items()}
+            if group_trials is not None:
+                out["group_trial_images_per_s"] = {str(k): v for k, v in group_trials.items()}
+            if sched_trials is not None:
+                out["schedule_trial_images_per_s"] = {"lanes%d_group%d" % k: v for k, v in sched_trials.items()}
+        if on_gpu and args.full:
             gf = stage_gflop(H, W, P, T, V)
             # the peak this run's arithmetic is priced against: fp32 MFMA, or -- for a whole run in the opt-in split-bf16 mode
             # (--math-mode 1) -- the dense bf16 MFMA peak / 6 (six bf16 products per fp32 multiply-add), as roofline_split_bf16 does
@@ -1162,15 +1217,6 @@ def main():
                 hb["rpn_nms"]["nms_launches_per_image"] = lk["nms_kernels"]["launches_per_image"]
             out["hbm_stages"] = hb
             out["warm_up_regions_images_per_s"] = warm_regions
-            out["lanes"] = args.lanes
-            out["host_enqueue_us_per_image"] = host_enqueue_us
-            out["group"] = args.group
-            if lane_trials is not None:
-                out["lanes_trial_images_per_s"] = {str(k): v for k, v in lane_trials.items()}
-            if group_trials is not None:
-                out["group_trial_images_per_s"] = {str(k): v for k, v in group_trials.items()}
-            if sched_trials is not None:
-                out["schedule_trial_images_per_s"] = {"lanes%d_group%d" % k: v for k, v in sched_trials.items()}
             if alt is not None:
                 # Captions AFTER the final NMS (dc_set_caption_order(1), what the CLIs run): the same outputs -- compared array by
                 # array with the reference-order results of the last timed region -- with the LSTM run only on the rows the final
@@ -1248,7 +1294,7 @@ def main():
             oracle_out, per_image = [], []
             for i in range(nb):
                 c0 = time.perf_counter()
-                oracle_out.append(O.forward_test(host[i % n_img], weights, 0.7, 0.3, P, 15, nms_impl="vector"))
+                oracle_out.append(O.forward_test(host[i % n_distinct], weights, 0.7, 0.3, P, 15, nms_impl="vector"))
                 per_image.append(time.perf_counter() - c0)
             cdt = sorted(per_image)[nb // 2] * nb              # median image x nb
             # the oracle's outputs of this leg double as an in-run parity check of the timed regions' own results
@@ -1272,7 +1318,7 @@ def main():
             for i in dep:
                 try:
                     from tests import parity as PAR
-                    r_ = PAR.strict_check(model, weights, host[i % n_img], P)
+                    r_ = PAR.strict_check(model, weights, host[i % n_distinct], P)
                     replayed.append({"image": i, "replayed": True, "K": r_.get("K"), "K_oracle": r_.get("K_oracle"),
                                      "matched": r_.get("matched"), "rpn_decisions_flipped": len(r_.get("rpn_flips", [])),
                                      "final_decisions_flipped": len(r_.get("final_list_flips", [])),

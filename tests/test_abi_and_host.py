@@ -18,6 +18,13 @@ def _declared_symbols(header="densecap.h"):
 DEBUG_SYMBOLS = ["dc_debug_fetch", "dc_debug_plan_gemm", "dc_debug_set", "dc_mfma_profile"]
 
 
+def _reference_facts():
+    """Option lists and statement counts recorded from the reference's scripts (tests/golden/make_reference_facts.py)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")) as f:
+        return json.load(f)
+
+
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as g
     if not os.path.exists(os.path.join(ROOT, "densecap_amd", "lib", "libdensecap_hip.so")):
@@ -156,21 +163,21 @@ def test_lua_ffi_cdef_matches_the_header():
 def test_lua_run_model_substitutions_match_the_reference():
     """lua/run_model_hip.lua runs the reference's own run_model.lua with two statements replaced (so every flag of
     run_model.lua:26-61 is kept without restating the script).  No Lua here: check that each Lua pattern, read as the
-    literal it escapes, occurs exactly once in the reference script -- where the reference tree is present."""
-    ref = "/root/reference/run_model.lua"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this box")
+    literal it escapes, occurs exactly once in the reference script (occurrence counts recorded per statement hash in
+    tests/golden/reference_facts.json)."""
+    from tests.golden.make_reference_facts import pattern_literal, sha256, substitution_patterns
+    facts = _reference_facts()
     lua = open(os.path.join(ROOT, "lua", "run_model_hip.lua")).read()
-    pats = re.findall(r'\{"((?:[^"\\]|\\.)*)",\s*\n\s*"((?:[^"\\]|\\.)*)"\}', lua)
+    pats = substitution_patterns()
     assert len(pats) == 2
-    text = open(ref).read()
+    counts = facts["run_model_statement_counts"]
     for pat, repl in pats:
-        literal = re.sub(r"%(.)", r"\1", pat)          # Lua escapes a magic character with %
-        assert text.count(literal) == 1, literal
+        literal = pattern_literal(pat)
+        assert counts.get(sha256(literal)) == 1, literal
         assert "DenseCapModelHIP" in repl or "torch.FloatTensor" in repl
     # the flags a user expects are the reference's own (they are never restated in our file)
     for flag in ("-input_dir", "-max_images", "-output_vis_dir", "-input_split"):
-        assert flag in text and ("'%s'" % flag) not in lua
+        assert flag in facts["cli_options"]["run_model.lua"] and ("'%s'" % flag) not in lua
 
 
 def test_run_model_cli_accepts_every_reference_flag(tmp_path):
@@ -178,18 +185,15 @@ def test_run_model_cli_accepts_every_reference_flag(tmp_path):
     passing `-use_cudnn 1` got an argparse error.  Every `cmd:option` of the reference script must parse, with the
     reference's default."""
     from densecap_amd import run_model as R
-    ref = "/root/reference/run_model.lua"
     flags = {"-checkpoint": "data/models/densecap/densecap-pretrained-vgg16.t7", "-image_size": 720, "-rpn_nms_thresh": 0.7,
              "-final_nms_thresh": 0.3, "-num_proposals": 1000, "-input_image": "", "-input_dir": "", "-input_split": "",
              "-splits_json": "info/densecap_splits.json", "-vg_img_root_dir": "", "-max_images": 100, "-output_dir": "",
              "-num_to_draw": 10, "-text_size": 2, "-box_width": 2, "-output_vis": 1, "-output_vis_dir": "vis/data", "-gpu": 0,
              "-use_cudnn": 1}
-    if os.path.exists(ref):            # the list above IS the reference's (checked where the reference tree is present)
-        src = open(ref).read()
-        found = dict(re.findall(r"cmd:option\('(-\w+)',\s*\n?\s*('[^']*'|[\d.]+)", src))
-        assert set(found) == set(flags), set(found) ^ set(flags)
-        for k, v in found.items():
-            assert str(flags[k]) == v.strip("'"), (k, v, flags[k])
+    found = _reference_facts()["cli_options"]["run_model.lua"]     # the list above IS the reference's
+    assert set(found) == set(flags), set(found) ^ set(flags)
+    for k, v in found.items():
+        assert str(flags[k]) == v, (k, v, flags[k])
     opt = R.build_parser().parse_args([])
     for k, v in flags.items():
         assert getattr(opt, k[1:]) == v, (k, getattr(opt, k[1:]), v)
@@ -211,20 +215,20 @@ def test_extract_features_and_daemon_clis_accept_every_reference_flag():
     with the reference's default."""
     from densecap_amd import daemon as D, extract_features as E
     cases = (
-        (E, "/root/reference/extract_features.lua",
+        (E, "extract_features.lua",
          {"-checkpoint": "data/models/densecap/densecap-pretrained-vgg16.t7", "-image_size": 720, "-rpn_nms_thresh": 0.7,
           "-final_nms_thresh": 0.4, "-num_proposals": 1000, "-boxes_per_image": 100, "-input_txt": "", "-max_images": 0,
           "-output_h5": "", "-gpu": 0, "-use_cudnn": 1}),
-        (D, "/root/reference/webcam/daemon.lua",
+        (D, "webcam/daemon.lua",
          {"-checkpoint": "data/models/densecap/densecap-pretrained-vgg16.t7", "-max_image_size": 720, "-input_dir": "webcam/inputs",
           "-input_ext": ".jpg", "-output_dir": "webcam/outputs", "-timing": 0, "-rpn_nms_thresh": 0.7, "-final_nms_thresh": 0.3,
           "-num_proposals": 1000, "-gpu": 0, "-use_cudnn": 1}))
+    facts = _reference_facts()["cli_options"]
     for mod, ref, flags in cases:
-        if os.path.exists(ref):        # the lists above ARE the reference's (checked where the reference tree is present)
-            found = dict(re.findall(r"cmd:option\('(-\w+)',\s*\n?\s*('[^']*'|[\d.]+)", open(ref).read()))
-            assert set(found) == set(flags), (ref, set(found) ^ set(flags))
-            for k, v in found.items():
-                assert str(flags[k]) == v.strip("'"), (ref, k, v, flags[k])
+        found = facts[ref]             # the lists above ARE the reference's
+        assert set(found) == set(flags), (ref, set(found) ^ set(flags))
+        for k, v in found.items():
+            assert str(flags[k]) == v, (ref, k, v, flags[k])
         opt = mod.build_parser().parse_args([])
         for k, v in flags.items():
             assert getattr(opt, k[1:]) == v, (mod.__name__, k, getattr(opt, k[1:]), v)

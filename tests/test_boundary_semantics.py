@@ -197,15 +197,16 @@ def test_lua_setTestArgs_has_the_reference_defaults_and_no_persistent_merge():
     assert re.search(r"getopt\(args,\s*'clip_boxes',\s*true\)", layer)
     assert re.search(r"getopt\(args,\s*'nms_thresh',\s*0\.7\)", layer)
     assert re.search(r"getopt\(args,\s*'max_proposals',\s*300\)", layer)
-    # the reference's own text has the same constants (where the reference tree is present)
-    ref = "/root/reference/densecap/DenseCapModel.lua"
-    if os.path.exists(ref):
-        rbody = _lua_function(open(ref).read(), "function DenseCapModel:setTestArgs(kwargs)")
-        for pat in (r"'rpn_nms_thresh',\s*0\.7", r"'num_proposals',\s*1000", r"'final_nms_thresh',\s*0\.3"):
-            assert re.search(pat, rbody) and re.search(pat, body)
-        rl = _lua_function(open("/root/reference/densecap/LocalizationLayer.lua").read(), "function layer:setTestArgs(args)")
-        for pat in (r"'clip_boxes',\s*true", r"'nms_thresh',\s*0\.7", r"'max_proposals',\s*300"):
-            assert re.search(pat, rl) and re.search(pat, layer)
+    # the reference's own text has the same constants (recorded in tests/golden/reference_facts.json)
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")) as f:
+        ref = json.load(f)["set_test_args_defaults"]
+    for want, shim in ((ref["DenseCapModel"], body), (ref["LocalizationLayer"], layer)):
+        assert len(want) == 3
+        for key, default in want.items():
+            assert re.search(r"'%s',\s*%s\b" % (key, re.escape(default)), shim), (key, default)
+    assert ref["DenseCapModel"] == {"rpn_nms_thresh": "0.7", "num_proposals": "1000", "final_nms_thresh": "0.3"}
+    assert ref["LocalizationLayer"] == {"clip_boxes": "true", "nms_thresh": "0.7", "max_proposals": "300"}
 
 
 def test_lua_initial_state_comes_from_the_checkpoint_object_and_travels_before_forward():

@@ -165,7 +165,7 @@ def _run_bench(nproc, extra):
 def test_bench_world2_branch_on_one_gpu():
     """bench.py launched exactly as the driver launches it for N = 2, both ranks on GPU 0 (gloo carrier): the HIP model
     runs in both ranks, rank 0 receives both shards through the one gather and prints the line."""
-    d = _run_bench(2, ["--dist-backend", "gloo"])
+    d = _run_bench(2, ["--full", "--dist-backend", "gloo"])
     assert d["n_gpus"] == 2 and d["data"] == "synthetic" and d["config"]["gather"].startswith("torch.distributed.gather")
     assert d["config"]["total_output_boxes"] > 0 and d["value"] > 0
     assert "roofline" in d and d["roofline"]["frac"] > 0
@@ -183,7 +183,7 @@ def test_bench_one_rank_under_torchrun_gathers_over_rccl():
 def test_bench_line_has_roofline_and_cpu_baseline():
     """Default single-GPU invocation shape (small workload so the CPU leg is quick): the contract's `roofline` and
     `cpu_baseline` objects, the per-stage fractions and the repeats are all in the one line."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--repeats", "2",
                         "--height", "224", "--width", "288", "--proposals", "100"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
