@@ -6,7 +6,6 @@
 // so that, fed the oracle's inputs, the picks are identical to box_utils.nms
 // (densecap/box_utils.lua:154-256).
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -585,7 +584,7 @@ __global__ __launch_bounds__(256) void nms_scan_band_kernel(const u64* __restric
   // (tens of milliseconds; a hand-off normally takes a microsecond) sets the sticky fault word -- the host then fails the call
   // and falls back to the chunk scan instead of delivering a list built on a missing hand-off -- and the wave moves on.
   constexpr unsigned kSpinLimit = 1u << 20;
-  auto give_up = [&]() { if (fault != nullptr && (threadIdx.x & 63) == 0) __hip_atomic_store(fault, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  auto give_up = [&]() { if (fault != nullptr && (threadIdx.x & 63) == 0) __hip_atomic_store(fault, kFaultNmsBand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   const int ntot = *nvalid;
   if (st->done) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -769,8 +768,8 @@ __global__ __launch_bounds__(256) void survivor_compact_kernel(const float* __re
 }
 
 // The results of a group in ONE launch (round 5; three gathers per image before): image = blockIdx.y.  A record is laid out
-// exactly as the pinned host staging expects it -- {int32 K at byte 0, uint32 fault word at byte 68 | 256: boxes (P,4) |
-// scores (P) | int32 tokens (P,T) or fc7 codes (P,D)} -- so that the whole group leaves in one device-to-host copy.
+// exactly as the pinned host staging expects it (kRecK / kRecFault / kRecPayload, common.h) -- so that the whole group leaves in
+// one device-to-host copy.
 // Row r < K of image i is row picks[i*P + r] of the per-RoI tensors (box_utils.nms order, DenseCapModel.lua:261-275);
 // tok_gather = 0: the token rows are already in final order, image by image (captions decoded after the final NMS, rows
 // [img*P, img*P + K)); tok_gather = 2: in final order and PACKED over the group (survivor_compact_kernel's row block: image
@@ -785,10 +784,10 @@ __global__ void final_pack_kernel(const float* __restrict__ final_boxes, const f
   const int K = min(count[(size_t)img * count_stride], P);
   char* rec = pack + (size_t)img * stride;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *reinterpret_cast<int32_t*>(rec) = K;
-    *reinterpret_cast<uint32_t*>(rec + 68) = fault != nullptr ? *fault : 0u;
+    *reinterpret_cast<int32_t*>(rec + kRecK) = K;
+    *reinterpret_cast<uint32_t*>(rec + kRecFault) = fault != nullptr ? *fault : 0u;
   }
-  float* ob = reinterpret_cast<float*>(rec + 256);
+  float* ob = reinterpret_cast<float*>(rec + kRecPayload);
   float* os = ob + (size_t)P * 4;
   uint32_t* ot = reinterpret_cast<uint32_t*>(os + P);
   const size_t r0 = (size_t)img * P;
@@ -845,9 +844,6 @@ hipError_t launch_rpn_decode(const float* heads, int nimg, int h, int w, int k, 
   return hipGetLastError();
 }
 
-// windows of <= NMS_BAND_ROWS rows take nms_scan_band_kernel (DC_NMS_BAND=0 in the environment or dc_debug_set "nms_band" 0:
-// every window through nms_scan_kernel -- an A/B and bisecting switch, the picks are the same)
-static int g_nms_band = [] { const char* e = getenv("DC_NMS_BAND"); return e != nullptr && e[0] == '0' ? 0 : 1; }();
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // window k covers sorted rows [win_start(k), win_start(k+1))
 // windows: 4096 boxes, then 32768 at a time (the scan kernel's LDS bit set holds 32768).  The pick budget is
@@ -899,7 +895,7 @@ hipError_t nms_workspace_bind(NmsWorkspace& ws, void* base, int n) {
 }
 
 hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
-                      const int32_t* n_dev, float thresh, int max_boxes, int32_t* picks, int32_t* count,
+                      const int32_t* n_dev, float thresh, int max_boxes, int32_t* picks, int32_t* count, bool band_scan,
                       hipStream_t s, uint32_t* fault) {
   if (n > ws.n_cap) return hipErrorInvalidValue;
   hipError_t e;
@@ -920,7 +916,7 @@ hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores,
     const int r1 = std::min(n, win_start(k + 1, graded));
     const int rows = std::max(r1 - r0, 0);
     const int wchunks = (rows + 63) / 64;
-    const bool band = g_nms_band && rows > 0 && rows <= NMS_BAND_ROWS;
+    const bool band = band_scan && rows > 0 && rows <= NMS_BAND_ROWS;
     if (rows > 0) {
       if (k > 0)
         hipLaunchKernelGGL(nms_cross_kernel, dim3(wchunks, 4), dim3(256), 0, s, ws.sboxes, ws.sarea, ws.nvalid, st,
@@ -941,8 +937,6 @@ hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores,
   }
   return hipGetLastError();
 }
-// measurement / test hook (dc_debug_set "nms_band"): 0 = every window through nms_scan_kernel
-void nms_set_scan_band(int on) { g_nms_band = on ? 1 : 0; }
 
 hipError_t launch_final_pack(const float* final_boxes, const float* obj, const int32_t* tokens, int tok_gather,
                              const float* codes, const int32_t* picks, const int32_t* count, int count_stride,

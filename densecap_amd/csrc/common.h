@@ -31,6 +31,20 @@ __device__ __forceinline__ void corners(float xc, float yc, float w, float h, fl
   y2 = __fadd_rn(hh, yc);
 }
 
+// ---- the ctx's sticky device fault word: what raised it ------------------------------------------------------------------
+constexpr uint32_t kFaultStreamK = 1u;   // a stream-K owner gave up waiting for a partner's partial tile (mfma_gemm.hip)
+constexpr uint32_t kFaultNmsBand = 2u;   // a hand-off between the waves of nms_scan_band_kernel did not arrive (boxes.hip)
+
+// ---- one image's packed result record (final_pack_kernel; the pinned host staging holds the same layout) ------------------
+// int32 K at kRecK, uint32 fault word at kRecFault; boxes (P,4) at kRecPayload, scores (P) at rec_scores(P), and from
+// rec_values(P) `words` 4-byte values per row: int32 tokens (T) or fc7 codes (D).  rec_stride: bytes of a record, 256-aligned.
+constexpr size_t kRecK = 0, kRecFault = 68, kRecPayload = 256;
+inline size_t rec_scores(int P) { return kRecPayload + (size_t)P * 16; }
+inline size_t rec_values(int P) { return rec_scores(P) + (size_t)P * 4; }
+inline size_t rec_stride(int P, size_t words) { return (rec_values(P) + (size_t)P * words * 4 + 255) & ~(size_t)255; }
+// int32 values between two images' NMS count slots (count1 / count2 of a lane): one 256-byte line per image
+constexpr int kCountStride = 64;
+
 // ---- ctx accessors for the other translation units (densecap.hip) ------------------
 int dc_ctx_device(const dc_ctx* ctx);
 void dc_ctx_set_error(dc_ctx* ctx, const char* msg);
@@ -235,12 +249,13 @@ struct NmsWorkspace {
 size_t nms_workspace_bytes(int n);
 hipError_t nms_workspace_bind(NmsWorkspace& ws, void* base, int n);
 // n_dev (optional device int32) overrides n at run time (n is then the capacity)
-// fault (optional): the ctx's sticky device word; nms_scan_band_kernel stores 2 there when a hand-off between its waves did not
-// arrive within the spin bound (the host then fails the call and switches the band scan off)
+// fault (optional): the ctx's sticky device word; nms_scan_band_kernel stores kFaultNmsBand there when a hand-off between its
+// waves did not arrive within the spin bound (the host then fails the call and switches the band scan off)
+// band: windows of <= NMS_BAND_ROWS rows take nms_scan_band_kernel (false: every window through nms_scan_kernel -- an A/B and
+// bisecting switch, the picks are the same)
 hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
-                      const int32_t* n_dev, float thresh, int max_boxes, int32_t* picks, int32_t* count,
-                      hipStream_t s, uint32_t* fault = nullptr);
-void nms_set_scan_band(int on);          // test hook: 0 = the per-chunk scan kernel for every window
+                      const int32_t* n_dev, float thresh, int max_boxes, int32_t* picks, int32_t* count, bool band,
+                      hipStream_t s, uint32_t* fault);
 // out[i] = src[idx[i]] rows of `width` floats for i < *count (rows >= *count zero-filled up to cap)
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, const int32_t* count, int cap, int width,
                               float* out, hipStream_t s);

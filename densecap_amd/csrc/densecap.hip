@@ -4,13 +4,14 @@
 // used to software-pipeline run_model.lua's image loop), and the per-stage HIP events.
 // The whole forward of one image is enqueued on one stream without host round trips
 // (box counts stay on the device); the host waits once, for the result copy.
+#include <limits.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <memory>
 
@@ -34,6 +35,45 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+
+// A ctx's settings: everything that reaches a kernel argument, a launch decision or the stream layout of a forward
+// (enqueue_body, run_gemm).  A captured forward bakes all of it in, so GraphKey holds the whole struct.  4-byte fields only:
+// graph keys compare it bytewise.
+struct Settings {
+  float rpn_nms_thresh = 0.7f, final_nms_thresh = 0.3f;
+  int num_proposals = 300;          // LocalizationLayer default (LocalizationLayer.lua:237); run_model sets 1000
+  int clip_boxes = 1;               // LocalizationLayer.test_clip_boxes (LocalizationLayer.lua:235)
+  int captions_after_final_nms = 0; // dc_set_caption_order
+  int serial_mode = 0;              // lanes == 1: idle CUs in a layer's last round are worth a tail split-K (dc_set_lanes)
+  int beam_size = 0;                // 0 = greedy LM:sample; > 0 = LM:beamsearch (LanguageModel.lua:129-131)
+  int math_mode = 0;                // dc_set_math_mode: 0 = fp32 MFMA (default), 1 = split-bf16 (three planes, six products, fp32 accumulate)
+  // dc_debug_set (include/densecap_debug.h)
+  int plan_mode = -1;               // -1 = planning follows the lane count, 0 = multi-lane planning, 1 = single-image planning
+  int tail_mode = 0;                // partial last round in single-image mode: 0 stream-K, 1 K-split tail plan, 2 whole tiles
+  int force_cfg = 0;                // measurement hook: tile configuration of plain launches
+  int v2_stages = 0;                // LDS ring depth of the 128x64-tile kernel: 0 by tile count, 2 or 3 forced
+  int stagger = 0;                  // measurement hook: start-up stagger of a launch's workgroups
+  int walk = 0;                     // measurement hook: 128x64 launches as one workgroup per slot walking its tiles
+  int epi_wide = 1;                 // plain interior epilogues as 16-byte stores staged through LDS
+  int bf3_presplit = 1;             // 0 = split the weights in registers too (mode 1 of the kernels)
+  int bf3_all = 0;                  // 1 = math mode 1 takes EVERY contraction, not only those mfma_gemm_bf3_pays names (test
+                                    // hook: small and ragged problems then exercise the split-bf16 kernels)
+  int nms_band = 1;                 // launch_nms `band`; dc_create reads the default from DC_NMS_BAND
+  // contractions planned for one image alone (stream-K / tail plans over partial last rounds): images then travel alone
+  bool serial_planning() const { return plan_mode < 0 ? serial_mode != 0 : plan_mode == 1; }
+};
+static_assert(sizeof(Settings) == 18 * 4, "Settings has 4-byte fields only (GraphKey compares it bytewise); a new field updates this count");
+
+// Everything a captured forward bakes in: workspace pointers (carve epoch, arena, staging), weights, shape and the settings.
+// Bytewise equality up to the end of `set`: 8-byte fields first, then 4-byte ones, so nothing in between is padding.
+struct GraphKey {
+  uint64_t carve_epoch = 0, weights_epoch = 0;
+  const void *fault_dev = nullptr, *arena = nullptr, *host_stage = nullptr, *splitk_ws = nullptr;
+  int H = 0, W = 0, P = 0, g = 0, features_only = 0;
+  Settings set;
+  bool operator==(const GraphKey& o) const { return memcmp(this, &o, offsetof(GraphKey, set) + sizeof(Settings)) == 0; }
+};
+static_assert(offsetof(GraphKey, set) == 6 * 8 + 5 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
 
 struct Lane {
   hipStream_t stream = nullptr;
@@ -81,7 +121,7 @@ struct Lane {
   // graph replay (dc_set_graph_replay): the forward of one (shape, settings) key, captured once and relaunched
   uint64_t carve_epoch = 0;             // bumped whenever lane_prepare hands out new workspace pointers
   hipGraphExec_t gexec = nullptr;
-  std::array<int64_t, 28> gkey{}, last_key{};
+  GraphKey gkey, last_key;
   bool last_key_valid = false;          // last_key = the key of the previous (eager) forward on this lane
   bool ran_graph = false;               // the group in flight was a graph launch (no stage events)
   bool nms_before_decode = false;       // the group in flight ran the final NMS before the decode (dc_set_caption_order(1))
@@ -95,26 +135,13 @@ struct dc_ctx {
   int device = 0;
   std::string err;
   bool have_weights = false;
-  float rpn_nms_thresh = 0.7f, final_nms_thresh = 0.3f;
+  Settings cfg;
   int max_lanes = 3;
-  bool captions_after_final_nms = false;
   int group = 0;             // images per lane group (dc_set_group): 0 = default (1), 1 .. kGemmMaxGroup
   int arena_allocs = 0;      // lane workspace (re)allocations so far (dc_debug_fetch "arena_allocs")
   double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last dc_forward_batch
-  int beam_size = 0;         // 0 = greedy LM:sample; > 0 = LM:beamsearch (LanguageModel.lua:129-131)
   int64_t beam_chunk_floats = (int64_t)1 << 28;   // cap of the beam search's full-logits buffer (dc_debug_set)
-  uint32_t* fault_dev = nullptr;   // sticky device word: a stream-K owner gave up waiting for its partner (checked with the results)
-  int force_cfg = 0;         // measurement hook: tile configuration of plain launches (dc_debug_set "force_cfg")
-  int stagger = 0;           // measurement hook: start-up stagger of a launch's workgroups (dc_debug_set "stagger")
-  int walk = 0;              // measurement hook: 128x64 launches as one workgroup per slot walking its tiles (dc_debug_set "walk")
-  int epi_wide = 1;          // plain interior epilogues as 16-byte stores staged through LDS (dc_debug_set "epi_wide")
-  int plan_mode = -1;        // measurement hook "plan_mode": -1 = planning follows the lane count, 0 = multi-lane planning, 1 = single-image planning
-  int v2_stages = 0;         // LDS ring depth of the 128x64-tile kernel (dc_debug_set "v2_stages": 0 by tile count, 2 or 3 forced)
-  int tail_mode = 0;         // partial last round in single-image mode: 0 stream-K, 1 K-split tail plan, 2 whole tiles (dc_debug_set)
-  bool serial_mode = false;  // lanes == 1: idle CUs in a layer's last round are worth a tail split-K (dc_set_lanes)
-  int num_proposals = 300;  // LocalizationLayer default (LocalizationLayer.lua:237); run_model sets 1000
-  bool clip_boxes = true;   // LocalizationLayer.test_clip_boxes (LocalizationLayer.lua:235)
-  int math_mode = 0;        // dc_set_math_mode: 0 = fp32 MFMA (default), 1 = split-bf16 (three planes, six products, fp32 accumulate)
+  uint32_t* fault_dev = nullptr;   // sticky device word: kFaultStreamK / kFaultNmsBand (common.h), checked with the results
   bool graphs = false;      // dc_set_graph_replay: repeated forwards of one shape are relaunched as a captured hipGraph
   uint64_t weights_epoch = 0;
   int graph_launches = 0, graph_captures = 0;    // dc_debug_fetch "graph_launches" / "graph_captures"
@@ -136,9 +163,6 @@ struct dc_ctx {
   // split-bf16 mode: weight matrices that can take it, and their bf16 planes (made when the mode is first switched on)
   struct PlaneEnt { const float* W; size_t rows; int K; uint16_t* planes; };
   std::vector<PlaneEnt> planes;
-  int bf3_presplit = 1;             // dc_debug_set "bf3_presplit": 0 = split the weights in registers too (mode 1 of the kernels)
-  int bf3_all = 0;                  // dc_debug_set "bf3_all": 1 = math mode 1 takes EVERY contraction, not only those mfma_gemm_bf3_pays
-                                    // names (test hook: small and ragged problems then exercise the split-bf16 kernels)
   DevBuf pre_src, pre_scratch;      // dc_preprocess_u8: uploaded bytes, width-pass plane (grow only)
   DevBuf pre_taps;                  // ... and the tap tables of the sizes in pre_key, kept while the sizes repeat (webcam frames)
   std::vector<char> pre_taps_host;  // (the host copy outlives its asynchronous upload)
@@ -226,14 +250,15 @@ static void ensure_fault_word(dc_ctx* ctx) {
 int run_gemm(dc_ctx* ctx, const GemmDesc& d_in, hipStream_t s, const Ws& w = Ws()) {
   float* const ws = w.p;
   const size_t ws_floats = w.floats;
+  const Settings& c = ctx->cfg;
   GemmDesc d = d_in;
-  d.stages = ctx->v2_stages;
-  d.force_cfg = ctx->force_cfg;
-  d.stagger = ctx->stagger;
-  d.walk = ctx->walk;
-  d.epi_wide = ctx->epi_wide;
-  d.bf3 = ctx->math_mode == 1 && (ctx->bf3_all || mfma_gemm_bf3_pays(d)) ? 1 : 0;
-  if (d.bf3 && ctx->bf3_presplit) {
+  d.stages = c.v2_stages;
+  d.force_cfg = c.force_cfg;
+  d.stagger = c.stagger;
+  d.walk = c.walk;
+  d.epi_wide = c.epi_wide;
+  d.bf3 = c.math_mode == 1 && (c.bf3_all || mfma_gemm_bf3_pays(d)) ? 1 : 0;
+  if (d.bf3 && c.bf3_presplit) {
     const uint16_t* pp = d_in.sk_slots != nullptr ? reinterpret_cast<const uint16_t*>(d_in.sk_slots) : nullptr;    // a caller's own planes (per-op entry points)
     int prow = d_in.sk_np;
     if (pp == nullptr)
@@ -249,8 +274,7 @@ int run_gemm(dc_ctx* ctx, const GemmDesc& d_in, hipStream_t s, const Ws& w = Ws(
   }
   hipError_t e = hipSuccess;
   GemmPlan pl;                                                // mfma_gemm_plan decides; this function only acts on it
-  const bool serial_plan = ctx->plan_mode < 0 ? ctx->serial_mode : ctx->plan_mode == 1;
-  mfma_gemm_plan(d, serial_plan, ctx->tail_mode, ws != nullptr ? ws_floats : 0, &pl);
+  mfma_gemm_plan(d, c.serial_planning(), c.tail_mode, ws != nullptr ? ws_floats : 0, &pl);
   const int m_split = pl.m_split;
   if (pl.kind == GEMM_PLAN_SPLITK) {
     // few tiles, long K: every tile is shared by `splitk` workgroups
@@ -356,35 +380,58 @@ constexpr size_t kSplitkWsFloats = (size_t)6400 * 128 * 128;  // 400 MiB per lan
 Ws lane_ws(const Lane& L) { return Ws{L.splitk_ws, L.splitk_ws ? kSplitkWsFloats : 0}; }
 
 int effective_proposals(const dc_ctx* ctx, int H, int W) {
-  if (ctx->num_proposals != -1) return ctx->num_proposals;
+  if (ctx->cfg.num_proposals != -1) return ctx->cfg.num_proposals;
   int fh = H, fw = W;
   for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
     if (kVgg[i].pool_after) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
   return ctx->k * fh * fw;
 }
 
-// bytes of one image's slot in the pinned result staging: {count; boxes; scores; tokens | fc7 codes}
-size_t host_stage_stride(const dc_ctx* ctx, int P) {
-  return al(256 + (size_t)P * (16 + 4 + (size_t)ctx->T * 4 + (size_t)ctx->D * 4));
+// bytes of one image's packed result record: tokens, or fc7 codes (extractFeatures)
+size_t pack_stride(const dc_ctx* ctx, int P, bool feats) { return rec_stride(P, feats ? ctx->D : ctx->T); }
+// bytes per image of a lane's record buffers (out_pack, host_stage), which hold either kind
+size_t host_stage_stride(const dc_ctx* ctx, int P) { return rec_stride(P, (size_t)ctx->T + ctx->D); }
+
+// A lane's streams and events, made on first use.
+int lane_streams(dc_ctx* ctx, Lane& L) {
+  if (L.stream != nullptr) return DC_OK;
+  HIPCHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&L.aux, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&L.aux2, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&L.ev_fork2, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&L.ev_join2, hipEventDisableTiming));
+  for (auto& e : L.ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming));
+  return DC_OK;
 }
 
-// bytes of one image's PACKED record (device and pinned host staging share the layout): {K, fault | boxes | scores | tokens or codes}
-size_t pack_stride(const dc_ctx* ctx, int P, bool feats) {
-  return al(256 + (size_t)P * (16 + 4 + (feats ? (size_t)ctx->D * 4 : (size_t)ctx->T * 4)));
+// Everything a lane owns, released (the device is idle).
+void lane_release(Lane& L) {
+  if (L.arena.p) (void)hipFree(L.arena.p);
+  if (L.beam_base) (void)hipFree(L.beam_base);
+  if (L.gexec) (void)hipGraphExecDestroy(L.gexec);
+  if (L.host_stage) (void)hipHostFree(L.host_stage);
+  for (auto& ev : L.ev) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {L.ev_fork, L.ev_join, L.ev_fork2, L.ev_join2}) if (ev) (void)hipEventDestroy(ev);
+  for (hipStream_t st : {L.aux, L.aux2, L.stream}) if (st) (void)hipStreamDestroy(st);
+}
+
+// Pieces of one allocation: `carve(cv, base)` points each *p at its own 256-byte aligned piece of `base` and returns the
+// bytes all of them take (base = null: only the bytes).
+struct Carve { void** p; size_t bytes; };
+size_t carve(const std::vector<Carve>& cv, void* base) {
+  size_t total = 0;
+  for (const Carve& c : cv) {
+    if (base != nullptr) *c.p = static_cast<char*>(base) + total;
+    total += al(c.bytes);
+  }
+  return total;
 }
 
 // (Re)build a lane's workspace for G images of size (H,W) side by side and proposal capacity P each.
 int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
-  if (L.stream == nullptr) {
-    HIPCHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&L.aux, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&L.aux2, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_fork2, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_join2, hipEventDisableTiming));
-    for (auto& e : L.ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming));
-  }
+  DCCHK(lane_streams(ctx, L));
   if (L.H == H && L.W == W && L.P == P && L.G == G && L.arena.p) return DC_OK;
   int fh = H, fw = W;
   for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
@@ -392,10 +439,9 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
   const int A = ctx->k * fh * fw;
   const int Tn = ctx->T, V1 = ctx->V + 1, Dm = ctx->D, E = ctx->E, Hd = ctx->Hd;
   const int nms_n = std::max(A, P);
-  struct Carve { void** p; size_t bytes; };
   const size_t act_bytes = (size_t)G * H * W * 64 * sizeof(float);
   const size_t GP = (size_t)G * P;          // rows of the per-RoI tensors: image i owns rows [i*P, (i+1)*P)
-  std::vector<Carve> cv = {
+  const std::vector<Carve> cv = {
       {(void**)&L.img, (size_t)G * 3 * H * W * 4},
       {(void**)&L.act[0], act_bytes},
       {(void**)&L.act[1], act_bytes},
@@ -407,9 +453,9 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
       {(void**)&L.rpn_valid, (size_t)G * A},
       {(void**)&L.nms_base, nms_workspace_bytes(nms_n)},          // one: the images' NMS runs follow each other on the stream
       {(void**)&L.picks1, GP * 4},
-      {(void**)&L.count1, (size_t)G * 256},
+      {(void**)&L.count1, (size_t)G * kCountStride * 4},
       {(void**)&L.picks2, GP * 4},
-      {(void**)&L.count2, (size_t)G * 256},
+      {(void**)&L.count2, (size_t)G * kCountStride * 4},
       {(void**)&L.surv_total, 256},
       {(void**)&L.roi_boxes, GP * 16},
       {(void**)&L.roi_feats, GP * 49 * 512 * 4},
@@ -431,8 +477,7 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
       {(void**)&L.out_feats, GP * Dm * 4},
       {(void**)&L.splitk_ws, kSplitkWsFloats * 4},
   };
-  size_t total = 0;
-  for (auto& c : cv) total += al(c.bytes);
+  const size_t total = carve(cv, nullptr);
   // The arena only grows: a directory of mixed sizes (720x480, 720x540, 480x720 ... the normal case for
   // run_model -input_dir) re-carves the existing allocation instead of a free + malloc of ~0.5 GB per image.
   if (L.arena.p == nullptr || total > L.arena.bytes) {
@@ -445,8 +490,7 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
     L.arena.bytes = total;
     ctx->arena_allocs += 1;
   }
-  char* p = static_cast<char*>(L.arena.p);
-  for (auto& c : cv) { *c.p = p; p += al(c.bytes); }
+  carve(cv, L.arena.p);
   L.carve_epoch += 1;                  // every captured pointer is stale now
   nms_workspace_bind(L.nms, L.nms_base, nms_n);
   const size_t hs = (size_t)G * host_stage_stride(ctx, P);
@@ -551,19 +595,18 @@ int lm_sample(dc_ctx* ctx, Lane& L, const float* codes, int n, int plan, const i
 // Proposals that advance together: all of them (rows = P x beam, one GEMM per step over every proposal) unless the
 // full-logits buffer rows x (V+1) would pass 2^28 floats (1 GiB) -- e.g. 5,114 proposals at beam 5 / V = 10,497.
 int beam_chunk(const dc_ctx* ctx, int n) {
-  const long cap = (long)(ctx->beam_chunk_floats / ((int64_t)ctx->beam_size * (ctx->V + 1)));
+  const long cap = (long)(ctx->beam_chunk_floats / ((int64_t)ctx->cfg.beam_size * (ctx->V + 1)));
   return (int)std::max<long>(1, std::min<long>(n, std::max<long>(64, cap)));
 }
 int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
-  const int beam = ctx->beam_size, rows = chunk * beam;
+  const int beam = ctx->cfg.beam_size, rows = chunk * beam;
   // bm_enc is sized by the chunk, bm_top_lp / bm_top_idx by rows x beam: the scratch is reusable only when NONE of the
   // three grew (beam 2 x 1000 proposals and beam 20 x 100 have the same row count but not the same carve)
   if (L.beam_base && L.beam_rows >= rows && L.beam_chunk >= chunk && L.beam_width >= beam) return DC_OK;
   if (L.beam_base) { HIPCHK(hipStreamSynchronize(L.stream)); HIPCHK(hipFree(L.beam_base)); L.beam_base = nullptr; }
   const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T;
   L.beam_base = nullptr; L.beam_rows = L.beam_chunk = L.beam_width = 0;
-  struct Carve { void** p; size_t bytes; };
-  std::vector<Carve> cv = {
+  const std::vector<Carve> cv = {
       {(void**)&L.bm_enc, (size_t)chunk * E * 4},      {(void**)&L.bm_gates, (size_t)rows * 4 * Hd * 4},
       {(void**)&L.bm_h[0], (size_t)rows * Hd * 4},     {(void**)&L.bm_h[1], (size_t)rows * Hd * 4},
       {(void**)&L.bm_c[0], (size_t)rows * Hd * 4},     {(void**)&L.bm_c[1], (size_t)rows * Hd * 4},
@@ -573,11 +616,8 @@ int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
       {(void**)&L.bm_beams[1], (size_t)rows * T * 4},  {(void**)&L.bm_parent, (size_t)rows * 4},
       {(void**)&L.bm_tok, (size_t)rows * 4},           {(void**)&L.bm_fin, (size_t)rows},
   };
-  size_t total = 0;
-  for (auto& c : cv) total += al(c.bytes);
-  HIPCHK(hipMalloc(&L.beam_base, total));
-  char* p = static_cast<char*>(L.beam_base);
-  for (auto& c : cv) { *c.p = p; p += al(c.bytes); }
+  HIPCHK(hipMalloc(&L.beam_base, carve(cv, nullptr)));
+  carve(cv, L.beam_base);
   L.beam_rows = rows; L.beam_chunk = chunk; L.beam_width = beam;
   return DC_OK;
 }
@@ -585,7 +625,7 @@ int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
 int lm_beamsearch(dc_ctx* ctx, Lane& L, const float* codes, int n, int32_t* seq_out, hipStream_t s) {
   const int kBeamChunk = beam_chunk(ctx, n);
   DCCHK(beam_prepare(ctx, L, kBeamChunk));
-  const int beam = ctx->beam_size, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
+  const int beam = ctx->cfg.beam_size, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
   auto step = [&](float* h, float* c, int rows) -> int {        // one LSTM step on the words in bm_tok, in place
     GemmDesc d;
     d.A = h; d.W = ctx->whT; d.C = L.bm_gates; d.M = rows; d.N = 4 * Hd; d.K = Hd; d.ldc = 4 * Hd;
@@ -652,6 +692,7 @@ int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int p
 // the group it travels in.
 // `events`: record the stage events (an eager enqueue; a captured graph carries none -- dc_stage_times then has nothing)
 int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
+  const Settings& cfg = ctx->cfg;
   hipStream_t s = L.stream;
   const int H = L.H, W = L.W, P = L.P;
 #define STAGE_EVENT(i) do { if (events) HIPCHK(hipEventRecord(L.ev[i], s)); } while (0)
@@ -678,17 +719,17 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   DCCHK(conv3x3(ctx, s, L.feat, ctx->rpn_w, ctx->rpn_b, L.rpn_hidden, g, h, w, 512, ctx->R, 1, lane_ws(L)));
   DCCHK(linear(ctx, s, L.rpn_hidden, ctx->heads_w, ctx->heads_b, L.heads, g * h * w, 6 * ctx->k, ctx->R, 0, Ws(), h * w));
   KCHK(launch_rpn_decode(L.heads, g, h, w, ctx->k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], H, W,
-                         L.rpn_boxes, nullptr, nullptr, L.rpn_xyxy, L.rpn_p, L.rpn_valid, ctx->clip_boxes ? 1 : 0, s));   // the whole group in one launch
+                         L.rpn_boxes, nullptr, nullptr, L.rpn_xyxy, L.rpn_p, L.rpn_valid, cfg.clip_boxes, s));   // the whole group in one launch
   STAGE_EVENT(2);
   // ---- RPN NMS (LocalizationLayer.lua:318-338) ------------------------------------------------
   ensure_fault_word(ctx);
   for (int i = 0; i < g; ++i)
     KCHK(launch_nms(L.nms, L.rpn_xyxy + (size_t)i * L.A * 4, L.rpn_p + (size_t)i * L.A, L.rpn_valid + (size_t)i * L.A, L.A,
-                    nullptr, ctx->rpn_nms_thresh, P, L.picks1 + (size_t)i * P, L.count1 + i * 64, s, ctx->fault_dev));
+                    nullptr, cfg.rpn_nms_thresh, P, L.picks1 + (size_t)i * P, L.count1 + i * kCountStride, cfg.nms_band, s, ctx->fault_dev));
   STAGE_EVENT(3);
   // ---- bilinear RoI pooling (LocalizationLayer.lua:338-349) -----------------------------------
   // one launch for the group; the picked RPN boxes are gathered by the kernel itself (and left in roi_boxes for the heads)
-  KCHK(launch_bilinear_roi_pool_group(L.feat, feat_elems, g, h, w, 512, L.roi_boxes, P, L.count1, 64, L.picks1, L.rpn_boxes,
+  KCHK(launch_bilinear_roi_pool_group(L.feat, feat_elems, g, h, w, 512, L.roi_boxes, P, L.count1, kCountStride, L.picks1, L.rpn_boxes,
                                       (size_t)L.A * 4, H, W, 7, 7, L.roi_feats, 1, s));
   STAGE_EVENT(4);
   // ---- recog_base fc6/fc7 (DenseCapModel.lua:133) ------------------------------------------------
@@ -700,12 +741,12 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes,
                           L.final_xyxy, R, ctx->D, s));
   STAGE_EVENT(6);
-  const bool survivors_only = ctx->captions_after_final_nms && !features_only;
+  const bool survivors_only = cfg.captions_after_final_nms && !features_only;
   // single-image mode, reference order: decode (two row blocks on two streams) and final NMS (a third stream) are
   // independent consumers of the heads' outputs.  Per-launch HIP-event profiling wants kernels that do not overlap:
   // everything stays on one stream while it is on.
-  const bool side_streams = ctx->serial_mode && !ctx->prof && !features_only && !survivors_only && R >= 256 &&
-                            ctx->beam_size == 0;
+  const bool side_streams = cfg.serial_mode && !ctx->prof && !features_only && !survivors_only && R >= 256 &&
+                            cfg.beam_size == 0;
   hipStream_t sn = side_streams ? L.aux2 : s;       // stream of the final NMS
   if (side_streams) {
     HIPCHK(hipEventRecord(L.ev_fork2, s));
@@ -713,7 +754,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   }
   // ---- language model (reference order: all P proposals, DenseCapModel.lua:127-162) -----------------
   if (!features_only && !survivors_only) {
-    if (ctx->beam_size > 0) DCCHK(lm_beamsearch(ctx, L, L.codes, R, L.seq, s));
+    if (cfg.beam_size > 0) DCCHK(lm_beamsearch(ctx, L, L.codes, R, L.seq, s));
     else if (side_streams) DCCHK(lm_sample_two_streams(ctx, L, L.codes, R, P, L.seq));
     else DCCHK(lm_sample(ctx, L, L.codes, R, P, nullptr, L.seq));
   }
@@ -723,12 +764,12 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
     const size_t r0 = (size_t)i * P;
     // forward_test skips the final NMS when final_nms_thresh <= 0 (DenseCapModel.lua:261); extractFeatures calls
     // box_utils.nms unconditionally (DenseCapModel.lua:285-304)
-    if (ctx->final_nms_thresh > 0.f || features_only) {
-      KCHK(launch_nms(L.nms, L.final_xyxy + r0 * 4, L.obj + r0, nullptr, P, L.count1 + i * 64, ctx->final_nms_thresh, -1,
-                      L.picks2 + r0, L.count2 + i * 64, sn, ctx->fault_dev));
+    if (cfg.final_nms_thresh > 0.f || features_only) {
+      KCHK(launch_nms(L.nms, L.final_xyxy + r0 * 4, L.obj + r0, nullptr, P, L.count1 + i * kCountStride, cfg.final_nms_thresh, -1,
+                      L.picks2 + r0, L.count2 + i * kCountStride, cfg.nms_band, sn, ctx->fault_dev));
     } else {
       // DenseCapModel.lua:261: no final NMS when final_nms_thresh <= 0 -> all RoIs, in RPN order
-      KCHK(launch_iota_count(L.picks2 + r0, L.count2 + i * 64, L.count1 + i * 64, P, sn));
+      KCHK(launch_iota_count(L.picks2 + r0, L.count2 + i * kCountStride, L.count1 + i * kCountStride, P, sn));
     }
   }
   if (side_streams) {
@@ -738,7 +779,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   // captions after the final NMS: event 7 sits between the two stages here as well, in the order they ran (harvest swaps the names)
   if (survivors_only) STAGE_EVENT(7);
   L.nms_before_decode = survivors_only;
-  const bool packed_decode = survivors_only && ctx->beam_size == 0;
+  const bool packed_decode = survivors_only && cfg.beam_size == 0;
   if (packed_decode) {
     // Identical outputs, less work: LSTM rows are independent, so only the rows the final NMS kept are decoded (~a quarter at
     // 1000 proposals / 0.3).  Round 6: ONCE PER GROUP -- the kept fc7 rows of all g images packed into one row block
@@ -746,13 +787,13 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
     // planned on one image's P rows as in the reference order: an element's arithmetic is the same in either order and in any
     // group (tests/test_gpu_e2e.py::test_caption_order_is_output_invariant).  final_pack reads the packed token rows back
     // image by image.
-    KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, 64, g, P, ctx->D, L.out_feats, L.surv_total, s));
+    KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, g, P, ctx->D, L.out_feats, L.surv_total, s));
     DCCHK(lm_sample(ctx, L, L.out_feats, R, P, L.surv_total, L.out_tokens));
   } else if (survivors_only) {
     // beam search after the final NMS: image by image (the beam rows of one image advance together)
     for (int i = 0; i < g; ++i) {
       const size_t r0 = (size_t)i * P;
-      const int32_t *pk = L.picks2 + r0, *cnt = L.count2 + i * 64;
+      const int32_t *pk = L.picks2 + r0, *cnt = L.count2 + i * kCountStride;
       KCHK(launch_gather_rows(L.codes + r0 * ctx->D, pk, cnt, P, ctx->D, L.out_feats + r0 * ctx->D, s));
       DCCHK(lm_beamsearch(ctx, L, L.out_feats + r0 * ctx->D, P, L.out_tokens + r0 * ctx->T, s));   // rows past K: zero codes, ignored
     }
@@ -760,7 +801,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   // ---- results: ONE gather launch for the group into packed records, ONE copy to the pinned host staging ---------------
   const size_t stride = pack_stride(ctx, P, features_only);
   KCHK(launch_final_pack(L.final_boxes, L.obj, survivors_only ? L.out_tokens : L.seq, packed_decode ? 2 : survivors_only ? 0 : 1,
-                         features_only ? L.codes : nullptr, L.picks2, L.count2, 64, ctx->fault_dev, g, P, ctx->T, ctx->D,
+                         features_only ? L.codes : nullptr, L.picks2, L.count2, kCountStride, ctx->fault_dev, g, P, ctx->T, ctx->D,
                          L.out_pack, stride, s));
   STAGE_EVENT(8);
   HIPCHK(hipMemcpyAsync(L.host_stage, L.out_pack, (size_t)g * stride, hipMemcpyDeviceToHost, s));
@@ -768,15 +809,13 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   return DC_OK;
 }
 
-// Everything a captured forward bakes in: workspace pointers (carve epoch, arena, staging), weights, shape, every setting
-// that reaches a kernel argument, a launch decision or the stream layout.
-std::array<int64_t, 28> graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only) {
-  auto f2i = [](float f) { int32_t i; memcpy(&i, &f, 4); return (int64_t)i; };
-  return {1, (int64_t)L.carve_epoch, (int64_t)ctx->weights_epoch, L.H, L.W, L.P, g, features_only ? 1 : 0,
-          f2i(ctx->rpn_nms_thresh), f2i(ctx->final_nms_thresh), ctx->num_proposals, ctx->clip_boxes ? 1 : 0,
-          ctx->captions_after_final_nms ? 1 : 0, ctx->serial_mode ? 1 : 0, ctx->plan_mode, ctx->tail_mode, ctx->force_cfg,
-          ctx->v2_stages, ctx->stagger, ctx->walk + 2 * ctx->epi_wide, ctx->beam_size, (int64_t)(uintptr_t)ctx->fault_dev,
-          (int64_t)(uintptr_t)L.arena.p, (int64_t)(uintptr_t)L.host_stage, (int64_t)(uintptr_t)L.splitk_ws, ctx->math_mode + 2 * ctx->bf3_presplit + 4 * ctx->bf3_all, 0, 0};
+GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only) {
+  GraphKey k;
+  k.carve_epoch = L.carve_epoch; k.weights_epoch = ctx->weights_epoch;
+  k.fault_dev = ctx->fault_dev; k.arena = L.arena.p; k.host_stage = L.host_stage; k.splitk_ws = L.splitk_ws;
+  k.H = L.H; k.W = L.W; k.P = L.P; k.g = g; k.features_only = features_only;
+  k.set = ctx->cfg;
+  return k;
 }
 
 // `img`: the g images back to back; `sep` (optional) = g separate images instead (a run of equal-sized images of a mixed list)
@@ -790,12 +829,12 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
     for (int i = 0; i < g; ++i) HIPCHK(hipMemcpyAsync(L.img + (size_t)i * img_elems, sep[i], img_elems * 4, kind, s));
   L.g = g;
   const size_t stride = pack_stride(ctx, L.P, features_only);
-  for (int i = 0; i < g; ++i) *reinterpret_cast<uint32_t*>(static_cast<char*>(L.host_stage) + i * stride + 68) = 0;
+  for (int i = 0; i < g; ++i) *reinterpret_cast<uint32_t*>(static_cast<char*>(L.host_stage) + i * stride + kRecFault) = 0;
   L.ran_graph = false;
   // Graph replay (dc_set_graph_replay): the FIRST forward of a key runs eagerly (lazy allocations, kernel attributes and
   // the stream-K fault word are all in place afterwards), the second is captured and instantiated, later ones are one
   // hipGraphLaunch.  Per-launch profiling and beam search (which allocates on first use) stay eager.
-  const bool eligible = ctx->graphs && !ctx->prof && ctx->beam_size == 0;
+  const bool eligible = ctx->graphs && !ctx->prof && ctx->cfg.beam_size == 0;
   if (eligible) {
     const auto key = graph_key(ctx, L, g, features_only);
     if (L.gexec != nullptr && key == L.gkey) {
@@ -847,6 +886,20 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
 }
 
 
+// The ctx's sticky fault word read `fault` (a hand-off between workgroups did not arrive within its spin bound): clear it, turn
+// off on this ctx what raised it -- the next forward has new settings, hence a new graph key -- and fail the call.
+int fail_on_fault(dc_ctx* ctx, uint32_t fault, const char* who) {
+  (void)hipMemset(ctx->fault_dev, 0, 64);
+  if (fault == kFaultNmsBand) {
+    ctx->cfg.nms_band = 0;          // every NMS window back on the chunk scan
+    return ctx->fail(DC_E_HIP, "%s: NMS band scan: a hand-off between the waves of nms_scan_band_kernel did not arrive within the "
+                               "spin bound; this ctx now scans every window by chunks -- repeat the call", who);
+  }
+  ctx->cfg.tail_mode = 1;           // stop sharing tiles between workgroups
+  return ctx->fail(DC_E_HIP, "%s: stream-K: a workgroup's partner never published its partial tile within the spin bound (GPU "
+                             "shared with another job?); this ctx now uses the K-split tail plan -- repeat the call", who);
+}
+
 // Wait for the lane's in-flight group and hand the results to the caller's buffers.
 int harvest(dc_ctx* ctx, Lane& L) {
   if (!L.busy) return DC_OK;
@@ -865,33 +918,25 @@ int harvest(dc_ctx* ctx, Lane& L) {
   const size_t stride = pack_stride(ctx, P, L.pending_feats);
   for (int i = 0; i < L.g; ++i) {
     const char* hs = static_cast<const char*>(L.host_stage) + i * stride;
-    if (const uint32_t fw = *reinterpret_cast<const uint32_t*>(hs + 68); fw != 0u) {
-      (void)hipMemset(ctx->fault_dev, 0, 64);
+    if (const uint32_t fw = *reinterpret_cast<const uint32_t*>(hs + kRecFault); fw != 0u) {
       L.pending = nullptr;
-      if (fw == 2u) {
-        nms_set_scan_band(0);       // every NMS window back on the chunk scan (process-wide)
-        return ctx->fail(DC_E_HIP, "NMS band scan: a hand-off between the waves of nms_scan_band_kernel did not arrive within the spin "
-                                   "bound; the band scan is now off (chunk scan for every window) -- repeat the call");
-      }
-      ctx->tail_mode = 1;           // stop sharing tiles between workgroups on this ctx
-      return ctx->fail(DC_E_HIP, "stream-K: a workgroup's partner never published its partial tile within the spin bound (GPU "
-                                 "shared with another job?); this ctx now uses the K-split tail plan -- repeat the call");
+      return fail_on_fault(ctx, fw, "forward");
     }
-    int K = *reinterpret_cast<const int32_t*>(hs);
+    int K = *reinterpret_cast<const int32_t*>(hs + kRecK);
     if (L.pending_feats) {
       K = std::min(K, L.pending_capacity);
       if (L.pending_k_dst) L.pending_k_dst[i] = K;
-      if (L.pending_box_dst) memcpy(L.pending_box_dst + (size_t)i * L.pending_capacity * 4, hs + 256, (size_t)K * 16);
+      if (L.pending_box_dst) memcpy(L.pending_box_dst + (size_t)i * L.pending_capacity * 4, hs + kRecPayload, (size_t)K * 16);
       if (L.pending_feat_dst)
-        memcpy(L.pending_feat_dst + (size_t)i * L.pending_capacity * ctx->D, hs + 256 + (size_t)P * 20, (size_t)K * ctx->D * 4);
+        memcpy(L.pending_feat_dst + (size_t)i * L.pending_capacity * ctx->D, hs + rec_values(P), (size_t)K * ctx->D * 4);
     } else if (L.pending) {
       dc_result* r = L.pending + i;
       K = std::min(K, (int)r->capacity);
       r->K = K;
       r->T = ctx->T;
-      if (r->boxes) memcpy(r->boxes, hs + 256, (size_t)K * 16);
-      if (r->scores) memcpy(r->scores, hs + 256 + (size_t)P * 16, (size_t)K * 4);
-      if (r->tokens) memcpy(r->tokens, hs + 256 + (size_t)P * 20, (size_t)K * ctx->T * 4);
+      if (r->boxes) memcpy(r->boxes, hs + kRecPayload, (size_t)K * 16);
+      if (r->scores) memcpy(r->scores, hs + rec_scores(P), (size_t)K * 4);
+      if (r->tokens) memcpy(r->tokens, hs + rec_values(P), (size_t)K * ctx->T * 4);
     }
   }
   L.pending = nullptr;
@@ -904,16 +949,7 @@ Lane& lane0(dc_ctx* ctx) {
 }
 int lane0_stream(dc_ctx* ctx, hipStream_t* s) {
   Lane& L = lane0(ctx);
-  if (L.stream == nullptr) {
-    HIPCHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&L.aux, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&L.aux2, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_fork2, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_join2, hipEventDisableTiming));
-    for (auto& e : L.ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming));
-  }
+  DCCHK(lane_streams(ctx, L));
   *s = L.stream;
   return DC_OK;
 }
@@ -942,6 +978,8 @@ int dc_create(dc_ctx** out, int hip_device) {
   if (e != hipSuccess) { g_last_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return DC_E_HIP; }
   dc_ctx* ctx = new dc_ctx();
   ctx->device = hip_device;
+  const char* band = getenv("DC_NMS_BAND");          // an A/B and bisecting switch: DC_NMS_BAND=0 starts with the band scan off
+  ctx->cfg.nms_band = band != nullptr && band[0] == '0' ? 0 : 1;
   *out = ctx;
   return DC_OK;
 }
@@ -950,21 +988,7 @@ void dc_destroy(dc_ctx* ctx) {
   if (!ctx) return;
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
-  for (auto& lp : ctx->lanes) {
-    Lane& L = *lp;
-    if (L.arena.p) hipFree(L.arena.p);
-    if (L.beam_base) hipFree(L.beam_base);
-    if (L.gexec) (void)hipGraphExecDestroy(L.gexec);
-    if (L.host_stage) hipHostFree(L.host_stage);
-    for (auto& ev : L.ev) if (ev) hipEventDestroy(ev);
-    if (L.ev_fork) hipEventDestroy(L.ev_fork);
-    if (L.ev_join) hipEventDestroy(L.ev_join);
-    if (L.ev_fork2) hipEventDestroy(L.ev_fork2);
-    if (L.ev_join2) hipEventDestroy(L.ev_join2);
-    if (L.aux) hipStreamDestroy(L.aux);
-    if (L.aux2) hipStreamDestroy(L.aux2);
-    if (L.stream) hipStreamDestroy(L.stream);
-  }
+  for (auto& lp : ctx->lanes) lane_release(*lp);
   for (void* p : ctx->owned) hipFree(p);
   if (ctx->pre_src.p) hipFree(ctx->pre_src.p);
   if (ctx->pre_scratch.p) hipFree(ctx->pre_scratch.p);
@@ -980,9 +1004,9 @@ int dc_set_localization_test_args(dc_ctx* ctx, int clip_boxes, float nms_thresh,
   if (!ctx) return DC_E_INVALID;
   if (max_proposals != -1 && (max_proposals <= 0 || max_proposals > (1 << 20)))
     return ctx->fail(DC_E_UNSUPPORTED, "num_proposals must be -1 (uncapped) or in [1,1048576] (got %d)", max_proposals);
-  ctx->clip_boxes = clip_boxes != 0;
-  ctx->rpn_nms_thresh = nms_thresh;
-  ctx->num_proposals = max_proposals;
+  ctx->cfg.clip_boxes = clip_boxes != 0;
+  ctx->cfg.rpn_nms_thresh = nms_thresh;
+  ctx->cfg.num_proposals = max_proposals;
   return DC_OK;
 }
 
@@ -990,7 +1014,7 @@ int dc_set_localization_test_args(dc_ctx* ctx, int clip_boxes, float nms_thresh,
 int dc_set_test_args(dc_ctx* ctx, float rpn_nms_thresh, float final_nms_thresh, int num_proposals) {
   if (!ctx) return DC_E_INVALID;
   DCCHK(dc_set_localization_test_args(ctx, 1, rpn_nms_thresh, num_proposals));
-  ctx->final_nms_thresh = final_nms_thresh;
+  ctx->cfg.final_nms_thresh = final_nms_thresh;
   return DC_OK;
 }
 
@@ -1000,7 +1024,7 @@ int dc_set_lanes(dc_ctx* ctx, int lanes) {
   ctx->max_lanes = lanes;
   // numerics depend only on this setting, never on how many images a call happens to carry: with one lane the
   // last partial round of a layer is K-split (different fp32 summation order for those rows)
-  ctx->serial_mode = lanes == 1;
+  ctx->cfg.serial_mode = lanes == 1;
   return DC_OK;
 }
 
@@ -1028,7 +1052,7 @@ int dc_set_beam_size(dc_ctx* ctx, int beam_size) {
   if (!ctx) return DC_E_INVALID;
   if (beam_size < 0 || beam_size > 32) return ctx->fail(DC_E_UNSUPPORTED, "dc_set_beam_size: beam_size must be in [0,32] (got %d)", beam_size);
   DCCHK(check_beam_fits(ctx, beam_size));          // before dc_load_weights the check runs there instead
-  ctx->beam_size = beam_size;
+  ctx->cfg.beam_size = beam_size;
   return DC_OK;
 }
 
@@ -1051,7 +1075,7 @@ int dc_set_math_mode(dc_ctx* ctx, int mode) {
   if (mode != DC_MATH_FP32 && mode != DC_MATH_SPLIT_BF16)
     return ctx->fail(DC_E_INVALID, "dc_set_math_mode: 0 (fp32 MFMA) or 1 (split-bf16), got %d", mode);
   if (mode == DC_MATH_SPLIT_BF16 && ctx->have_weights) DCCHK(make_weight_planes(ctx));
-  ctx->math_mode = mode;
+  ctx->cfg.math_mode = mode;
   return DC_OK;
 }
 
@@ -1063,7 +1087,7 @@ int dc_set_graph_replay(dc_ctx* ctx, int on) {
 
 int dc_set_caption_order(dc_ctx* ctx, int after_final_nms) {
   if (!ctx) return DC_E_INVALID;
-  ctx->captions_after_final_nms = after_final_nms != 0;
+  ctx->cfg.captions_after_final_nms = after_final_nms != 0;
   return DC_OK;
 }
 
@@ -1179,11 +1203,11 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   ctx->planes.push_back({ctx->fc6_w, (size_t)D, 49 * 512, nullptr});
   ctx->planes.push_back({ctx->fc7_w, (size_t)D, D, nullptr});
   ctx->planes.push_back({ctx->dec_w, (size_t)ctx->V1pad + 4 * Hd, Hd, nullptr});
-  if (ctx->math_mode == DC_MATH_SPLIT_BF16) DCCHK(make_weight_planes(ctx));
+  if (ctx->cfg.math_mode == DC_MATH_SPLIT_BF16) DCCHK(make_weight_planes(ctx));
   ctx->have_weights = true;
   ctx->weights_epoch += 1;                 // captured graphs hold the old weight pointers
-  if (int rc = check_beam_fits(ctx, ctx->beam_size); rc != DC_OK) {   // dc_set_beam_size came first: validate it now
-    ctx->beam_size = 0;
+  if (int rc = check_beam_fits(ctx, ctx->cfg.beam_size); rc != DC_OK) {   // dc_set_beam_size came first: validate it now
+    ctx->cfg.beam_size = 0;
     return rc;
   }
   return DC_OK;
@@ -1221,7 +1245,7 @@ static int check_image_size(dc_ctx* ctx, int H, int W, const char* who) {
 
 // images of a group share one 32-bit operand offset space in conv1_x (the pooled conv counts window slots)
 static int clamp_group(const dc_ctx* ctx, int G, int H, int W) {
-  if (ctx->plan_mode < 0 ? ctx->serial_mode : ctx->plan_mode == 1) return 1;       // single-image planning: images travel alone
+  if (ctx->cfg.serial_planning()) return 1;       // single-image planning: images travel alone
   const size_t rows1 = std::max((size_t)H * W, (size_t)4 * ((H + 1) / 2) * ((W + 1) / 2));
   while (G > 1 && (size_t)G * rows1 * 64 * 4 >= 0xffffe000ull) --G;
   return std::max(G, 1);
@@ -1526,54 +1550,25 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value) {
     ctx->beam_chunk_floats = value;
     return DC_OK;
   }
-  if (strcmp(name, "nms_band") == 0) {                 // process-wide: 0 = nms_scan_kernel for every NMS window
-    if (value < 0 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: nms_band must be 0 or 1");
-    nms_set_scan_band((int)value);
-    return DC_OK;
-  }
-  if (strcmp(name, "v2_stages") == 0) {
-    if (value != 0 && value != 2 && value != 3) return ctx->fail(DC_E_INVALID, "dc_debug_set: v2_stages must be 0, 2 or 3");
-    ctx->v2_stages = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "force_cfg") == 0) {
-    if (value < 0 || value > 6) return ctx->fail(DC_E_INVALID, "dc_debug_set: force_cfg must be 0..6");
-    ctx->force_cfg = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "plan_mode") == 0) {
-    if (value < -1 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: plan_mode must be -1, 0 or 1");
-    ctx->plan_mode = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "stagger") == 0) {
-    if (value < 0 || value > 4096) return ctx->fail(DC_E_INVALID, "dc_debug_set: stagger must be 0..4096 (64-cycle sleeps)");
-    ctx->stagger = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "epi_wide") == 0) {
-    if (value < 0 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: epi_wide must be 0 or 1");
-    ctx->epi_wide = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "walk") == 0) {
-    if (value < 0 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: walk must be 0 or 1");
-    ctx->walk = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "bf3_all") == 0) {
-    if (value < 0 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: bf3_all must be 0 or 1");
-    ctx->bf3_all = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "bf3_presplit") == 0) {
-    if (value < 0 || value > 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: bf3_presplit must be 0 or 1");
-    ctx->bf3_presplit = (int)value;
-    return DC_OK;
-  }
-  if (strcmp(name, "tail_mode") == 0) {
-    if (value < 0 || value > 2) return ctx->fail(DC_E_INVALID, "dc_debug_set: tail_mode must be 0, 1 or 2");
-    ctx->tail_mode = (int)value;
+  // the knobs kept in Settings: accepted values lo..hi, except `hole`
+  struct Knob { const char* name; int Settings::*field; int lo, hi; const char* accepted; int hole = INT_MIN; };
+  static const Knob kKnobs[] = {
+      {"nms_band", &Settings::nms_band, 0, 1, "0 or 1"},
+      {"v2_stages", &Settings::v2_stages, 0, 3, "0, 2 or 3", 1},
+      {"force_cfg", &Settings::force_cfg, 0, 6, "0..6"},
+      {"plan_mode", &Settings::plan_mode, -1, 1, "-1, 0 or 1"},
+      {"stagger", &Settings::stagger, 0, 4096, "0..4096 (64-cycle sleeps)"},
+      {"epi_wide", &Settings::epi_wide, 0, 1, "0 or 1"},
+      {"walk", &Settings::walk, 0, 1, "0 or 1"},
+      {"bf3_all", &Settings::bf3_all, 0, 1, "0 or 1"},
+      {"bf3_presplit", &Settings::bf3_presplit, 0, 1, "0 or 1"},
+      {"tail_mode", &Settings::tail_mode, 0, 2, "0, 1 or 2"},
+  };
+  for (const Knob& k : kKnobs) {
+    if (strcmp(name, k.name) != 0) continue;
+    if (value < k.lo || value > k.hi || value == k.hole)
+      return ctx->fail(DC_E_INVALID, "dc_debug_set: %s must be %s", k.name, k.accepted);
+    ctx->cfg.*k.field = (int)value;
     return DC_OK;
   }
   return ctx->fail(DC_E_INVALID, "dc_debug_set: unknown name '%s'", name);
@@ -1609,26 +1604,18 @@ int dc_synchronize(dc_ctx* ctx) {
 }
 
 
-// stream-K fault word after a synchronised per-op call
-static int check_sk_fault(dc_ctx* ctx, const char* who) {
+// the fault word after a synchronised per-op call
+static int check_fault_word(dc_ctx* ctx, const char* who) {
   if (ctx->fault_dev == nullptr) return DC_OK;
   uint32_t f = 0;
   if (hipMemcpy(&f, ctx->fault_dev, 4, hipMemcpyDeviceToHost) != hipSuccess) return ctx->fail(DC_E_HIP, "%s: fault word read failed", who);
-  if (f == 0) return DC_OK;
-  (void)hipMemset(ctx->fault_dev, 0, 64);
-  if (f == 2u) {
-    nms_set_scan_band(0);
-    return ctx->fail(DC_E_HIP, "%s: a hand-off between the waves of nms_scan_band_kernel did not arrive within the spin bound; the band "
-                               "scan is now off -- repeat the call", who);
-  }
-  ctx->tail_mode = 1;
-  return ctx->fail(DC_E_HIP, "%s: stream-K partner never published its partial tile within the spin bound", who);
+  return f == 0 ? DC_OK : fail_on_fault(ctx, f, who);
 }
 
 // split-bf16 mode on a per-op call: the caller's weight matrix gets temporary planes (the model's own are made once)
 static int op_planes(dc_ctx* ctx, hipStream_t s, const float* W, int N, int K, uint16_t** out) {
   *out = nullptr;
-  if (ctx->math_mode != DC_MATH_SPLIT_BF16 || !ctx->bf3_presplit || K % 32) return DC_OK;
+  if (ctx->cfg.math_mode != DC_MATH_SPLIT_BF16 || !ctx->cfg.bf3_presplit || K % 32) return DC_OK;
   HIPCHK(hipMalloc(reinterpret_cast<void**>(out), (size_t)3 * N * K * 2));
   if (hipError_t e = launch_split_planes(W, *out, (size_t)N, K, s); e != hipSuccess) {
     (void)hipFree(*out);                     // (round-5 advisor finding: the planes leaked when the launch failed)
@@ -1674,7 +1661,7 @@ int dc_op_conv3x3(dc_ctx* ctx, const float* in, const float* w, const float* b, 
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_conv3x3 sync: %s", hipGetErrorString(e2));
-  return check_sk_fault(ctx, "dc_op_conv3x3");
+  return check_fault_word(ctx, "dc_op_conv3x3");
 }
 int dc_op_conv3x3_relu_pool(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int H, int W,
                             int Cin, int Cout) {
@@ -1692,7 +1679,7 @@ int dc_op_conv3x3_relu_pool(dc_ctx* ctx, const float* in, const float* w, const 
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_conv3x3_relu_pool sync: %s", hipGetErrorString(e2));
-  return check_sk_fault(ctx, "dc_op_conv3x3_relu_pool");
+  return check_fault_word(ctx, "dc_op_conv3x3_relu_pool");
 }
 int dc_op_conv3x3_c3(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int H, int W, int Cout,
                      int relu) {
@@ -1719,7 +1706,7 @@ int dc_op_linear(dc_ctx* ctx, const float* A, const float* W, const float* bias,
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_linear sync: %s", hipGetErrorString(e2));
-  return check_sk_fault(ctx, "dc_op_linear");
+  return check_fault_word(ctx, "dc_op_linear");
 }
 int dc_op_make_anchors(dc_ctx* ctx, float* out, int h, int w, float x0, float y0, float sx, float sy,
                        const float* anchors_dev, int k) {
@@ -1756,12 +1743,13 @@ int dc_op_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_
   NmsWorkspace ws;
   nms_workspace_bind(ws, base, n);
   ensure_fault_word(ctx);
-  hipError_t e = launch_nms(ws, boxes, scores, valid, n, nullptr, thresh, max_boxes, picks, count, s, ctx->fault_dev);
+  hipError_t e = launch_nms(ws, boxes, scores, valid, n, nullptr, thresh, max_boxes, picks, count, ctx->cfg.nms_band, s,
+                            ctx->fault_dev);
   hipError_t e2 = hipStreamSynchronize(s);
   hipFree(base);
   if (e != hipSuccess) return ctx->fail(DC_E_HIP, "nms launch: %s", hipGetErrorString(e));
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms sync: %s", hipGetErrorString(e2));
-  return check_sk_fault(ctx, "dc_op_nms");
+  return check_fault_word(ctx, "dc_op_nms");
 }
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B,
                             int img_h, int img_w, int HH, int WW, float* out, int out_layout) {
@@ -1778,18 +1766,15 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   // private scratch for n rows
   const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1;
   struct Sav { float *enc, *gates, *h, *c, *logits; int32_t* tok; } sv{L.enc, L.gates, L.hstate, L.cstate, L.logits, L.tok};
-  const size_t bytes = al((size_t)n * E * 4) + al((size_t)n * 4 * Hd * 4) + 2 * al((size_t)n * Hd * 4) +
-                       al((size_t)n * std::max(V1, ctx->V1pad / 16) * 4) + al((size_t)n * 4);
-  char* base = nullptr;
-  HIPCHK(hipMalloc((void**)&base, bytes));
-  char* p = base;
-  L.enc = (float*)p; p += al((size_t)n * E * 4);
-  L.gates = (float*)p; p += al((size_t)n * 4 * Hd * 4);
-  L.hstate = (float*)p; p += al((size_t)n * Hd * 4);
-  L.cstate = (float*)p; p += al((size_t)n * Hd * 4);
-  L.logits = (float*)p; p += al((size_t)n * std::max(V1, ctx->V1pad / 16) * 4);
-  L.tok = (int32_t*)p;
-  int rc = ctx->beam_size > 0 ? lm_beamsearch(ctx, L, codes, n, tokens, s) : lm_sample(ctx, L, codes, n, 0, nullptr, tokens);
+  const std::vector<Carve> cv = {
+      {(void**)&L.enc, (size_t)n * E * 4},     {(void**)&L.gates, (size_t)n * 4 * Hd * 4},
+      {(void**)&L.hstate, (size_t)n * Hd * 4}, {(void**)&L.cstate, (size_t)n * Hd * 4},
+      {(void**)&L.logits, (size_t)n * std::max(V1, ctx->V1pad / 16) * 4}, {(void**)&L.tok, (size_t)n * 4},
+  };
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+  carve(cv, base);
+  int rc = ctx->cfg.beam_size > 0 ? lm_beamsearch(ctx, L, codes, n, tokens, s) : lm_sample(ctx, L, codes, n, 0, nullptr, tokens);
   hipError_t e2 = hipStreamSynchronize(s);
   L.enc = sv.enc; L.gates = sv.gates; L.hstate = sv.h; L.cstate = sv.c; L.logits = sv.logits; L.tok = sv.tok;
   hipFree(base);

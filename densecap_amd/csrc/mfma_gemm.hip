@@ -1240,7 +1240,7 @@ __device__ __forceinline__ void ks_segment(const GemmDesc& d, const int m0, cons
         while (__hip_atomic_load(d.sk_flags + sk_wg + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
           __builtin_amdgcn_s_sleep(4);
           if (++spins > SK_SPIN_LIMIT) {          // the partner never published: report it (sticky word the host checks), do not hang
-            if (d.sk_fault != nullptr) __hip_atomic_store(d.sk_fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (d.sk_fault != nullptr) __hip_atomic_store(d.sk_fault, kFaultStreamK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
           }
         }

@@ -594,6 +594,7 @@ def test_graph_replay_is_bit_identical_and_follows_the_inputs(weights):
     changed setting or shape must not reuse a stale graph, and every entry point (single image, batch over lanes, groups,
     caption order, extractFeatures) must survive replay."""
     from densecap_amd import DenseCapModel
+    from densecap_amd._lib import check
     from densecap_amd.weights import make_synthetic_image
     m = DenseCapModel(weights, device=0)
     try:
@@ -613,6 +614,17 @@ def test_graph_replay_is_bit_identical_and_follows_the_inputs(weights):
             for x, y in zip(a, b):
                 np.testing.assert_array_equal(x, y)
         assert len(eager[0][0]) > 0 and not np.array_equal(eager[0][0], eager[1][0])
+        # the NMS band switch (a debug knob, also the band-fault fallback) is part of the key too: eager once, captured again,
+        # and the chunk scan's picks are the band scan's
+        check(m.ctx.h, m.ctx.lib.dc_debug_set(m.ctx.h, b"nms_band", 0), "dc_debug_set")
+        band_off = [m.forward_raw(imgs[0]) for _ in range(3)]
+        check(m.ctx.h, m.ctx.lib.dc_debug_set(m.ctx.h, b"nms_band", 1), "dc_debug_set")
+        cb, lb = counters()
+        assert cb - c1 == 1 and lb - l1 == 2, (c1, l1, cb, lb)
+        for r in band_off:
+            for x, y in zip(r, eager[0]):
+                np.testing.assert_array_equal(x, y)
+        c1, l1 = cb, lb
         # a changed setting is a new key: eager once, captured again -- never the old graph
         m.setTestArgs(rpn_nms_thresh=0.5, final_nms_thresh=0.3, num_proposals=100)
         r2 = [m.forward_raw(imgs[0]) for _ in range(3)]
@@ -792,6 +804,15 @@ def test_abi_edge_cases_report_errors_and_truncate(model, weights):
     assert lib.dc_set_lanes(h, 0) == -1 and lib.dc_set_lanes(h, 5) == -1
     assert lib.dc_set_beam_size(h, -1) == -5 and lib.dc_set_group(h, 9) == -1                # DC_E_UNSUPPORTED / DC_E_INVALID
     assert lib.dc_debug_fetch(h, b"no_such_tensor", b.ctypes.data, b.nbytes) < 0
+    # every dc_debug_set knob refuses values just outside what it accepts, with a message naming it; unknown names too
+    refused = {"beam_chunk_floats": [0], "nms_band": [-1, 2], "v2_stages": [-1, 1, 4], "force_cfg": [-1, 7],
+               "plan_mode": [-2, 2], "stagger": [-1, 4097], "epi_wide": [-1, 2], "walk": [-1, 2], "bf3_all": [-1, 2],
+               "bf3_presplit": [-1, 2], "tail_mode": [-1, 3]}
+    for name, values in refused.items():
+        for v in values:
+            assert lib.dc_debug_set(h, name.encode(), v) == -1, (name, v)
+            assert name.encode() in lib.dc_last_error(h), (name, v)
+    assert lib.dc_debug_set(h, b"no_such_knob", 0) == -1
     # an image whose conv1 activation would pass the kernels' 32-bit operand offsets (~16 Mpx) is refused up front
     assert lib.dc_forward_test(h, img.ctypes.data, 4200, 4200, 0, C.byref(r2)) == -5
     assert b"16 Mpx" in lib.dc_last_error(h)
