@@ -107,6 +107,9 @@ _SIGS = {
     "dc_op_bilinear_roi_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "dc_op_lm_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dc_op_lm_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dc_score_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.POINTER(DcResult), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

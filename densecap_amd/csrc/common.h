@@ -78,6 +78,11 @@ struct GemmDesc {
   const float* rowterm = nullptr;
   const int32_t* rowidx = nullptr;   // values are 1-based token ids -> row = id-1
   int rowterm_ld = 0;
+  // rowidx together with amax_val (and no rowterm): fused row LOG-SUM-EXP instead of the arg-max (teacher-forced scoring,
+  // densecap.hip::lm_score).  rowidx[m] = the row's 1-based target token (column rowidx[m] - 1 < amax_n); every (row, 32-column
+  // half) writes its partial (max v, sum exp(v - max)) over the real columns to amax_val[m * amax_ld + 2 * slot + {0, 1}] (slot as
+  // for the arg-max), the lane holding the target column writes the biased target logit to amax_val[m * amax_ld + amax_ld - 1];
+  // amax_ld >= 4 * ceil(amax columns / 64) + 1, amax_idx unused.  Same routes, tiles and amax_cols handling as the arg-max.
   // optional fused row arg-max (vocab projection): instead of storing C, every (row, 32-column half of a 64-column tile)
   // writes its best (value, column) to amax_val/amax_idx[m * amax_ld + 2 * tile_n + half] (columns ascend with the slot);
   // amax_ld >= 2 * ceil(N / 64); C may be null.
@@ -187,6 +192,15 @@ hipError_t launch_iota_count(int32_t* idx, int32_t* count_out, const int32_t* co
 hipError_t launch_lstm_step_tail(const float* pval, const int32_t* pidx, int ntiles, int ld, int fixed_tok,
                                  const float* xg, const float* gates_pre, float* c, float* h, int n,
                                  const int32_t* n_dev, int Hd, int zero_c, int32_t* seq, int T, int t, hipStream_t s);
+// Teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup per row m < n: lse = log-sum-exp of the row's
+// `nslots` partials (part[m*ld + 2s], part[m*ld + 2s + 1]: max, sum), combined in double in a fixed order; the target logit
+// part[m*ld + ld - 1]; acc[m] += (double)tlogit - lse.  Then, if the row's target tgt[m] is not `end_tok` and gates_pre != null,
+// the LSTM point-wise update of lstm_step_tail with the target fed: gates = xg[tgt - 1] + gates_pre[m], c, h in place.
+// dst_a / dst_b = `copies` back-to-back repeats of src_a / src_b (len floats each, len % 4 == 0)
+hipError_t launch_repeat_rows2(const float* src_a, const float* src_b, size_t len, int copies, float* dst_a, float* dst_b,
+                               hipStream_t s);
+hipError_t launch_lse_step_tail(const float* part, int nslots, int ld, const int32_t* tgt, int end_tok, const float* xg,
+                                const float* gates_pre, float* c, float* h, double* acc, int n, int Hd, hipStream_t s);
 // split-bf16 mode: W (N, K) fp32 -> 3 x N x K bf16 planes, k permuted per 32-tile as the kernels read them (elementwise.hip)
 hipError_t launch_split_planes(const float* W, uint16_t* planes, size_t N, int K, hipStream_t s);
 // objectness + box regression heads + final ApplyBoxTransform (DenseCapModel.lua:134,139-140)

@@ -69,11 +69,11 @@ static_assert(sizeof(Settings) == 18 * 4, "Settings has 4-byte fields only (Grap
 struct GraphKey {
   uint64_t carve_epoch = 0, weights_epoch = 0;
   const void *fault_dev = nullptr, *arena = nullptr, *host_stage = nullptr, *splitk_ws = nullptr;
-  int H = 0, W = 0, P = 0, g = 0, features_only = 0;
+  int H = 0, W = 0, P = 0, g = 0, features_only = 0, no_decode = 0;
   Settings set;
   bool operator==(const GraphKey& o) const { return memcmp(this, &o, offsetof(GraphKey, set) + sizeof(Settings)) == 0; }
 };
-static_assert(offsetof(GraphKey, set) == 6 * 8 + 5 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
+static_assert(offsetof(GraphKey, set) == 6 * 8 + 6 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
 
 struct Lane {
   hipStream_t stream = nullptr;
@@ -141,6 +141,7 @@ struct dc_ctx {
   int arena_allocs = 0;      // lane workspace (re)allocations so far (dc_debug_fetch "arena_allocs")
   double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last dc_forward_batch
   int64_t beam_chunk_floats = (int64_t)1 << 28;   // cap of the beam search's full-logits buffer (dc_debug_set)
+  int64_t score_rows_cap = 0;      // rows (region x query) one chunk of dc_score_captions / dc_op_lm_score may hold (dc_debug_set); 0 = ~512 MiB of scratch
   uint32_t* fault_dev = nullptr;   // sticky device word: kFaultStreamK / kFaultNmsBand (common.h), checked with the results
   bool graphs = false;      // dc_set_graph_replay: repeated forwards of one shape are relaunched as a captured hipGraph
   uint64_t weights_epoch = 0;
@@ -667,6 +668,134 @@ int lm_beamsearch(dc_ctx* ctx, Lane& L, const float* codes, int n, int32_t* seq_
   return DC_OK;
 }
 
+constexpr int kScorePlanRows = 4096;    // lm_score: rows its per-region GEMMs are planned on, at most (see there)
+
+// Teacher-forced scoring: LanguageModel:updateOutput with a gt_sequence (LanguageModel.lua:106-127) and the targets of
+// getTarget (:148-167) -- for region code r and query w_1..w_L the inputs [image vector, START, w_1 .. w_L], targets
+// [null, w_1 .. w_L, END], loglik = sum over positions 2..L+2 of LogSoftMax(h_p.Wout^T + b)[y_p] (L+1 terms, END included).
+// Schedule:
+//   per region (n rows, as lm_sample_parts): enc, image step, h_0.Wh, START step
+//   per chunk of whole queries (rows = q * n + r, queries sorted by length, longest first): copy the START state to every row,
+//   then for projection j = 1 .. Lmax+1: [log-sum-exp partials of h.Wout^T + b | G = h.Wh] ONE GEMM over the rows still alive
+//   (a prefix: their queries have >= j - 1 words; the last projection has no Wh half) + lse_step_tail (log p of the target
+//   added to the row's double sum; rows whose target is a word take the LSTM step with that word fed).
+// Every GEMM is planned on min(n, kScorePlanRows) rows (plan_M) without split-K workspace, every element's arithmetic is a
+// function of its row alone, and the per-row sums run in step order: a row's loglik does not depend on Q, the query order,
+// the chunking or the other regions scored.
+// Always fp32 MFMA (the epilogue has no split-bf16 variant) and eager.  `qry` (Q, Tq) host, validated; out[r * ldo + q].
+int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* qry, int Q, int Tq, float* out, int ldo) {
+  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, D = ctx->D, V1pad = ctx->V1pad;
+  const int nslots = V1pad / 32, ld = 2 * nslots + 1;
+  std::vector<int> len(Q), order(Q);
+  for (int q = 0; q < Q; ++q) {
+    int L = 0;
+    while (L < Tq && qry[(size_t)q * Tq + L] != 0) ++L;
+    len[q] = L;
+    order[q] = q;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+  const int steps_max = len[order[0]] + 1;
+  struct MathGuard {      // scoring is fp32 whatever dc_set_math_mode says
+    Settings& c; int saved;
+    ~MathGuard() { c.math_mode = saved; }
+  } mg{ctx->cfg, ctx->cfg.math_mode};
+  ctx->cfg.math_mode = 0;
+  // chunk of whole queries under the row cap
+  const size_t row_bytes = (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps_max * 4;
+  const int64_t cap = ctx->score_rows_cap > 0 ? ctx->score_rows_cap : (int64_t)(((size_t)512 << 20) / row_bytes);
+  const int qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(Q, cap / n));
+  // The per-region GEMMs are planned on min(n, kScorePlanRows) rows: every plan then stays on the sequential-K v2 kernels (the
+  // image encoder, K = 4096, would take the K-split kernel -- another summation order -- from about 6,300 planned rows on), and
+  // a v2 element's K order does not depend on its tile, so a region's numbers do not depend on the other regions scored.
+  const int plan = std::min(n, kScorePlanRows);
+  const size_t rmax = (size_t)qchunk * n;
+  float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr, *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;
+  double* acc = nullptr;
+  int32_t* tgt = nullptr;
+  const std::vector<Carve> cv = {
+      {(void**)&enc, (size_t)n * E * 4},    {(void**)&g0, (size_t)n * 4 * Hd * 4}, {(void**)&h0, (size_t)n * Hd * 4},
+      {(void**)&c0, (size_t)n * Hd * 4},    {(void**)&h, rmax * Hd * 4},            {(void**)&c, rmax * Hd * 4},
+      {(void**)&gates, rmax * 4 * Hd * 4},  {(void**)&part, rmax * ld * 4},         {(void**)&acc, rmax * 8},
+      {(void**)&tgt, rmax * steps_max * 4},
+  };
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+  carve(cv, base);
+  auto body = [&]() -> int {
+    // ---- per region: image step and START step (lm_sample_parts' first four launches) ----
+    DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, enc, n, E, D, 1, Ws(), plan));
+    DCCHK(linear(ctx, s, enc, ctx->wxT, ctx->lstm_b, g0, n, 4 * Hd, E, 0, Ws(), plan));
+    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, g0, c0, h0, n, nullptr, Hd, 1, nullptr, 1, 0, s));
+    DCCHK(linear(ctx, s, h0, ctx->whT, nullptr, g0, n, 4 * Hd, Hd, 0, Ws(), plan));
+    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, g0, c0, h0, n, nullptr, Hd, 0, nullptr, 1, 0, s));
+    std::vector<int32_t> th;
+    std::vector<double> ah;
+    for (int a = 0; a < Q; a += qchunk) {
+      const int nq = std::min(qchunk, Q - a), steps = len[order[a]] + 1;
+      const size_t rows = (size_t)nq * n;
+      th.assign(rows * steps, 0);
+      for (int j = 1; j <= steps; ++j)
+        for (int i = 0; i < nq; ++i) {
+          const int q = order[a + i];
+          if (len[q] + 1 < j) break;
+          const int32_t tok = j <= len[q] ? qry[(size_t)q * Tq + j - 1] : V1;
+          std::fill(th.begin() + (j - 1) * rows + (size_t)i * n, th.begin() + (j - 1) * rows + (size_t)(i + 1) * n, tok);
+        }
+      HIPCHK(hipMemcpyAsync(tgt, th.data(), th.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemsetAsync(acc, 0, rows * 8, s));
+      KCHK(launch_repeat_rows2(h0, c0, (size_t)n * Hd, nq, h, c, s));      // the START state of every query's row block
+      int alive = nq;
+      for (int j = 1; j <= steps; ++j) {
+        while (alive > 0 && len[order[a + alive - 1]] + 1 < j) --alive;
+        const bool last = j == steps;
+        const int m = alive * n;
+        GemmDesc v;
+        v.A = h; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = m; v.K = Hd; v.plan_M = plan;
+        v.amax_val = part; v.amax_ld = ld; v.rowidx = tgt + (size_t)(j - 1) * rows;
+        if (last) {
+          v.N = V1; v.ldc = V1;
+        } else {
+          v.N = V1pad + 4 * Hd; v.amax_cols = V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
+        }
+        DCCHK(run_gemm(ctx, v, s));
+        KCHK(launch_lse_step_tail(part, nslots, ld, v.rowidx, V1, ctx->xg, last ? nullptr : gates, c, h, acc, m, Hd, s));
+      }
+      ah.resize(rows);
+      HIPCHK(hipMemcpyAsync(ah.data(), acc, rows * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (int i = 0; i < nq; ++i)
+        for (int r = 0; r < n; ++r) out[(size_t)r * ldo + order[a + i]] = (float)ah[(size_t)i * n + r];
+    }
+    return DC_OK;
+  };
+  const int rc = body();
+  const hipError_t e = hipStreamSynchronize(s);
+  hipFree(base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "lm_score: %s", hipGetErrorString(e));
+  return DC_OK;
+}
+
+// the validity rules of docs/SEMANTICS.md for a (Q, Tq) block of queries in host memory
+int check_queries(dc_ctx* ctx, const int32_t* qry, int Q, int Tq, const char* who) {
+  if (Q < 1) return ctx->fail(DC_E_INVALID, "%s: Q must be >= 1 (got %d)", who, Q);
+  if (Tq < 1 || Tq > 64) return ctx->fail(DC_E_INVALID, "%s: Tq must be in 1..64 (got %d)", who, Tq);
+  const int V = ctx->V;
+  for (int q = 0; q < Q; ++q) {
+    bool ended = false;
+    for (int t = 0; t < Tq; ++t) {
+      const int32_t w = qry[(size_t)q * Tq + t];
+      if (w == 0) { ended = true; continue; }
+      if (w < 0 || w > V)
+        return ctx->fail(DC_E_INVALID, "%s: query %d, column %d: token %d is outside 1..%d", who, q, t, (int)w, V);
+      if (ended)
+        return ctx->fail(DC_E_INVALID, "%s: query %d, column %d: a word after a zero (a query is words, then zero padding)", who, q, t);
+    }
+  }
+  return DC_OK;
+}
+
 // Single-image mode (lanes == 1): nothing else is in flight, so the small kernels and partial tile rounds of the 15
 // decode steps leave the chip idle (~25 % of the decode).  The rows are cut into two blocks on two streams; their
 // kernels fill each other's gaps.  Same outputs bit for bit (tests/test_gpu_e2e.py::test_single_lane_mode_parity).
@@ -691,7 +820,9 @@ int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int p
 // decision that changes a sum's order is planned per image (GemmDesc::plan_M), so an image's numbers do not depend on
 // the group it travels in.
 // `events`: record the stage events (an eager enqueue; a captured graph carries none -- dc_stage_times then has nothing)
-int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
+// `no_decode`: boxes and scores only, no language model (dc_score_captions without tokens); the records' token rows are then
+// stale and must not be read
+int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, bool no_decode = false) {
   const Settings& cfg = ctx->cfg;
   hipStream_t s = L.stream;
   const int H = L.H, W = L.W, P = L.P;
@@ -746,14 +877,14 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   // independent consumers of the heads' outputs.  Per-launch HIP-event profiling wants kernels that do not overlap:
   // everything stays on one stream while it is on.
   const bool side_streams = cfg.serial_mode && !ctx->prof && !features_only && !survivors_only && R >= 256 &&
-                            cfg.beam_size == 0;
+                            cfg.beam_size == 0 && !no_decode;
   hipStream_t sn = side_streams ? L.aux2 : s;       // stream of the final NMS
   if (side_streams) {
     HIPCHK(hipEventRecord(L.ev_fork2, s));
     HIPCHK(hipStreamWaitEvent(L.aux2, L.ev_fork2, 0));
   }
   // ---- language model (reference order: all P proposals, DenseCapModel.lua:127-162) -----------------
-  if (!features_only && !survivors_only) {
+  if (!features_only && !survivors_only && !no_decode) {
     if (cfg.beam_size > 0) DCCHK(lm_beamsearch(ctx, L, L.codes, R, L.seq, s));
     else if (side_streams) DCCHK(lm_sample_two_streams(ctx, L, L.codes, R, P, L.seq));
     else DCCHK(lm_sample(ctx, L, L.codes, R, P, nullptr, L.seq));
@@ -780,7 +911,9 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   if (survivors_only) STAGE_EVENT(7);
   L.nms_before_decode = survivors_only;
   const bool packed_decode = survivors_only && cfg.beam_size == 0;
-  if (packed_decode) {
+  if (no_decode) {
+    // no language model in either order
+  } else if (packed_decode) {
     // Identical outputs, less work: LSTM rows are independent, so only the rows the final NMS kept are decoded (~a quarter at
     // 1000 proposals / 0.3).  Round 6: ONCE PER GROUP -- the kept fc7 rows of all g images packed into one row block
     // (survivor_compact_kernel), ONE decode over it with the device-side row count (row tiles past it exit at once), routes
@@ -809,18 +942,18 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events) {
   return DC_OK;
 }
 
-GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only) {
+GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only, bool no_decode) {
   GraphKey k;
   k.carve_epoch = L.carve_epoch; k.weights_epoch = ctx->weights_epoch;
   k.fault_dev = ctx->fault_dev; k.arena = L.arena.p; k.host_stage = L.host_stage; k.splitk_ws = L.splitk_ws;
-  k.H = L.H; k.W = L.W; k.P = L.P; k.g = g; k.features_only = features_only;
+  k.H = L.H; k.W = L.W; k.P = L.P; k.g = g; k.features_only = features_only; k.no_decode = no_decode;
   k.set = ctx->cfg;
   return k;
 }
 
 // `img`: the g images back to back; `sep` (optional) = g separate images instead (a run of equal-sized images of a mixed list)
 int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_device, bool features_only,
-                    const float* const* sep = nullptr) {
+                    const float* const* sep = nullptr, bool no_decode = false) {
   hipStream_t s = L.stream;
   const size_t img_elems = (size_t)3 * L.H * L.W;
   const hipMemcpyKind kind = img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -836,7 +969,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
   // hipGraphLaunch.  Per-launch profiling and beam search (which allocates on first use) stay eager.
   const bool eligible = ctx->graphs && !ctx->prof && ctx->cfg.beam_size == 0;
   if (eligible) {
-    const auto key = graph_key(ctx, L, g, features_only);
+    const auto key = graph_key(ctx, L, g, features_only, no_decode);
     if (L.gexec != nullptr && key == L.gkey) {
       HIPCHK(hipGraphLaunch(L.gexec, s));
       ctx->graph_launches += 1;
@@ -845,7 +978,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
       if (L.gexec != nullptr) { (void)hipGraphExecDestroy(L.gexec); L.gexec = nullptr; }
       hipGraph_t graph = nullptr;
       HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-      const int rc = enqueue_body(ctx, L, g, features_only, false);
+      const int rc = enqueue_body(ctx, L, g, features_only, false, no_decode);
       const hipError_t e = hipStreamEndCapture(s, &graph);
       hipError_t e2 = hipSuccess;
       if (rc == DC_OK && e == hipSuccess && graph != nullptr) e2 = hipGraphInstantiate(&L.gexec, graph, nullptr, nullptr, 0);
@@ -863,7 +996,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
         fprintf(stderr, "libdensecap_hip: %s\n", note);
         ctx->graph_note = note;
         if (rc != DC_OK) return rc;
-        DCCHK(enqueue_body(ctx, L, g, features_only, true));
+        DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
       } else {
         L.gkey = key;
         ctx->graph_captures += 1;
@@ -872,12 +1005,12 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
         L.ran_graph = true;
       }
     } else {
-      DCCHK(enqueue_body(ctx, L, g, features_only, true));
+      DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
       L.last_key = key;
       L.last_key_valid = true;
     }
   } else {
-    DCCHK(enqueue_body(ctx, L, g, features_only, true));
+    DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
     L.last_key_valid = false;
   }
   L.busy = true;
@@ -1258,7 +1391,9 @@ static int group_run(const dc_ctx* ctx, const int* H, const int* W, int i, int n
   return g;
 }
 
-static int forward_common(dc_ctx* ctx, const float* imgs, int n, int H, int W, int on_dev, dc_result* outs) {
+// no_decode: no language model (dc_score_captions without tokens); outs[i].tokens must then be null
+static int forward_common(dc_ctx* ctx, const float* imgs, int n, int H, int W, int on_dev, dc_result* outs,
+                          bool no_decode = false) {
   if (!ctx) return DC_E_INVALID;
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_forward_*: weights not loaded");
   if (!imgs || !outs || n <= 0 || H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "dc_forward_*: bad arguments");
@@ -1285,7 +1420,7 @@ static int forward_common(dc_ctx* ctx, const float* imgs, int n, int H, int W, i
     DCCHK_DRAIN(harvest(ctx, L));
     L.pending = &outs[i];
     const auto t0 = std::chrono::steady_clock::now();
-    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + img_elems * i, g, on_dev, false));
+    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + img_elems * i, g, on_dev, false, nullptr, no_decode));
     enq_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   for (int l = 0; l < nl; ++l) DCCHK_DRAIN(harvest(ctx, *ctx->lanes[l]));
@@ -1550,6 +1685,11 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value) {
     ctx->beam_chunk_floats = value;
     return DC_OK;
   }
+  if (strcmp(name, "score_rows_cap") == 0) {
+    if (value < 0) return ctx->fail(DC_E_INVALID, "dc_debug_set: score_rows_cap must be >= 0 (0 = the default cap)");
+    ctx->score_rows_cap = value;
+    return DC_OK;
+  }
   // the knobs kept in Settings: accepted values lo..hi, except `hole`
   struct Knob { const char* name; int Settings::*field; int lo, hi; const char* accepted; int hole = INT_MIN; };
   static const Knob kKnobs[] = {
@@ -1782,6 +1922,41 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   if (rc != DC_OK) return rc;
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "lm_sample sync: %s", hipGetErrorString(e2));
   return DC_OK;
+}
+
+
+int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* queries, int Q, int Tq, float* loglik) {
+  OP_PROLOGUE();
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_op_lm_score: weights not loaded");
+  if (!codes || !queries || !loglik) return ctx->fail(DC_E_INVALID, "dc_op_lm_score: null pointer");
+  if (n <= 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_score: n must be > 0");
+  if (Q < 1 || Tq < 1 || Tq > 64) return check_queries(ctx, nullptr, Q, Tq, "dc_op_lm_score");
+  std::vector<int32_t> qh((size_t)Q * Tq);
+  HIPCHK(hipMemcpy(qh.data(), queries, qh.size() * 4, hipMemcpyDeviceToHost));
+  DCCHK(check_queries(ctx, qh.data(), Q, Tq, "dc_op_lm_score"));
+  std::vector<float> out((size_t)n * Q);
+  DCCHK(lm_score(ctx, s, codes, n, qh.data(), Q, Tq, out.data(), Q));
+  HIPCHK(hipMemcpy(loglik, out.data(), out.size() * 4, hipMemcpyHostToDevice));
+  OP_EPILOGUE();
+}
+
+int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const int32_t* queries, int Q,
+                      int Tq, dc_result* out, float* loglik) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_score_captions: weights not loaded");
+  if (!img_chw || !queries || !out || !loglik) return ctx->fail(DC_E_INVALID, "dc_score_captions: null pointer");
+  DCCHK(check_queries(ctx, queries, Q, Tq, "dc_score_captions"));
+  // the forward of dc_forward_test (one image: lane 0; without the language model when no tokens are wanted), then the rows
+  // it returned, compacted from the lane's fc7 codes into its survivor block (the lane is idle once the forward is harvested)
+  DCCHK(forward_common(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr));
+  Lane& L = lane0(ctx);
+  const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
+  if (K > out->capacity)
+    return ctx->fail(DC_E_INVALID, "dc_score_captions: the image has %d regions but out->capacity is %d", K, (int)out->capacity);
+  if (K == 0) return DC_OK;
+  hipStream_t s = L.stream;
+  KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, s));
+  return lm_score(ctx, s, L.out_feats, K, queries, Q, Tq, loglik, Q);
 }
 
 }  // extern "C"

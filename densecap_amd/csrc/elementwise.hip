@@ -310,6 +310,100 @@ __global__ __launch_bounds__(256) void lstm_step_tail_kernel(const float* __rest
   }
 }
 
+// ---- teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup (256 threads) per row -------------------
+// The row's log-sum-exp from the GEMM's partials (max, sum exp(v - max)) per 32-column slot: the row max M over the slots,
+// then sum_s sum_s' * exp(max_s - M) in double -- every thread its slots tid, tid + 256, ... in ascending order, then a fixed
+// butterfly over the wave and the four waves in order -- and lse = M + log(sum), as THNN's LogSoftMax forms max + log(sum).
+// log p(target) = tlogit - lse is added to the row's double sum (one term per step, in step order).  The row then takes the
+// LSTM step of lstm_step_tail_kernel with its target word fed (teacher forcing), unless the target is END (its last term).
+__global__ __launch_bounds__(256) void lse_step_tail_kernel(const float* __restrict__ part, int nslots, int ld,
+                                                            const int32_t* __restrict__ tgt, int end_tok,
+                                                            const float* __restrict__ xg,
+                                                            const float* __restrict__ gates_pre, float* __restrict__ c,
+                                                            float* __restrict__ h, double* __restrict__ acc, int Hd) {
+  const int m = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ float smx[4];
+  __shared__ double ssum[4];
+  // the point-wise operands of the first pass are requested first: they travel while the log-sum-exp is being reduced
+  const int tok = tgt[m];
+  const bool feed = tok != end_tok && gates_pre != nullptr;
+  constexpr int UPT = 2;                            // hidden units per thread and pass (Hd = 512: one pass)
+  float gpre[UPT][4], cprev[UPT];
+  const float* g = feed ? gates_pre + (size_t)m * 4 * Hd : nullptr;
+  if (feed) {
+#pragma unroll
+    for (int u = 0; u < UPT; ++u) {
+      const int j = tid + u * 256;
+      if (j < Hd) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
+        cprev[u] = c[(size_t)m * Hd + j];
+      }
+    }
+  }
+  const float* p = part + (size_t)m * ld;
+  float mx = -INFINITY;
+  for (int s = tid; s < nslots; s += 256) { const float v = p[2 * s]; mx = v > mx ? v : mx; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(mx, o, 64); mx = ov > mx ? ov : mx; }
+  if (lane == 0) smx[wid] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
+  double sum = 0.0;
+  for (int s = tid; s < nslots; s += 256) {
+    const float pm = p[2 * s];
+    if (pm != -INFINITY) sum += (double)p[2 * s + 1] * exp((double)pm - (double)mx);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (lane == 0) ssum[wid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    const double lse = (double)mx + log(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
+    acc[m] += (double)p[ld - 1] - lse;
+  }
+  if (!feed) return;
+  const float* x = xg + (size_t)(tok - 1) * 4 * Hd;
+  for (int j0 = 0; j0 < Hd; j0 += 256 * UPT) {
+    if (j0 > 0) {                                   // Hd > 512: further passes load in place
+#pragma unroll
+      for (int u = 0; u < UPT; ++u) {
+        const int j = j0 + tid + u * 256;
+        if (j < Hd) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
+          cprev[u] = c[(size_t)m * Hd + j];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UPT; ++u) {
+      const int j = j0 + tid + u * 256;
+      if (j >= Hd) continue;
+      const float gi = x[j] + gpre[u][0], gf = x[Hd + j] + gpre[u][1], go = x[2 * Hd + j] + gpre[u][2],
+                  gg = x[3 * Hd + j] + gpre[u][3];
+      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
+      const float gt = th_tanhf(gg);
+      const size_t i = (size_t)m * Hd + j;
+      const float cn = fg * cprev[u] + ig * gt;
+      c[i] = cn;
+      h[i] = og * th_tanhf(cn);
+    }
+  }
+}
+
+// dst_a / dst_b = `copies` back-to-back repeats of src_a / src_b (len floats each; len % 4 == 0): the START state of every
+// query's row block in lm_score, one launch instead of two copies per query
+__global__ void repeat_rows2_kernel(const f32x4* __restrict__ src_a, const f32x4* __restrict__ src_b, size_t len4, size_t total4,
+                                    f32x4* __restrict__ dst_a, f32x4* __restrict__ dst_b) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t k = i % len4;
+    dst_a[i] = src_a[k];
+    dst_b[i] = src_b[k];
+  }
+}
+
 // split-K finish: C = act(sum_s ws[s] + bias), fixed order
 // (m_dev: device-side row count -- the slices sit M rows apart, only rows < *m_dev were written and are finished)
 __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int S, const float* __restrict__ bias,
@@ -488,6 +582,22 @@ hipError_t launch_lstm_step_tail(const float* pval, const int32_t* pidx, int nti
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(lstm_step_tail_kernel, dim3(n), dim3(256), 0, s, pval, pidx, ntiles, ld, fixed_tok, xg, gates_pre,
                      c, h, n, n_dev, Hd, zero_c, seq, T, t);
+  return hipGetLastError();
+}
+hipError_t launch_repeat_rows2(const float* src_a, const float* src_b, size_t len, int copies, float* dst_a, float* dst_b,
+                               hipStream_t s) {
+  if (len % 4 || copies < 0) return hipErrorInvalidValue;
+  if (len == 0 || copies == 0) return hipSuccess;
+  const size_t total4 = len / 4 * (size_t)copies;
+  hipLaunchKernelGGL(repeat_rows2_kernel, dim3(grid_for(total4)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(src_a),
+                     reinterpret_cast<const f32x4*>(src_b), len / 4, total4, reinterpret_cast<f32x4*>(dst_a),
+                     reinterpret_cast<f32x4*>(dst_b));
+  return hipGetLastError();
+}
+hipError_t launch_lse_step_tail(const float* part, int nslots, int ld, const int32_t* tgt, int end_tok, const float* xg,
+                                const float* gates_pre, float* c, float* h, double* acc, int n, int Hd, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(lse_step_tail_kernel, dim3(n), dim3(256), 0, s, part, nslots, ld, tgt, end_tok, xg, gates_pre, c, h, acc, Hd);
   return hipGetLastError();
 }
 hipError_t launch_splitk_reduce(const float* ws, int S, const float* bias, float* C, int M, int N, int ldc, int relu,

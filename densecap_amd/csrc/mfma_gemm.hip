@@ -172,10 +172,12 @@ __device__ __forceinline__ float pool_window(const GemmDesc& d, int win, float v
 // One output tile [m0, m0+BM) x [n0, n0+BN) (tile_n = n0 / BN indexes the arg-max partials); Meff = rows of the problem.
 // BF3: 0 = fp32 MFMA; 1 = split-bf16, both operands split in registers; 2 = split-bf16 with the B operand (weights) split ONCE
 // at load: three bf16 planes in HBM (GemmDesc::sk_slots carries the pointer in this mode), fetched by LDS-DMA as they are
-template <int TM, int TN, bool CONV, int NS, bool AMAX, int BF3 = 0>
+// LSE (with AMAX): the fused row log-sum-exp epilogue of teacher-forced scoring instead of the arg-max (see GemmDesc::rowidx).
+template <int TM, int TN, bool CONV, int NS, bool AMAX, int BF3 = 0, int LSE = 0>
 __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const int n0, const int tile_n, const int Meff,
                                         float* const smem) {
   static_assert(!(AMAX && CONV), "arg-max epilogue is for dense GEMMs");
+  static_assert(!LSE || (AMAX && TN == 1 && BF3 == 0), "log-sum-exp epilogue: fp32 64-column tiles of the transposed (AMAX) layout");
   constexpr int BM = 64 * TM, BN = 64 * TN;
   constexpr int PA = BM / 32, PB = BN / 32;
   // floats per ring stage; BF3 == 2: the B tile is three bf16 planes of BN rows x 32 k (64 bytes a row) instead of fp32 rows
@@ -721,6 +723,45 @@ __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const i
       }
       return;
     }
+    if constexpr (LSE) {
+      // ---- fused row log-sum-exp (teacher-forced scoring, densecap.hip::lm_score) ----
+      // Same slots as the arg-max: every (row, 32-column half) writes (max v, sum exp(v - max)) over its real vocabulary
+      // columns (v = logit + bias; padding columns >= amax_n left out) to amax_val[m * amax_ld + 2 * slot + {0, 1}]; the lane
+      // holding the row's target column (rowidx[m] - 1) also writes the biased target logit to amax_val[m * amax_ld + amax_ld - 1].
+      // A slot with no real column writes (-inf, 0).  Per row and slot a pure function of the row's accumulators.
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int m = m0 + wm * 32 * TM + i * 32 + r;
+        const int tcol = m < Meff ? d.rowidx[m] - 1 : -1;
+        float v[16];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const int nb = n0 + wn * 32 + 8 * q4 + 4 * hsel;
+          const f32x4 bv = amax_bias[0][q4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            v[q4 * 4 + c] = nb + c < an ? acc[i][0][q4 * 4 + c] + bv[c] : -INFINITY;
+            mx = v[q4 * 4 + c] > mx ? v[q4 * 4 + c] : mx;
+            if (nb + c == tcol) EPI_STORE(d.amax_val[(size_t)m * d.amax_ld + d.amax_ld - 1], v[q4 * 4 + c]);
+          }
+        }
+        const float omx = __shfl_xor(mx, 32, 64);     // the other lane half holds the interleaved columns of the same row
+        mx = omx > mx ? omx : mx;
+        float sum = 0.f;
+        if (mx != -INFINITY) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sum += v[e] != -INFINITY ? __expf(v[e] - mx) : 0.f;
+        }
+        const float osum = __shfl_xor(sum, 32, 64);
+        if (hsel == 0 && m < Meff) {
+          const size_t slot = (size_t)m * d.amax_ld + 2 * (2 * tile_n + wn);
+          EPI_STORE(d.amax_val[slot], mx);
+          EPI_STORE(d.amax_val[slot + 1], sum + osum);
+        }
+      }
+      return;
+    }
     // One partial per (row, 32-column half of the tile): partial slot 2 * tile_n + wn, columns ascending with the slot.
     // Every wave finishes on its own: a compare chain inside the lane, one exchange between the two lane halves, two stores
     // -- no LDS, no workgroup barrier (the row kernel that reduces the partials reads twice as many of them: 2.6 KB a row).
@@ -926,7 +967,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + o;
 }
 
-template <int TM, int TN, bool CONV, int NS, bool AMAX = false, int BF3 = 0>
+template <int TM, int TN, bool CONV, int NS, bool AMAX = false, int BF3 = 0, int LSE = 0>
 __global__ __launch_bounds__(256) void mfma_gemm_v2_kernel(GemmDesc d, int ntm, int ntn, int m_fastest) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   start_stagger(d);
@@ -945,7 +986,7 @@ __global__ __launch_bounds__(256) void mfma_gemm_v2_kernel(GemmDesc d, int ntm, 
   int tile_m, tile_n;
   if (m_fastest) { tile_m = bid % ntm; tile_n = bid / ntm; }
   else           { tile_n = bid % ntn; tile_m = bid / ntn; }
-  v2_tile<TM, TN, CONV, NS, AMAX, BF3>(d, tile_m * (64 * TM), tile_n * (64 * TN), tile_n, Meff, smem);
+  v2_tile<TM, TN, CONV, NS, AMAX, BF3, LSE>(d, tile_m * (64 * TM), tile_n * (64 * TN), tile_n, Meff, smem);
 }
 
 // 128x64-tile launches with a FINER LAST ROUND (the decode-step GEMM, conv1_2 .. conv3_3).  The 128x64 tiles of one launch
@@ -955,7 +996,7 @@ __global__ __launch_bounds__(256) void mfma_gemm_v2_kernel(GemmDesc d, int ntm, 
 // are 128x64 and each leftover tile is cut into two 64x64 tiles on the SAME launch -- twice the workgroups at half the
 // duration in the ragged round.  An element's K order does not depend on the tile it falls in (same fragment/lane walk
 // for every v2 shape), so results are bit-identical to the plain launch.
-template <bool CONV, int NS, bool AMAX, int BF3 = 0>
+template <bool CONV, int NS, bool AMAX, int BF3 = 0, int LSE = 0>
 __global__ __launch_bounds__(256) void mfma_gemm_v2_mixed_kernel(GemmDesc d, int ntm, int ntn, int m_fastest, int nbig,
                                                                  int nwalk, int slots) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -994,8 +1035,8 @@ __global__ __launch_bounds__(256) void mfma_gemm_v2_mixed_kernel(GemmDesc d, int
       else           { tile_n = bid % ntn; tile_m = bid / ntn; }
       if (tile_m * 128 >= Meff) continue;
       // a row tile with <= 64 live rows (the last 44 of a 300-proposal decode): the 64x64 variant does half the MFMAs
-      if (Meff - tile_m * 128 <= 64) v2_tile<1, 1, CONV, NS, AMAX, BF3>(d, tile_m * 128, tile_n * 64, tile_n, Meff, smem);
-      else v2_tile<2, 1, CONV, NS, AMAX, BF3>(d, tile_m * 128, tile_n * 64, tile_n, Meff, smem);
+      if (Meff - tile_m * 128 <= 64) v2_tile<1, 1, CONV, NS, AMAX, BF3, LSE>(d, tile_m * 128, tile_n * 64, tile_n, Meff, smem);
+      else v2_tile<2, 1, CONV, NS, AMAX, BF3, LSE>(d, tile_m * 128, tile_n * 64, tile_n, Meff, smem);
     }
   } else {
     const int r = b - nwalk, bid = nbig + (r >> 1), half = r & 1;
@@ -1004,7 +1045,7 @@ __global__ __launch_bounds__(256) void mfma_gemm_v2_mixed_kernel(GemmDesc d, int
     else           { tile_n = bid % ntn; tile_m = bid / ntn; }
     const int m0 = tile_m * 128 + half * 64;
     if (m0 >= Meff) return;
-    v2_tile<1, 1, CONV, NS, AMAX, BF3>(d, m0, tile_n * 64, tile_n, Meff, smem);
+    v2_tile<1, 1, CONV, NS, AMAX, BF3, LSE>(d, m0, tile_n * 64, tile_n, Meff, smem);
   }
 }
 
@@ -1482,7 +1523,7 @@ inline int v2_pick_stages(int total, int cus) {
   return 2 * total >= 5 * cus && v2_cost_units(total, 2, cus) < v2_cost_units(total, 3, cus) ? 2 : 3;
 }
 
-template <bool CONV, bool AMAX, int BF3 = 0>
+template <bool CONV, bool AMAX, int BF3 = 0, int LSE = 0>
 hipError_t launch_mixed(const GemmDesc& d, hipStream_t stream, int ntm, int ntn, int m_fastest, size_t lds) {
   // Ring depth: two stages (48 KiB) put three workgroups on a CU instead of two (72 KiB), which hides more of each tile's
   // prologue / epilogue behind its neighbours' K loops -- measured +5% on conv1_2, conv2_1 and the vocabulary projection --
@@ -1499,16 +1540,16 @@ hipError_t launch_mixed(const GemmDesc& d, hipStream_t stream, int ntm, int ntn,
   const int nwalk = d.walk > 0 && nbig > slots ? slots : nbig;     // measurement hook: one workgroup per slot walks its tiles
   if (stages == 2) {
     const size_t lds2 = BF3 == 2 ? lds : lds / 3 * 2;
-    const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_mixed_kernel<CONV, 2, AMAX, BF3>);
+    const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_mixed_kernel<CONV, 2, AMAX, BF3, LSE>);
     if (hipError_t e = ensure_dyn_lds(fn, lds2); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mfma_gemm_v2_mixed_kernel<CONV, 2, AMAX, BF3>), dim3(nwalk + 2 * tail), dim3(256), lds2, stream, d, ntm, ntn,
+    hipLaunchKernelGGL((mfma_gemm_v2_mixed_kernel<CONV, 2, AMAX, BF3, LSE>), dim3(nwalk + 2 * tail), dim3(256), lds2, stream, d, ntm, ntn,
                        m_fastest, nbig, nwalk, slots);
     return hipGetLastError();
   }
   if constexpr (BF3 != 2) {
-    const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_mixed_kernel<CONV, 3, AMAX, BF3>);
+    const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_mixed_kernel<CONV, 3, AMAX, BF3, LSE>);
     if (hipError_t e = ensure_dyn_lds(fn, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mfma_gemm_v2_mixed_kernel<CONV, 3, AMAX, BF3>), dim3(nwalk + 2 * tail), dim3(256), lds, stream, d, ntm, ntn,
+    hipLaunchKernelGGL((mfma_gemm_v2_mixed_kernel<CONV, 3, AMAX, BF3, LSE>), dim3(nwalk + 2 * tail), dim3(256), lds, stream, d, ntm, ntn,
                        m_fastest, nbig, nwalk, slots);
     return hipGetLastError();
   }
@@ -1565,6 +1606,26 @@ hipError_t launch_cfg(const GemmDesc& d, hipStream_t stream) {
   // operands are addressed through 32-bit buffer offsets
   const bool fits = CONV ? ((size_t)(d.a_rows > d.M ? d.a_rows : d.M) * d.Cin * 4 < CV_PAD && d.Cin <= 2048) : ((size_t)BM * d.K * 4 < 0xfffffff0ull);
   if (!fits || (size_t)BN * d.K * 4 >= 0xfffffff0ull) return hipErrorInvalidValue;
+  if (d.amax_val != nullptr && d.rowidx != nullptr) {
+    // log-sum-exp epilogue (GemmDesc::rowidx): fp32, plain launches of the 64-column tiles, as the arg-max
+    if constexpr (!CONV && TN == 1) {
+      if (d.bf3 || d.splitk > 1 || d.m_begin != 0 || d.a_rows != 0 || d.rowterm != nullptr ||
+          d.amax_ld < 4 * (d.amax_cols > 0 ? d.amax_cols / BN : ntn) + 1 ||
+          d.amax_cols % BN != 0 || (d.amax_cols > 0 && (d.C == nullptr || d.amax_n > d.amax_cols || d.amax_cols > d.N)))
+        return hipErrorInvalidValue;
+      const size_t lds3 = (size_t)3 * (BM + BN) * BK * sizeof(float);
+      if constexpr (TM == 2) {
+        return launch_mixed<false, true, 0, 1>(d, stream, ntm, ntn, m_fastest, lds3);
+      } else {
+        const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_kernel<TM, TN, false, 3, true, 0, 1>);
+        if (hipError_t e = ensure_dyn_lds(fn, lds3); e != hipSuccess) return e;
+        hipLaunchKernelGGL((mfma_gemm_v2_kernel<TM, TN, false, 3, true, 0, 1>), dim3(ntm * ntn), dim3(256), lds3, stream, d, ntm,
+                           ntn, m_fastest);
+        return hipGetLastError();
+      }
+    }
+    return hipErrorInvalidValue;
+  }
   if (d.bf3) {
     // ---- split-bf16 arithmetic (opt-in): the 2x2-wave kernels only, plain launches only (no K sharing between workgroups)
     if (d.splitk > 1 || d.m_begin != 0 || d.a_rows != 0) return hipErrorInvalidValue;

@@ -47,6 +47,49 @@ def decode_sequence(seq, idx_to_token, vocab_size):
     return caps
 
 
+# preprocess.py::words_preprocess: these replacements, lower case, punctuation removed, split on whitespace
+_WORD_REPLACEMENTS = ((u"\u00bd", u"half"), (u"\u2014", u"-"), (u"\u2122", u""), (u"\u00a2", u"cent"), (u"\u00e7", u"c"),
+                      (u"\u00fb", u"u"), (u"\u00e9", u"e"), (u"\u00b0", u" degree"), (u"\u00e8", u"e"), (u"\u2026", u""))
+
+
+def words_preprocess(phrase):
+    """preprocess.py::words_preprocess: replace a few characters, lower case, drop ASCII punctuation, split on whitespace."""
+    import string
+    for k, v in _WORD_REPLACEMENTS:
+        phrase = phrase.replace(k, v)
+    return phrase.lower().translate({ord(c): None for c in string.punctuation}).split()
+
+
+def encode_captions(texts, idx_to_token, max_len):
+    """Query phrases -> (Q, max_len) int32 of 1-based word ids, zero-padded (preprocess.py::encode_caption).  A word the
+    vocabulary lacks maps to <UNK> if the vocabulary has it, else ValueError; so does a phrase of more than max_len words.
+    texts: strings, or sequences of ids (taken as they are, zero-padded)."""
+    if isinstance(texts, str):
+        texts = [texts]
+    token_to_idx = {}
+    for k, v in (idx_to_token or {}).items():
+        token_to_idx[str(v)] = int(k)
+    out = np.zeros((len(texts), max_len), np.int32)
+    for i, t in enumerate(texts):
+        if isinstance(t, str):
+            ids = []
+            for w in words_preprocess(t):
+                if w in token_to_idx:
+                    ids.append(token_to_idx[w])
+                elif "<UNK>" in token_to_idx:
+                    ids.append(token_to_idx["<UNK>"])
+                else:
+                    raise ValueError("query %d: word %r is not in the vocabulary (and it has no <UNK>)" % (i, w))
+        else:
+            ids = [int(v) for v in np.asarray(t).reshape(-1)]
+            while ids and ids[-1] == 0:
+                ids.pop()
+        if len(ids) > max_len:
+            raise ValueError("query %d has %d words; at most %d" % (i, len(ids), max_len))
+        out[i, :len(ids)] = ids
+    return out
+
+
 def getopt(opt, key, default_value=None):
     """utils.getopt (densecap/utils.lua:67-75): opt[key], or the default when the key is absent / nil (None here);
     a missing key without a default is an error, as in the reference."""
@@ -426,6 +469,34 @@ class DenseCapModel:
                                                               feats.ctypes.data, K.ctypes.data_as(_lib.c_int32_p)),
               "dc_extract_features_images")
         return [(boxes[i, :K[i]].copy(), feats[i, :K[i]].copy()) for i in range(n)]
+
+    def scoreCaptions(self, img, captions, return_captions=False, max_len=None):
+        """Score query phrases against the image's regions (dc_score_captions): the regions forward_test returns, each with
+        log p(query | region) under the language model, teacher-forced (LanguageModel.lua:106-127, targets :148-167).
+        captions: strings (encoded by encode_captions) or id rows.  Returns (boxes (K,4) xcycwh, scores (K,), loglik (K,Q)),
+        plus the regions' own captions when return_captions."""
+        self._push_test_args()
+        if isinstance(captions, np.ndarray) and captions.ndim == 2:
+            q = np.ascontiguousarray(captions, dtype=np.int32)
+        else:
+            caps = [captions] if isinstance(captions, str) else list(captions)
+            width = max_len or max([1] + [len(words_preprocess(c)) if isinstance(c, str) else np.asarray(c).size for c in caps])
+            q = encode_captions(caps, self.idx_to_token, max(1, width))
+        img = self._check_input(img)
+        P = self._capacity(img.shape[1], img.shape[2])
+        r, boxes, scores, tokens = self._new_result(P)
+        if not return_captions:
+            r.tokens = None
+        Q, Tq = q.shape
+        loglik = np.zeros((P, max(Q, 1)), np.float32)
+        check(self.ctx.h, self.lib.dc_score_captions(self.ctx.h, img.ctypes.data, img.shape[1], img.shape[2], 0,
+                                                     q.ctypes.data, Q, Tq, C.byref(r), loglik.ctypes.data),
+              "dc_score_captions")
+        K = r.K
+        res = (boxes[:K].copy(), scores[:K].copy(), loglik[:K, :Q].copy())
+        if return_captions:
+            res = res + (self.decodeSequence(tokens[:K]),)
+        return res
 
     def decodeSequence(self, seq):
         """LanguageModel:decodeSequence (LanguageModel.lua:86-103)."""

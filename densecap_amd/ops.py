@@ -270,3 +270,19 @@ def bilinear_roi_pool(ctx, feat_chw, boxes, img_h, img_w, HH=7, WW=7, out_layout
     check(ctx.h, ctx.lib.dc_op_bilinear_roi_pool(ctx.h, fd.ptr, h, w, C_, bd.ptr, B, img_h, img_w, HH, WW, o.ptr,
                                                  out_layout), "dc_op_bilinear_roi_pool")
     return o.numpy()
+
+
+# ---- language model -------------------------------------------------------------------------------
+def lm_score(ctx, codes, queries):
+    """Teacher-forced log p(query | code) with the ctx's loaded language model (dc_op_lm_score): codes (n, fc_dim),
+    queries (Q, Tq) int 1-based word ids, zero-padded -> loglik (n, Q) float32."""
+    x = _f32(codes)
+    q = np.ascontiguousarray(queries, dtype=np.int32)
+    if q.ndim != 2:
+        raise ValueError("queries must be (Q, Tq)")
+    n = x.shape[0]
+    Q, Tq = q.shape
+    xd = ctx.to_device(x); qd = ctx.to_device(q)
+    o = ctx.empty((n, max(Q, 1)))
+    check(ctx.h, ctx.lib.dc_op_lm_score(ctx.h, xd.ptr, n, qd.ptr, Q, Tq, o.ptr), "dc_op_lm_score")
+    return o.numpy()

@@ -124,6 +124,18 @@ int dc_set_localization_test_args(dc_ctx* ctx, int clip_boxes, float nms_thresh,
  * (3,H,W) BGR, mean-subtracted (run_model.lua:67-74).  img_on_device != 0 means
  * `img_chw` is a device pointer (inputs resident in HBM).  Synchronous. */
 int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out);
+/* Score query phrases against the image's regions: log p(query | region) by the language model, teacher-forced
+ * (LanguageModel:updateOutput with a gt_sequence, LanguageModel.lua:106-127; targets of getTarget, :148-167; the
+ * captioning loss reads the same scores, DenseCapModel.lua:120,440-445).  For region code c and query w_1..w_L the LSTM
+ * reads [image vector, START, w_1 .. w_L] and loglik = sum of log LogSoftMax(scores)[y] over the targets
+ * [w_1 .. w_L, END] (L+1 terms, natural log).  The regions are the K rows dc_forward_test returns for the same image and
+ * settings, in the same order; `out` is filled as dc_forward_test fills it.  out->tokens == NULL: the forward runs without
+ * the caption decode (boxes, scores and loglik are the same bits either way).
+ * queries: host (Q, Tq) int32, each row 1-based ids in [1, V] followed by zeros (an all-zero row is the empty query),
+ * 1 <= Tq <= 64, Q >= 1.  loglik: host (out->capacity, Q), entry k*Q + q.  fp32 MFMA whatever dc_set_math_mode says,
+ * never graph-replayed; results do not depend on Q, the query order or the chunking.  K > out->capacity is refused. */
+int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
+                      const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
 /* run_model.lua:160-180 host loop over images, n images of identical size laid out
  * back to back; images are software-pipelined over the ctx's lanes (streams). */
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device,
@@ -314,6 +326,9 @@ int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, in
 /* LanguageModel:sample, greedy (LanguageModel.lua:293-348) with the ctx's loaded language
  * model: codes (n,fc_dim) -> tokens (n,T) int32 1-based.  With dc_set_beam_size > 0: LanguageModel:beamsearch. */
 int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens);
+/* The scoring of dc_score_captions on given fc7 codes (n, fc_dim): loglik (n, Q), entry r*Q + q.  Device pointers
+ * throughout (codes, queries, loglik); synchronous.  Same rules for the queries. */
+int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* queries, int Q, int Tq, float* loglik);
 
 #ifdef __cplusplus
 }

@@ -259,6 +259,32 @@ function Model:forward_test(input)
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq)
 end
 
+-- Rank the regions of one image by log p(query | region) (teacher-forced LanguageModel:updateOutput with a gt_sequence,
+-- LanguageModel.lua:106-127, targets of getTarget :148-167).  queries: IntTensor (Q, Tq) of 1-based word ids, zero-padded.
+-- Returns the boxes, scores and captions forward_test returns, and loglik (K, Q).
+function Model:scoreCaptions(input, queries)
+  self:_push_test_args()
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local q = queries:int():contiguous()
+  local H, W, T = img:size(3), img:size(4), self.seq_length
+  local Q, Tq = q:size(1), q:size(2)
+  local P = self:_capacity(H, W)
+  local boxes, scores = torch.FloatTensor(P, 4), torch.FloatTensor(P, 1)
+  local tokens = torch.IntTensor(P, T)
+  local loglik = torch.FloatTensor(P, Q)
+  local r = ffi.new('dc_result')
+  r.capacity = P
+  r.boxes, r.scores = torch.data(boxes), torch.data(scores)
+  r.tokens = torch.data(tokens)
+  hip.check(self.ctx, C.dc_score_captions(self.ctx, fptr(img), H, W, 0, torch.data(q), Q, Tq, r, torch.data(loglik)),
+            'dc_score_captions')
+  local K = r.K
+  if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, torch.FloatTensor() end
+  local seq = tokens[{{1, K}}]:long()
+  return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), loglik[{{1, K}}]:clone()
+end
+
 function Model:extractFeatures(input)
   self:_push_test_args()
   local img = input:float():contiguous()

@@ -42,6 +42,8 @@ int dc_set_graph_replay(dc_ctx* ctx, int on);
 int dc_set_beam_size(dc_ctx* ctx, int beam_size);
 int dc_set_group(dc_ctx* ctx, int images);
 int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out);
+int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
+                      const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device, dc_result* outs);
 int dc_forward_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
                       dc_result* outs);
