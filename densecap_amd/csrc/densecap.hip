@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <memory>
 
 #include "common.h"
@@ -75,6 +76,18 @@ struct GraphKey {
 };
 static_assert(offsetof(GraphKey, set) == 6 * 8 + 6 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
 
+// Where one image's results go: its K rows (at most `capacity`) of boxes, scores and values -- tokens (T per row) or fc7
+// codes (D per row, extractFeatures) -- and its K and T.  Null pointers are skipped.
+struct Dest {
+  float *boxes = nullptr, *scores = nullptr;
+  void* values = nullptr;
+  int32_t *K = nullptr, *T = nullptr;
+  int capacity = 0;
+};
+
+// What a forward computes: boxes, scores and captions; boxes and fc7 codes (extractFeatures); boxes and scores only
+enum Mode { MODE_RESULTS, MODE_FEATURES, MODE_NO_DECODE };
+
 struct Lane {
   hipStream_t stream = nullptr;
   hipEvent_t ev[ST_COUNT + 1] = {};
@@ -102,10 +115,8 @@ struct Lane {
   void* host_stage = nullptr;
   size_t host_stage_bytes = 0;
   bool busy = false;
-  dc_result* pending = nullptr;      // results of the group in flight: pending[0..g)
-  bool pending_feats = false;
-  float* pending_feat_dst = nullptr; float* pending_box_dst = nullptr; int32_t* pending_k_dst = nullptr;
-  int pending_capacity = 0;
+  const Dest* dst = nullptr;         // where the group in flight goes: dst[0..g)
+  bool feats = false;                // ... and its records hold fc7 codes, not tokens
   float stage_ms[ST_COUNT] = {};
   bool have_times = false;
   // beam search scratch (allocated on first use; beam_chunk() proposals x beam rows at a time)
@@ -139,7 +150,7 @@ struct dc_ctx {
   int max_lanes = 3;
   int group = 0;             // images per lane group (dc_set_group): 0 = default (1), 1 .. kGemmMaxGroup
   int arena_allocs = 0;      // lane workspace (re)allocations so far (dc_debug_fetch "arena_allocs")
-  double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last dc_forward_batch
+  double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last forward call (run_images)
   int64_t beam_chunk_floats = (int64_t)1 << 28;   // cap of the beam search's full-logits buffer (dc_debug_set)
   int64_t score_rows_cap = 0;      // rows (region x query) one chunk of dc_score_captions / dc_op_lm_score may hold (dc_debug_set); 0 = ~512 MiB of scratch
   uint32_t* fault_dev = nullptr;   // sticky device word: kFaultStreamK / kFaultNmsBand (common.h), checked with the results
@@ -951,15 +962,16 @@ GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only, 
   return k;
 }
 
-// `img`: the g images back to back; `sep` (optional) = g separate images instead (a run of equal-sized images of a mixed list)
-int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_device, bool features_only,
-                    const float* const* sep = nullptr, bool no_decode = false) {
+// imgs[0..g): the group's images.  `packed`: they are one buffer of the caller, back to back, and arrive in one copy; a list's
+// images are copied one by one (two allocations whose addresses happen to follow each other are still not one buffer).
+int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int img_on_device, bool packed, Mode mode) {
   hipStream_t s = L.stream;
+  const bool features_only = mode == MODE_FEATURES, no_decode = mode == MODE_NO_DECODE;
   const size_t img_elems = (size_t)3 * L.H * L.W;
   const hipMemcpyKind kind = img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (sep == nullptr) HIPCHK(hipMemcpyAsync(L.img, img, g * img_elems * 4, kind, s));
-  else
-    for (int i = 0; i < g; ++i) HIPCHK(hipMemcpyAsync(L.img + (size_t)i * img_elems, sep[i], img_elems * 4, kind, s));
+  const int per_copy = packed ? g : 1;
+  for (int i = 0; i < g; i += per_copy)
+    HIPCHK(hipMemcpyAsync(L.img + (size_t)i * img_elems, imgs[i], per_copy * img_elems * 4, kind, s));
   L.g = g;
   const size_t stride = pack_stride(ctx, L.P, features_only);
   for (int i = 0; i < g; ++i) *reinterpret_cast<uint32_t*>(static_cast<char*>(L.host_stage) + i * stride + kRecFault) = 0;
@@ -1014,7 +1026,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* img, int g, int img_on_de
     L.last_key_valid = false;
   }
   L.busy = true;
-  L.pending_feats = features_only;
+  L.feats = features_only;
   return DC_OK;
 }
 
@@ -1048,31 +1060,23 @@ int harvest(dc_ctx* ctx, Lane& L) {
   }
   L.have_times = !L.ran_graph;                            // a replayed graph carries no stage events
   const int P = L.P;
-  const size_t stride = pack_stride(ctx, P, L.pending_feats);
+  const size_t stride = pack_stride(ctx, P, L.feats);
+  const size_t row_bytes = (size_t)(L.feats ? ctx->D : ctx->T) * 4;      // values of one row: codes or tokens
   for (int i = 0; i < L.g; ++i) {
     const char* hs = static_cast<const char*>(L.host_stage) + i * stride;
     if (const uint32_t fw = *reinterpret_cast<const uint32_t*>(hs + kRecFault); fw != 0u) {
-      L.pending = nullptr;
+      L.dst = nullptr;
       return fail_on_fault(ctx, fw, "forward");
     }
-    int K = *reinterpret_cast<const int32_t*>(hs + kRecK);
-    if (L.pending_feats) {
-      K = std::min(K, L.pending_capacity);
-      if (L.pending_k_dst) L.pending_k_dst[i] = K;
-      if (L.pending_box_dst) memcpy(L.pending_box_dst + (size_t)i * L.pending_capacity * 4, hs + kRecPayload, (size_t)K * 16);
-      if (L.pending_feat_dst)
-        memcpy(L.pending_feat_dst + (size_t)i * L.pending_capacity * ctx->D, hs + rec_values(P), (size_t)K * ctx->D * 4);
-    } else if (L.pending) {
-      dc_result* r = L.pending + i;
-      K = std::min(K, (int)r->capacity);
-      r->K = K;
-      r->T = ctx->T;
-      if (r->boxes) memcpy(r->boxes, hs + kRecPayload, (size_t)K * 16);
-      if (r->scores) memcpy(r->scores, hs + rec_scores(P), (size_t)K * 4);
-      if (r->tokens) memcpy(r->tokens, hs + rec_values(P), (size_t)K * ctx->T * 4);
-    }
+    const Dest& d = L.dst[i];
+    const int K = std::min(*reinterpret_cast<const int32_t*>(hs + kRecK), d.capacity);
+    if (d.K) *d.K = K;
+    if (d.T) *d.T = ctx->T;
+    if (d.boxes) memcpy(d.boxes, hs + kRecPayload, (size_t)K * 16);
+    if (d.scores) memcpy(d.scores, hs + rec_scores(P), (size_t)K * 4);
+    if (d.values) memcpy(d.values, hs + rec_values(P), K * row_bytes);
   }
-  L.pending = nullptr;
+  L.dst = nullptr;
   return DC_OK;
 }
 
@@ -1356,8 +1360,7 @@ static void drain_lanes(dc_ctx* ctx) {
     if (L.aux) (void)hipStreamSynchronize(L.aux);
     if (L.aux2) (void)hipStreamSynchronize(L.aux2);
     L.busy = false;
-    L.pending = nullptr;
-    L.pending_box_dst = nullptr; L.pending_feat_dst = nullptr; L.pending_k_dst = nullptr;
+    L.dst = nullptr;
   }
   (void)hipGetLastError();
 }
@@ -1376,57 +1379,69 @@ static int check_image_size(dc_ctx* ctx, int H, int W, const char* who) {
   return DC_OK;
 }
 
-// images of a group share one 32-bit operand offset space in conv1_x (the pooled conv counts window slots)
-static int clamp_group(const dc_ctx* ctx, int G, int H, int W) {
-  if (ctx->cfg.serial_planning()) return 1;       // single-image planning: images travel alone
-  const size_t rows1 = std::max((size_t)H * W, (size_t)4 * ((H + 1) / 2) * ((W + 1) / 2));
-  while (G > 1 && (size_t)G * rows1 * 64 * 4 >= 0xffffe000ull) --G;
-  return std::max(G, 1);
-}
-// length of the run of equal-sized images starting at i that may travel as one group
+// Length of the run of equal-sized images starting at i that may travel as one group (dc_set_group).  Single-image planning
+// (dc_set_lanes(1)) shares a layer's partial last round along K -- plans made for ONE image's tile count, which a group does
+// not have: images travel alone there, so that results never depend on the group.  A group's conv1_x activation shares one
+// 32-bit operand offset space; the pooled conv counts window slots (4 per 2x2 window: a pixel more per odd side).
 static int group_run(const dc_ctx* ctx, const int* H, const int* W, int i, int n) {
-  const int G = clamp_group(ctx, std::max(1, ctx->group), H[i], W[i]);
+  if (ctx->cfg.serial_planning()) return 1;
+  const size_t rows1 = std::max((size_t)H[i] * W[i], (size_t)4 * ((H[i] + 1) / 2) * ((W[i] + 1) / 2));
   int g = 1;
-  while (g < G && i + g < n && H[i + g] == H[i] && W[i + g] == W[i]) ++g;
+  while (g < ctx->group && i + g < n && H[i + g] == H[i] && W[i + g] == W[i] && (size_t)(g + 1) * rows1 * 64 * 4 < 0xffffe000ull)
+    ++g;
   return g;
 }
 
-// no_decode: no language model (dc_score_captions without tokens); outs[i].tokens must then be null
-static int forward_common(dc_ctx* ctx, const float* imgs, int n, int H, int W, int on_dev, dc_result* outs,
-                          bool no_decode = false) {
-  if (!ctx) return DC_E_INVALID;
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_forward_*: weights not loaded");
-  if (!imgs || !outs || n <= 0 || H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "dc_forward_*: bad arguments");
-  DCCHK(check_image_size(ctx, H, W, "dc_forward_*"));
+// The driver of every forward entry point, after the entry point's own argument checks: image i is imgs[i], (3, H[i], W[i]),
+// and its results go to dst[i].  Runs of consecutive equal-sized images travel as groups (dc_set_group: the dense stages
+// share launches), pipelined over the lanes.  A lane that takes a run of g images keeps its group capacity if it already
+// holds their size, else it is carved for g; results do not depend on the capacity (every route is planned per image).
+// `packed`: the images are one buffer of the caller, back to back (enqueue_forward).
+static int run_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev, bool packed,
+                      Mode mode, const Dest* dst) {
   HIPCHK(hipSetDevice(ctx->device));
-  const int P = effective_proposals(ctx, H, W);
-  for (int i = 0; i < n; ++i)
-    if (outs[i].capacity <= 0) return ctx->fail(DC_E_INVALID, "dc_result.capacity must be > 0");
-  // images travel in groups of G through a lane (dc_set_group): the group's dense stages share launches
-  // Single-image planning (dc_set_lanes(1)) shares a layer's partial last round along K -- plans made for ONE image's tile
-  // count, which a group does not have: images travel alone there, so that results never depend on the group.
-  // A group's conv1_x activation shares one 32-bit offset space; the pooled conv counts window slots (4 per 2x2 window: a
-  // pixel more per odd side) -- the same count the launch itself checks.
-  const int G = clamp_group(ctx, std::max(1, std::min(ctx->group > 0 ? ctx->group : 1, n)), H, W);
-  const int ngroups = (n + G - 1) / G;
-  const int nl = std::min(ngroups, ctx->max_lanes);
+  int runs = 0;
+  for (int i = 0; i < n; i += group_run(ctx, H, W, i, n)) ++runs;
+  const int nl = std::min(runs, ctx->max_lanes);
   while ((int)ctx->lanes.size() < nl) ctx->lanes.emplace_back(new Lane());
-  for (int l = 0; l < nl; ++l) DCCHK(lane_prepare(ctx, *ctx->lanes[l], H, W, P, G));
-  const size_t img_elems = (size_t)3 * H * W;
   double enq_ms = 0;
-  for (int gi = 0; gi < ngroups; ++gi) {
-    const int i = gi * G, g = std::min(G, n - i);
-    Lane& L = *ctx->lanes[gi % nl];
-    DCCHK_DRAIN(harvest(ctx, L));
-    L.pending = &outs[i];
+  for (int i = 0, r = 0; i < n; ++r) {
+    const int g = group_run(ctx, H, W, i, n);
+    Lane& L = *ctx->lanes[r % nl];
+    DCCHK_DRAIN(harvest(ctx, L));                 // the lane's previous images leave before its workspace is re-carved
+    const int G = L.H == H[i] && L.W == W[i] ? std::max(g, L.G) : g;
+    DCCHK_DRAIN(lane_prepare(ctx, L, H[i], W[i], effective_proposals(ctx, H[i], W[i]), G));
+    L.dst = dst + i;
     const auto t0 = std::chrono::steady_clock::now();
-    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + img_elems * i, g, on_dev, false, nullptr, no_decode));
+    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + i, g, on_dev, packed, mode));
     enq_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    i += g;
   }
   for (int l = 0; l < nl; ++l) DCCHK_DRAIN(harvest(ctx, *ctx->lanes[l]));
   ctx->host_enqueue_ms = enq_ms / n;       // host time spent enqueueing, per image (dc_debug_fetch "host_enqueue_us")
   prof_collect(ctx);
   return DC_OK;
+}
+
+static std::vector<Dest> result_dests(dc_result* r, int n) {
+  std::vector<Dest> d(n);
+  for (int i = 0; i < n; ++i) d[i] = Dest{r[i].boxes, r[i].scores, r[i].tokens, &r[i].K, &r[i].T, r[i].capacity};
+  return d;
+}
+
+// dc_forward_test, dc_forward_batch and the forward of dc_score_captions: n images of one size, back to back at `imgs`
+static int forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int on_dev, dc_result* outs, Mode mode) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_forward_*: weights not loaded");
+  if (!imgs || !outs || n <= 0 || H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "dc_forward_*: bad arguments");
+  DCCHK(check_image_size(ctx, H, W, "dc_forward_*"));
+  for (int i = 0; i < n; ++i)
+    if (outs[i].capacity <= 0) return ctx->fail(DC_E_INVALID, "dc_result.capacity must be > 0");
+  std::vector<const float*> ptrs(n);
+  for (int i = 0; i < n; ++i) ptrs[i] = imgs + (size_t)3 * H * W * i;
+  const std::vector<int> Hs(n, H), Ws(n, W);
+  const std::vector<Dest> dst = result_dests(outs, n);
+  return run_images(ctx, ptrs.data(), Hs.data(), Ws.data(), n, on_dev, true, mode, dst.data());
 }
 
 int dc_forward_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev, dc_result* outs) {
@@ -1438,30 +1453,15 @@ int dc_forward_images(dc_ctx* ctx, const float* const* imgs, const int* H, const
       return ctx->fail(DC_E_INVALID, "dc_forward_images: image %d: null pointer, side below 32 px or capacity <= 0", i);
     DCCHK(check_image_size(ctx, H[i], W[i], "dc_forward_images"));
   }
-  HIPCHK(hipSetDevice(ctx->device));
-  const int nl = std::min(n, ctx->max_lanes);
-  while ((int)ctx->lanes.size() < nl) ctx->lanes.emplace_back(new Lane());
-  // runs of consecutive images of ONE size travel as groups (dc_set_group), like the images of dc_forward_batch
-  int gi = 0;
-  for (int i = 0; i < n; ++gi) {
-    const int g = group_run(ctx, H, W, i, n);
-    Lane& L = *ctx->lanes[gi % nl];
-    DCCHK_DRAIN(harvest(ctx, L));                 // the lane's previous images leave before its workspace is re-carved
-    DCCHK_DRAIN(lane_prepare(ctx, L, H[i], W[i], effective_proposals(ctx, H[i], W[i]), std::max(g, L.H == H[i] && L.W == W[i] ? L.G : 1)));
-    L.pending = &outs[i];
-    DCCHK_DRAIN(enqueue_forward(ctx, L, nullptr, g, on_dev, false, imgs + i));
-    i += g;
-  }
-  for (int l = 0; l < nl; ++l) DCCHK_DRAIN(harvest(ctx, *ctx->lanes[l]));
-  prof_collect(ctx);
-  return DC_OK;
+  const std::vector<Dest> dst = result_dests(outs, n);
+  return run_images(ctx, imgs, H, W, n, on_dev, false, MODE_RESULTS, dst.data());
 }
 
 int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out) {
-  return forward_common(ctx, img_chw, 1, H, W, img_on_device, out);
+  return forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, MODE_RESULTS);
 }
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device, dc_result* outs) {
-  return forward_common(ctx, imgs, n, H, W, imgs_on_device, outs);
+  return forward_batch(ctx, imgs, n, H, W, imgs_on_device, outs, MODE_RESULTS);
 }
 
 int dc_extract_features(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, int capacity,
@@ -1470,16 +1470,8 @@ int dc_extract_features(dc_ctx* ctx, const float* img_chw, int H, int W, int img
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_extract_features: weights not loaded");
   if (!img_chw || capacity <= 0 || H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "dc_extract_features: bad arguments");
   DCCHK(check_image_size(ctx, H, W, "dc_extract_features"));
-  HIPCHK(hipSetDevice(ctx->device));
-  Lane& L = lane0(ctx);
-  DCCHK(harvest(ctx, L));
-  DCCHK(lane_prepare(ctx, L, H, W, effective_proposals(ctx, H, W), std::max(L.G, 1)));
-  L.pending = nullptr;
-  L.pending_capacity = capacity; L.pending_box_dst = boxes; L.pending_feat_dst = feats; L.pending_k_dst = K;
-  DCCHK_DRAIN(enqueue_forward(ctx, L, img_chw, 1, img_on_device, true));
-  DCCHK_DRAIN(harvest(ctx, L));
-  prof_collect(ctx);
-  return DC_OK;
+  const Dest dst{boxes, nullptr, feats, K, nullptr, capacity};
+  return run_images(ctx, &img_chw, &H, &W, 1, img_on_device, true, MODE_FEATURES, &dst);
 }
 
 int dc_extract_features_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev,
@@ -1493,27 +1485,10 @@ int dc_extract_features_images(dc_ctx* ctx, const float* const* imgs, const int*
       return ctx->fail(DC_E_INVALID, "dc_extract_features_images: image %d: null pointer or side below 32 px", i);
     DCCHK(check_image_size(ctx, H[i], W[i], "dc_extract_features_images"));
   }
-  HIPCHK(hipSetDevice(ctx->device));
-  const int nl = std::min(n, ctx->max_lanes);
-  while ((int)ctx->lanes.size() < nl) ctx->lanes.emplace_back(new Lane());
-  // runs of equal-sized images travel as groups here too (round-4 verdict: extractFeatures always ran groups of one)
-  int gi = 0;
-  for (int i = 0; i < n; ++gi) {
-    const int g = group_run(ctx, H, W, i, n);
-    Lane& L = *ctx->lanes[gi % nl];
-    DCCHK_DRAIN(harvest(ctx, L));
-    DCCHK_DRAIN(lane_prepare(ctx, L, H[i], W[i], effective_proposals(ctx, H[i], W[i]), std::max(g, L.H == H[i] && L.W == W[i] ? L.G : 1)));
-    L.pending = nullptr;
-    L.pending_capacity = capacity;
-    L.pending_box_dst = boxes + (size_t)i * capacity * 4;           // image j of the group: j * capacity rows further on
-    L.pending_feat_dst = feats + (size_t)i * capacity * ctx->D;
-    L.pending_k_dst = K + i;
-    DCCHK_DRAIN(enqueue_forward(ctx, L, nullptr, g, on_dev, true, imgs + i));
-    i += g;
-  }
-  for (int l = 0; l < nl; ++l) DCCHK_DRAIN(harvest(ctx, *ctx->lanes[l]));
-  prof_collect(ctx);
-  return DC_OK;
+  std::vector<Dest> dst(n);
+  for (int i = 0; i < n; ++i)      // image i: `capacity` rows further on in each array
+    dst[i] = Dest{boxes + (size_t)i * capacity * 4, nullptr, feats + (size_t)i * capacity * ctx->D, K + i, nullptr, capacity};
+  return run_images(ctx, imgs, H, W, n, on_dev, false, MODE_FEATURES, dst.data());
 }
 
 // run_model.lua:67-74 on the device.  Synchronous; runs on the ctx's primary stream.
@@ -1785,41 +1760,41 @@ int dc_op_hwc_to_chw(dc_ctx* ctx, const float* in, float* out, int C, int H, int
 int dc_op_pack_conv3x3_weights(dc_ctx* ctx, const float* w, float* out, int Cout, int Cin) {
   OP_PROLOGUE(); KCHK(launch_pack_conv3x3(w, out, Cout, Cin, s)); OP_EPILOGUE();
 }
-int dc_op_conv3x3(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int n_img, int H, int W,
-                  int Cin, int Cout, int relu) {
-  OP_PROLOGUE();
-  if (Cin % 32 || n_img <= 0 || H <= 0 || W <= 0 || Cout <= 0)
-    return ctx->fail(DC_E_INVALID, "dc_op_conv3x3: need Cin %% 32 == 0 and positive sizes");
+// A per-op contraction with the weight `w` (N x K): `run(ws, planes)` on the split-K scratch and (split-bf16 mode) temporary
+// planes of `w`, then synchronise, free both and read the fault word.  `who` names the entry point in the messages.
+static int op_gemm(dc_ctx* ctx, hipStream_t s, const float* w, int N, int K, const char* who,
+                   const std::function<int(const Ws&, const uint16_t*)>& run) {
   float* ws = nullptr;
   HIPCHK(hipMalloc((void**)&ws, kSplitkWsFloats * 4));
   uint16_t* pl = nullptr;
-  if (int rc0 = op_planes(ctx, s, w, Cout, 9 * Cin, &pl); rc0 != DC_OK) { (void)hipFree(ws); return rc0; }
-  int rc = conv3x3(ctx, s, in, w, b, out, n_img, H, W, Cin, Cout, relu, Ws{ws, kSplitkWsFloats}, pl);
+  if (int rc0 = op_planes(ctx, s, w, N, K, &pl); rc0 != DC_OK) { (void)hipFree(ws); return rc0; }
+  int rc = run(Ws{ws, kSplitkWsFloats}, pl);
   hipError_t e2 = hipStreamSynchronize(s);
   (void)hipFree(ws);
   if (pl) (void)hipFree(pl);
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_conv3x3 sync: %s", hipGetErrorString(e2));
-  return check_fault_word(ctx, "dc_op_conv3x3");
+  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "%s sync: %s", who, hipGetErrorString(e2));
+  return check_fault_word(ctx, who);
+}
+
+int dc_op_conv3x3(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int n_img, int H, int W,
+                  int Cin, int Cout, int relu) {
+  OP_PROLOGUE();
+  if (Cin % 32 || n_img <= 0 || H <= 0 || W <= 0 || Cout <= 0)
+    return ctx->fail(DC_E_INVALID, "dc_op_conv3x3: need Cin %% 32 == 0 and positive sizes");
+  return op_gemm(ctx, s, w, Cout, 9 * Cin, "dc_op_conv3x3", [&](const Ws& ws, const uint16_t* pl) {
+    return conv3x3(ctx, s, in, w, b, out, n_img, H, W, Cin, Cout, relu, ws, pl);
+  });
 }
 int dc_op_conv3x3_relu_pool(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int H, int W,
                             int Cin, int Cout) {
   OP_PROLOGUE();
   if (Cin % 32 || Cout % 4 || H <= 0 || W <= 0 || Cout <= 0)
     return ctx->fail(DC_E_INVALID, "dc_op_conv3x3_relu_pool: need Cin %% 32 == 0, Cout %% 4 == 0 and positive sizes");
-  float* ws = nullptr;
-  HIPCHK(hipMalloc((void**)&ws, kSplitkWsFloats * 4));
-  uint16_t* pl = nullptr;
-  if (int rc0 = op_planes(ctx, s, w, Cout, 9 * Cin, &pl); rc0 != DC_OK) { (void)hipFree(ws); return rc0; }
-  int rc = conv3x3_pool(ctx, s, in, w, b, out, 1, H, W, Cin, Cout, 1, Ws{ws, kSplitkWsFloats}, pl);
-  hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(ws);
-  if (pl) (void)hipFree(pl);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_conv3x3_relu_pool sync: %s", hipGetErrorString(e2));
-  return check_fault_word(ctx, "dc_op_conv3x3_relu_pool");
+  return op_gemm(ctx, s, w, Cout, 9 * Cin, "dc_op_conv3x3_relu_pool", [&](const Ws& ws, const uint16_t* pl) {
+    return conv3x3_pool(ctx, s, in, w, b, out, 1, H, W, Cin, Cout, 1, ws, pl);
+  });
 }
 int dc_op_conv3x3_c3(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int H, int W, int Cout,
                      int relu) {
@@ -1835,18 +1810,9 @@ int dc_op_linear(dc_ctx* ctx, const float* A, const float* W, const float* bias,
                  int relu) {
   OP_PROLOGUE();
   if (K % 32 || M <= 0 || N <= 0) return ctx->fail(DC_E_INVALID, "dc_op_linear: need K %% 32 == 0");
-  float* ws = nullptr;
-  HIPCHK(hipMalloc((void**)&ws, kSplitkWsFloats * 4));
-  uint16_t* pl = nullptr;
-  if (int rc0 = op_planes(ctx, s, W, N, K, &pl); rc0 != DC_OK) { (void)hipFree(ws); return rc0; }
-  int rc = linear(ctx, s, A, W, bias, C, M, N, K, relu, Ws{ws, kSplitkWsFloats}, 0, pl);
-  hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(ws);
-  if (pl) (void)hipFree(pl);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_linear sync: %s", hipGetErrorString(e2));
-  return check_fault_word(ctx, "dc_op_linear");
+  return op_gemm(ctx, s, W, N, K, "dc_op_linear", [&](const Ws& ws, const uint16_t* pl) {
+    return linear(ctx, s, A, W, bias, C, M, N, K, relu, ws, 0, pl);
+  });
 }
 int dc_op_make_anchors(dc_ctx* ctx, float* out, int h, int w, float x0, float y0, float sx, float sy,
                        const float* anchors_dev, int k) {
@@ -1948,7 +1914,7 @@ int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   DCCHK(check_queries(ctx, queries, Q, Tq, "dc_score_captions"));
   // the forward of dc_forward_test (one image: lane 0; without the language model when no tokens are wanted), then the rows
   // it returned, compacted from the lane's fc7 codes into its survivor block (the lane is idle once the forward is harvested)
-  DCCHK(forward_common(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr));
+  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
   Lane& L = lane0(ctx);
   const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
   if (K > out->capacity)

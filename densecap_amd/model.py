@@ -340,16 +340,31 @@ class DenseCapModel:
             H, W = (H + 1) // 2, (W + 1) // 2
         return self.num_anchors * H * W
 
+    def _results(self, caps, copy=True):
+        """A DcResult array for images of these capacities, and a function that slices each image's K rows back after the
+        call: [(boxes, scores, tokens)], copies or (copy=False) views of the arrays the library wrote."""
+        made = [self._new_result(P) for P in caps]
+        res = (DcResult * len(made))(*[m[0] for m in made])
+
+        def rows():
+            return [tuple(x[:r.K].copy() if copy else x[:r.K] for x in m[1:]) for r, m in zip(res, made)]
+        return res, rows
+
+    @staticmethod
+    def _image_list(imgs):
+        """(pointers, H, W) ctypes arrays of a list of (3,H,W) host arrays or ops.DeviceArrays."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data if isinstance(a, np.ndarray) else a.ptr.value for a in imgs])
+        return ptrs, (C.c_int * n)(*[a.shape[1] for a in imgs]), (C.c_int * n)(*[a.shape[2] for a in imgs])
+
     def forward_raw(self, img):
         """forward_test without string decoding: (boxes (K,4) xcycwh, scores (K,), tokens (K,T))."""
         self._push_test_args()
         img = self._check_input(img)
-        P = self._capacity(img.shape[1], img.shape[2])
-        r, boxes, scores, tokens = self._new_result(P)
-        check(self.ctx.h, self.lib.dc_forward_test(self.ctx.h, img.ctypes.data, img.shape[1], img.shape[2], 0,
-                                                   C.byref(r)), "dc_forward_test")
-        K = r.K
-        return boxes[:K].copy(), scores[:K].copy(), tokens[:K].copy()
+        res, rows = self._results([self._capacity(img.shape[1], img.shape[2])])
+        check(self.ctx.h, self.lib.dc_forward_test(self.ctx.h, img.ctypes.data, img.shape[1], img.shape[2], 0, res),
+              "dc_forward_test")
+        return rows()[0]
 
     def forward_test(self, img):
         """Returns final_boxes (K,4), objectness_scores (K,1), captions (list of K strings)."""
@@ -360,84 +375,55 @@ class DenseCapModel:
         """run_model.lua's image loop over n device-resident images of one size; returns a list of
         (boxes, scores, tokens).  imgs_dev_ptr: device pointer to (n,3,H,W) fp32."""
         self._push_test_args()
-        P = self._capacity(H, W)
-        arr = (DcResult * n)()
-        keep = []
-        for i in range(n):
-            r, b, s, t = self._new_result(P)
-            arr[i] = r
-            keep.append((b, s, t))
-        check(self.ctx.h, self.lib.dc_forward_batch(self.ctx.h, imgs_dev_ptr, n, H, W, 1, arr), "dc_forward_batch")
-        return [(b[:arr[i].K], s[:arr[i].K], t[:arr[i].K]) for i, (b, s, t) in enumerate(keep)]
+        res, rows = self._results([self._capacity(H, W)] * n, copy=False)
+        check(self.ctx.h, self.lib.dc_forward_batch(self.ctx.h, imgs_dev_ptr, n, H, W, 1, res), "dc_forward_batch")
+        return rows()
 
     def forward_batch(self, imgs):
         self._push_test_args()
         imgs = np.ascontiguousarray(imgs, dtype=np.float32)
         n, c, H, W = imgs.shape
         assert c == 3
-        P = self._capacity(H, W)
-        arr = (DcResult * n)()
-        keep = []
-        for i in range(n):
-            r, b, s, t = self._new_result(P)
-            arr[i] = r
-            keep.append((b, s, t))
-        check(self.ctx.h, self.lib.dc_forward_batch(self.ctx.h, imgs.ctypes.data, n, H, W, 0, arr), "dc_forward_batch")
-        return [(b[:arr[i].K].copy(), s[:arr[i].K].copy(), t[:arr[i].K].copy()) for i, (b, s, t) in enumerate(keep)]
+        res, rows = self._results([self._capacity(H, W)] * n)
+        check(self.ctx.h, self.lib.dc_forward_batch(self.ctx.h, imgs.ctypes.data, n, H, W, 0, res), "dc_forward_batch")
+        return rows()
 
     def forward_images(self, imgs):
         """run_model.lua's loop over a list of images of DIFFERENT sizes, pipelined over the lanes (dc_forward_images);
         imgs: sequence of (3,H,W) / (1,3,H,W) arrays.  Returns a list of (boxes, scores, tokens)."""
         self._push_test_args()
-        arrs = [self._check_input(im) for im in imgs]
-        n = len(arrs)
-        if n == 0:
-            return []
-        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
-        Hs = (C.c_int * n)(*[a.shape[1] for a in arrs])
-        Ws = (C.c_int * n)(*[a.shape[2] for a in arrs])
-        res = (DcResult * n)()
-        keep = []
-        for i, a in enumerate(arrs):
-            r, b, s, t = self._new_result(self._capacity(a.shape[1], a.shape[2]))
-            res[i] = r
-            keep.append((b, s, t))
-        check(self.ctx.h, self.lib.dc_forward_images(self.ctx.h, ptrs, Hs, Ws, n, 0, res), "dc_forward_images")
-        return [(b[:res[i].K].copy(), s[:res[i].K].copy(), t[:res[i].K].copy()) for i, (b, s, t) in enumerate(keep)]
+        return self._forward_images([self._check_input(im) for im in imgs], 0)
 
     def forward_images_device(self, dev_imgs):
         """forward_images on images that are ALREADY on the device: dev_imgs = sequence of ops.DeviceArray (3,H,W) float32
         (ops.preprocess_u8 makes them).  Runs of equal-sized images travel as groups (setGroup)."""
         self._push_test_args()
-        n = len(dev_imgs)
-        if n == 0:
+        return self._forward_images(dev_imgs, 1)
+
+    def _forward_images(self, imgs, on_device):
+        if len(imgs) == 0:
             return []
-        ptrs = (C.c_void_p * n)(*[a.ptr.value for a in dev_imgs])
-        Hs = (C.c_int * n)(*[a.shape[1] for a in dev_imgs])
-        Ws = (C.c_int * n)(*[a.shape[2] for a in dev_imgs])
-        res = (DcResult * n)()
-        keep = []
-        for i, a in enumerate(dev_imgs):
-            r, b, s, t = self._new_result(self._capacity(a.shape[1], a.shape[2]))
-            res[i] = r
-            keep.append((b, s, t))
-        check(self.ctx.h, self.lib.dc_forward_images(self.ctx.h, ptrs, Hs, Ws, n, 1, res), "dc_forward_images")
-        return [(b[:res[i].K].copy(), s[:res[i].K].copy(), t[:res[i].K].copy()) for i, (b, s, t) in enumerate(keep)]
+        res, rows = self._results([self._capacity(a.shape[1], a.shape[2]) for a in imgs])
+        check(self.ctx.h, self.lib.dc_forward_images(self.ctx.h, *self._image_list(imgs), len(imgs), on_device, res),
+              "dc_forward_images")
+        return rows()
 
     def extractFeatures_images_device(self, dev_imgs):
         """extractFeatures_images on device-resident images (ops.preprocess_u8): list of (boxes, feats)."""
         self._push_test_args()
-        n = len(dev_imgs)
+        return self._extract_features_images(dev_imgs, 1)
+
+    def _extract_features_images(self, imgs, on_device):
+        n = len(imgs)
         if n == 0:
             return []
-        cap = max(self._capacity(a.shape[1], a.shape[2]) for a in dev_imgs)
-        ptrs = (C.c_void_p * n)(*[a.ptr.value for a in dev_imgs])
-        Hs = (C.c_int * n)(*[a.shape[1] for a in dev_imgs])
-        Ws = (C.c_int * n)(*[a.shape[2] for a in dev_imgs])
+        cap = max(self._capacity(a.shape[1], a.shape[2]) for a in imgs)
         boxes = np.zeros((n, cap, 4), np.float32); feats = np.zeros((n, cap, self.fc_dim), np.float32)
-        K = (C.c_int32 * n)()
-        check(self.ctx.h, self.lib.dc_extract_features_images(self.ctx.h, ptrs, Hs, Ws, n, 1, cap, boxes.ctypes.data,
-                                                              feats.ctypes.data, K), "dc_extract_features_images")
+        K = np.zeros((n,), np.int32)
+        check(self.ctx.h, self.lib.dc_extract_features_images(self.ctx.h, *self._image_list(imgs), n, on_device, cap,
+                                                              boxes.ctypes.data, feats.ctypes.data,
+                                                              K.ctypes.data_as(_lib.c_int32_p)),
+              "dc_extract_features_images")
         return [(boxes[i, :K[i]].copy(), feats[i, :K[i]].copy()) for i in range(n)]
 
     def extractFeatures(self, img):
@@ -455,20 +441,7 @@ class DenseCapModel:
     def extractFeatures_images(self, imgs):
         """extract_features.lua's loop over images (any sizes), pipelined over the lanes: list of (boxes, feats)."""
         self._push_test_args()
-        arrs = [self._check_input(im) for im in imgs]
-        n = len(arrs)
-        if n == 0:
-            return []
-        cap = max(self._capacity(a.shape[1], a.shape[2]) for a in arrs)
-        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
-        Hs = (C.c_int * n)(*[a.shape[1] for a in arrs])
-        Ws = (C.c_int * n)(*[a.shape[2] for a in arrs])
-        boxes = np.zeros((n, cap, 4), np.float32); feats = np.zeros((n, cap, self.fc_dim), np.float32)
-        K = np.zeros((n,), np.int32)
-        check(self.ctx.h, self.lib.dc_extract_features_images(self.ctx.h, ptrs, Hs, Ws, n, 0, cap, boxes.ctypes.data,
-                                                              feats.ctypes.data, K.ctypes.data_as(_lib.c_int32_p)),
-              "dc_extract_features_images")
-        return [(boxes[i, :K[i]].copy(), feats[i, :K[i]].copy()) for i in range(n)]
+        return self._extract_features_images([self._check_input(im) for im in imgs], 0)
 
     def scoreCaptions(self, img, captions, return_captions=False, max_len=None):
         """Score query phrases against the image's regions (dc_score_captions): the regions forward_test returns, each with

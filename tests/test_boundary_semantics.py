@@ -169,6 +169,127 @@ def test_a_refused_setTestArgs_leaves_the_previous_state_usable():
     assert _state(lib) == before
 
 
+# the forward entry points: position of n among the arguments (None: one image); the last argument returns K
+_FORWARDS = {"dc_forward_test": None, "dc_extract_features": None, "dc_forward_batch": 2, "dc_forward_images": 4,
+             "dc_extract_features_images": 4}
+
+
+class _ForwardRecordingLib(_RecordingLib):
+    """_RecordingLib that also keeps every call's raw arguments and, like the library, returns K = i + 1 for image i."""
+
+    def __init__(self):
+        super().__init__()
+        self.raw = []
+
+    def __getattr__(self, name):
+        fn = _RecordingLib.__getattr__(self, name)
+
+        def rec(*args):
+            self.raw.append((name,) + args)
+            if name in _FORWARDS:
+                n = 1 if _FORWARDS[name] is None else args[_FORWARDS[name]]
+                out = getattr(args[-1], "_obj", args[-1])        # C.byref(x), or a ctypes array / pointer
+                for i in range(n):
+                    if hasattr(out, "capacity"):
+                        out.K = 1
+                    elif hasattr(out, "value"):
+                        out.value = 1
+                    elif hasattr(out[i], "capacity"):
+                        out[i].K = i + 1
+                    else:
+                        out[i] = i + 1
+            return fn(*args)
+        return rec
+
+
+def _results_passed(arg):
+    """The DcResults a dc_forward_* call received: C.byref(r), or a DcResult array."""
+    return [arg._obj] if hasattr(arg, "_obj") else list(arg)
+
+
+def test_every_forward_method_passes_sizes_and_capacities():
+    """Each public forward method on one image and on two: the entry point it calls, n / H / W / on_device / capacity, the
+    capacity of every DcResult, and what comes back (K rows of each image; views from forward_batch_device only)."""
+    import ctypes as C
+    from densecap_amd.ops import DeviceArray
+    m, _ = _model()
+    m.setTestArgs(num_proposals=-1)                       # uncapped: the capacity follows each image's size
+    lib = m.lib = m.ctx.lib = _ForwardRecordingLib()
+    T, D = m.seq_length, m.fc_dim
+    sizes = [(64, 96), (80, 48)]
+    cap = {hw: m.num_anchors * -(-hw[0] // 16) * -(-hw[1] // 16) for hw in sizes}
+    assert len(set(cap.values())) == 2
+
+    def host(hw):
+        return np.zeros((3,) + hw, np.float32)
+
+    def dev(i, hw):
+        a = DeviceArray(m.ctx, (3,) + hw, np.float32)
+        a.ptr = C.c_void_p(0x10000 * (i + 1))
+        return a
+
+    def check_rows(out, widths, owns):
+        assert len(out) == len(widths)
+        for i, (parts, want) in enumerate(zip(out, widths)):
+            assert len(parts) == len(want)
+            for a, (w, dt) in zip(parts, want):
+                assert a.dtype == dt and a.shape == ((i + 1,) if w is None else (i + 1, w))
+                assert a.flags.owndata == owns
+
+    det = [(4, np.float32), (None, np.float32), (T, np.int32)]
+    feat = [(4, np.float32), (D, np.float32)]
+    for n in (1, 2):
+        lists = sizes[:n]
+        one = sizes[0]
+        # one image of one size (n = 1), or a batch of n images of sizes[0]
+        cases = [
+            ("forward_batch", lambda: m.forward_batch(np.zeros((n, 3) + one, np.float32)), "dc_forward_batch", (n,) + one + (0,),
+             [cap[one]] * n, det, True),
+            ("forward_batch_device", lambda: m.forward_batch_device(0x20000, n, *one), "dc_forward_batch", (n,) + one + (1,),
+             [cap[one]] * n, det, False),
+            ("forward_images", lambda: m.forward_images([host(hw) for hw in lists]), "dc_forward_images", (n, 0),
+             [cap[hw] for hw in lists], det, True),
+            ("forward_images_device", lambda: m.forward_images_device([dev(i, hw) for i, hw in enumerate(lists)]),
+             "dc_forward_images", (n, 1), [cap[hw] for hw in lists], det, True),
+            ("extractFeatures_images", lambda: m.extractFeatures_images([host(hw) for hw in lists]),
+             "dc_extract_features_images", (n, 0, max(cap[hw] for hw in lists)), None, feat, True),
+            ("extractFeatures_images_device",
+             lambda: m.extractFeatures_images_device([dev(i, hw) for i, hw in enumerate(lists)]),
+             "dc_extract_features_images", (n, 1, max(cap[hw] for hw in lists)), None, feat, True),
+        ]
+        if n == 1:
+            cases += [
+                ("forward_raw", lambda: [m.forward_raw(host(one))], "dc_forward_test", one + (0,), [cap[one]], det, True),
+                ("forward_test", lambda: [m.forward_test(host(one))[:1]], "dc_forward_test", one + (0,), [cap[one]],
+                 det[:1], True),                          # (its scores are a (K,1) view, its captions strings)
+                ("extractFeatures", lambda: [m.extractFeatures(host(one))], "dc_extract_features", one + (0, cap[one]),
+                 None, feat, True),
+            ]
+        for what, call, entry, ints, caps, widths, owns in cases:
+            lib.raw.clear()
+            out = call()
+            hits = [c for c in lib.raw if c[0] in _FORWARDS]
+            assert [c[0] for c in hits] == [entry], what
+            args = hits[0][2:]
+            names = [c[0] for c in lib.raw]
+            assert names.index("dc_set_test_args") < names.index(entry), what
+            if entry in ("dc_forward_images", "dc_extract_features_images"):
+                assert [list(args[1]), list(args[2])] == [[hw[0] for hw in lists], [hw[1] for hw in lists]], what
+                assert tuple(args[3:3 + len(ints)]) == ints, what
+            elif entry == "dc_forward_batch":
+                assert tuple(args[1:5]) == ints, what
+            else:
+                assert tuple(args[1:1 + len(ints)]) == ints, what
+            if caps is not None:
+                assert [r.capacity for r in _results_passed(args[-1])] == caps, what
+            check_rows(out, [widths] * len(out), owns)
+    # an empty list: the test args still travel, no forward entry point is called
+    for method in (m.forward_images, m.forward_images_device, m.extractFeatures_images, m.extractFeatures_images_device):
+        lib.raw.clear()
+        assert method([]) == []
+        assert [c[0] for c in lib.raw] == ["dc_set_test_args"]
+
+
 # ---- the Lua twin (text checks: no LuaJIT in this image) -----------------------------------------------------------------
 def _lua():
     return open(os.path.join(ROOT, "lua", "DenseCapModelHIP.lua")).read()
