@@ -35,6 +35,13 @@ class DcResult(C.Structure):
                 ("boxes", c_float_p), ("scores", c_float_p), ("tokens", c_int32_p)]
 
 
+DC_BOXES_CLIP = 1
+
+
+class DcBoxList(C.Structure):
+    _fields_ = [("boxes", c_float_p), ("n", C.c_int32), ("src", c_int32_p)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -62,6 +69,13 @@ _SIGS = {
                                       C.c_void_p, c_int32_p]),
     "dc_extract_features_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                              C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_int32_p]),
+    "dc_forward_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcBoxList), C.c_int,
+                                   C.POINTER(DcResult)]),
+    "dc_forward_boxes_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                          C.c_int, C.POINTER(DcBoxList), C.c_int, C.POINTER(DcResult)]),
+    "dc_extract_features_boxes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.c_int, C.c_int, C.POINTER(DcBoxList), C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, c_int32_p]),
     "dc_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), c_float_p, C.c_int]),
     "dc_mfma_profile": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double)]),

@@ -767,6 +767,57 @@ __global__ __launch_bounds__(256) void survivor_compact_kernel(const float* __re
   }
 }
 
+// Caller-supplied boxes in the place of the RPN's (dc_forward_boxes): one workgroup per image of a group (blockIdx.x) reads the
+// image's n = min(in_n[img], P) rows of `in` -- n from DEVICE memory, so a captured forward does not depend on it -- and
+// writes the rows that stay, in their order, to roi_boxes, the caller's row index of each to box_src and their number to
+// count[img * count_stride]: what the RPN NMS + gather leave behind for RoI pooling and everything after it.
+// clip: box_utils.clip_boxes(boxes, {1, 1, W, H}, 'xcycwh') in rpn_decode_kernel's arithmetic (clip_one), rows that come out
+// invalid are dropped (LocalizationLayer.lua:272-300); without it every row stays as given.
+// Order-preserving compaction, 256 rows a step: a ballot per wave, the waves' counts through LDS, rank = rows kept so far +
+// kept by the earlier waves + kept by the lower lanes.  Rows [count, P) are zero-filled like the dead rows of the RPN path
+// (fc6 .. decode run over all P rows), their box_src is -1.
+__global__ __launch_bounds__(256) void boxes_ingest_kernel(const float* __restrict__ in, const int32_t* __restrict__ in_n, int P,
+                                                           int clip, float img_h, float img_w, float* __restrict__ roi_boxes,
+                                                           int32_t* __restrict__ box_src, int32_t* __restrict__ count,
+                                                           int count_stride) {
+  __shared__ int s_wave[4];
+  const int img = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t r0 = (size_t)img * P;
+  const int n = max(0, min(in_n[img], P));
+  int kept = 0;                                            // rows kept by the steps so far (the same in every thread)
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    f32x4 b = {0.f, 0.f, 0.f, 0.f}, o = b;
+    bool v = false;
+    if (i < n) {
+      b = *reinterpret_cast<const f32x4*>(in + (r0 + i) * 4);
+      o = b;
+      v = clip ? clip_one(b, 1.f, 1.f, img_w, img_h, o) : true;
+    }
+    const u64 bal = __ballot(v);
+    if (lane == 0) s_wave[wave] = __builtin_popcountll(bal);
+    __syncthreads();
+    int before = 0, step = 0;
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_wave[w];
+      if (w < wave) before += c;
+      step += c;
+    }
+    if (v) {
+      const int pos = kept + before + __builtin_popcountll(bal & ((1ull << lane) - 1ull));     // < n <= P
+      *reinterpret_cast<f32x4*>(roi_boxes + (r0 + pos) * 4) = o;
+      box_src[r0 + pos] = i;
+    }
+    kept += step;
+    __syncthreads();                                       // s_wave is rewritten by the next step
+  }
+  for (int i = kept + (int)threadIdx.x; i < P; i += 256) {
+    *reinterpret_cast<f32x4*>(roi_boxes + (r0 + i) * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    box_src[r0 + i] = -1;
+  }
+  if (threadIdx.x == 0) count[(size_t)img * count_stride] = kept;
+}
+
 // The results of a group in ONE launch (round 5; three gathers per image before): image = blockIdx.y.  A record is laid out
 // exactly as the pinned host staging expects it (kRecK / kRecFault / kRecPayload, common.h) -- so that the whole group leaves in
 // one device-to-host copy.
@@ -774,11 +825,15 @@ __global__ __launch_bounds__(256) void survivor_compact_kernel(const float* __re
 // tok_gather = 0: the token rows are already in final order, image by image (captions decoded after the final NMS, rows
 // [img*P, img*P + K)); tok_gather = 2: in final order and PACKED over the group (survivor_compact_kernel's row block: image
 // img's rows start at the sum of the earlier images' counts).
+// kSrc (a forward on caller-supplied boxes): the record carries one more int32 per row after the values, box_src[pick] -- the
+// caller's row the region came from (boxes_ingest_kernel's map composed with the final picks).  The instantiation without it
+// is the kernel of every other entry point, unchanged.
+template <bool kSrc>
 __global__ void final_pack_kernel(const float* __restrict__ final_boxes, const float* __restrict__ obj,
                                   const int32_t* __restrict__ tokens, int tok_gather, const float* __restrict__ codes,
                                   const int32_t* __restrict__ picks, const int32_t* __restrict__ count, int count_stride,
                                   const uint32_t* __restrict__ fault, int P, int T, int D, char* __restrict__ pack,
-                                  size_t stride) {
+                                  size_t stride, const int32_t* __restrict__ box_src) {
   const int img = blockIdx.y;
   const int W = 5 + (codes != nullptr ? D : T);               // 4-byte words of a row: box, score, tokens | codes
   const int K = min(count[(size_t)img * count_stride], P);
@@ -795,6 +850,10 @@ __global__ void final_pack_kernel(const float* __restrict__ final_boxes, const f
   if (tok_gather == 2) {
     tok0 = 0;
     for (int j = 0; j < img; ++j) tok0 += (size_t)min(count[(size_t)j * count_stride], P);
+  }
+  if (kSrc) {
+    int32_t* osrc = reinterpret_cast<int32_t*>(ot + (size_t)P * (W - 5));
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < K; r += gridDim.x * blockDim.x) osrc[r] = box_src[r0 + (size_t)picks[r0 + r]];
   }
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < (long)K * W; t += (long)gridDim.x * blockDim.x) {
     const int r = (int)(t / W), c = (int)(t - (long)r * W);
@@ -940,12 +999,25 @@ hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores,
 
 hipError_t launch_final_pack(const float* final_boxes, const float* obj, const int32_t* tokens, int tok_gather,
                              const float* codes, const int32_t* picks, const int32_t* count, int count_stride,
-                             const uint32_t* fault, int nimg, int P, int T, int D, void* pack, size_t stride, hipStream_t s) {
+                             const uint32_t* fault, int nimg, int P, int T, int D, void* pack, size_t stride, hipStream_t s,
+                             const int32_t* box_src) {
   if (nimg <= 0 || nimg > 65535 || P <= 0) return hipErrorInvalidValue;
   const long per = (long)P * (5 + (codes != nullptr ? D : T));
   const int gx = (int)std::min<long>((per + 255) / 256, 2048);
-  hipLaunchKernelGGL(final_pack_kernel, dim3(gx, nimg), dim3(256), 0, s, final_boxes, obj, tokens, tok_gather, codes, picks,
-                     count, count_stride, fault, P, T, D, static_cast<char*>(pack), stride);
+  if (box_src != nullptr)
+    hipLaunchKernelGGL(final_pack_kernel<true>, dim3(gx, nimg), dim3(256), 0, s, final_boxes, obj, tokens, tok_gather, codes, picks,
+                       count, count_stride, fault, P, T, D, static_cast<char*>(pack), stride, box_src);
+  else
+    hipLaunchKernelGGL(final_pack_kernel<false>, dim3(gx, nimg), dim3(256), 0, s, final_boxes, obj, tokens, tok_gather, codes, picks,
+                       count, count_stride, fault, P, T, D, static_cast<char*>(pack), stride, box_src);
+  return hipGetLastError();
+}
+
+hipError_t launch_boxes_ingest(const float* in, const int32_t* in_n, int nimg, int P, int clip, int img_h, int img_w,
+                               float* roi_boxes, int32_t* box_src, int32_t* count, int count_stride, hipStream_t s) {
+  if (nimg <= 0 || P <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boxes_ingest_kernel, dim3(nimg), dim3(256), 0, s, in, in_n, P, clip, (float)img_h, (float)img_w, roi_boxes,
+                     box_src, count, count_stride);
   return hipGetLastError();
 }
 

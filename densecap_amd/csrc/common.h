@@ -42,6 +42,8 @@ constexpr size_t kRecK = 0, kRecFault = 68, kRecPayload = 256;
 inline size_t rec_scores(int P) { return kRecPayload + (size_t)P * 16; }
 inline size_t rec_values(int P) { return rec_scores(P) + (size_t)P * 4; }
 inline size_t rec_stride(int P, size_t words) { return (rec_values(P) + (size_t)P * words * 4 + 255) & ~(size_t)255; }
+// a forward on caller-supplied boxes appends int32 src (P) to the values: a record of `words` + 1 words per row
+inline size_t rec_src(int P, size_t words) { return rec_values(P) + (size_t)P * words * 4; }
 // int32 values between two images' NMS count slots (count1 / count2 of a lane): one 256-byte line per image
 constexpr int kCountStride = 64;
 
@@ -282,9 +284,17 @@ hipError_t launch_survivor_compact(const float* codes, const int32_t* picks, con
 
 // the results of a group of images gathered by their final-NMS picks into packed records (see final_pack_kernel);
 // tok_gather: 1 = token rows are per RoI (gathered by pick), 0 = already in final order per image, 2 = final order, packed over the group
+// box_src != null (a forward on caller-supplied boxes): every record also carries int32 box_src[pick] per row, at rec_src
 hipError_t launch_final_pack(const float* final_boxes, const float* obj, const int32_t* tokens, int tok_gather,
                              const float* codes, const int32_t* picks, const int32_t* count, int count_stride,
-                             const uint32_t* fault, int nimg, int P, int T, int D, void* pack, size_t stride, hipStream_t s);
+                             const uint32_t* fault, int nimg, int P, int T, int D, void* pack, size_t stride, hipStream_t s,
+                             const int32_t* box_src = nullptr);
+
+// Caller-supplied boxes in the place of the RPN's: image i of the group has in_n[i] (device) rows at in + i*P*4; the rows that
+// stay (all of them, or with `clip` those that box_utils.clip_boxes leaves valid, clipped) go to roi_boxes in their order,
+// their caller-side row index to box_src, their number to count[i * count_stride] (boxes_ingest_kernel)
+hipError_t launch_boxes_ingest(const float* in, const int32_t* in_n, int nimg, int P, int clip, int img_h, int img_w,
+                               float* roi_boxes, int32_t* box_src, int32_t* count, int count_stride, hipStream_t s);
 
 // ---- bilinear RoI pooling (roipool.hip) ---------------------------------------------
 // group form: nimg feature maps feat_stride floats apart, B rows of boxes / output per image, live counts

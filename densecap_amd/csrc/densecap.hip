@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <functional>
 #include <memory>
 
@@ -71,18 +72,28 @@ struct GraphKey {
   uint64_t carve_epoch = 0, weights_epoch = 0;
   const void *fault_dev = nullptr, *arena = nullptr, *host_stage = nullptr, *splitk_ws = nullptr;
   int H = 0, W = 0, P = 0, g = 0, features_only = 0, no_decode = 0;
+  int box_src = 0, box_clip = 0;    // the RoI boxes are the caller's (dc_forward_boxes), clipped on the way in (DC_BOXES_CLIP)
   Settings set;
   bool operator==(const GraphKey& o) const { return memcmp(this, &o, offsetof(GraphKey, set) + sizeof(Settings)) == 0; }
 };
-static_assert(offsetof(GraphKey, set) == 6 * 8 + 6 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
+static_assert(offsetof(GraphKey, set) == 6 * 8 + 8 * 4, "GraphKey is compared bytewise: no padding in front of `set`");
 
 // Where one image's results go: its K rows (at most `capacity`) of boxes, scores and values -- tokens (T per row) or fc7
-// codes (D per row, extractFeatures) -- and its K and T.  Null pointers are skipped.
+// codes (D per row, extractFeatures) -- and its K and T; `src` (a forward on caller-supplied boxes): the caller's row each
+// result row came from.  Null pointers are skipped.
 struct Dest {
   float *boxes = nullptr, *scores = nullptr;
   void* values = nullptr;
   int32_t *K = nullptr, *T = nullptr;
   int capacity = 0;
+  int32_t* src = nullptr;
+};
+
+// Where a forward's RoI boxes come from: the RPN (bl == nullptr), or the caller -- image i's boxes are bl[i], validated by
+// check_box_lists; `clip`: DC_BOXES_CLIP
+struct BoxSource {
+  const dc_box_list* bl = nullptr;
+  bool clip = false;
 };
 
 // What a forward computes: boxes, scores and captions; boxes and fc7 codes (extractFeatures); boxes and scores only
@@ -102,6 +113,9 @@ struct Lane {
   NmsWorkspace nms;
   void* nms_base = nullptr;
   int32_t *picks1 = nullptr, *count1 = nullptr, *picks2 = nullptr, *count2 = nullptr;
+  float* in_boxes = nullptr;         // caller-supplied boxes of the group (P rows per image) and their counts, as copied in ...
+  int32_t *in_n = nullptr, *box_src = nullptr;   // ... and the caller's row behind every row of roi_boxes (boxes_ingest_kernel)
+  std::vector<int32_t> in_n_host;    // (source of the asynchronous copy to in_n)
   float *roi_boxes = nullptr, *roi_feats = nullptr, *fc6_out = nullptr, *codes = nullptr;
   float *obj = nullptr, *final_trans = nullptr, *final_boxes = nullptr, *final_xyxy = nullptr;
   float *enc = nullptr, *gates = nullptr, *hstate = nullptr, *cstate = nullptr, *logits = nullptr;
@@ -117,6 +131,7 @@ struct Lane {
   bool busy = false;
   const Dest* dst = nullptr;         // where the group in flight goes: dst[0..g)
   bool feats = false;                // ... and its records hold fc7 codes, not tokens
+  bool boxes_in = false;             // ... computed on caller-supplied boxes (records carry rec_src; no RPN stages ran)
   float stage_ms[ST_COUNT] = {};
   bool have_times = false;
   // beam search scratch (allocated on first use; beam_chunk() proposals x beam rows at a time)
@@ -400,8 +415,10 @@ int effective_proposals(const dc_ctx* ctx, int H, int W) {
 }
 
 // bytes of one image's packed result record: tokens, or fc7 codes (extractFeatures)
-size_t pack_stride(const dc_ctx* ctx, int P, bool feats) { return rec_stride(P, feats ? ctx->D : ctx->T); }
-// bytes per image of a lane's record buffers (out_pack, host_stage), which hold either kind
+// (with_src: a forward on caller-supplied boxes, one more word per row)
+size_t pack_words(const dc_ctx* ctx, bool feats) { return feats ? ctx->D : ctx->T; }
+size_t pack_stride(const dc_ctx* ctx, int P, bool feats, bool with_src = false) { return rec_stride(P, pack_words(ctx, feats) + (with_src ? 1 : 0)); }
+// bytes per image of a lane's record buffers (out_pack, host_stage), which hold any kind (T + D >= max(T, D) + 1)
 size_t host_stage_stride(const dc_ctx* ctx, int P) { return rec_stride(P, (size_t)ctx->T + ctx->D); }
 
 // A lane's streams and events, made on first use.
@@ -469,6 +486,9 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
       {(void**)&L.picks2, GP * 4},
       {(void**)&L.count2, (size_t)G * kCountStride * 4},
       {(void**)&L.surv_total, 256},
+      {(void**)&L.in_boxes, GP * 16},
+      {(void**)&L.in_n, (size_t)G * 4},
+      {(void**)&L.box_src, GP * 4},
       {(void**)&L.roi_boxes, GP * 16},
       {(void**)&L.roi_feats, GP * 49 * 512 * 4},
       {(void**)&L.fc6_out, GP * Dm * 4},
@@ -833,7 +853,10 @@ int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int p
 // `events`: record the stage events (an eager enqueue; a captured graph carries none -- dc_stage_times then has nothing)
 // `no_decode`: boxes and scores only, no language model (dc_score_captions without tokens); the records' token rows are then
 // stale and must not be read
-int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, bool no_decode = false) {
+// `boxes_in`: the RoI boxes are the caller's, already in L.in_boxes / L.in_n (enqueue_forward): the stages between the trunk
+// and RoI pooling are replaced by the ingest launch (their events follow each other at once).  `clip_in`: DC_BOXES_CLIP
+int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, bool no_decode = false, bool boxes_in = false,
+                 bool clip_in = false) {
   const Settings& cfg = ctx->cfg;
   hipStream_t s = L.stream;
   const int H = L.H, W = L.W, P = L.P;
@@ -857,22 +880,31 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
   L.feat = L.act[cur];
   const size_t feat_elems = (size_t)h * w * 512;
   STAGE_EVENT(1);
-  // ---- RPN (LocalizationLayer.lua:265, build_rpn :609-690) ----------------------------------
-  DCCHK(conv3x3(ctx, s, L.feat, ctx->rpn_w, ctx->rpn_b, L.rpn_hidden, g, h, w, 512, ctx->R, 1, lane_ws(L)));
-  DCCHK(linear(ctx, s, L.rpn_hidden, ctx->heads_w, ctx->heads_b, L.heads, g * h * w, 6 * ctx->k, ctx->R, 0, Ws(), h * w));
-  KCHK(launch_rpn_decode(L.heads, g, h, w, ctx->k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], H, W,
-                         L.rpn_boxes, nullptr, nullptr, L.rpn_xyxy, L.rpn_p, L.rpn_valid, cfg.clip_boxes, s));   // the whole group in one launch
-  STAGE_EVENT(2);
-  // ---- RPN NMS (LocalizationLayer.lua:318-338) ------------------------------------------------
-  ensure_fault_word(ctx);
-  for (int i = 0; i < g; ++i)
-    KCHK(launch_nms(L.nms, L.rpn_xyxy + (size_t)i * L.A * 4, L.rpn_p + (size_t)i * L.A, L.rpn_valid + (size_t)i * L.A, L.A,
-                    nullptr, cfg.rpn_nms_thresh, P, L.picks1 + (size_t)i * P, L.count1 + i * kCountStride, cfg.nms_band, s, ctx->fault_dev));
-  STAGE_EVENT(3);
-  // ---- bilinear RoI pooling (LocalizationLayer.lua:338-349) -----------------------------------
-  // one launch for the group; the picked RPN boxes are gathered by the kernel itself (and left in roi_boxes for the heads)
-  KCHK(launch_bilinear_roi_pool_group(L.feat, feat_elems, g, h, w, 512, L.roi_boxes, P, L.count1, kCountStride, L.picks1, L.rpn_boxes,
-                                      (size_t)L.A * 4, H, W, 7, 7, L.roi_feats, 1, s));
+  ensure_fault_word(ctx);            // every forward has an NMS and a final pack that report through it: made before any capture
+  if (boxes_in) {
+    STAGE_EVENT(2);
+    STAGE_EVENT(3);
+    // ---- the caller's boxes in the place of the localisation layer's roi_boxes (DenseCapModel.lua:242-275) ----------------
+    KCHK(launch_boxes_ingest(L.in_boxes, L.in_n, g, P, clip_in ? 1 : 0, H, W, L.roi_boxes, L.box_src, L.count1, kCountStride, s));
+    KCHK(launch_bilinear_roi_pool_group(L.feat, feat_elems, g, h, w, 512, L.roi_boxes, P, L.count1, kCountStride, nullptr, nullptr,
+                                        0, H, W, 7, 7, L.roi_feats, 1, s));
+  } else {
+    // ---- RPN (LocalizationLayer.lua:265, build_rpn :609-690) ----------------------------------
+    DCCHK(conv3x3(ctx, s, L.feat, ctx->rpn_w, ctx->rpn_b, L.rpn_hidden, g, h, w, 512, ctx->R, 1, lane_ws(L)));
+    DCCHK(linear(ctx, s, L.rpn_hidden, ctx->heads_w, ctx->heads_b, L.heads, g * h * w, 6 * ctx->k, ctx->R, 0, Ws(), h * w));
+    KCHK(launch_rpn_decode(L.heads, g, h, w, ctx->k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], H, W,
+                           L.rpn_boxes, nullptr, nullptr, L.rpn_xyxy, L.rpn_p, L.rpn_valid, cfg.clip_boxes, s));   // the whole group in one launch
+    STAGE_EVENT(2);
+    // ---- RPN NMS (LocalizationLayer.lua:318-338) ------------------------------------------------
+    for (int i = 0; i < g; ++i)
+      KCHK(launch_nms(L.nms, L.rpn_xyxy + (size_t)i * L.A * 4, L.rpn_p + (size_t)i * L.A, L.rpn_valid + (size_t)i * L.A, L.A,
+                      nullptr, cfg.rpn_nms_thresh, P, L.picks1 + (size_t)i * P, L.count1 + i * kCountStride, cfg.nms_band, s, ctx->fault_dev));
+    STAGE_EVENT(3);
+    // ---- bilinear RoI pooling (LocalizationLayer.lua:338-349) -----------------------------------
+    // one launch for the group; the picked RPN boxes are gathered by the kernel itself (and left in roi_boxes for the heads)
+    KCHK(launch_bilinear_roi_pool_group(L.feat, feat_elems, g, h, w, 512, L.roi_boxes, P, L.count1, kCountStride, L.picks1, L.rpn_boxes,
+                                        (size_t)L.A * 4, H, W, 7, 7, L.roi_feats, 1, s));
+  }
   STAGE_EVENT(4);
   // ---- recog_base fc6/fc7 (DenseCapModel.lua:133) ------------------------------------------------
   const int R = g * P;                      // RoI rows of the group
@@ -906,7 +938,8 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
     const size_t r0 = (size_t)i * P;
     // forward_test skips the final NMS when final_nms_thresh <= 0 (DenseCapModel.lua:261); extractFeatures calls
     // box_utils.nms unconditionally (DenseCapModel.lua:285-304)
-    if (cfg.final_nms_thresh > 0.f || features_only) {
+    // (... on the RPN's boxes; a caller who passes boxes and no threshold wants the codes of those boxes: dc_extract_features_boxes)
+    if (cfg.final_nms_thresh > 0.f || (features_only && !boxes_in)) {
       KCHK(launch_nms(L.nms, L.final_xyxy + r0 * 4, L.obj + r0, nullptr, P, L.count1 + i * kCountStride, cfg.final_nms_thresh, -1,
                       L.picks2 + r0, L.count2 + i * kCountStride, cfg.nms_band, sn, ctx->fault_dev));
     } else {
@@ -943,28 +976,32 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
     }
   }
   // ---- results: ONE gather launch for the group into packed records, ONE copy to the pinned host staging ---------------
-  const size_t stride = pack_stride(ctx, P, features_only);
+  const size_t stride = pack_stride(ctx, P, features_only, boxes_in);
   KCHK(launch_final_pack(L.final_boxes, L.obj, survivors_only ? L.out_tokens : L.seq, packed_decode ? 2 : survivors_only ? 0 : 1,
                          features_only ? L.codes : nullptr, L.picks2, L.count2, kCountStride, ctx->fault_dev, g, P, ctx->T, ctx->D,
-                         L.out_pack, stride, s));
+                         L.out_pack, stride, s, boxes_in ? L.box_src : nullptr));
   STAGE_EVENT(8);
   HIPCHK(hipMemcpyAsync(L.host_stage, L.out_pack, (size_t)g * stride, hipMemcpyDeviceToHost, s));
 #undef STAGE_EVENT
   return DC_OK;
 }
 
-GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only, bool no_decode) {
+GraphKey graph_key(const dc_ctx* ctx, const Lane& L, int g, bool features_only, bool no_decode, const BoxSource& bs) {
   GraphKey k;
   k.carve_epoch = L.carve_epoch; k.weights_epoch = ctx->weights_epoch;
   k.fault_dev = ctx->fault_dev; k.arena = L.arena.p; k.host_stage = L.host_stage; k.splitk_ws = L.splitk_ws;
   k.H = L.H; k.W = L.W; k.P = L.P; k.g = g; k.features_only = features_only; k.no_decode = no_decode;
+  k.box_src = bs.bl != nullptr; k.box_clip = bs.bl != nullptr && bs.clip;
   k.set = ctx->cfg;
   return k;
 }
 
 // imgs[0..g): the group's images.  `packed`: they are one buffer of the caller, back to back, and arrive in one copy; a list's
 // images are copied one by one (two allocations whose addresses happen to follow each other are still not one buffer).
-int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int img_on_device, bool packed, Mode mode) {
+// `bs`: the group's box lists, bs.bl[0..g) (or none): their rows and counts travel to the lane beside the images, outside
+// the captured body -- a replayed forward reads them from the lane.
+int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int img_on_device, bool packed, Mode mode,
+                    const BoxSource& bs) {
   hipStream_t s = L.stream;
   const bool features_only = mode == MODE_FEATURES, no_decode = mode == MODE_NO_DECODE;
   const size_t img_elems = (size_t)3 * L.H * L.W;
@@ -972,8 +1009,17 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int i
   const int per_copy = packed ? g : 1;
   for (int i = 0; i < g; i += per_copy)
     HIPCHK(hipMemcpyAsync(L.img + (size_t)i * img_elems, imgs[i], per_copy * img_elems * 4, kind, s));
+  const bool boxes_in = bs.bl != nullptr, clip_in = boxes_in && bs.clip;
+  if (boxes_in) {
+    L.in_n_host.resize(g);
+    for (int i = 0; i < g; ++i) {
+      L.in_n_host[i] = bs.bl[i].n;
+      HIPCHK(hipMemcpyAsync(L.in_boxes + (size_t)i * L.P * 4, bs.bl[i].boxes, (size_t)bs.bl[i].n * 16, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(L.in_n, L.in_n_host.data(), (size_t)g * 4, hipMemcpyHostToDevice, s));
+  }
   L.g = g;
-  const size_t stride = pack_stride(ctx, L.P, features_only);
+  const size_t stride = pack_stride(ctx, L.P, features_only, boxes_in);
   for (int i = 0; i < g; ++i) *reinterpret_cast<uint32_t*>(static_cast<char*>(L.host_stage) + i * stride + kRecFault) = 0;
   L.ran_graph = false;
   // Graph replay (dc_set_graph_replay): the FIRST forward of a key runs eagerly (lazy allocations, kernel attributes and
@@ -981,7 +1027,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int i
   // hipGraphLaunch.  Per-launch profiling and beam search (which allocates on first use) stay eager.
   const bool eligible = ctx->graphs && !ctx->prof && ctx->cfg.beam_size == 0;
   if (eligible) {
-    const auto key = graph_key(ctx, L, g, features_only, no_decode);
+    const auto key = graph_key(ctx, L, g, features_only, no_decode, bs);
     if (L.gexec != nullptr && key == L.gkey) {
       HIPCHK(hipGraphLaunch(L.gexec, s));
       ctx->graph_launches += 1;
@@ -990,7 +1036,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int i
       if (L.gexec != nullptr) { (void)hipGraphExecDestroy(L.gexec); L.gexec = nullptr; }
       hipGraph_t graph = nullptr;
       HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-      const int rc = enqueue_body(ctx, L, g, features_only, false, no_decode);
+      const int rc = enqueue_body(ctx, L, g, features_only, false, no_decode, boxes_in, clip_in);
       const hipError_t e = hipStreamEndCapture(s, &graph);
       hipError_t e2 = hipSuccess;
       if (rc == DC_OK && e == hipSuccess && graph != nullptr) e2 = hipGraphInstantiate(&L.gexec, graph, nullptr, nullptr, 0);
@@ -1008,7 +1054,7 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int i
         fprintf(stderr, "libdensecap_hip: %s\n", note);
         ctx->graph_note = note;
         if (rc != DC_OK) return rc;
-        DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
+        DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode, boxes_in, clip_in));
       } else {
         L.gkey = key;
         ctx->graph_captures += 1;
@@ -1017,16 +1063,17 @@ int enqueue_forward(dc_ctx* ctx, Lane& L, const float* const* imgs, int g, int i
         L.ran_graph = true;
       }
     } else {
-      DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
+      DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode, boxes_in, clip_in));
       L.last_key = key;
       L.last_key_valid = true;
     }
   } else {
-    DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode));
+    DCCHK(enqueue_body(ctx, L, g, features_only, true, no_decode, boxes_in, clip_in));
     L.last_key_valid = false;
   }
   L.busy = true;
   L.feats = features_only;
+  L.boxes_in = boxes_in;
   return DC_OK;
 }
 
@@ -1057,10 +1104,11 @@ int harvest(dc_ctx* ctx, Lane& L) {
       L.stage_ms[i] = ms / (float)std::max(L.g, 1);       // per image of the group
     }
     if (L.nms_before_decode) std::swap(L.stage_ms[ST_LSTM], L.stage_ms[ST_NMS2]);    // events 6..7 timed the NMS, 7..8 the decode
+    if (L.boxes_in) L.stage_ms[ST_RPN] = L.stage_ms[ST_NMS1] = 0.f;                   // nothing ran between their events
   }
   L.have_times = !L.ran_graph;                            // a replayed graph carries no stage events
   const int P = L.P;
-  const size_t stride = pack_stride(ctx, P, L.feats);
+  const size_t stride = pack_stride(ctx, P, L.feats, L.boxes_in);
   const size_t row_bytes = (size_t)(L.feats ? ctx->D : ctx->T) * 4;      // values of one row: codes or tokens
   for (int i = 0; i < L.g; ++i) {
     const char* hs = static_cast<const char*>(L.host_stage) + i * stride;
@@ -1075,6 +1123,7 @@ int harvest(dc_ctx* ctx, Lane& L) {
     if (d.boxes) memcpy(d.boxes, hs + kRecPayload, (size_t)K * 16);
     if (d.scores) memcpy(d.scores, hs + rec_scores(P), (size_t)K * 4);
     if (d.values) memcpy(d.values, hs + rec_values(P), K * row_bytes);
+    if (d.src && L.boxes_in) memcpy(d.src, hs + rec_src(P, pack_words(ctx, L.feats)), (size_t)K * 4);
   }
   L.dst = nullptr;
   return DC_OK;
@@ -1397,8 +1446,9 @@ static int group_run(const dc_ctx* ctx, const int* H, const int* W, int i, int n
 // share launches), pipelined over the lanes.  A lane that takes a run of g images keeps its group capacity if it already
 // holds their size, else it is carved for g; results do not depend on the capacity (every route is planned per image).
 // `packed`: the images are one buffer of the caller, back to back (enqueue_forward).
+// `bs`: caller-supplied boxes, bs.bl[i] for image i (checked by check_box_lists), or none.
 static int run_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev, bool packed,
-                      Mode mode, const Dest* dst) {
+                      Mode mode, const Dest* dst, const BoxSource& bs = BoxSource()) {
   HIPCHK(hipSetDevice(ctx->device));
   int runs = 0;
   for (int i = 0; i < n; i += group_run(ctx, H, W, i, n)) ++runs;
@@ -1413,7 +1463,7 @@ static int run_images(dc_ctx* ctx, const float* const* imgs, const int* H, const
     DCCHK_DRAIN(lane_prepare(ctx, L, H[i], W[i], effective_proposals(ctx, H[i], W[i]), G));
     L.dst = dst + i;
     const auto t0 = std::chrono::steady_clock::now();
-    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + i, g, on_dev, packed, mode));
+    DCCHK_DRAIN(enqueue_forward(ctx, L, imgs + i, g, on_dev, packed, mode, BoxSource{bs.bl ? bs.bl + i : nullptr, bs.clip}));
     enq_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     i += g;
   }
@@ -1489,6 +1539,67 @@ int dc_extract_features_images(dc_ctx* ctx, const float* const* imgs, const int*
   for (int i = 0; i < n; ++i)      // image i: `capacity` rows further on in each array
     dst[i] = Dest{boxes + (size_t)i * capacity * 4, nullptr, feats + (size_t)i * capacity * ctx->D, K + i, nullptr, capacity};
   return run_images(ctx, imgs, H, W, n, on_dev, false, MODE_FEATURES, dst.data());
+}
+
+// The checks every entry point on caller-supplied boxes makes before anything is enqueued (docs/SEMANTICS.md): image i's list
+// has 1 .. P boxes (P = the row capacity of a forward of that size) with finite coordinates and w, h > 0, and the rows fit
+// `cap(i)`, the capacity of the result that receives them.
+static int check_box_lists(dc_ctx* ctx, const char* who, const float* const* imgs, const int* H, const int* W, int n,
+                           const dc_box_list* bl, int flags, const std::function<int(int)>& cap) {
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!imgs || !H || !W || !bl || n <= 0) return ctx->fail(DC_E_INVALID, "%s: bad arguments (null pointer or n <= 0)", who);
+  if (flags & ~DC_BOXES_CLIP) return ctx->fail(DC_E_INVALID, "%s: unknown flags 0x%x (DC_BOXES_CLIP is the only one)", who, flags);
+  for (int i = 0; i < n; ++i) {
+    if (!imgs[i] || H[i] < 32 || W[i] < 32) return ctx->fail(DC_E_INVALID, "%s: image %d: null pointer or side below 32 px", who, i);
+    DCCHK(check_image_size(ctx, H[i], W[i], who));
+    const int P = effective_proposals(ctx, H[i], W[i]);
+    if (!bl[i].boxes || bl[i].n < 1) return ctx->fail(DC_E_INVALID, "%s: image %d: a box list needs boxes and n >= 1 (got n = %d)", who, i, (int)bl[i].n);
+    if (bl[i].n > P)
+      return ctx->fail(DC_E_INVALID, "%s: image %d: %d boxes exceed the row capacity %d of a forward; raise num_proposals with dc_set_test_args",
+                       who, i, (int)bl[i].n, P);
+    if (cap(i) < bl[i].n)
+      return ctx->fail(DC_E_INVALID, "%s: image %d: capacity %d is below its %d boxes", who, i, cap(i), (int)bl[i].n);
+    for (int b = 0; b < bl[i].n; ++b) {
+      const float* x = bl[i].boxes + (size_t)b * 4;
+      if (!(std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]) && std::isfinite(x[3]) && x[2] > 0.f && x[3] > 0.f))
+        return ctx->fail(DC_E_INVALID, "%s: image %d: box %d (%g, %g, %g, %g) needs finite xc, yc and finite w, h > 0", who, i, b,
+                         (double)x[0], (double)x[1], (double)x[2], (double)x[3]);
+    }
+  }
+  return DC_OK;
+}
+
+// dc_forward_boxes (one image) and dc_forward_boxes_images; `who` names the entry point in the messages
+static int forward_boxes(dc_ctx* ctx, const char* who, const float* const* imgs, const int* H, const int* W, int n, int on_dev,
+                         const dc_box_list* bl, int flags, dc_result* outs) {
+  if (!ctx) return DC_E_INVALID;
+  if (!outs) return ctx->fail(DC_E_INVALID, "%s: null results", who);
+  DCCHK(check_box_lists(ctx, who, imgs, H, W, n, bl, flags, [&](int i) { return (int)outs[i].capacity; }));
+  std::vector<Dest> dst = result_dests(outs, n);
+  bool decode = false;                   // no result wants tokens: the language model is not run (as in dc_score_captions)
+  for (int i = 0; i < n; ++i) { dst[i].src = bl[i].src; decode = decode || outs[i].tokens != nullptr; }
+  return run_images(ctx, imgs, H, W, n, on_dev, false, decode ? MODE_RESULTS : MODE_NO_DECODE, dst.data(),
+                    BoxSource{bl, (flags & DC_BOXES_CLIP) != 0});
+}
+
+int dc_forward_boxes_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev,
+                            const dc_box_list* bl, int flags, dc_result* outs) {
+  return forward_boxes(ctx, "dc_forward_boxes_images", imgs, H, W, n, on_dev, bl, flags, outs);
+}
+int dc_forward_boxes(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_box_list* bl, int flags,
+                     dc_result* out) {
+  return forward_boxes(ctx, "dc_forward_boxes", &img_chw, &H, &W, 1, img_on_device, bl, flags, out);
+}
+
+int dc_extract_features_boxes(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int on_dev,
+                              const dc_box_list* bl, int flags, int capacity, float* boxes, float* feats, int32_t* K) {
+  if (!ctx) return DC_E_INVALID;
+  if (!boxes || !feats || !K) return ctx->fail(DC_E_INVALID, "dc_extract_features_boxes: null output");
+  DCCHK(check_box_lists(ctx, "dc_extract_features_boxes", imgs, H, W, n, bl, flags, [&](int) { return capacity; }));
+  std::vector<Dest> dst(n);
+  for (int i = 0; i < n; ++i)
+    dst[i] = Dest{boxes + (size_t)i * capacity * 4, nullptr, feats + (size_t)i * capacity * ctx->D, K + i, nullptr, capacity, bl[i].src};
+  return run_images(ctx, imgs, H, W, n, on_dev, false, MODE_FEATURES, dst.data(), BoxSource{bl, (flags & DC_BOXES_CLIP) != 0});
 }
 
 // run_model.lua:67-74 on the device.  Synchronous; runs on the ctx's primary stream.
@@ -1593,6 +1704,7 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
       {"lm_h", L.hstate, (int64_t)P * ctx->Hd, 4},
       {"lm_c", L.cstate, (int64_t)P * ctx->Hd, 4},
       {"survivor_rows", L.surv_total, 1, 4},
+      {"box_src", L.box_src, (int64_t)P, 4},
   };
   if (strcmp(name, "host_enqueue_us") == 0) {
     if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
@@ -1608,6 +1720,17 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
     *static_cast<int32_t*>(host_buf) = ctx->graphs ? 1 : 0;
     if (!ctx->graphs && !ctx->graph_note.empty()) ctx->err = ctx->graph_note;      // readable through dc_last_error
+    return 1;
+  }
+  if (strcmp(name, "fault_word") == 0) {
+    if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    int32_t v = -1;
+    if (ctx->fault_dev != nullptr) {
+      HIPCHK(hipSetDevice(ctx->device));
+      HIPCHK(hipStreamSynchronize(L.stream));
+      HIPCHK(hipMemcpy(&v, ctx->fault_dev, 4, hipMemcpyDeviceToHost));
+    }
+    *static_cast<int32_t*>(host_buf) = v;
     return 1;
   }
   if (strcmp(name, "arena_allocs") == 0) {

@@ -17,7 +17,7 @@ import sys
 
 import numpy as np
 
-from .run_model import ImagePipeline, xcycwh_to_xywh
+from .run_model import ImagePipeline, read_input_boxes, xcycwh_to_xywh
 
 
 def build_parser():
@@ -40,6 +40,11 @@ def build_parser():
     a("-io_threads", type=int, default=8, help="threads that decode the input files")
     a("-host_preprocess", type=int, default=0, help="1: image.scale on the host (NumPy restatement) instead of dc_preprocess_u8")
     a("-use_cudnn", type=int, default=1, help="accepted for compatibility (extract_features.lua:27); this path has no cuDNN / MIOpen to switch")
+    a("-input_boxes", default="",
+      help="a results.json as run_model writes it (results[i].img_name, results[i].boxes as x,y,w,h in the resized frame): "
+           "the codes of THOSE boxes instead of the RPN's (final NMS as usual; -final_nms_thresh 0: every box, in input "
+           "order); the output gains /src (N, M) int32, the row of the image's boxes behind every output row")
+    a("-clip_input_boxes", type=int, default=0, help="1: clip the -input_boxes to the image first and drop the invalid ones")
     a("-timing", type=int, default=0, help="1: print the images/s of the image loop at the end")
     a("-math_mode", type=int, default=0, choices=[0, 1],
       help="dc_set_math_mode: 0 = fp32 MFMA (default; the reference's arithmetic), 1 = split-bf16 (opt-in: six bf16 partial products per fp32 multiply-add on the bf16 matrix cores, fp32-class accuracy, ~1.2-1.3x images/s)")
@@ -48,11 +53,14 @@ def build_parser():
     return p
 
 
-def write_datasets(path, feats, boxes):
-    """extract_features.lua:92-96: `/feats` and `/boxes` in one HDF5 file (contiguous fp32 datasets)."""
+def write_datasets(path, feats, boxes, src=None):
+    """extract_features.lua:92-96: `/feats` and `/boxes` in one HDF5 file (contiguous fp32 datasets); with -input_boxes also
+    `/src` (int32)."""
     from .hdf5_min import write_hdf5
-    return write_hdf5(path, {"feats": np.ascontiguousarray(feats, np.float32),
-                             "boxes": np.ascontiguousarray(boxes, np.float32)})
+    sets = {"feats": np.ascontiguousarray(feats, np.float32), "boxes": np.ascontiguousarray(boxes, np.float32)}
+    if src is not None:
+        sets["src"] = np.ascontiguousarray(src, np.int32)
+    return write_hdf5(path, sets)
 
 
 def main(argv=None):
@@ -65,12 +73,13 @@ def main(argv=None):
         paths = [ln.strip() for ln in f if ln.strip()]
     if opt.max_images > 0:
         paths = paths[:opt.max_images]
+    import os
+    in_boxes = read_input_boxes(opt.input_boxes, [os.path.basename(p) for p in paths]) if opt.input_boxes else None
     from . import DenseCapModel
     if opt.synthetic_weights:
         from .weights import make_synthetic_weights
         weights = make_synthetic_weights()
     else:
-        import os
         from . import t7
         if not os.path.exists(opt.checkpoint):
             raise SystemExit("checkpoint %s not found (use -synthetic_weights 1 for random weights)" % opt.checkpoint)
@@ -85,6 +94,7 @@ def main(argv=None):
     N, M = len(paths), opt.boxes_per_image
     all_boxes = np.zeros((N, M, 4), np.float32)
     all_feats = None
+    all_src = np.zeros((N, M), np.int32) if in_boxes is not None else None
     import time
     t_loop = time.perf_counter()
     # extract_features.lua:79-91 as a pipeline: files decoded ahead on io threads, image.scale & co on the device
@@ -94,8 +104,14 @@ def main(argv=None):
         for chunk in pipe:
             for i, _, _ in chunk:
                 print("Processing image %d / %d" % (i + 1, N))
-            outs = model.extractFeatures_images_device([d for _, d, _ in chunk])
-            for (i, dev, _), (boxes_xcycwh, feats) in zip(chunk, outs):
+            if in_boxes is None:
+                outs = model.extractFeatures_images_device([d for _, d, _ in chunk])
+            else:
+                outs = model.extractFeatures_boxes_device([d for _, d, _ in chunk],
+                                                          [in_boxes[os.path.basename(paths[i])] for i, _, _ in chunk],
+                                                          clip=bool(opt.clip_input_boxes))
+            for (i, dev, _), out in zip(chunk, outs):
+                boxes_xcycwh, feats = out[:2]
                 pipe.recycle(dev)
                 if len(boxes_xcycwh) < M:     # the reference's boxes[{{1, M}}] raises on a short result as well
                     raise SystemExit("image %s: only %d boxes survive the final NMS, -boxes_per_image is %d"
@@ -104,6 +120,8 @@ def main(argv=None):
                     all_feats = np.zeros((N, M, feats.shape[1]), np.float32)
                 all_boxes[i] = xcycwh_to_xywh(boxes_xcycwh)[:M]
                 all_feats[i] = feats[:M]
+                if all_src is not None:
+                    all_src[i] = out[2][:M]
     finally:
         pipe.close()
     if opt.timing:
@@ -113,7 +131,7 @@ def main(argv=None):
                                               "host" if opt.host_preprocess else "device"))
     if all_feats is None:
         all_feats = np.zeros((0, M, 4096), np.float32)
-    write_datasets(opt.output_h5, all_feats, all_boxes)
+    write_datasets(opt.output_h5, all_feats, all_boxes, all_src)
     return 0
 
 

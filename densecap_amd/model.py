@@ -408,6 +408,103 @@ class DenseCapModel:
               "dc_forward_images")
         return rows()
 
+    # ---- caller-supplied boxes (dc_forward_boxes*, docs/SEMANTICS.md "Caller-supplied boxes") -----------------------------
+    @staticmethod
+    def _box_lists(boxes_list, caps):
+        """A DcBoxList array for one (n,4) xcycwh box array per image, each checked as the library checks it (1 <= n <=
+        capacity, finite coordinates, w, h > 0), the int32 `src` arrays the library fills, and the fp32 box arrays (to be
+        kept alive over the call)."""
+        kept, srcs = [], []
+        bl = (_lib.DcBoxList * len(caps))()
+        for i, (b, P) in enumerate(zip(boxes_list, caps)):
+            b = _np32(b)
+            if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] < 1:
+                raise ValueError("image %d: boxes must be (n,4) xc,yc,w,h with n >= 1 (got shape %s)" % (i, b.shape))
+            if b.shape[0] > P:
+                raise ValueError("image %d: %d boxes exceed the row capacity %d of a forward; raise num_proposals "
+                                 "(setTestArgs)" % (i, b.shape[0], P))
+            bad = np.flatnonzero(~(np.isfinite(b).all(axis=1) & (b[:, 2] > 0) & (b[:, 3] > 0)))
+            if bad.size:
+                raise ValueError("image %d: box %d %s needs finite xc, yc and finite w, h > 0" % (i, bad[0], b[bad[0]].tolist()))
+            src = np.full((P,), -1, np.int32)
+            bl[i].boxes = b.ctypes.data_as(_lib.c_float_p)
+            bl[i].n = b.shape[0]
+            bl[i].src = src.ctypes.data_as(_lib.c_int32_p)
+            kept.append(b); srcs.append(src)
+        return bl, srcs, kept
+
+    def _forward_boxes(self, imgs, boxes_list, on_device, clip, single=False):
+        if len(boxes_list) != len(imgs):
+            raise ValueError("%d images but %d box lists" % (len(imgs), len(boxes_list)))
+        if len(imgs) == 0:
+            return []
+        caps = [self._capacity(a.shape[1], a.shape[2]) for a in imgs]
+        bl, srcs, _kept = self._box_lists(boxes_list, caps)
+        res, rows = self._results(caps)
+        flags = _lib.DC_BOXES_CLIP if clip else 0
+        ptrs, H, W = self._image_list(imgs)
+        if single:
+            check(self.ctx.h, self.lib.dc_forward_boxes(self.ctx.h, ptrs[0], H[0], W[0], on_device, bl, flags, res),
+                  "dc_forward_boxes")
+        else:
+            check(self.ctx.h, self.lib.dc_forward_boxes_images(self.ctx.h, ptrs, H, W, len(imgs), on_device, bl, flags, res),
+                  "dc_forward_boxes_images")
+        return [r + (s[:len(r[0])].copy(),) for r, s in zip(rows(), srcs)]
+
+    def forward_boxes(self, img, boxes, clip=False):
+        """The model after the RPN on the caller's boxes (dc_forward_boxes): boxes (n,4) xc,yc,w,h in the pixel frame of
+        `img` (the frame forward_raw returns), 1 <= n <= num_proposals.  clip: box_utils.clip_boxes first, invalid boxes
+        dropped (not for boxes that came out of the library: the reference's clip takes a pixel off w and h every time).
+        Returns (boxes (K,4), scores (K,), tokens (K,T), src (K,)): src[r] = the row of `boxes` behind result row r; rows
+        are in input order when final_nms_thresh <= 0, else in decreasing objectness after the final NMS."""
+        self._push_test_args()
+        return self._forward_boxes([self._check_input(img)], [boxes], 0, clip, single=True)[0]
+
+    def forward_boxes_device(self, dev_img, boxes, clip=False):
+        """forward_boxes on an image that is already on the device (ops.DeviceArray (3,H,W) float32); boxes stay host memory."""
+        self._push_test_args()
+        return self._forward_boxes([dev_img], [boxes], 1, clip, single=True)[0]
+
+    def forward_boxes_images(self, imgs, boxes_list, clip=False):
+        """forward_boxes over a list of images of any sizes, boxes_list[i] the boxes of imgs[i] (dc_forward_boxes_images:
+        pipelined over the lanes, equal-sized runs grouped).  Returns a list of (boxes, scores, tokens, src)."""
+        self._push_test_args()
+        return self._forward_boxes([self._check_input(im) for im in imgs], list(boxes_list), 0, clip)
+
+    def forward_boxes_images_device(self, dev_imgs, boxes_list, clip=False):
+        """forward_boxes_images on device-resident images (ops.preprocess_u8)."""
+        self._push_test_args()
+        return self._forward_boxes(list(dev_imgs), list(boxes_list), 1, clip)
+
+    def _extract_features_boxes(self, imgs, boxes_list, on_device, clip):
+        n = len(imgs)
+        if len(boxes_list) != n:
+            raise ValueError("%d images but %d box lists" % (n, len(boxes_list)))
+        if n == 0:
+            return []
+        caps = [self._capacity(a.shape[1], a.shape[2]) for a in imgs]
+        bl, srcs, _kept = self._box_lists(boxes_list, caps)
+        cap = max(b.n for b in bl)                       # rows per image of the output arrays: no image returns more than it passed
+        boxes = np.zeros((n, cap, 4), np.float32); feats = np.zeros((n, cap, self.fc_dim), np.float32)
+        K = np.zeros((n,), np.int32)
+        check(self.ctx.h, self.lib.dc_extract_features_boxes(self.ctx.h, *self._image_list(imgs), n, on_device, bl,
+                                                             _lib.DC_BOXES_CLIP if clip else 0, cap, boxes.ctypes.data,
+                                                             feats.ctypes.data, K.ctypes.data_as(_lib.c_int32_p)),
+              "dc_extract_features_boxes")
+        return [(boxes[i, :K[i]].copy(), feats[i, :K[i]].copy(), srcs[i][:K[i]].copy()) for i in range(n)]
+
+    def extractFeatures_boxes(self, imgs, boxes_list, clip=False):
+        """fc7 codes of the caller's boxes (dc_extract_features_boxes): list of (boxes after regression (K,4), feats
+        (K,fc_dim), src (K,)) per image.  The final NMS runs as in extractFeatures, except that final_nms_thresh <= 0 means
+        none: every box, in input order (src = 0..n-1)."""
+        self._push_test_args()
+        return self._extract_features_boxes([self._check_input(im) for im in imgs], list(boxes_list), 0, clip)
+
+    def extractFeatures_boxes_device(self, dev_imgs, boxes_list, clip=False):
+        """extractFeatures_boxes on device-resident images."""
+        self._push_test_args()
+        return self._extract_features_boxes(list(dev_imgs), list(boxes_list), 1, clip)
+
     def extractFeatures_images_device(self, dev_imgs):
         """extractFeatures_images on device-resident images (ops.preprocess_u8): list of (boxes, feats)."""
         self._push_test_args()

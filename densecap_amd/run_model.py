@@ -58,6 +58,10 @@ def build_parser():
     a("-io_threads", type=int, default=8, help="threads that decode the input files / write the output images")
     a("-host_preprocess", type=int, default=0,
       help="1: image.scale on the host (the NumPy restatement) instead of dc_preprocess_u8; same bits, ~100x slower")
+    a("-input_boxes", default="",
+      help="a results.json as this tool writes it: every image is described on ITS boxes there (results[i].img_name, "
+           "results[i].boxes as x,y,w,h in the resized frame) instead of the RPN's; the output gains `src` per image")
+    a("-clip_input_boxes", type=int, default=0, help="1: clip the -input_boxes to the image first and drop the invalid ones")
     a("-timing", type=int, default=0, help="1: print the images/s of the image loop (files in -> results out) at the end")
     a("-math_mode", type=int, default=0, choices=[0, 1],
       help="dc_set_math_mode: 0 = fp32 MFMA (default; the reference's arithmetic), 1 = split-bf16 (opt-in: six bf16 partial products per fp32 multiply-add on the bf16 matrix cores, fp32-class accuracy, ~1.2-1.3x images/s)")
@@ -165,6 +169,36 @@ def xcycwh_to_xywh(boxes):
     hh = (b[:, 3] - np.float32(1)) / np.float32(2)
     x1 = -hw + b[:, 0]; y1 = -hh + b[:, 1]; x2 = hw + b[:, 0]; y2 = hh + b[:, 1]
     return np.stack([x1, y1, x2 - x1 + np.float32(1), y2 - y1 + np.float32(1)], 1)
+
+
+def xywh_to_xcycwh(boxes):
+    """The algebraic inverse of xcycwh_to_xywh above, in fp32: w and h are kept, xc = x + (w - 1) / 2, yc = y + (h - 1) / 2."""
+    b = np.asarray(boxes, np.float32).reshape(-1, 4)
+    hw = (b[:, 2] - np.float32(1)) / np.float32(2)
+    hh = (b[:, 3] - np.float32(1)) / np.float32(2)
+    return np.stack([b[:, 0] + hw, b[:, 1] + hh, b[:, 2], b[:, 3]], 1)
+
+
+def read_input_boxes(path, names):
+    """-input_boxes: {img_name: (n,4) fp32 xc,yc,w,h} from a file shaped like the results.json this tool writes.  Every image
+    of `names` needs an entry with at least one box; the first that has none is refused by name.  Lists are keyed by file
+    name, as results.json is: a name that the file lists twice, or that two input paths share, is refused too."""
+    with open(path) as f:
+        listed = {}
+        for r in json.load(f)["results"]:
+            if r["img_name"] in listed:
+                raise SystemExit("-input_boxes %s lists image %s more than once" % (path, r["img_name"]))
+            listed[r["img_name"]] = r["boxes"]
+    out = {}
+    for name in names:
+        if name in out:
+            raise SystemExit("-input_boxes: two input images are called %s; box lists are looked up by file name" % name)
+        if name not in listed:
+            raise SystemExit("-input_boxes %s has no entry for image %s" % (path, name))
+        if len(listed[name]) == 0:
+            raise SystemExit("-input_boxes %s lists no boxes for image %s" % (path, name))
+        out[name] = xywh_to_xcycwh(listed[name])
+    return out
 
 
 def get_input_images(opt):
@@ -374,9 +408,10 @@ def main(argv=None):
             print("warning: %s -- reading %s again without the writer-habit checks" % (e, opt.checkpoint), file=sys.stderr)
             ck = t7.load(opt.checkpoint, strict=False)
         weights = t7.weights_from_checkpoint(ck)
-    model = DenseCapModel(weights, device=opt.gpu)                      # utils.setup_gpus + model:convert
     paths = get_input_images(opt)
     num = min(len(paths), opt.max_images)
+    in_boxes = read_input_boxes(opt.input_boxes, [os.path.basename(p) for p in paths[:num]]) if opt.input_boxes else None
+    model = DenseCapModel(weights, device=opt.gpu)                      # utils.setup_gpus + model:convert
     # one image: single-image mode (lowest latency, like the reference); several: pipelined over the lanes, runs of
     # equal-sized images sharing their dense launches -- results identical to one-by-one processing
     model.setLanes(1 if num == 1 else opt.lanes)
@@ -403,7 +438,7 @@ def main(argv=None):
 
     def finish(i, rgb, out):
         """run_model.lua:78-95,170-180 for one image (runs on an io thread while the device works on the next chunk)"""
-        boxes, scores, tokens = out
+        boxes, scores, tokens = out[:3]
         xywh = xcycwh_to_xywh(boxes)
         captions = model.decodeSequence(tokens)
         name = os.path.basename(paths[i])
@@ -414,13 +449,20 @@ def main(argv=None):
             Image.fromarray(rgb).save(os.path.join(opt.output_vis_dir, name))
             rj = result_to_json(xywh, scores, captions)
             rj["img_name"] = name
+            if in_boxes is not None:
+                rj["src"] = [int(v) for v in out[3]]         # the row of the image's -input_boxes behind every result row
             results[i] = rj
 
     try:
         for chunk in pipe:
             for i, _, _ in chunk:
                 print("%d/%d processing image %s" % (i + 1, num, paths[i]))
-            outs = model.forward_images_device([d for _, d, _ in chunk])
+            if in_boxes is None:
+                outs = model.forward_images_device([d for _, d, _ in chunk])
+            else:
+                outs = model.forward_boxes_images_device([d for _, d, _ in chunk],
+                                                         [in_boxes[os.path.basename(paths[i])] for i, _, _ in chunk],
+                                                         clip=bool(opt.clip_input_boxes))
             for (i, dev, rgb), out in zip(chunk, outs):
                 pipe.recycle(dev)
                 writes.append(pool.submit(finish, i, rgb, out))

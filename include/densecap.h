@@ -208,6 +208,47 @@ int dc_extract_features(dc_ctx* ctx, const float* img_chw, int H, int W, int img
 int dc_extract_features_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n,
                                int imgs_on_device, int capacity, float* boxes, float* feats, int32_t* K);
 
+/* ---- caller-supplied boxes ------------------------------------------------ */
+/* DenseCapModel:updateOutput's test path (DenseCapModel.lua:242-275) with the caller's boxes in the place of the
+ * localisation layer's roi_boxes: bilinear RoI pooling on conv5_3, fc6 / fc7, objectness and box regression,
+ * final_boxes = ApplyBoxTransform(boxes, final_trans), the language model and the final NMS (final_nms_thresh > 0).  The
+ * RPN convolution, its heads, the anchor decode and the RPN NMS are not run; everything after them behaves as in
+ * dc_forward_test under the same settings (caption order, beam size, math mode, lanes, groups, graph replay).  It is the
+ * inference form of LocalizationLayer:_forward_train's ground-truth path (LocalizationLayer.lua:383-527).
+ *  - boxes: HOST memory, (n,4) fp32 xc,yc,w,h, 1-based pixels of the RESIZED image handed to the call -- the frame
+ *    dc_result.boxes is written in: an output of the library is a valid input;
+ *  - 1 <= n <= P, the row capacity of a forward of that image size (num_proposals of dc_set_test_args; every GEMM is
+ *    planned as for a forward whose RPN NMS kept n boxes).  More boxes are refused: raise num_proposals;
+ *  - a non-finite coordinate, w <= 0 or h <= 0 in any box refuses the whole call (DC_E_INVALID, dc_last_error names the
+ *    first bad box) before anything is enqueued;
+ *  - flags = 0: the boxes are used as given, like the ground-truth boxes of _forward_train.  DC_BOXES_CLIP:
+ *    box_utils.clip_boxes(boxes, {1,1,W,H}, 'xcycwh') first (box_utils.lua:486-523, the RPN path's clip: every box loses
+ *    one pixel of w and h, so do NOT set it for boxes that came out of the library), boxes that come out invalid are
+ *    dropped and the rest keep their order (LocalizationLayer.lua:272-300); all dropped: K = 0, DC_OK;
+ *  - src (optional, per list): src[r] = 0-based index, into the caller's array and counted before any drop, of the box
+ *    behind result row r.  Rows come back in input order when final_nms_thresh <= 0 (DenseCapModel.lua:261), else in
+ *    decreasing objectness -- the raw logits of the recognition net, which say how box-like the model finds a region: a
+ *    caller who wants EVERY box described sets final_nms_thresh to 0;
+ *  - the matching result needs capacity >= n; out->tokens == NULL (in every result of the call) skips the caption decode,
+ *    as in dc_score_captions. */
+#define DC_BOXES_CLIP 1
+typedef struct dc_box_list {
+  const float* boxes; /* in  (n,4) xc,yc,w,h, host memory */
+  int32_t n;          /* in  */
+  int32_t* src;       /* out (capacity of the matching result) or NULL */
+} dc_box_list;
+int dc_forward_boxes(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_box_list* bl, int flags,
+                     dc_result* out);
+/* The loop over n images of possibly different sizes, bl[i] the boxes of image i (each its own n); pipelined over the lanes
+ * and grouped (dc_set_group) like dc_forward_images.  Results are those of dc_forward_boxes image by image. */
+int dc_forward_boxes_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
+                            const dc_box_list* bl, int flags, dc_result* outs);
+/* dc_extract_features_images on the caller's boxes: image i writes K[i] rows (box after regression, fc7 code) to
+ * boxes + i*capacity*4 and feats + i*capacity*fc_dim, capacity >= every n.  The final NMS runs as in extractFeatures
+ * (DenseCapModel.lua:285-304) EXCEPT that final_nms_thresh <= 0 means no NMS here: all rows, in input order -- a caller of
+ * this function wants the codes of the boxes it passed. */
+int dc_extract_features_boxes(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
+                              const dc_box_list* bl, int flags, int capacity, float* boxes, float* feats, int32_t* K);
 /* run_model.lua:67-74 (`run_image` before the forward) on the device: image.load's byte -> float conversion (byte / 255),
  * image.scale(img, image_size) -- torch/image's scaleBilinear: scaleLinear_rowcol along the width, then the height; linear
  * interpolation where a side grows, area averaging where it shrinks; the longer side becomes image_size --, RGB -> BGR,

@@ -8,6 +8,8 @@ Same method names / return values as the reference:
   model:evaluate()
   boxes, scores, captions = model:forward_test(img)                         (:319-327)
   boxes, feats = model:extractFeatures(img)                                 (:285-304)
+and, without a counterpart among the reference's methods:
+  boxes, scores, captions, src = model:forward_boxes(img, boxes[, clip])    the test path (:242-275) on the caller's boxes
   model.nets.language_model:decodeSequence(seq)                             (LanguageModel.lua:86-103)
 
 Construction: DenseCapModelHIP.fromCheckpoint(checkpoint.model, gpu) walks the Torch7
@@ -283,6 +285,33 @@ function Model:scoreCaptions(input, queries)
   if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, torch.FloatTensor() end
   local seq = tokens[{{1, K}}]:long()
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), loglik[{{1, K}}]:clone()
+end
+
+-- The model after the RPN on the caller's boxes (dc_forward_boxes; DenseCapModel.lua:242-275 with `boxes` in the place of
+-- the localisation layer's roi_boxes).  boxes: FloatTensor (n, 4) xc,yc,w,h in the pixel frame of `input` (the frame
+-- forward_test returns), 1 <= n <= num_proposals; clip (optional): box_utils.clip_boxes first, invalid boxes dropped.
+-- Returns boxes, scores, captions and src: LongTensor (K), the 1-based row of `boxes` behind each result row.
+function Model:forward_boxes(input, boxes, clip)
+  self:_push_test_args()
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  assert(boxes:dim() == 2 and boxes:size(2) == 4, 'boxes must be (n, 4) xc,yc,w,h')
+  local img = input:float():contiguous()
+  local inb = boxes:float():contiguous()
+  local H, W, T = img:size(3), img:size(4), self.seq_length
+  local P = self:_capacity(H, W)
+  local out_boxes, scores = torch.FloatTensor(P, 4), torch.FloatTensor(P, 1)
+  local tokens, src = torch.IntTensor(P, T), torch.IntTensor(P)
+  local r = ffi.new('dc_result')
+  r.capacity = P
+  r.boxes, r.scores = torch.data(out_boxes), torch.data(scores)
+  r.tokens = torch.data(tokens)
+  local bl = ffi.new('dc_box_list')
+  bl.boxes, bl.n, bl.src = torch.data(inb), inb:size(1), torch.data(src)
+  hip.check(self.ctx, C.dc_forward_boxes(self.ctx, fptr(img), H, W, 0, bl, clip and 1 or 0, r), 'dc_forward_boxes')
+  local K = r.K
+  if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, torch.LongTensor() end
+  local seq = tokens[{{1, K}}]:long()
+  return out_boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), src[{{1, K}}]:long():add(1)
 end
 
 function Model:extractFeatures(input)

@@ -51,6 +51,15 @@ int dc_extract_features(dc_ctx* ctx, const float* img_chw, int H, int W, int img
                         int capacity, float* boxes, float* feats, int32_t* K);
 int dc_extract_features_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n,
                                int imgs_on_device, int capacity, float* boxes, float* feats, int32_t* K);
+typedef struct dc_box_list {
+  const float* boxes; int32_t n; int32_t* src;
+} dc_box_list;
+int dc_forward_boxes(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_box_list* bl, int flags,
+                     dc_result* out);
+int dc_forward_boxes_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
+                            const dc_box_list* bl, int flags, dc_result* outs);
+int dc_extract_features_boxes(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
+                              const dc_box_list* bl, int flags, int capacity, float* boxes, float* feats, int32_t* K);
 int dc_preprocess_size(int H0, int W0, int image_size, int* H, int* W);
 int dc_preprocess_u8(dc_ctx* ctx, const uint8_t* rgb_hwc, int H0, int W0, int on_device, int image_size, float* out_chw_dev,
                      uint8_t* scaled_rgb_dev);
