@@ -42,6 +42,10 @@ class DcBoxList(C.Structure):
     _fields_ = [("boxes", c_float_p), ("n", C.c_int32), ("src", c_int32_p)]
 
 
+class DcSampleOpts(C.Structure):
+    _fields_ = [("num_samples", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -124,6 +128,10 @@ _SIGS = {
     "dc_op_lm_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dc_score_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.POINTER(DcResult), C.c_void_p]),
+    "dc_sample_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcSampleOpts),
+                                     C.POINTER(DcResult), C.c_void_p, C.c_void_p]),
+    "dc_op_lm_sample_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DcSampleOpts), C.c_void_p,
+                                    C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

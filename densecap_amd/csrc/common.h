@@ -1,6 +1,7 @@
 // Shared declarations for libdensecap_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -18,6 +19,30 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float th_expf(float x) { return (float)exp((double)x); }
 __device__ __forceinline__ float th_sigmoidf(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
 __device__ __forceinline__ float th_tanhf(float x) { return (float)tanh((double)x); }
+
+// ---- the noise of caption sampling (docs/SEMANTICS.md, "Sampling captions") ---------------------------------------------------
+// Philox4x32-10 (the Random123 function): counter (c0..c3), key (k0, k1) -> four 32-bit words.  Counter-based: a word is a pure
+// function of its coordinates, whichever lane, tile or launch asks for it.
+struct Philox4 { uint32_t w[4]; };
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+// Standard Gumbel noise of 32 random bits: u = ((bits >> 9) + 0.5) * 2^-23 lies strictly inside (0, 1) and is exact in fp32, and so
+// is w = 1 - u; g = -log(-log(u)) with the inner logarithm taken as log1p(-w), so that u next to 1 loses nothing (log of a number
+// next to 1 would).  Within 1e-5 of the double-precision value for all 2^23 values of u
+// (tests/test_gpu_sample.py evaluates the copy compiled into mfma_gemm.hip, the one that draws).
+__device__ __forceinline__ float gumbel_from_bits(uint32_t bits) {
+  const uint32_t k = bits >> 9;
+  const float w = ((float)((1u << 23) - k) - 0.5f) * 0x1p-23f;
+  return -logf(-log1pf(-w));
+}
 
 // (shared by boxes.hip and the recognition heads: one definition of the conversion every NMS input goes through)
 __device__ __forceinline__ void corners(float xc, float yc, float w, float h, float& x1, float& y1, float& x2,
@@ -80,6 +105,16 @@ struct GemmDesc {
   const float* rowterm = nullptr;
   const int32_t* rowidx = nullptr;   // values are 1-based token ids -> row = id-1
   int rowterm_ld = 0;
+  // Sampling epilogue (densecap.hip::lm_sample_n; docs/SEMANTICS.md "Sampling captions"): samp_t >= 1 (the step) together with
+  // amax_val and rowidx selects it in the place of the log-sum-exp.  rowidx[2m], rowidx[2m + 1] = the row's (r, s) of the noise
+  // counter; every (row, 32-column half) writes five floats to amax_val[m * amax_ld + 5 * slot + ..]: the log-sum-exp partial
+  // (max v, sum exp(v - max)) exactly as below, then the best perturbed entry (v * samp_inv_temp + g, its column as int bits, v at
+  // that column), first maximum on ties; samp_inv_temp == 0: no noise and no scaling (the greedy rule).  amax_ld >= 10 per
+  // 64-column tile.  The four fields sit in alignment holes, as `bf3` does: the struct keeps its size, so neither a field nor a
+  // kernel argument behind the descriptor moves and no existing kernel's code changes.
+  // Where they are (offsets in bytes; the remaining hole is at 196, behind sk_np): samp_t 100 (behind rowterm_ld), samp_seed_lo 132
+  // (behind amax_n), samp_seed_hi 148 (behind splitk), samp_inv_temp 180 (behind walk).
+  int samp_t = 0;
   // rowidx together with amax_val (and no rowterm): fused row LOG-SUM-EXP instead of the arg-max (teacher-forced scoring,
   // densecap.hip::lm_score).  rowidx[m] = the row's 1-based target token (column rowidx[m] - 1 < amax_n); every (row, 32-column
   // half) writes its partial (max v, sum exp(v - max)) over the real columns to amax_val[m * amax_ld + 2 * slot + {0, 1}] (slot as
@@ -96,11 +131,13 @@ struct GemmDesc {
   // entries; columns [amax_cols, N) are stored raw to C[m*ldc + (n - amax_cols)].  amax_cols = 0: every column.
   int amax_cols = 0;
   int amax_n = 0;
+  uint32_t samp_seed_lo = 0;  // sampling epilogue: the noise key (seed & 0xffffffff, seed >> 32) ...
   // optional device-side row count: effective M = min(M, *m_dev); workgroups past it exit at once
   const int32_t* m_dev = nullptr;
   // split-K (K-split 128x128 kernel only): `splitk` workgroups share one tile, each sums a contiguous K range
   // and writes its raw partial tile to splitk_ws[(slice*M + m)*N + n]; launch_splitk_reduce finishes the job
   int splitk = 1;
+  uint32_t samp_seed_hi = 0;  // ... its upper half
   float* splitk_ws = nullptr;
   // stream-K over the tiles of rows [m_begin, M) (K-split kernel, launch_mfma_gemm_sk): sk_lo[0..sk_wgs] = unit offsets
   // of the workgroups on the line of K units (unit = 2 K-tiles, sk_np units per tile, tiles n-fastest); sk_slots =
@@ -112,6 +149,7 @@ struct GemmDesc {
   int stagger = 0;            // measurement hook (dc_debug_set "stagger"): workgroups start after a pseudo-random pause of up to this many 64-cycle sleeps
   int epi_wide = 1;           // interior tiles of plain epilogues leave as 16-byte stores staged through the wave's LDS (dc_debug_set "epi_wide": 0 = dword stores)
   int walk = 0;               // measurement hook (dc_debug_set "walk"): 128x64 launches run one workgroup per slot that walks its tiles
+  float samp_inv_temp = 0.f;  // sampling epilogue: 1 / temperature in fp32, 0 = the greedy rule
   const int* sk_lo = nullptr;
   int sk_np = 0;
   float* sk_slots = nullptr;
@@ -122,6 +160,9 @@ struct GemmDesc {
   int m_begin = 0;
   int a_rows = 0;
 };
+static_assert(offsetof(GemmDesc, samp_t) == 100 && offsetof(GemmDesc, samp_seed_lo) == 132 && offsetof(GemmDesc, samp_seed_hi) == 148 &&
+              offsetof(GemmDesc, samp_inv_temp) == 180, "the sampling fields sit in the alignment holes listed at samp_t");
+static_assert(sizeof(GemmDesc) == 232, "GemmDesc is a kernel argument: a new field goes into an alignment hole or every kernel's argument offsets move");
 // C = act(sum_s ws[s] + bias): fixed summation order s = 0..S-1
 // m_dev (optional): device-side row count, rows >= *m_dev are left alone (their partials were never written)
 hipError_t launch_splitk_reduce(const float* ws, int S, const float* bias, float* C, int M, int N, int ldc, int relu,
@@ -203,6 +244,18 @@ hipError_t launch_repeat_rows2(const float* src_a, const float* src_b, size_t le
                                hipStream_t s);
 hipError_t launch_lse_step_tail(const float* part, int nslots, int ld, const int32_t* tgt, int end_tok, const float* xg,
                                 const float* gates_pre, float* c, float* h, double* acc, int n, int Hd, hipStream_t s);
+// Sampling step tail (densecap.hip::lm_sample_n), one workgroup per row m < n, on the partials of the sampling epilogue
+// (GemmDesc::samp_t; part[m*ld + 5s + 0..4] = max, sum, best perturbed score, its column, the logit there): tok = 1 + column of
+// the best perturbed entry over the slots (first maximum on ties); lse as launch_lse_step_tail forms it; with fin[m] == 0:
+// seq[m*T + t] = tok, acc[m] += (double)logit - lse, and fin[m] = 1 if tok == end_tok; with fin[m] != 0: seq[m*T + t] = 0.
+// Then, gates_pre != null, the LSTM point-wise update of lstm_step_tail with tok fed, finished or not (every row runs all T steps).
+hipError_t launch_sample_step_tail(const float* part, int nslots, int ld, int end_tok, const float* xg, const float* gates_pre,
+                                   float* c, float* h, double* acc, uint8_t* fin, int32_t* seq, int T, int t, int n, int Hd,
+                                   hipStream_t s);
+// test hooks of the sampling noise (mfma_gemm.hip, so that the build that draws the words is the one tested; dc_debug_fetch): out[i] = gumbel_from_bits((first + i) << 9), i < count;
+// bits[i] = the Philox word of the coordinates srtv[4i..4i+3] = (s, r, t, v) under `seed`
+hipError_t launch_sample_noise_gumbel(uint32_t first, size_t count, float* out, hipStream_t s);
+hipError_t launch_sample_noise_bits(uint64_t seed, const int32_t* srtv, size_t count, uint32_t* bits, hipStream_t s);
 // split-bf16 mode: W (N, K) fp32 -> 3 x N x K bf16 planes, k permuted per 32-tile as the kernels read them (elementwise.hip)
 hipError_t launch_split_planes(const float* W, uint16_t* planes, size_t N, int K, hipStream_t s);
 // objectness + box regression heads + final ApplyBoxTransform (DenseCapModel.lua:134,139-140)

@@ -4,6 +4,7 @@
 // used to software-pipeline run_model.lua's image loop), and the per-stage HIP events.
 // The whole forward of one image is enqueued on one stream without host round trips
 // (box counts stay on the device); the host waits once, for the result copy.
+#include <errno.h>
 #include <limits.h>
 #include <stdarg.h>
 #include <stddef.h>
@@ -168,6 +169,7 @@ struct dc_ctx {
   double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last forward call (run_images)
   int64_t beam_chunk_floats = (int64_t)1 << 28;   // cap of the beam search's full-logits buffer (dc_debug_set)
   int64_t score_rows_cap = 0;      // rows (region x query) one chunk of dc_score_captions / dc_op_lm_score may hold (dc_debug_set); 0 = ~512 MiB of scratch
+  int64_t sample_rows_cap = 0;     // rows (region x draw) one chunk of dc_sample_captions / dc_op_lm_sample_n may hold (dc_debug_set); 0 = ~512 MiB of scratch
   uint32_t* fault_dev = nullptr;   // sticky device word: kFaultStreamK / kFaultNmsBand (common.h), checked with the results
   bool graphs = false;      // dc_set_graph_replay: repeated forwards of one shape are relaunched as a captured hipGraph
   uint64_t weights_epoch = 0;
@@ -805,6 +807,121 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
   if (e != hipSuccess) return ctx->fail(DC_E_HIP, "lm_score: %s", hipGetErrorString(e));
+  return DC_OK;
+}
+
+// the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
+int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
+  if (o == nullptr) return ctx->fail(DC_E_INVALID, "%s: null options", who);
+  if (o->num_samples < 1 || o->num_samples > 256)
+    return ctx->fail(DC_E_INVALID, "%s: num_samples must be in 1..256 (got %d)", who, (int)o->num_samples);
+  const float tp = o->temperature;
+  if (!(tp == 0.f || (tp >= 0.01f && tp <= 100.f)))
+    return ctx->fail(DC_E_INVALID, "%s: temperature must be 0 or in [0.01, 100] (got %g)", who, (double)tp);
+  if (tp == 0.f && o->num_samples != 1)
+    return ctx->fail(DC_E_INVALID, "%s: temperature 0 is the greedy rule, num_samples must be 1 (got %d)", who, (int)o->num_samples);
+  return DC_OK;
+}
+
+// Sampling captions: LanguageModel:sample with sample_argmax = false (LanguageModel.lua:40-41,328-333) -- S draws per region, each
+// word drawn from SoftMax(scores / temperature) by the Gumbel-max rule with counter-based noise, and the model's own
+// log-probability of every draw (definition: docs/SEMANTICS.md, "Sampling captions").
+// Schedule (lm_score's shape):
+//   per region (n rows): enc, image step, h_0.Wh, START step -- the state before the first word does not depend on the draw
+//   per chunk of whole draws (rows = s * n + i): copy the START state to every row, then for step t = 1 .. T:
+//   [sampling partials of h.Wout^T + b | G = h.Wh] ONE GEMM over all rows of the chunk (the last step without the Wh half) +
+//   sample_step_tail (word, log p added to the row's double sum, LSTM step with the word fed).  Finished rows stay in the launch:
+//   where a row ends is data-dependent, there is no prefix to cut.
+// Planned like lm_score (min(n, kScorePlanRows) rows, no split-K workspace), noise a function of (seed, s, r, t, column) alone
+// with r = row_ids[i] (or i): a draw does not depend on S, the chunking, or the other regions in the call.
+// Always fp32 MFMA and eager.  row_ids: host (n) or null; samples (n, S, T) and logprob (n, S): host.
+int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts& o,
+                int32_t* samples, float* logprob) {
+  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, D = ctx->D, V1pad = ctx->V1pad, T = ctx->T, S = o.num_samples;
+  const int nslots = V1pad / 32, ld = 5 * nslots;
+  struct MathGuard {      // sampling is fp32 whatever dc_set_math_mode says
+    Settings& c; int saved;
+    ~MathGuard() { c.math_mode = saved; }
+  } mg{ctx->cfg, ctx->cfg.math_mode};
+  ctx->cfg.math_mode = 0;
+  // chunk of whole draws under the row cap
+  const size_t row_bytes = (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1;
+  const int64_t cap = ctx->sample_rows_cap > 0 ? ctx->sample_rows_cap : (int64_t)(((size_t)512 << 20) / row_bytes);
+  const int dchunk = (int)std::max<int64_t>(1, std::min<int64_t>(S, cap / n));
+  const int plan = std::min(n, kScorePlanRows);       // see lm_score
+  const size_t rmax = (size_t)dchunk * n;
+  if (rmax > (size_t)INT32_MAX / (size_t)std::max(ld, 4 * Hd))
+    return ctx->fail(DC_E_INVALID, "lm_sample_n: %d regions are too many rows for one launch", n);
+  float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr, *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;
+  double* acc = nullptr;
+  int32_t *seq = nullptr, *keys = nullptr;
+  uint8_t* fin = nullptr;
+  const std::vector<Carve> cv = {
+      {(void**)&enc, (size_t)n * E * 4},    {(void**)&g0, (size_t)n * 4 * Hd * 4}, {(void**)&h0, (size_t)n * Hd * 4},
+      {(void**)&c0, (size_t)n * Hd * 4},    {(void**)&h, rmax * Hd * 4},            {(void**)&c, rmax * Hd * 4},
+      {(void**)&gates, rmax * 4 * Hd * 4},  {(void**)&part, rmax * ld * 4},         {(void**)&acc, rmax * 8},
+      {(void**)&seq, rmax * T * 4},         {(void**)&keys, rmax * 8},              {(void**)&fin, rmax},
+  };
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+  carve(cv, base);
+  auto body = [&]() -> int {
+    // ---- per region: image step and START step (lm_sample_parts' first four launches) ----
+    DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, enc, n, E, D, 1, Ws(), plan));
+    DCCHK(linear(ctx, s, enc, ctx->wxT, ctx->lstm_b, g0, n, 4 * Hd, E, 0, Ws(), plan));
+    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, g0, c0, h0, n, nullptr, Hd, 1, nullptr, 1, 0, s));
+    DCCHK(linear(ctx, s, h0, ctx->whT, nullptr, g0, n, 4 * Hd, Hd, 0, Ws(), plan));
+    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, g0, c0, h0, n, nullptr, Hd, 0, nullptr, 1, 0, s));
+    std::vector<int32_t> kh, sh;
+    std::vector<double> ah;
+    for (int a = 0; a < S; a += dchunk) {
+      const int nd = std::min(dchunk, S - a);
+      const size_t rows = (size_t)nd * n;
+      kh.resize(rows * 2);
+      for (int i = 0; i < nd; ++i)
+        for (int r = 0; r < n; ++r) {
+          kh[2 * ((size_t)i * n + r)] = row_ids ? row_ids[r] : r;
+          kh[2 * ((size_t)i * n + r) + 1] = a + i;
+        }
+      HIPCHK(hipMemcpyAsync(keys, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemsetAsync(acc, 0, rows * 8, s));
+      HIPCHK(hipMemsetAsync(fin, 0, rows, s));
+      KCHK(launch_repeat_rows2(h0, c0, (size_t)n * Hd, nd, h, c, s));      // the START state of every draw's row block
+      for (int t = 1; t <= T; ++t) {
+        const bool last = t == T;
+        GemmDesc v;
+        v.A = h; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = (int)rows; v.K = Hd; v.plan_M = plan;
+        v.amax_val = part; v.amax_ld = ld; v.rowidx = keys;
+        v.samp_t = t; v.samp_seed_lo = (uint32_t)(o.seed & 0xffffffffu); v.samp_seed_hi = (uint32_t)(o.seed >> 32);
+        v.samp_inv_temp = o.temperature == 0.f ? 0.f : 1.f / o.temperature;
+        if (last) {
+          v.N = V1; v.ldc = V1;
+        } else {
+          v.N = V1pad + 4 * Hd; v.amax_cols = V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
+        }
+        DCCHK(run_gemm(ctx, v, s));
+        KCHK(launch_sample_step_tail(part, nslots, ld, V1, ctx->xg, last ? nullptr : gates, c, h, acc, fin, seq, T, t - 1,
+                                     (int)rows, Hd, s));
+      }
+      ah.resize(rows);
+      sh.resize(rows * T);
+      HIPCHK(hipMemcpyAsync(ah.data(), acc, rows * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(sh.data(), seq, rows * T * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (int i = 0; i < nd; ++i)
+        for (int r = 0; r < n; ++r) {
+          logprob[(size_t)r * S + a + i] = (float)ah[(size_t)i * n + r];
+          memcpy(samples + ((size_t)r * S + a + i) * T, sh.data() + ((size_t)i * n + r) * T, (size_t)T * 4);
+        }
+    }
+    return DC_OK;
+  };
+  const int rc = body();
+  const hipError_t e = hipStreamSynchronize(s);
+  hipFree(base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "lm_sample_n: %s", hipGetErrorString(e));
   return DC_OK;
 }
 
@@ -1675,8 +1792,52 @@ int dc_mfma_profile(dc_ctx* ctx, int reset, int64_t* launches, double* total_ms,
   return DC_OK;
 }
 
+// the noise of caption sampling as the device computes it (dc_debug_fetch "sample_gumbel@..." / "sample_bits@..."):
+// what 0: host_out[i] = g of the 23-bit index first + i; what 1: host_out[i] = the Philox word of (s, r, t, v) = srtv[4i..4i+3]
+static int64_t sample_noise_debug(dc_ctx* ctx, int what, uint64_t seed, const int32_t* srtv, uint32_t first, int64_t count,
+                                  void* host_out) {
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  if (!host_out || count < 0 || count > ((int64_t)1 << 23) || (what != 0 && what != 1) || (what == 1 && !srtv) ||
+      (what == 0 && (int64_t)first + count > ((int64_t)1 << 23)))
+    return ctx->fail(DC_E_INVALID, "dc_debug_fetch: sample noise: at most 2^23 values, indices below 2^23");
+  if (count == 0) return 0;
+  void* dev = nullptr;
+  HIPCHK(hipMalloc(&dev, (size_t)count * (what == 1 ? 20 : 4)));
+  hipError_t e = hipSuccess;
+  if (what == 0) {
+    e = launch_sample_noise_gumbel(first, (size_t)count, static_cast<float*>(dev), s);
+  } else {
+    int32_t* kd = reinterpret_cast<int32_t*>(static_cast<char*>(dev) + (size_t)count * 4);
+    e = hipMemcpyAsync(kd, srtv, (size_t)count * 16, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_sample_noise_bits(seed, kd, (size_t)count, static_cast<uint32_t*>(dev), s);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out, dev, (size_t)count * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(dev);
+  if (e != hipSuccess || e2 != hipSuccess)
+    return ctx->fail(DC_E_HIP, "dc_debug_fetch: sample noise: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  return count;
+}
+
+
 int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t capacity_bytes) {
   if (!ctx || !name || !host_buf) return DC_E_INVALID;
+  if (strncmp(name, "sample_gumbel@", 14) == 0 || strncmp(name, "sample_bits@", 12) == 0) {
+    // the number behind the '@': decimal digits only, nothing after them, no overflow
+    const bool bits = name[7] == 'b';
+    const char* num = name + (bits ? 12 : 14);
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long val = strtoull(num, &end, 10);
+    if (*num < '0' || *num > '9' || *end != '\0' || errno != 0 || (!bits && val >= (1ull << 23)))
+      return ctx->fail(DC_E_INVALID, "dc_debug_fetch: '%s': a decimal %s must follow the '@'", name, bits ? "64-bit seed" : "index below 2^23");
+    if (!bits) return sample_noise_debug(ctx, 0, 0, nullptr, (uint32_t)val, capacity_bytes / 4, host_buf);
+    const int64_t count = capacity_bytes / 16;
+    std::vector<int32_t> coords(static_cast<const int32_t*>(host_buf), static_cast<const int32_t*>(host_buf) + count * 4);
+    return sample_noise_debug(ctx, 1, val, coords.data(), 0, count, host_buf);
+  }
   if (ctx->lanes.empty() || !ctx->lanes[0]->arena.p) return ctx->fail(DC_E_STATE, "no forward has run yet");
   Lane& L = *ctx->lanes[0];
   const int P = L.P;
@@ -1781,6 +1942,11 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value) {
   if (strcmp(name, "beam_chunk_floats") == 0) {
     if (value < 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: beam_chunk_floats must be >= 1");
     ctx->beam_chunk_floats = value;
+    return DC_OK;
+  }
+  if (strcmp(name, "sample_rows_cap") == 0) {
+    if (value < 0) return ctx->fail(DC_E_INVALID, "dc_debug_set: sample_rows_cap must be >= 0 (0 = the default cap)");
+    ctx->sample_rows_cap = value;
     return DC_OK;
   }
   if (strcmp(name, "score_rows_cap") == 0) {
@@ -2046,6 +2212,48 @@ int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   hipStream_t s = L.stream;
   KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, s));
   return lm_score(ctx, s, L.out_feats, K, queries, Q, Tq, loglik, Q);
+}
+
+int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                      int32_t* samples, float* logprob) {
+  OP_PROLOGUE();
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_op_lm_sample_n: weights not loaded");
+  if (!codes || !samples || !logprob) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: null pointer");
+  if (n <= 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: n must be > 0");
+  DCCHK(check_sample_opts(ctx, opts, "dc_op_lm_sample_n"));
+  std::vector<int32_t> ids;
+  if (row_ids != nullptr) {
+    ids.resize(n);
+    HIPCHK(hipMemcpy(ids.data(), row_ids, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i)
+      if (ids[i] < 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: row_ids[%d] = %d is negative", i, (int)ids[i]);
+  }
+  const size_t S = (size_t)opts->num_samples;
+  std::vector<int32_t> tok((size_t)n * S * ctx->T);
+  std::vector<float> lp((size_t)n * S);
+  DCCHK(lm_sample_n(ctx, s, codes, n, row_ids ? ids.data() : nullptr, *opts, tok.data(), lp.data()));
+  HIPCHK(hipMemcpy(samples, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(logprob, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+  OP_EPILOGUE();
+}
+
+int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                       dc_result* out, int32_t* samples, float* logprob) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_sample_captions: weights not loaded");
+  if (!img_chw || !out || !samples || !logprob) return ctx->fail(DC_E_INVALID, "dc_sample_captions: null pointer");
+  DCCHK(check_sample_opts(ctx, opts, "dc_sample_captions"));
+  // as dc_score_captions: the forward of dc_forward_test on lane 0 (without the greedy decode when no tokens are wanted), the
+  // rows it returned compacted into the lane's survivor block, then the sampling on those rows (r = output row)
+  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
+  Lane& L = lane0(ctx);
+  const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
+  if (K > out->capacity)
+    return ctx->fail(DC_E_INVALID, "dc_sample_captions: the image has %d regions but out->capacity is %d", K, (int)out->capacity);
+  if (K == 0) return DC_OK;
+  hipStream_t s = L.stream;
+  KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, s));
+  return lm_sample_n(ctx, s, L.out_feats, K, nullptr, *opts, samples, logprob);
 }
 
 }  // extern "C"

@@ -393,6 +393,121 @@ __global__ __launch_bounds__(256) void lse_step_tail_kernel(const float* __restr
   }
 }
 
+// ---- sampling step tail (densecap.hip::lm_sample_n), one workgroup (256 threads) per row -----------------------------------
+// The row's partials come from the sampling epilogue of the step GEMM, five floats per 32-column slot: (max, sum exp) as the
+// scorer's, then the slot's best perturbed entry (score, column, logit at that column).  The word drawn is the best entry over
+// the slots -- every thread its slots tid, tid + 256, ... in ascending order, then the butterfly of lstm_step_tail_kernel, lower
+// column on ties -- and its log-probability is logit - lse with lse formed exactly as in lse_step_tail_kernel: a row that ends in
+// END therefore carries the number the scorer returns for that caption.  A finished row (END drawn at an earlier step) writes
+// zeros and adds nothing, but still takes the LSTM step with the word drawn: all T steps run for every row, as in LM:sample.
+__global__ __launch_bounds__(256) void sample_step_tail_kernel(const float* __restrict__ part, int nslots, int ld, int end_tok,
+                                                               const float* __restrict__ xg,
+                                                               const float* __restrict__ gates_pre, float* __restrict__ c,
+                                                               float* __restrict__ h, double* __restrict__ acc,
+                                                               uint8_t* __restrict__ fin, int32_t* __restrict__ seq, int T,
+                                                               int t, int Hd) {
+  const int m = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ float smx[4], sv[4], sl[4];
+  __shared__ int si[4];
+  __shared__ double ssum[4];
+  constexpr int UPT = 2;                            // hidden units per thread and pass (Hd = 512: one pass)
+  float gpre[UPT][4], cprev[UPT];
+  const float* g = gates_pre ? gates_pre + (size_t)m * 4 * Hd : nullptr;
+  if (g != nullptr) {
+#pragma unroll
+    for (int u = 0; u < UPT; ++u) {
+      const int j = tid + u * 256;
+      if (j < Hd) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
+        cprev[u] = c[(size_t)m * Hd + j];
+      }
+    }
+  }
+  const float* p = part + (size_t)m * ld;
+  float mx = -INFINITY, best = -INFINITY, bl = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int s = tid; s < nslots; s += 256) {
+    const float v = p[5 * s];
+    mx = v > mx ? v : mx;
+    const float pv = p[5 * s + 2];
+    const int i = __builtin_bit_cast(int, p[5 * s + 3]);
+    if (i != 0x7fffffff && (bi == 0x7fffffff || pv > best)) { best = pv; bi = i; bl = p[5 * s + 4]; }   // ascending slot = ascending column
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(mx, o, 64);
+    mx = om > mx ? om : mx;
+    const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bl, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; bl = ol; }
+  }
+  if (lane == 0) { smx[wid] = mx; sv[wid] = best; si[wid] = bi; sl[wid] = bl; }
+  __syncthreads();
+  mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
+  best = sv[0]; bi = si[0]; bl = sl[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float ov = sv[w], ol = sl[w];
+    const int oi = si[w];
+    if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; bl = ol; }
+  }
+  // No entry at all (bi still the sentinel): every perturbed score of the row is NaN -- a NaN or Inf in the caller's codes.  The
+  // row then has no word: it writes 0, ends, its log-probability becomes NaN, and like lstm_step_tail_kernel with tok == 0 it
+  // takes the LSTM step without an embedding row.  A column from the epilogue is below amax_n; anything else is treated alike,
+  // so no address is ever formed from a value that was not checked.
+  const bool none = bi < 0 || bi >= end_tok;
+  const int tok = none ? 0 : bi + 1;
+  double sum = 0.0;
+  for (int s = tid; s < nslots; s += 256) {
+    const float pm = p[5 * s];
+    if (pm != -INFINITY) sum += (double)p[5 * s + 1] * exp((double)pm - (double)mx);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (lane == 0) ssum[wid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    const bool done = fin[m] != 0;
+    seq[(size_t)m * T + t] = done ? 0 : tok;
+    if (!done) {
+      const double lse = (double)mx + log(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
+      if (none) acc[m] = (double)NAN;
+      else acc[m] += (double)bl - lse;
+      if (none || tok == end_tok) fin[m] = 1;
+    }
+  }
+  if (g == nullptr) return;
+  const float* x = tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr;
+  for (int j0 = 0; j0 < Hd; j0 += 256 * UPT) {
+    if (j0 > 0) {                                   // Hd > 512: further passes load in place
+#pragma unroll
+      for (int u = 0; u < UPT; ++u) {
+        const int j = j0 + tid + u * 256;
+        if (j < Hd) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
+          cprev[u] = c[(size_t)m * Hd + j];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UPT; ++u) {
+      const int j = j0 + tid + u * 256;
+      if (j >= Hd) continue;
+      float gi = gpre[u][0], gf = gpre[u][1], go = gpre[u][2], gg = gpre[u][3];
+      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
+      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
+      const float gt = th_tanhf(gg);
+      const size_t i = (size_t)m * Hd + j;
+      const float cn = fg * cprev[u] + ig * gt;
+      c[i] = cn;
+      h[i] = og * th_tanhf(cn);
+    }
+  }
+}
+
 // dst_a / dst_b = `copies` back-to-back repeats of src_a / src_b (len floats each; len % 4 == 0): the START state of every
 // query's row block in lm_score, one launch instead of two copies per query
 __global__ void repeat_rows2_kernel(const f32x4* __restrict__ src_a, const f32x4* __restrict__ src_b, size_t len4, size_t total4,
@@ -598,6 +713,15 @@ hipError_t launch_lse_step_tail(const float* part, int nslots, int ld, const int
                                 const float* gates_pre, float* c, float* h, double* acc, int n, int Hd, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(lse_step_tail_kernel, dim3(n), dim3(256), 0, s, part, nslots, ld, tgt, end_tok, xg, gates_pre, c, h, acc, Hd);
+  return hipGetLastError();
+}
+hipError_t launch_sample_step_tail(const float* part, int nslots, int ld, int end_tok, const float* xg, const float* gates_pre,
+                                   float* c, float* h, double* acc, uint8_t* fin, int32_t* seq, int T, int t, int n, int Hd,
+                                   hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (t < 0 || t >= T || ld < 5 * nslots) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sample_step_tail_kernel, dim3(n), dim3(256), 0, s, part, nslots, ld, end_tok, xg, gates_pre, c, h, acc, fin,
+                     seq, T, t, Hd);
   return hipGetLastError();
 }
 hipError_t launch_splitk_reduce(const float* ws, int S, const float* bias, float* C, int M, int N, int ldc, int relu,

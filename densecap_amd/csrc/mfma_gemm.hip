@@ -26,6 +26,7 @@
 // summation order, identical for A and B and for both kernels.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <mutex>
 #include <type_traits>
 
@@ -172,7 +173,8 @@ __device__ __forceinline__ float pool_window(const GemmDesc& d, int win, float v
 // One output tile [m0, m0+BM) x [n0, n0+BN) (tile_n = n0 / BN indexes the arg-max partials); Meff = rows of the problem.
 // BF3: 0 = fp32 MFMA; 1 = split-bf16, both operands split in registers; 2 = split-bf16 with the B operand (weights) split ONCE
 // at load: three bf16 planes in HBM (GemmDesc::sk_slots carries the pointer in this mode), fetched by LDS-DMA as they are
-// LSE (with AMAX): the fused row log-sum-exp epilogue of teacher-forced scoring instead of the arg-max (see GemmDesc::rowidx).
+// LSE (with AMAX): 1 = the fused row log-sum-exp epilogue of teacher-forced scoring instead of the arg-max (see GemmDesc::rowidx);
+// 2 = the fused row sampling epilogue (Gumbel-max draw + the same log-sum-exp partials, see GemmDesc::samp_t).
 template <int TM, int TN, bool CONV, int NS, bool AMAX, int BF3 = 0, int LSE = 0>
 __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const int n0, const int tile_n, const int Meff,
                                         float* const smem) {
@@ -723,7 +725,62 @@ __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const i
       }
       return;
     }
-    if constexpr (LSE) {
+    if constexpr (LSE == 2) {
+      // ---- fused row sampling (densecap.hip::lm_sample_n; docs/SEMANTICS.md "Sampling captions") ----
+      // Gumbel-max: argmax_v (v * inv_temp + g_v) with independent standard Gumbel noise g_v is a draw from SoftMax(v * inv_temp), so
+      // the draw is the arg-max epilogue with a perturbation -- one pass over logits that never reach HBM.  Every (row, 32-column
+      // half) writes five floats to amax_val[m * amax_ld + 5 * slot ..]: the log-sum-exp partial (max v, sum exp(v - max)) formed
+      // exactly as in the LSE epilogue below (same operations in the same order: log p of the drawn word is then the scorer's
+      // number), and the best perturbed entry (score, column, v there), first maximum on ties.  The noise of column n is word n & 3
+      // of Philox4x32-10(counter (n >> 2, t, r, s), key seed): one call serves the 16-byte run of four columns a lane holds per q4.
+      // (r, s) = rowidx[2m], rowidx[2m + 1].  inv_temp == 0: no noise, no scaling (wave-uniform branch).
+      const float inv_temp = d.samp_inv_temp;
+      const uint32_t step = (uint32_t)d.samp_t, k0 = d.samp_seed_lo, k1 = d.samp_seed_hi;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int m = m0 + wm * 32 * TM + i * 32 + r;
+        const uint32_t kr = m < Meff ? (uint32_t)d.rowidx[2 * (size_t)m] : 0u, ks = m < Meff ? (uint32_t)d.rowidx[2 * (size_t)m + 1] : 0u;
+        float v[16];
+        float mx = -INFINITY, best = -INFINITY, bl = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const int nb = n0 + wn * 32 + 8 * q4 + 4 * hsel;
+          const f32x4 bv = amax_bias[0][q4];
+          Philox4 nz = {{0u, 0u, 0u, 0u}};
+          if (inv_temp != 0.f && nb < an) nz = philox4x32_10((uint32_t)nb >> 2, step, kr, ks, k0, k1);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            v[q4 * 4 + c] = nb + c < an ? acc[i][0][q4 * 4 + c] + bv[c] : -INFINITY;
+            mx = v[q4 * 4 + c] > mx ? v[q4 * 4 + c] : mx;
+            float pv = v[q4 * 4 + c];
+            if (inv_temp != 0.f && nb + c < an) pv = __fadd_rn(__fmul_rn(pv, inv_temp), gumbel_from_bits(nz.w[c]));
+            if (pv > best) { best = pv; bi = nb + c; bl = v[q4 * 4 + c]; }
+          }
+        }
+        const float omx = __shfl_xor(mx, 32, 64);     // the other lane half holds the interleaved columns of the same row
+        mx = omx > mx ? omx : mx;
+        const float ov = __shfl_xor(best, 32, 64), ol = __shfl_xor(bl, 32, 64);
+        const int oi = __shfl_xor(bi, 32, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; bl = ol; }
+        float sum = 0.f;
+        if (mx != -INFINITY) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sum += v[e] != -INFINITY ? __expf(v[e] - mx) : 0.f;
+        }
+        const float osum = __shfl_xor(sum, 32, 64);
+        if (hsel == 0 && m < Meff) {
+          const size_t slot = (size_t)m * d.amax_ld + 5 * (2 * tile_n + wn);
+          EPI_STORE(d.amax_val[slot], mx);
+          EPI_STORE(d.amax_val[slot + 1], sum + osum);
+          EPI_STORE(d.amax_val[slot + 2], best);
+          EPI_STORE(d.amax_val[slot + 3], __builtin_bit_cast(float, bi));
+          EPI_STORE(d.amax_val[slot + 4], bl);
+        }
+      }
+      return;
+    }
+    if constexpr (LSE == 1) {
       // ---- fused row log-sum-exp (teacher-forced scoring, densecap.hip::lm_score) ----
       // Same slots as the arg-max: every (row, 32-column half) writes (max v, sum exp(v - max)) over its real vocabulary
       // columns (v = logit + bias; padding columns >= amax_n left out) to amax_val[m * amax_ld + 2 * slot + {0, 1}]; the lane
@@ -950,6 +1007,20 @@ __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const i
   }
 }
 
+
+// test hooks of the sampling noise: gumbel_from_bits / philox4x32_10 as THIS file's build compiles them -- the build whose
+// epilogue draws the words -- evaluated where a test asks (dc_debug_fetch "sample_gumbel@" / "sample_bits@")
+__global__ void sample_noise_gumbel_kernel(uint32_t first, size_t count, float* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = gumbel_from_bits((first + (uint32_t)i) << 9);
+}
+__global__ void sample_noise_bits_kernel(uint32_t k0, uint32_t k1, const int32_t* __restrict__ srtv, size_t count,
+                                         uint32_t* __restrict__ bits) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t sd = (uint32_t)srtv[4 * i], rr = (uint32_t)srtv[4 * i + 1], tt = (uint32_t)srtv[4 * i + 2], v = (uint32_t)srtv[4 * i + 3];
+    bits[i] = philox4x32_10(v >> 2, tt, rr, sd, k0, k1).w[v & 3];
+  }
+}
 
 // Measurement hook (GemmDesc::stagger): a launch's workgroups all start within a microsecond and then march through their
 // K loops in lockstep -- every CU asks for its next K-tile at the same moment.  A one-off pseudo-random pause of up to
@@ -1606,6 +1677,26 @@ hipError_t launch_cfg(const GemmDesc& d, hipStream_t stream) {
   // operands are addressed through 32-bit buffer offsets
   const bool fits = CONV ? ((size_t)(d.a_rows > d.M ? d.a_rows : d.M) * d.Cin * 4 < CV_PAD && d.Cin <= 2048) : ((size_t)BM * d.K * 4 < 0xfffffff0ull);
   if (!fits || (size_t)BN * d.K * 4 >= 0xfffffff0ull) return hipErrorInvalidValue;
+  if (d.amax_val != nullptr && d.rowidx != nullptr && d.samp_t > 0) {
+    // sampling epilogue (GemmDesc::samp_t): fp32, plain launches of the 64-column tiles, as the log-sum-exp below
+    if constexpr (!CONV && TN == 1) {
+      if (d.bf3 || d.splitk > 1 || d.m_begin != 0 || d.a_rows != 0 || d.rowterm != nullptr || d.m_dev != nullptr ||
+          d.amax_ld < 10 * (d.amax_cols > 0 ? d.amax_cols / BN : ntn) || !(d.samp_inv_temp >= 0.f) ||
+          d.amax_cols % BN != 0 || (d.amax_cols > 0 && (d.C == nullptr || d.amax_n > d.amax_cols || d.amax_cols > d.N)))
+        return hipErrorInvalidValue;
+      const size_t lds3 = (size_t)3 * (BM + BN) * BK * sizeof(float);
+      if constexpr (TM == 2) {
+        return launch_mixed<false, true, 0, 2>(d, stream, ntm, ntn, m_fastest, lds3);
+      } else {
+        const void* fn = reinterpret_cast<const void*>(&mfma_gemm_v2_kernel<TM, TN, false, 3, true, 0, 2>);
+        if (hipError_t e = ensure_dyn_lds(fn, lds3); e != hipSuccess) return e;
+        hipLaunchKernelGGL((mfma_gemm_v2_kernel<TM, TN, false, 3, true, 0, 2>), dim3(ntm * ntn), dim3(256), lds3, stream, d, ntm,
+                           ntn, m_fastest);
+        return hipGetLastError();
+      }
+    }
+    return hipErrorInvalidValue;
+  }
   if (d.amax_val != nullptr && d.rowidx != nullptr) {
     // log-sum-exp epilogue (GemmDesc::rowidx): fp32, plain launches of the 64-column tiles, as the arg-max
     if constexpr (!CONV && TN == 1) {
@@ -2002,6 +2093,18 @@ void mfma_gemm_plan(const GemmDesc& d, bool serial_mode, int tail_mode, size_t w
     }
     default: p->route = GEMM_ROUTE_V2_64x64;
   }
+}
+
+hipError_t launch_sample_noise_gumbel(uint32_t first, size_t count, float* out, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sample_noise_gumbel_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 2048)), dim3(256), 0, s, first, count, out);
+  return hipGetLastError();
+}
+hipError_t launch_sample_noise_bits(uint64_t seed, const int32_t* srtv, size_t count, uint32_t* bits, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sample_noise_bits_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 2048)), dim3(256), 0, s, (uint32_t)(seed & 0xffffffffu),
+                     (uint32_t)(seed >> 32), srtv, count, bits);
+  return hipGetLastError();
 }
 
 hipError_t launch_mfma_gemm(const GemmDesc& d, hipStream_t stream) {

@@ -171,6 +171,7 @@ class DenseCapModel:
         w.fc_dim = int(_np32(weights["fc7_w"]).shape[0])
         self.fc_dim = w.fc_dim
         check(self.ctx.h, self.lib.dc_load_weights(self.ctx.h, C.byref(w)), "dc_load_weights")
+        self.ctx.seq_length = self.seq_length          # ops.lm_sample_n sizes its outputs by it
         self._keep = []
         self._push_test_args()
 
@@ -567,6 +568,37 @@ class DenseCapModel:
         if return_captions:
             res = res + (self.decodeSequence(tokens[:K]),)
         return res
+
+    def sampleCaptions(self, img, num_samples, temperature=1.0, seed=0, want_tokens=True):
+        """Sample captions for the image's regions (dc_sample_captions; LM:sample with sample_argmax = false,
+        LanguageModel.lua:40-41,328-333): the regions forward_test returns, each with num_samples draws whose words come from
+        SoftMax(scores / temperature), and the model's log-probability of every draw.  temperature 0 (num_samples 1) is the
+        greedy rule.  Returns (boxes (K,4) xcycwh, scores (K,), tokens (K,T) -- the greedy captions, or None without
+        want_tokens --, samples (K,S,T) int32, logprob (K,S)); decodeSequence(samples[:, s]) gives the strings of draw s."""
+        from .ops import DeviceArray, check_sample_args
+        opts = check_sample_args(num_samples, temperature, seed)
+        self._push_test_args()
+        on_device = isinstance(img, DeviceArray)       # a (3,H,W) float32 image already on the device (ops.preprocess_u8)
+        if on_device:
+            if img.dtype != np.float32 or len(img.shape) != 3 or img.shape[0] != 3:
+                raise ValueError("sampleCaptions wants a (3,H,W) float32 device image")
+            ptr = img.ptr
+        else:
+            img = self._check_input(img)
+            ptr = img.ctypes.data
+        P = self._capacity(img.shape[1], img.shape[2])
+        r, boxes, scores, tokens = self._new_result(P)
+        if not want_tokens:
+            r.tokens = None
+        S = opts.num_samples
+        samples = np.zeros((P, S, self.seq_length), np.int32)
+        logprob = np.zeros((P, S), np.float32)
+        check(self.ctx.h, self.lib.dc_sample_captions(self.ctx.h, ptr, img.shape[1], img.shape[2], int(on_device),
+                                                      C.byref(opts), C.byref(r), samples.ctypes.data, logprob.ctypes.data),
+              "dc_sample_captions")
+        K = r.K
+        return (boxes[:K].copy(), scores[:K].copy(), tokens[:K].copy() if want_tokens else None, samples[:K].copy(),
+                logprob[:K].copy())
 
     def decodeSequence(self, seq):
         """LanguageModel:decodeSequence (LanguageModel.lua:86-103)."""

@@ -286,3 +286,49 @@ def lm_score(ctx, codes, queries):
     o = ctx.empty((n, max(Q, 1)))
     check(ctx.h, ctx.lib.dc_op_lm_score(ctx.h, xd.ptr, n, qd.ptr, Q, Tq, o.ptr), "dc_op_lm_score")
     return o.numpy()
+
+
+def check_sample_args(num_samples, temperature, seed):
+    """The rules of dc_sample_opts (docs/SEMANTICS.md, "Sampling captions"), checked before the library is called.
+    Returns the filled DcSampleOpts."""
+    S = int(num_samples)
+    if S != num_samples or not 1 <= S <= 256:
+        raise ValueError("num_samples must be an integer in 1..256 (got %r)" % (num_samples,))
+    t = float(np.float32(temperature))
+    if not (t == 0.0 or 0.01 <= t <= 100.0):         # NaN fails both
+        raise ValueError("temperature must be 0 or in [0.01, 100] (got %r)" % (temperature,))
+    if t == 0.0 and S != 1:
+        raise ValueError("temperature 0 is the greedy rule: num_samples must be 1 (got %d)" % S)
+    sd = int(seed)
+    if sd != seed or not 0 <= sd < 1 << 64:
+        raise ValueError("seed must be an integer in 0..2^64-1 (got %r)" % (seed,))
+    return _lib.DcSampleOpts(S, t, sd)
+
+
+def lm_sample_n(ctx, codes, num_samples, temperature=1.0, seed=0, row_ids=None, seq_length=None):
+    """num_samples draws per code row from the ctx's loaded language model (dc_op_lm_sample_n): every word drawn from
+    SoftMax(scores / temperature) (temperature 0, num_samples 1: the greedy rule), noise a function of (seed, draw, row id,
+    step, word) alone.  codes (n, fc_dim); row_ids (n) ints >= 0 or None (= 0..n-1).  Returns (samples (n, S, T) int32 --
+    word ids up to and including the first END, zeros after it --, logprob (n, S) float32: the model's log-probability of
+    the words written; NaN, with an all-zero row from that step on, for a row whose scores became NaN -- non-finite codes).
+    seq_length: the loaded model's T; needed only when the weights were not loaded through DenseCapModel."""
+    opts = check_sample_args(num_samples, temperature, seed)
+    x = _f32(codes)
+    if x.ndim != 2 or x.shape[0] < 1:
+        raise ValueError("codes must be (n, fc_dim) with n >= 1")
+    n, S = x.shape[0], opts.num_samples
+    ids = None
+    if row_ids is not None:
+        ids = np.ascontiguousarray(row_ids, dtype=np.int32)
+        if ids.shape != (n,) or (ids < 0).any():
+            raise ValueError("row_ids must be (n,) ints >= 0")
+    # T of the loaded model sizes the outputs: the caller's seq_length, or what DenseCapModel noted on the ctx it loaded
+    T = int(seq_length or getattr(ctx, "seq_length", 0) or 0)
+    if T < 1:
+        raise ValueError("lm_sample_n: pass seq_length= (the loaded model's T) for a ctx that DenseCapModel did not load")
+    xd = ctx.to_device(x)
+    idd = ctx.to_device(ids) if ids is not None else None
+    tok = ctx.empty((n, S, T), np.int32); lp = ctx.empty((n, S), np.float32)
+    check(ctx.h, ctx.lib.dc_op_lm_sample_n(ctx.h, xd.ptr, n, idd.ptr if idd is not None else None, C.byref(opts), tok.ptr,
+                                           lp.ptr), "dc_op_lm_sample_n")
+    return tok.numpy(), lp.numpy()

@@ -71,7 +71,16 @@ def build_parser():
       help="dc_set_caption_order: 1 (default) = final NMS first, captions only for the boxes it keeps -- one packed decode per group "
            "of images; the outputs are the reference's bit for bit (LSTM rows are independent), ~1.3x images/s at 1000 proposals; "
            "0 = the reference's order (DenseCapModel.lua:127-162: all proposals are captioned, then the final NMS picks)")
+    a("-num_samples", type=int, default=0,
+      help="N > 0: every image also gets N sampled captions per region (dc_sample_captions; words drawn from "
+           "SoftMax(scores / temperature)) and their log-probabilities: `sampled_captions` / `sampled_logprobs` in results.json; "
+           "0 (default): output as without the flag")
+    a("-temperature", type=float, default=1.0, help="temperature of -num_samples: 0.01..100, or 0 with -num_samples 1 (the greedy rule)")
+    a("-sample_seed", type=int, default=0, help="seed of -num_samples: image i of the run uses seed + i")
     return p
+
+
+SAMPLING_FLAGS = ("num_samples", "temperature", "sample_seed")
 
 
 def _scale_linear_axis(src, dst_len, axis):
@@ -408,8 +417,18 @@ def main(argv=None):
             print("warning: %s -- reading %s again without the writer-habit checks" % (e, opt.checkpoint), file=sys.stderr)
             ck = t7.load(opt.checkpoint, strict=False)
         weights = t7.weights_from_checkpoint(ck)
+    if opt.num_samples:
+        try:                               # at start-up, not at the image whose seed would leave the range
+            ops.check_sample_args(opt.num_samples, opt.temperature, opt.sample_seed)
+        except ValueError as e:
+            raise SystemExit("-num_samples / -temperature / -sample_seed: %s" % e)
+        if opt.input_boxes:
+            raise SystemExit("-num_samples with -input_boxes: sample on the boxes' codes instead (extract_features_boxes, then "
+                             "ops.lm_sample_n)")
     paths = get_input_images(opt)
     num = min(len(paths), opt.max_images)
+    if opt.num_samples and opt.sample_seed + max(num, 1) - 1 >= 1 << 64:
+        raise SystemExit("-sample_seed %d: image i uses seed + i, which leaves 0..2^64-1 within these %d images" % (opt.sample_seed, num))
     in_boxes = read_input_boxes(opt.input_boxes, [os.path.basename(p) for p in paths[:num]]) if opt.input_boxes else None
     model = DenseCapModel(weights, device=opt.gpu)                      # utils.setup_gpus + model:convert
     # one image: single-image mode (lowest latency, like the reference); several: pipelined over the lanes, runs of
@@ -451,13 +470,20 @@ def main(argv=None):
             rj["img_name"] = name
             if in_boxes is not None:
                 rj["src"] = [int(v) for v in out[3]]         # the row of the image's -input_boxes behind every result row
+            if opt.num_samples:
+                samples, logprob = out[3], out[4]
+                rj["sampled_captions"] = [model.decodeSequence(samples[k]) for k in range(len(samples))]
+                rj["sampled_logprobs"] = [[float(v) for v in row] for row in logprob]
             results[i] = rj
 
     try:
         for chunk in pipe:
             for i, _, _ in chunk:
                 print("%d/%d processing image %s" % (i + 1, num, paths[i]))
-            if in_boxes is None:
+            if opt.num_samples:
+                # image by image: dc_sample_captions runs the forward itself (lane 0), then the draws -- same boxes, scores, captions
+                outs = [model.sampleCaptions(d, opt.num_samples, opt.temperature, opt.sample_seed + i) for i, d, _ in chunk]
+            elif in_boxes is None:
                 outs = model.forward_images_device([d for _, d, _ in chunk])
             else:
                 outs = model.forward_boxes_images_device([d for _, d, _ in chunk],
@@ -477,7 +503,8 @@ def main(argv=None):
                                                                       "host" if opt.host_preprocess else "device"))
     results = [r for r in results if r is not None]
     if results:
-        out = dict(results=results, opt={k: v for k, v in vars(opt).items()})
+        # (without -num_samples the file is what it was before the flag existed: the sampling flags are left out of `opt`)
+        out = dict(results=results, opt={k: v for k, v in vars(opt).items() if opt.num_samples or k not in SAMPLING_FLAGS})
         with open(os.path.join(opt.output_vis_dir, "results.json"), "w") as f:
             json.dump(out, f)
     return 0

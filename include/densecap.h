@@ -136,6 +136,22 @@ int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_
  * never graph-replayed; results do not depend on Q, the query order or the chunking.  K > out->capacity is refused. */
 int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
                       const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
+/* Sample captions: LanguageModel:sample with sample_argmax = false (LanguageModel.lua:40-41,328-333).  num_samples = S draws
+ * per region (1..256); every word is drawn from SoftMax(scores / temperature), temperature in [0.01, 100], or with
+ * temperature 0 (S must then be 1) taken by the greedy rule; seed selects the noise, which is counter-based: a draw depends on
+ * (seed, draw s, region row r, step, word) and on nothing else.  Definition and rules: docs/SEMANTICS.md, "Sampling captions". */
+typedef struct dc_sample_opts {
+  int32_t num_samples; float temperature; uint64_t seed;
+} dc_sample_opts;
+/* The forward of dc_forward_test, then S draws for each of the K regions it returns, in its order (r = output row).  `out` is
+ * filled as dc_forward_test fills it; out->tokens == NULL skips the greedy decode (boxes, scores, samples and logprob are the
+ * same bits either way).  samples: host (out->capacity, S, T) int32, entry (k*S + s)*T + t: 1-based word ids up to and
+ * including the first END (= V+1), zeros after it.  logprob: host (out->capacity, S): the model's own natural-log probability
+ * (temperature 1) of the words written, END included; for a row that contains END it is the number dc_op_lm_score returns for
+ * that caption on that region.  fp32 MFMA whatever dc_set_math_mode says, never graph-replayed, beam size ignored.  Options
+ * outside the ranges above are refused with DC_E_INVALID before anything is enqueued; K > out->capacity is refused. */
+int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                       dc_result* out, int32_t* samples, float* logprob);
 /* run_model.lua:160-180 host loop over images, n images of identical size laid out
  * back to back; images are software-pipelined over the ctx's lanes (streams). */
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device,
@@ -370,6 +386,11 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens);
 /* The scoring of dc_score_captions on given fc7 codes (n, fc_dim): loglik (n, Q), entry r*Q + q.  Device pointers
  * throughout (codes, queries, loglik); synchronous.  Same rules for the queries. */
 int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* queries, int Q, int Tq, float* loglik);
+/* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
+ * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
+ * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */
+int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                      int32_t* samples, float* logprob);
 
 #ifdef __cplusplus
 }

@@ -31,11 +31,17 @@ int dc_mfma_profile(dc_ctx* ctx, int reset, int64_t* launches, double* total_ms,
  * packed result carries -- 0 after a clean forward, -1 if it does not exist), or
  * "arena_allocs" (int32: how many times a lane workspace has been (re)allocated -- it only grows), or
  * "host_enqueue_us" (int32: host microseconds per image spent enqueueing in the last dc_forward_batch).
+ * The noise of caption sampling as the device computes it (docs/SEMANTICS.md, "Sampling captions"; no forward needed):
+ * "sample_gumbel@<first>" fills host_buf with capacity_bytes / 4 floats, g = -log(-log(u)) of the 23-bit indices first, first + 1,
+ * ... (u = (index + 0.5) * 2^-23; at most 2^23 values a call); "sample_bits@<seed>" reads capacity_bytes / 16 rows of int32
+ * (s, r, t, v) from host_buf and writes the uint32 noise bits of those coordinates under that seed to the front of host_buf.
  * Returns the number of elements copied (or <0). */
 int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t capacity_bytes);
 /* Test hooks (never needed for correct results; every setting gives the same outputs bit for bit):
  *   "beam_chunk_floats"  cap, in floats, of the beam search's full-logits buffer (default 2^28): proposals advance in
  *                        chunks of max(64, cap / (beam * (V+1))) -- lets a test walk the chunk loop with few rows;
+ *   "sample_rows_cap"    rows (region x draw) one chunk of dc_sample_captions / dc_op_lm_sample_n may hold; 0 (default) =
+ *                        about 512 MiB of scratch.  Chunks are whole draws; lets a test walk the chunk loop with few rows.
  *   "decode_route"       0 / 1 = the GEMM decode (default), 2 = the persistent LDS-resident decode (one launch for all
  *                        T+1 LSTM steps, [Wout; Wh^T] resident in LDS) wherever it applies: greedy decode of <= 64 rows,
  *                        rnn_size 512.  Tokens are bit-identical on both routes; measured no faster.

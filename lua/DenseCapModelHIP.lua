@@ -287,6 +287,38 @@ function Model:scoreCaptions(input, queries)
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), loglik[{{1, K}}]:clone()
 end
 
+-- Sample captions (LanguageModel:sample with sample_argmax = false, LanguageModel.lua:40-41,328-333): num_samples draws for
+-- each region forward_test returns, every word drawn from SoftMax(scores / temperature) (temperature default 1; 0 with
+-- num_samples 1 is the greedy rule), noise selected by `seed` (default 0, a non-negative integer below 2^53 from Lua).
+-- Returns boxes, scores, the greedy captions, samples: IntTensor (K, S, T) of word ids (up to and including the first END,
+-- zeros after it; self:decodeSequence(samples[{{}, s}]:long()) gives the strings of draw s) and logprob (K, S), the model's
+-- log-probability of every draw.
+function Model:sampleCaptions(input, num_samples, temperature, seed)
+  self:_push_test_args()
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local H, W, T = img:size(3), img:size(4), self.seq_length
+  local S = num_samples
+  assert(type(S) == 'number' and S >= 1 and S <= 256 and S == math.floor(S), 'num_samples must be an integer in 1..256')
+  local P = self:_capacity(H, W)
+  local boxes, scores = torch.FloatTensor(P, 4), torch.FloatTensor(P, 1)
+  local tokens = torch.IntTensor(P, T)
+  local samples, logprob = torch.IntTensor(P, S, T):zero(), torch.FloatTensor(P, S):zero()
+  local o = ffi.new('dc_sample_opts')
+  o.num_samples, o.temperature, o.seed = S, temperature or 1, seed or 0
+  local r = ffi.new('dc_result')
+  r.capacity = P
+  r.boxes, r.scores = torch.data(boxes), torch.data(scores)
+  r.tokens = torch.data(tokens)
+  hip.check(self.ctx, C.dc_sample_captions(self.ctx, fptr(img), H, W, 0, o, r, torch.data(samples), torch.data(logprob)),
+            'dc_sample_captions')
+  local K = r.K
+  if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, torch.IntTensor(), torch.FloatTensor() end
+  local seq = tokens[{{1, K}}]:long()
+  return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), samples[{{1, K}}]:clone(),
+         logprob[{{1, K}}]:clone()
+end
+
 -- The model after the RPN on the caller's boxes (dc_forward_boxes; DenseCapModel.lua:242-275 with `boxes` in the place of
 -- the localisation layer's roi_boxes).  boxes: FloatTensor (n, 4) xc,yc,w,h in the pixel frame of `input` (the frame
 -- forward_test returns), 1 <= n <= num_proposals; clip (optional): box_utils.clip_boxes first, invalid boxes dropped.

@@ -44,6 +44,13 @@ int dc_set_group(dc_ctx* ctx, int images);
 int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out);
 int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
                       const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
+typedef struct dc_sample_opts {
+  int32_t num_samples; float temperature; uint64_t seed;
+} dc_sample_opts;
+int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                       dc_result* out, int32_t* samples, float* logprob);
+int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                      int32_t* samples, float* logprob);
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device, dc_result* outs);
 int dc_forward_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
                       dc_result* outs);
