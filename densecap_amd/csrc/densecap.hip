@@ -543,9 +543,52 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
 // element does not depend on the tile it falls in), only the kernels of the blocks overlap in time.
 struct LmPart { hipStream_t s; int r0, n; Ws ws; };
 
-// LanguageModel:sample greedy decode (LanguageModel.lua:293-348) for the rows of `codes` covered by `parts`
+// The buffers of one greedy decode, one row per code row: encoder output (E), gate pre-activations (4 Hd), LSTM state (Hd
+// each) and the step GEMM's arg-max partials (2 x V1pad/32).  The forward passes its lane's, dc_op_lm_sample a carve of its own.
+struct LmBufs { float *enc, *gates, *h, *c, *amax; };
+LmBufs lane_lm_bufs(const Lane& L) { return LmBufs{L.enc, L.gates, L.hstate, L.cstate, L.logits}; }
+
+// From fc7 codes to the state after the START token: the first five launches of the schedule in lm_sample_parts (there is the
+// description), for n rows.  Every schedule of the language model but the beam search starts here.  Only enqueues (capture-safe).
+// `plan`: GemmDesc::plan_M; m_dev: optional device-side row count; enc_ws: scratch of the encoder GEMM (K = 4096), the only one
+// of the three that may take a split-K route.
+int lm_start_state(dc_ctx* ctx, hipStream_t s, const float* codes, int n, float* enc, float* gates, float* c, float* h, int plan,
+                   const int32_t* m_dev, const Ws& enc_ws) {
+  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1;
+  GemmDesc g;                // image_encoder: Linear(4096,E)+ReLU (:27-30)
+  g.A = codes; g.W = ctx->enc_w; g.bias = ctx->enc_b; g.C = enc; g.M = n; g.N = E; g.K = ctx->D; g.ldc = E; g.relu = 1;
+  g.m_dev = m_dev; g.plan_M = plan;
+  DCCHK(run_gemm(ctx, g, s, enc_ws));
+  g = GemmDesc();            // step 0: gates = (b + enc.Wx) + 0.Wh ; c0 = 0 (output ignored, no vocab projection needed)
+  g.A = enc; g.W = ctx->wxT; g.bias = ctx->lstm_b; g.C = gates; g.M = n; g.N = 4 * Hd; g.K = E; g.ldc = 4 * Hd;
+  g.m_dev = m_dev; g.plan_M = plan;
+  DCCHK(run_gemm(ctx, g, s));
+  KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, gates, c, h, n, m_dev, Hd, 1, nullptr, 1, 0, s));
+  g = GemmDesc();            // h_0.Wh, then the START token's xg row (:32,320) joins it in the tail
+  g.A = h; g.W = ctx->whT; g.C = gates; g.M = n; g.N = 4 * Hd; g.K = Hd; g.ldc = 4 * Hd; g.m_dev = m_dev; g.plan_M = plan;
+  DCCHK(run_gemm(ctx, g, s));
+  KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, gates, c, h, n, m_dev, Hd, 0, nullptr, 1, 0, s));
+  return DC_OK;
+}
+
+// The GEMM of one decode step on `rows` rows of h: the vocabulary projection, whose epilogue reduces every row to partials
+// (the logits never reach HBM), and -- except after the last step -- in the same launch G = h.Wh for the next step's gates
+// (W = [Wout; pad; Wh]).  The caller adds the fields of its epilogue: amax_val / amax_idx / amax_ld, rowidx, samp_*.
+GemmDesc decode_step_desc(const dc_ctx* ctx, const float* h, int rows, int plan, bool last, float* gates) {
+  const int V1 = ctx->V + 1, Hd = ctx->Hd;
+  GemmDesc v;
+  v.A = h; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = rows; v.K = Hd; v.plan_M = plan;
+  if (last) {
+    v.N = V1; v.ldc = V1;
+  } else {
+    v.N = ctx->V1pad + 4 * Hd; v.amax_cols = ctx->V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
+  }
+  return v;
+}
+
+// LanguageModel:sample greedy decode (LanguageModel.lua:293-348) for the rows of `codes` covered by `parts`, on the buffers `b`
 // (n_dev: optional device-side row count <= n of a single part starting at row 0; rows past it are not computed).
-int lm_sample_parts(dc_ctx* ctx, Lane& L, const float* codes, const LmPart* parts, int nparts, const int32_t* n_dev,
+int lm_sample_parts(dc_ctx* ctx, const LmBufs& b, const float* codes, const LmPart* parts, int nparts, const int32_t* n_dev,
                     int32_t* seq_out, int plan = 0) {
   // Schedule of one decode (h_t = LSTM state after t steps past the image step, tok_0 = START):
   //   enc = ReLU(codes.Wenc^T + b)                      GEMM   (:27-30)
@@ -560,66 +603,40 @@ int lm_sample_parts(dc_ctx* ctx, Lane& L, const float* codes, const LmPart* part
   // only need h_t) and fills its partial last round of tiles; the token-dependent half of the gates (a row of the
   // precomputed xg = b + Emb.Wx table) is added where the token is produced.  Per element the arithmetic and its order
   // are those of torch-rnn's nn.LSTM: (b + x.Wx) + h.Wh, sigmoid/tanh, c' = f*c + i*g, h' = o*tanh(c').
-  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
-  const int V1pad = ctx->V1pad, ntn = V1pad / 32;       // arg-max partials per row: one (value, column) per 32-column half of a 64-column tile
+  // The first five lines are lm_start_state, the GEMM of a step is decode_step_desc: lm_score and lm_sample_n share both.
+  const int E = ctx->E, Hd = ctx->Hd, T = ctx->T, D = ctx->D;
+  const int ntn = ctx->V1pad / 32;       // arg-max partials per row: one (value, column) per 32-column half of a 64-column tile
   for (int pi = 0; pi < nparts; ++pi) {
     const LmPart& p = parts[pi];
-    hipStream_t s = p.s;
-    float* gates = L.gates + (size_t)p.r0 * 4 * Hd;
-    float* hstate = L.hstate + (size_t)p.r0 * Hd;
-    float* cstate = L.cstate + (size_t)p.r0 * Hd;
-    {  // image_encoder: Linear(4096,E)+ReLU (:27-30)
-      GemmDesc g;
-      g.A = codes + (size_t)p.r0 * D; g.W = ctx->enc_w; g.bias = ctx->enc_b; g.C = L.enc + (size_t)p.r0 * E;
-      g.M = p.n; g.N = E; g.K = D; g.ldc = E; g.relu = 1; g.m_dev = n_dev; g.plan_M = plan;
-      DCCHK(run_gemm(ctx, g, s, p.ws));
-    }
-    {  // step 0: gates = (b + enc.Wx) + 0.Wh ; c0 = 0 (output ignored, no vocab projection needed)
-      GemmDesc g;
-      g.A = L.enc + (size_t)p.r0 * E; g.W = ctx->wxT; g.bias = ctx->lstm_b; g.C = gates;
-      g.M = p.n; g.N = 4 * Hd; g.K = E; g.ldc = 4 * Hd; g.m_dev = n_dev; g.plan_M = plan;
-      DCCHK(run_gemm(ctx, g, s));
-    }
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, gates, cstate, hstate, p.n, n_dev, Hd, 1, nullptr, T, 0, s));
-    {  // h_0.Wh, then the START token's xg row (:32,320) joins it in the tail
-      GemmDesc g;
-      g.A = hstate; g.W = ctx->whT; g.C = gates; g.M = p.n; g.N = 4 * Hd; g.K = Hd; g.ldc = 4 * Hd; g.m_dev = n_dev;
-      g.plan_M = plan;
-      DCCHK(run_gemm(ctx, g, s));
-    }
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, gates, cstate, hstate, p.n, n_dev, Hd, 0, nullptr, T, 0, s));
+    const size_t r0 = p.r0;
+    DCCHK(lm_start_state(ctx, p.s, codes + r0 * D, p.n, b.enc + r0 * E, b.gates + r0 * 4 * Hd, b.c + r0 * Hd, b.h + r0 * Hd,
+                         plan, n_dev, p.ws));
   }
   for (int t = 0; t < T; ++t) {
     const bool last = t == T - 1;
     for (int pi = 0; pi < nparts; ++pi) {
       const LmPart& p = parts[pi];
-      hipStream_t s = p.s;
-      float* gates = L.gates + (size_t)p.r0 * 4 * Hd;
-      float* hstate = L.hstate + (size_t)p.r0 * Hd;
-      // vocab projection with the row arg-max fused into the GEMM epilogue (logits never reach HBM); except after
-      // the last step the same launch also produces h.Wh for the next step's gates
-      GemmDesc v;
-      v.A = hstate; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = p.n; v.K = Hd; v.m_dev = n_dev; v.plan_M = plan;
-      v.amax_val = L.logits + (size_t)p.r0 * 2 * ntn;
+      const size_t r0 = p.r0;
+      float* gates = b.gates + r0 * 4 * Hd;
+      float* hstate = b.h + r0 * Hd;
+      GemmDesc v = decode_step_desc(ctx, hstate, p.n, plan, last, gates);     // epilogue: the row arg-max
+      v.m_dev = n_dev;
+      v.amax_val = b.amax + r0 * 2 * ntn;
       v.amax_idx = reinterpret_cast<int32_t*>(v.amax_val + (size_t)p.n * ntn);
       v.amax_ld = ntn;
-      if (last) {
-        v.N = V1; v.ldc = V1;
-      } else {
-        v.N = V1pad + 4 * Hd; v.amax_cols = V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
-      }
-      DCCHK(run_gemm(ctx, v, s));
-      KCHK(launch_lstm_step_tail(v.amax_val, v.amax_idx, ntn, ntn, 0, ctx->xg, last ? nullptr : gates,
-                                 L.cstate + (size_t)p.r0 * Hd, hstate, p.n, n_dev, Hd, 0, seq_out + (size_t)p.r0 * T, T, t, s));
+      DCCHK(run_gemm(ctx, v, p.s));
+      KCHK(launch_lstm_step_tail(v.amax_val, v.amax_idx, ntn, ntn, 0, ctx->xg, last ? nullptr : gates, b.c + r0 * Hd, hstate,
+                                 p.n, n_dev, Hd, 0, seq_out + r0 * T, T, t, p.s));
     }
   }
   return DC_OK;
 }
 
 // `plan`: rows of one image when n covers a group (0 = n); see GemmDesc::plan_M
-int lm_sample(dc_ctx* ctx, Lane& L, const float* codes, int n, int plan, const int32_t* n_dev, int32_t* seq_out) {
-  const LmPart whole{L.stream, 0, n, lane_ws(L)};
-  return lm_sample_parts(ctx, L, codes, &whole, 1, n_dev, seq_out, plan);
+int lm_sample(dc_ctx* ctx, hipStream_t s, const LmBufs& b, const Ws& ws, const float* codes, int n, int plan, const int32_t* n_dev,
+              int32_t* seq_out) {
+  const LmPart whole{s, 0, n, ws};
+  return lm_sample_parts(ctx, b, codes, &whole, 1, n_dev, seq_out, plan);
 }
 // LanguageModel:beamsearch (LanguageModel.lua:170-290), dispatched by LM:updateOutput when self.beam_size is set
 // (:129-131; no reference script sets it).  The reference walks the proposals one by one with the beams in the
@@ -703,11 +720,81 @@ int lm_beamsearch(dc_ctx* ctx, Lane& L, const float* codes, int n, int32_t* seq_
 
 constexpr int kScorePlanRows = 4096;    // lm_score: rows its per-region GEMMs are planned on, at most (see there)
 
+// ---- what lm_score and lm_sample_n share ------------------------------------------------------------------------------------
+// Both run `items` (queries / draws) on n region codes: rows = item * n + region, in chunks of whole items under a row cap, on
+// scratch of their own, eager, and always with the fp32 MFMA kernels (their epilogues have no split-bf16 variant).
+struct Fp32Guard {        // math_mode = 0 while one lives, whatever dc_set_math_mode says
+  Settings& c; int saved;
+  explicit Fp32Guard(Settings& cfg) : c(cfg), saved(cfg.math_mode) { c.math_mode = 0; }
+  ~Fp32Guard() { c.math_mode = saved; }
+};
+struct LmRows {
+  int n = 0, plan = 0, chunk = 0;       // region rows; rows every GEMM is planned on; whole items per chunk
+  size_t rmax = 0;                      // rows of a full chunk
+  float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr;          // per region: encoder output, gates, START state
+  float *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;        // per row: state, gates, the step GEMM's partials
+  double* acc = nullptr;                // per row: the sum of its log-probability terms
+  void* base = nullptr;
+  std::vector<double> acc_host;         // acc of the chunk just run (lm_chunk_end)
+};
+// The chunk: as many whole items as `rows_cap` rows hold (the caller's dc_debug_set knob; 0 = ~512 MiB of scratch at row_bytes a
+// row), at least one.  The per-region GEMMs are planned on min(n, kScorePlanRows) rows: every plan then stays on the
+// sequential-K v2 kernels (the image encoder, K = 4096, would take the K-split kernel -- another summation order -- from about
+// 6,300 planned rows on), and a v2 element's K order does not depend on its tile, so a region's numbers do not depend on the
+// other regions in the call.
+void lm_rows_plan(LmRows& w, int n, int items, int64_t rows_cap, size_t row_bytes) {
+  const int64_t cap = rows_cap > 0 ? rows_cap : (int64_t)(((size_t)512 << 20) / row_bytes);
+  w.n = n;
+  w.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(items, cap / n));
+  w.plan = std::min(n, kScorePlanRows);
+  w.rmax = (size_t)w.chunk * n;
+}
+// One allocation for the shared pieces (ld: floats of partials per row) and the caller's `extra` ones; lm_rows_finish frees it.
+int lm_rows_alloc(dc_ctx* ctx, LmRows& w, int ld, const std::vector<Carve>& extra) {
+  const size_t n = w.n, E = ctx->E, Hd = ctx->Hd;
+  std::vector<Carve> cv = {
+      {(void**)&w.enc, n * E * 4},            {(void**)&w.g0, n * 4 * Hd * 4},        {(void**)&w.h0, n * Hd * 4},
+      {(void**)&w.c0, n * Hd * 4},            {(void**)&w.h, w.rmax * Hd * 4},        {(void**)&w.c, w.rmax * Hd * 4},
+      {(void**)&w.gates, w.rmax * 4 * Hd * 4}, {(void**)&w.part, w.rmax * ld * 4},    {(void**)&w.acc, w.rmax * 8},
+  };
+  cv.insert(cv.end(), extra.begin(), extra.end());
+  HIPCHK(hipMalloc(&w.base, carve(cv, nullptr)));
+  carve(cv, w.base);
+  return DC_OK;
+}
+// A chunk of ni items begins: the rows' integers go up (`ints` to `ints_dev`), acc -- and `flags`, one byte per row, where the
+// caller keeps some -- are zeroed, and every item's row block starts from the regions' START state.
+int lm_chunk_begin(dc_ctx* ctx, hipStream_t s, LmRows& w, int ni, int32_t* ints_dev, const std::vector<int32_t>& ints,
+                   uint8_t* flags = nullptr) {
+  const size_t rows = (size_t)ni * w.n;
+  HIPCHK(hipMemcpyAsync(ints_dev, ints.data(), ints.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(w.acc, 0, rows * 8, s));
+  if (flags != nullptr) HIPCHK(hipMemsetAsync(flags, 0, rows, s));
+  KCHK(launch_repeat_rows2(w.h0, w.c0, (size_t)w.n * ctx->Hd, ni, w.h, w.c, s));
+  return DC_OK;
+}
+// ... and ends: acc comes back into w.acc_host (row = item * n + region) and the stream is drained
+int lm_chunk_end(dc_ctx* ctx, hipStream_t s, LmRows& w, int ni) {
+  w.acc_host.resize((size_t)ni * w.n);
+  HIPCHK(hipMemcpyAsync(w.acc_host.data(), w.acc, w.acc_host.size() * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return DC_OK;
+}
+// Every exit path of the two ends here with rc, the status of what was enqueued: drain, free, report.
+int lm_rows_finish(dc_ctx* ctx, hipStream_t s, LmRows& w, int rc, const char* who) {
+  const hipError_t e = hipStreamSynchronize(s);
+  hipFree(w.base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return DC_OK;
+}
+
 // Teacher-forced scoring: LanguageModel:updateOutput with a gt_sequence (LanguageModel.lua:106-127) and the targets of
 // getTarget (:148-167) -- for region code r and query w_1..w_L the inputs [image vector, START, w_1 .. w_L], targets
 // [null, w_1 .. w_L, END], loglik = sum over positions 2..L+2 of LogSoftMax(h_p.Wout^T + b)[y_p] (L+1 terms, END included).
 // Schedule:
-//   per region (n rows, as lm_sample_parts): enc, image step, h_0.Wh, START step
+//   per region (n rows): lm_start_state -- enc, image step, h_0.Wh, START step, as lm_sample_parts describes them
 //   per chunk of whole queries (rows = q * n + r, queries sorted by length, longest first): copy the START state to every row,
 //   then for projection j = 1 .. Lmax+1: [log-sum-exp partials of h.Wout^T + b | G = h.Wh] ONE GEMM over the rows still alive
 //   (a prefix: their queries have >= j - 1 words; the last projection has no Wh half) + lse_step_tail (log p of the target
@@ -715,10 +802,10 @@ constexpr int kScorePlanRows = 4096;    // lm_score: rows its per-region GEMMs a
 // Every GEMM is planned on min(n, kScorePlanRows) rows (plan_M) without split-K workspace, every element's arithmetic is a
 // function of its row alone, and the per-row sums run in step order: a row's loglik does not depend on Q, the query order,
 // the chunking or the other regions scored.
-// Always fp32 MFMA (the epilogue has no split-bf16 variant) and eager.  `qry` (Q, Tq) host, validated; out[r * ldo + q].
+// `qry` (Q, Tq) host, validated; out[r * ldo + q].
 int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* qry, int Q, int Tq, float* out, int ldo) {
-  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, D = ctx->D, V1pad = ctx->V1pad;
-  const int nslots = V1pad / 32, ld = 2 * nslots + 1;
+  const int Hd = ctx->Hd, V1 = ctx->V + 1;
+  const int nslots = ctx->V1pad / 32, ld = 2 * nslots + 1;
   std::vector<int> len(Q), order(Q);
   for (int q = 0; q < Q; ++q) {
     int L = 0;
@@ -728,43 +815,16 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
   }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
   const int steps_max = len[order[0]] + 1;
-  struct MathGuard {      // scoring is fp32 whatever dc_set_math_mode says
-    Settings& c; int saved;
-    ~MathGuard() { c.math_mode = saved; }
-  } mg{ctx->cfg, ctx->cfg.math_mode};
-  ctx->cfg.math_mode = 0;
-  // chunk of whole queries under the row cap
-  const size_t row_bytes = (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps_max * 4;
-  const int64_t cap = ctx->score_rows_cap > 0 ? ctx->score_rows_cap : (int64_t)(((size_t)512 << 20) / row_bytes);
-  const int qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(Q, cap / n));
-  // The per-region GEMMs are planned on min(n, kScorePlanRows) rows: every plan then stays on the sequential-K v2 kernels (the
-  // image encoder, K = 4096, would take the K-split kernel -- another summation order -- from about 6,300 planned rows on), and
-  // a v2 element's K order does not depend on its tile, so a region's numbers do not depend on the other regions scored.
-  const int plan = std::min(n, kScorePlanRows);
-  const size_t rmax = (size_t)qchunk * n;
-  float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr, *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;
-  double* acc = nullptr;
-  int32_t* tgt = nullptr;
-  const std::vector<Carve> cv = {
-      {(void**)&enc, (size_t)n * E * 4},    {(void**)&g0, (size_t)n * 4 * Hd * 4}, {(void**)&h0, (size_t)n * Hd * 4},
-      {(void**)&c0, (size_t)n * Hd * 4},    {(void**)&h, rmax * Hd * 4},            {(void**)&c, rmax * Hd * 4},
-      {(void**)&gates, rmax * 4 * Hd * 4},  {(void**)&part, rmax * ld * 4},         {(void**)&acc, rmax * 8},
-      {(void**)&tgt, rmax * steps_max * 4},
-  };
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-  carve(cv, base);
+  Fp32Guard fp32(ctx->cfg);
+  LmRows w;
+  lm_rows_plan(w, n, Q, ctx->score_rows_cap, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps_max * 4);
+  int32_t* tgt = nullptr;       // the rows' targets, step by step
+  DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&tgt, w.rmax * steps_max * 4}}));
   auto body = [&]() -> int {
-    // ---- per region: image step and START step (lm_sample_parts' first four launches) ----
-    DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, enc, n, E, D, 1, Ws(), plan));
-    DCCHK(linear(ctx, s, enc, ctx->wxT, ctx->lstm_b, g0, n, 4 * Hd, E, 0, Ws(), plan));
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, g0, c0, h0, n, nullptr, Hd, 1, nullptr, 1, 0, s));
-    DCCHK(linear(ctx, s, h0, ctx->whT, nullptr, g0, n, 4 * Hd, Hd, 0, Ws(), plan));
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, g0, c0, h0, n, nullptr, Hd, 0, nullptr, 1, 0, s));
+    DCCHK(lm_start_state(ctx, s, codes, n, w.enc, w.g0, w.c0, w.h0, w.plan, nullptr, Ws()));
     std::vector<int32_t> th;
-    std::vector<double> ah;
-    for (int a = 0; a < Q; a += qchunk) {
-      const int nq = std::min(qchunk, Q - a), steps = len[order[a]] + 1;
+    for (int a = 0; a < Q; a += w.chunk) {
+      const int nq = std::min(w.chunk, Q - a), steps = len[order[a]] + 1;
       const size_t rows = (size_t)nq * n;
       th.assign(rows * steps, 0);
       for (int j = 1; j <= steps; ++j)
@@ -774,40 +834,24 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
           const int32_t tok = j <= len[q] ? qry[(size_t)q * Tq + j - 1] : V1;
           std::fill(th.begin() + (j - 1) * rows + (size_t)i * n, th.begin() + (j - 1) * rows + (size_t)(i + 1) * n, tok);
         }
-      HIPCHK(hipMemcpyAsync(tgt, th.data(), th.size() * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemsetAsync(acc, 0, rows * 8, s));
-      KCHK(launch_repeat_rows2(h0, c0, (size_t)n * Hd, nq, h, c, s));      // the START state of every query's row block
+      DCCHK(lm_chunk_begin(ctx, s, w, nq, tgt, th));
       int alive = nq;
       for (int j = 1; j <= steps; ++j) {
         while (alive > 0 && len[order[a + alive - 1]] + 1 < j) --alive;
         const bool last = j == steps;
         const int m = alive * n;
-        GemmDesc v;
-        v.A = h; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = m; v.K = Hd; v.plan_M = plan;
-        v.amax_val = part; v.amax_ld = ld; v.rowidx = tgt + (size_t)(j - 1) * rows;
-        if (last) {
-          v.N = V1; v.ldc = V1;
-        } else {
-          v.N = V1pad + 4 * Hd; v.amax_cols = V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
-        }
+        GemmDesc v = decode_step_desc(ctx, w.h, m, w.plan, last, w.gates);     // epilogue: log-sum-exp partials, target's logit
+        v.amax_val = w.part; v.amax_ld = ld; v.rowidx = tgt + (size_t)(j - 1) * rows;
         DCCHK(run_gemm(ctx, v, s));
-        KCHK(launch_lse_step_tail(part, nslots, ld, v.rowidx, V1, ctx->xg, last ? nullptr : gates, c, h, acc, m, Hd, s));
+        KCHK(launch_lse_step_tail(w.part, nslots, ld, v.rowidx, V1, ctx->xg, last ? nullptr : w.gates, w.c, w.h, w.acc, m, Hd, s));
       }
-      ah.resize(rows);
-      HIPCHK(hipMemcpyAsync(ah.data(), acc, rows * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
+      DCCHK(lm_chunk_end(ctx, s, w, nq));
       for (int i = 0; i < nq; ++i)
-        for (int r = 0; r < n; ++r) out[(size_t)r * ldo + order[a + i]] = (float)ah[(size_t)i * n + r];
+        for (int r = 0; r < n; ++r) out[(size_t)r * ldo + order[a + i]] = (float)w.acc_host[(size_t)i * n + r];
     }
     return DC_OK;
   };
-  const int rc = body();
-  const hipError_t e = hipStreamSynchronize(s);
-  hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "lm_score: %s", hipGetErrorString(e));
-  return DC_OK;
+  return lm_rows_finish(ctx, s, w, body(), "lm_score");
 }
 
 // the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
@@ -826,56 +870,32 @@ int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
 // Sampling captions: LanguageModel:sample with sample_argmax = false (LanguageModel.lua:40-41,328-333) -- S draws per region, each
 // word drawn from SoftMax(scores / temperature) by the Gumbel-max rule with counter-based noise, and the model's own
 // log-probability of every draw (definition: docs/SEMANTICS.md, "Sampling captions").
-// Schedule (lm_score's shape):
-//   per region (n rows): enc, image step, h_0.Wh, START step -- the state before the first word does not depend on the draw
+// Schedule (lm_score's shape, on the same shared pieces):
+//   per region (n rows): lm_start_state -- the state before the first word does not depend on the draw
 //   per chunk of whole draws (rows = s * n + i): copy the START state to every row, then for step t = 1 .. T:
 //   [sampling partials of h.Wout^T + b | G = h.Wh] ONE GEMM over all rows of the chunk (the last step without the Wh half) +
 //   sample_step_tail (word, log p added to the row's double sum, LSTM step with the word fed).  Finished rows stay in the launch:
 //   where a row ends is data-dependent, there is no prefix to cut.
 // Planned like lm_score (min(n, kScorePlanRows) rows, no split-K workspace), noise a function of (seed, s, r, t, column) alone
 // with r = row_ids[i] (or i): a draw does not depend on S, the chunking, or the other regions in the call.
-// Always fp32 MFMA and eager.  row_ids: host (n) or null; samples (n, S, T) and logprob (n, S): host.
+// row_ids: host (n) or null; samples (n, S, T) and logprob (n, S): host.
 int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts& o,
                 int32_t* samples, float* logprob) {
-  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, D = ctx->D, V1pad = ctx->V1pad, T = ctx->T, S = o.num_samples;
-  const int nslots = V1pad / 32, ld = 5 * nslots;
-  struct MathGuard {      // sampling is fp32 whatever dc_set_math_mode says
-    Settings& c; int saved;
-    ~MathGuard() { c.math_mode = saved; }
-  } mg{ctx->cfg, ctx->cfg.math_mode};
-  ctx->cfg.math_mode = 0;
-  // chunk of whole draws under the row cap
-  const size_t row_bytes = (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1;
-  const int64_t cap = ctx->sample_rows_cap > 0 ? ctx->sample_rows_cap : (int64_t)(((size_t)512 << 20) / row_bytes);
-  const int dchunk = (int)std::max<int64_t>(1, std::min<int64_t>(S, cap / n));
-  const int plan = std::min(n, kScorePlanRows);       // see lm_score
-  const size_t rmax = (size_t)dchunk * n;
-  if (rmax > (size_t)INT32_MAX / (size_t)std::max(ld, 4 * Hd))
+  const int Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, S = o.num_samples;
+  const int nslots = ctx->V1pad / 32, ld = 5 * nslots;
+  Fp32Guard fp32(ctx->cfg);
+  LmRows w;
+  lm_rows_plan(w, n, S, ctx->sample_rows_cap, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1);
+  if (w.rmax > (size_t)INT32_MAX / (size_t)std::max(ld, 4 * Hd))
     return ctx->fail(DC_E_INVALID, "lm_sample_n: %d regions are too many rows for one launch", n);
-  float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr, *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;
-  double* acc = nullptr;
-  int32_t *seq = nullptr, *keys = nullptr;
-  uint8_t* fin = nullptr;
-  const std::vector<Carve> cv = {
-      {(void**)&enc, (size_t)n * E * 4},    {(void**)&g0, (size_t)n * 4 * Hd * 4}, {(void**)&h0, (size_t)n * Hd * 4},
-      {(void**)&c0, (size_t)n * Hd * 4},    {(void**)&h, rmax * Hd * 4},            {(void**)&c, rmax * Hd * 4},
-      {(void**)&gates, rmax * 4 * Hd * 4},  {(void**)&part, rmax * ld * 4},         {(void**)&acc, rmax * 8},
-      {(void**)&seq, rmax * T * 4},         {(void**)&keys, rmax * 8},              {(void**)&fin, rmax},
-  };
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-  carve(cv, base);
+  int32_t *seq = nullptr, *keys = nullptr;      // the rows' words; their (row id, draw) noise keys
+  uint8_t* fin = nullptr;                       // END drawn at an earlier step
+  DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&seq, w.rmax * T * 4}, {(void**)&keys, w.rmax * 8}, {(void**)&fin, w.rmax}}));
   auto body = [&]() -> int {
-    // ---- per region: image step and START step (lm_sample_parts' first four launches) ----
-    DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, enc, n, E, D, 1, Ws(), plan));
-    DCCHK(linear(ctx, s, enc, ctx->wxT, ctx->lstm_b, g0, n, 4 * Hd, E, 0, Ws(), plan));
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, g0, c0, h0, n, nullptr, Hd, 1, nullptr, 1, 0, s));
-    DCCHK(linear(ctx, s, h0, ctx->whT, nullptr, g0, n, 4 * Hd, Hd, 0, Ws(), plan));
-    KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, V1, ctx->xg, g0, c0, h0, n, nullptr, Hd, 0, nullptr, 1, 0, s));
+    DCCHK(lm_start_state(ctx, s, codes, n, w.enc, w.g0, w.c0, w.h0, w.plan, nullptr, Ws()));
     std::vector<int32_t> kh, sh;
-    std::vector<double> ah;
-    for (int a = 0; a < S; a += dchunk) {
-      const int nd = std::min(dchunk, S - a);
+    for (int a = 0; a < S; a += w.chunk) {
+      const int nd = std::min(w.chunk, S - a);
       const size_t rows = (size_t)nd * n;
       kh.resize(rows * 2);
       for (int i = 0; i < nd; ++i)
@@ -883,46 +903,29 @@ int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int
           kh[2 * ((size_t)i * n + r)] = row_ids ? row_ids[r] : r;
           kh[2 * ((size_t)i * n + r) + 1] = a + i;
         }
-      HIPCHK(hipMemcpyAsync(keys, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemsetAsync(acc, 0, rows * 8, s));
-      HIPCHK(hipMemsetAsync(fin, 0, rows, s));
-      KCHK(launch_repeat_rows2(h0, c0, (size_t)n * Hd, nd, h, c, s));      // the START state of every draw's row block
+      DCCHK(lm_chunk_begin(ctx, s, w, nd, keys, kh, fin));
       for (int t = 1; t <= T; ++t) {
         const bool last = t == T;
-        GemmDesc v;
-        v.A = h; v.W = ctx->dec_w; v.bias = ctx->out_b; v.M = (int)rows; v.K = Hd; v.plan_M = plan;
-        v.amax_val = part; v.amax_ld = ld; v.rowidx = keys;
+        GemmDesc v = decode_step_desc(ctx, w.h, (int)rows, w.plan, last, w.gates);     // epilogue: the sampling partials
+        v.amax_val = w.part; v.amax_ld = ld; v.rowidx = keys;
         v.samp_t = t; v.samp_seed_lo = (uint32_t)(o.seed & 0xffffffffu); v.samp_seed_hi = (uint32_t)(o.seed >> 32);
         v.samp_inv_temp = o.temperature == 0.f ? 0.f : 1.f / o.temperature;
-        if (last) {
-          v.N = V1; v.ldc = V1;
-        } else {
-          v.N = V1pad + 4 * Hd; v.amax_cols = V1pad; v.amax_n = V1; v.C = gates; v.ldc = 4 * Hd;
-        }
         DCCHK(run_gemm(ctx, v, s));
-        KCHK(launch_sample_step_tail(part, nslots, ld, V1, ctx->xg, last ? nullptr : gates, c, h, acc, fin, seq, T, t - 1,
+        KCHK(launch_sample_step_tail(w.part, nslots, ld, V1, ctx->xg, last ? nullptr : w.gates, w.c, w.h, w.acc, fin, seq, T, t - 1,
                                      (int)rows, Hd, s));
       }
-      ah.resize(rows);
       sh.resize(rows * T);
-      HIPCHK(hipMemcpyAsync(ah.data(), acc, rows * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(sh.data(), seq, rows * T * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
+      DCCHK(lm_chunk_end(ctx, s, w, nd));
       for (int i = 0; i < nd; ++i)
         for (int r = 0; r < n; ++r) {
-          logprob[(size_t)r * S + a + i] = (float)ah[(size_t)i * n + r];
+          logprob[(size_t)r * S + a + i] = (float)w.acc_host[(size_t)i * n + r];
           memcpy(samples + ((size_t)r * S + a + i) * T, sh.data() + ((size_t)i * n + r) * T, (size_t)T * 4);
         }
     }
     return DC_OK;
   };
-  const int rc = body();
-  const hipError_t e = hipStreamSynchronize(s);
-  hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "lm_sample_n: %s", hipGetErrorString(e));
-  return DC_OK;
+  return lm_rows_finish(ctx, s, w, body(), "lm_sample_n");
 }
 
 // the validity rules of docs/SEMANTICS.md for a (Q, Tq) block of queries in host memory
@@ -949,13 +952,13 @@ int check_queries(dc_ctx* ctx, const int32_t* qry, int Q, int Tq, const char* wh
 // kernels fill each other's gaps.  Same outputs bit for bit (tests/test_gpu_e2e.py::test_single_lane_mode_parity).
 int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int plan, int32_t* seq_out) {
   const int h = std::min(n, ((n / 2 + 127) / 128) * 128);
-  if (h >= n || L.aux == nullptr) return lm_sample(ctx, L, codes, n, plan, nullptr, seq_out);
+  if (h >= n || L.aux == nullptr) return lm_sample(ctx, L.stream, lane_lm_bufs(L), lane_ws(L), codes, n, plan, nullptr, seq_out);
   const size_t wsf = L.splitk_ws ? kSplitkWsFloats / 2 : 0;     // each block its own half of the partial-tile scratch
   const LmPart parts[2] = {{L.stream, 0, h, Ws{L.splitk_ws, wsf}},
                            {L.aux, h, n - h, Ws{L.splitk_ws ? L.splitk_ws + wsf : nullptr, wsf}}};
   HIPCHK(hipEventRecord(L.ev_fork, L.stream));
   HIPCHK(hipStreamWaitEvent(L.aux, L.ev_fork, 0));
-  DCCHK(lm_sample_parts(ctx, L, codes, parts, 2, nullptr, seq_out, plan));
+  DCCHK(lm_sample_parts(ctx, lane_lm_bufs(L), codes, parts, 2, nullptr, seq_out, plan));
   HIPCHK(hipEventRecord(L.ev_join, L.aux));
   HIPCHK(hipStreamWaitEvent(L.stream, L.ev_join, 0));
   return DC_OK;
@@ -1047,7 +1050,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
   if (!features_only && !survivors_only && !no_decode) {
     if (cfg.beam_size > 0) DCCHK(lm_beamsearch(ctx, L, L.codes, R, L.seq, s));
     else if (side_streams) DCCHK(lm_sample_two_streams(ctx, L, L.codes, R, P, L.seq));
-    else DCCHK(lm_sample(ctx, L, L.codes, R, P, nullptr, L.seq));
+    else DCCHK(lm_sample(ctx, s, lane_lm_bufs(L), lane_ws(L), L.codes, R, P, nullptr, L.seq));
   }
   if (!survivors_only) STAGE_EVENT(7);
   // ---- final NMS + gather (DenseCapModel.lua:261-275) ----------------------------------------------
@@ -1082,7 +1085,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
     // group (tests/test_gpu_e2e.py::test_caption_order_is_output_invariant).  final_pack reads the packed token rows back
     // image by image.
     KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, g, P, ctx->D, L.out_feats, L.surv_total, s));
-    DCCHK(lm_sample(ctx, L, L.out_feats, R, P, L.surv_total, L.out_tokens));
+    DCCHK(lm_sample(ctx, s, lane_lm_bufs(L), lane_ws(L), L.out_feats, R, P, L.surv_total, L.out_tokens));
   } else if (survivors_only) {
     // beam search after the final NMS: image by image (the beam rows of one image advance together)
     for (int i = 0; i < g; ++i) {
@@ -2157,21 +2160,19 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   OP_PROLOGUE();
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_op_lm_sample: weights not loaded");
   if (n <= 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample: n must be > 0");
-  Lane& L = lane0(ctx);
-  // private scratch for n rows
-  const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1;
-  struct Sav { float *enc, *gates, *h, *c, *logits; int32_t* tok; } sv{L.enc, L.gates, L.hstate, L.cstate, L.logits, L.tok};
+  // private scratch for n rows (the beam search brings its own: beam_prepare)
+  const size_t E = ctx->E, Hd = ctx->Hd, rows = n;
+  LmBufs b{};               // sized as lane_prepare sizes the lane's
   const std::vector<Carve> cv = {
-      {(void**)&L.enc, (size_t)n * E * 4},     {(void**)&L.gates, (size_t)n * 4 * Hd * 4},
-      {(void**)&L.hstate, (size_t)n * Hd * 4}, {(void**)&L.cstate, (size_t)n * Hd * 4},
-      {(void**)&L.logits, (size_t)n * std::max(V1, ctx->V1pad / 16) * 4}, {(void**)&L.tok, (size_t)n * 4},
+      {(void**)&b.enc, rows * E * 4},  {(void**)&b.gates, rows * 4 * Hd * 4},       {(void**)&b.h, rows * Hd * 4},
+      {(void**)&b.c, rows * Hd * 4},   {(void**)&b.amax, rows * std::max(ctx->V + 1, ctx->V1pad / 16) * 4},
   };
   void* base = nullptr;
   HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
   carve(cv, base);
-  int rc = ctx->cfg.beam_size > 0 ? lm_beamsearch(ctx, L, codes, n, tokens, s) : lm_sample(ctx, L, codes, n, 0, nullptr, tokens);
+  int rc = ctx->cfg.beam_size > 0 ? lm_beamsearch(ctx, lane0(ctx), codes, n, tokens, s)
+                                  : lm_sample(ctx, s, b, lane_ws(lane0(ctx)), codes, n, 0, nullptr, tokens);
   hipError_t e2 = hipStreamSynchronize(s);
-  L.enc = sv.enc; L.gates = sv.gates; L.hstate = sv.h; L.cstate = sv.c; L.logits = sv.logits; L.tok = sv.tok;
   hipFree(base);
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
@@ -2195,23 +2196,32 @@ int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* querie
   OP_EPILOGUE();
 }
 
+// What dc_score_captions and dc_sample_captions (`who`) do before their language-model pass: the forward of dc_forward_test (one
+// image: lane 0; without the greedy decode when no tokens are wanted), then the *K rows it returned, compacted from the lane's
+// fc7 codes into L.out_feats, its survivor block (the lane is idle once the forward is harvested).  *K = 0: no rows, nothing enqueued.
+static int forward_kept_codes(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out, const char* who,
+                              int* K) {
+  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
+  Lane& L = lane0(ctx);
+  *K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
+  if (*K > out->capacity)
+    return ctx->fail(DC_E_INVALID, "%s: the image has %d regions but out->capacity is %d", who, *K, (int)out->capacity);
+  if (*K > 0)
+    KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, L.stream));
+  return DC_OK;
+}
+
 int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const int32_t* queries, int Q,
                       int Tq, dc_result* out, float* loglik) {
   if (!ctx) return DC_E_INVALID;
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_score_captions: weights not loaded");
   if (!img_chw || !queries || !out || !loglik) return ctx->fail(DC_E_INVALID, "dc_score_captions: null pointer");
   DCCHK(check_queries(ctx, queries, Q, Tq, "dc_score_captions"));
-  // the forward of dc_forward_test (one image: lane 0; without the language model when no tokens are wanted), then the rows
-  // it returned, compacted from the lane's fc7 codes into its survivor block (the lane is idle once the forward is harvested)
-  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
-  Lane& L = lane0(ctx);
-  const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
-  if (K > out->capacity)
-    return ctx->fail(DC_E_INVALID, "dc_score_captions: the image has %d regions but out->capacity is %d", K, (int)out->capacity);
+  int K = 0;
+  DCCHK(forward_kept_codes(ctx, img_chw, H, W, img_on_device, out, "dc_score_captions", &K));
   if (K == 0) return DC_OK;
-  hipStream_t s = L.stream;
-  KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, s));
-  return lm_score(ctx, s, L.out_feats, K, queries, Q, Tq, loglik, Q);
+  Lane& L = lane0(ctx);
+  return lm_score(ctx, L.stream, L.out_feats, K, queries, Q, Tq, loglik, Q);
 }
 
 int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
@@ -2243,17 +2253,11 @@ int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_sample_captions: weights not loaded");
   if (!img_chw || !out || !samples || !logprob) return ctx->fail(DC_E_INVALID, "dc_sample_captions: null pointer");
   DCCHK(check_sample_opts(ctx, opts, "dc_sample_captions"));
-  // as dc_score_captions: the forward of dc_forward_test on lane 0 (without the greedy decode when no tokens are wanted), the
-  // rows it returned compacted into the lane's survivor block, then the sampling on those rows (r = output row)
-  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
-  Lane& L = lane0(ctx);
-  const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
-  if (K > out->capacity)
-    return ctx->fail(DC_E_INVALID, "dc_sample_captions: the image has %d regions but out->capacity is %d", K, (int)out->capacity);
+  int K = 0;
+  DCCHK(forward_kept_codes(ctx, img_chw, H, W, img_on_device, out, "dc_sample_captions", &K));
   if (K == 0) return DC_OK;
-  hipStream_t s = L.stream;
-  KCHK(launch_survivor_compact(L.codes, L.picks2, L.count2, kCountStride, 1, L.P, ctx->D, L.out_feats, L.surv_total, s));
-  return lm_sample_n(ctx, s, L.out_feats, K, nullptr, *opts, samples, logprob);
+  Lane& L = lane0(ctx);
+  return lm_sample_n(ctx, L.stream, L.out_feats, K, nullptr, *opts, samples, logprob);      // r = output row
 }
 
 }  // extern "C"

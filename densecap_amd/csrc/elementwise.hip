@@ -221,6 +221,73 @@ __global__ void lstm_pointwise_kernel(const float* __restrict__ gates, float* __
   }
 }
 
+// ---- what the three decode step tails below share --------------------------------------------------------------------------
+// The LSTM point-wise half: thread tid owns hidden units j0 + tid + u * 256 (u < kTailUPT) of its row in the pass that starts
+// at j0.  tail_load requests a pass's token-independent operands (the h.Wh gates, c); the kernels call it for j0 = 0 before
+// their reduction, so the operands travel while the word is being found.  tail_update then runs every pass -- the ones past
+// the first (Hd > 512) load in place -- with the word's xg row `x` (null: no embedding row) added: per element
+// (x + gates_pre), sigmoid/tanh, c' = f*c + i*g, h' = o*tanh(c'), c and h in place.
+constexpr int kTailUPT = 2;                         // hidden units per thread and pass (Hd = 512: one pass)
+struct TailRegs { float gpre[kTailUPT][4], cprev[kTailUPT]; };
+__device__ __forceinline__ void tail_load(TailRegs& r, const float* __restrict__ g, const float* __restrict__ c_row, int Hd,
+                                          int j0, int tid, int zero_c) {
+#pragma unroll
+  for (int u = 0; u < kTailUPT; ++u) {
+    const int j = j0 + tid + u * 256;
+    if (j < Hd) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.gpre[u][q] = g[q * Hd + j];
+      r.cprev[u] = zero_c ? 0.f : c_row[j];
+    }
+  }
+}
+__device__ __forceinline__ void tail_update(TailRegs& r, const float* __restrict__ g, const float* __restrict__ x,
+                                            float* __restrict__ c_row, float* __restrict__ h_row, int Hd, int tid, int zero_c) {
+  for (int j0 = 0; j0 < Hd; j0 += 256 * kTailUPT) {
+    if (j0 > 0) tail_load(r, g, c_row, Hd, j0, tid, zero_c);
+#pragma unroll
+    for (int u = 0; u < kTailUPT; ++u) {
+      const int j = j0 + tid + u * 256;
+      if (j >= Hd) continue;
+      float gi = r.gpre[u][0], gf = r.gpre[u][1], go = r.gpre[u][2], gg = r.gpre[u][3];
+      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
+      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
+      const float gt = th_tanhf(gg);
+      const float cn = fg * r.cprev[u] + ig * gt;
+      c_row[j] = cn;
+      h_row[j] = og * th_tanhf(cn);
+    }
+  }
+}
+
+// Arg-best merge: (ov, oi) replaces (best, bi) -- true is returned, for a caller that carries more with the entry -- when it
+// is an entry at all and the larger one, the lower column on ties.  kNoCol: no entry yet.
+constexpr int kNoCol = 0x7fffffff;
+__device__ __forceinline__ bool argbest_merge(float& best, int& bi, float ov, int oi) {
+  if (oi != kNoCol && (bi == kNoCol || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; return true; }
+  return false;
+}
+
+// Row log-sum-exp from the GEMM's (max, sum exp(v - max)) partials, `stride` floats apart per 32-column slot, given the row
+// max mx over the slots: sum_s sum_s' * exp(max_s - mx) in double -- every thread its slots tid, tid + 256, ... in ascending
+// order, then a fixed butterfly over the wave; after lse_wave_sums (which ends in a barrier) ssum holds the four waves' sums
+// and lse_finish joins them in order: lse = mx + log(sum), as THNN's LogSoftMax forms max + log(sum).  The scorer and the
+// sampler both form lse here: a sampled caption's log-probability is the scorer's number bit for bit.
+__device__ __forceinline__ void lse_wave_sums(const float* __restrict__ p, int stride, int nslots, float mx, double* ssum, int tid) {
+  double sum = 0.0;
+  for (int s = tid; s < nslots; s += 256) {
+    const float pm = p[stride * s];
+    if (pm != -INFINITY) sum += (double)p[stride * s + 1] * exp((double)pm - (double)mx);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if ((tid & 63) == 0) ssum[tid >> 6] = sum;
+  __syncthreads();
+}
+__device__ __forceinline__ double lse_finish(float mx, const double* ssum) {
+  return (double)mx + log(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
+}
+
 // ---- decode step tail: arg-max finalize + LSTM point-wise, one workgroup (256 threads) per row ---------------------
 // Replaces argmax_finalize + the gate row-term epilogue + lstm_pointwise of one step (3 launches and an 8 MB gate
 // round trip) by one launch: the token a row just produced selects its xg row here, so the h.Wh product of the NEXT
@@ -239,83 +306,38 @@ __global__ __launch_bounds__(256) void lstm_step_tail_kernel(const float* __rest
   __shared__ float sv[4];
   __shared__ int si[4];
   // the token-independent operands are requested first: they travel while the arg-max is being reduced
-  constexpr int UPT = 2;                            // hidden units per thread and pass (Hd = 512: one pass)
-  float gpre[UPT][4], cprev[UPT];
+  TailRegs r;
   const float* g = gates_pre ? gates_pre + (size_t)m * 4 * Hd : nullptr;
-  if (g != nullptr) {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = tid + u * 256;
-      if (j < Hd) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-        cprev[u] = zero_c ? 0.f : c[(size_t)m * Hd + j];
-      }
-    }
-  }
+  float* c_row = c + (size_t)m * Hd;
+  if (g != nullptr) tail_load(r, g, c_row, Hd, 0, tid, zero_c);
   int tok = fixed_tok;
   if (pval != nullptr) {
     float best = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = kNoCol;
     for (int j = tid; j < ntiles; j += 256) {
       const float v = pval[(size_t)m * ld + j];
       const int i = pidx[(size_t)m * ld + j];
-      if (bi == 0x7fffffff || v > best) { best = v; bi = i; }      // ascending j = ascending column: first max stays
+      if (bi == kNoCol || v > best) { best = v; bi = i; }      // ascending j = ascending column: first max stays
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-    }
+    for (int o = 32; o > 0; o >>= 1) argbest_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
     if (lane == 0) { sv[wid] = best; si[wid] = bi; }
     __syncthreads();
     best = sv[0]; bi = si[0];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float ov = sv[w];
-      const int oi = si[w];
-      if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-    }
+    for (int w = 1; w < 4; ++w) argbest_merge(best, bi, sv[w], si[w]);
     tok = bi + 1;
     if (tid == 0) seq[(size_t)m * T + t] = tok;
   }
   if (g == nullptr) return;
-  const float* x = tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr;
-  for (int j0 = 0; j0 < Hd; j0 += 256 * UPT) {
-    if (j0 > 0) {                                   // Hd > 512: further passes load in place
-#pragma unroll
-      for (int u = 0; u < UPT; ++u) {
-        const int j = j0 + tid + u * 256;
-        if (j < Hd) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-          cprev[u] = zero_c ? 0.f : c[(size_t)m * Hd + j];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = j0 + tid + u * 256;
-      if (j >= Hd) continue;
-      float gi = gpre[u][0], gf = gpre[u][1], go = gpre[u][2], gg = gpre[u][3];
-      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
-      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
-      const float gt = th_tanhf(gg);
-      const size_t i = (size_t)m * Hd + j;
-      const float cn = fg * cprev[u] + ig * gt;
-      c[i] = cn;
-      h[i] = og * th_tanhf(cn);
-    }
-  }
+  tail_update(r, g, tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr, c_row, h + (size_t)m * Hd, Hd, tid, zero_c);
 }
 
 // ---- teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup (256 threads) per row -------------------
 // The row's log-sum-exp from the GEMM's partials (max, sum exp(v - max)) per 32-column slot: the row max M over the slots,
-// then sum_s sum_s' * exp(max_s - M) in double -- every thread its slots tid, tid + 256, ... in ascending order, then a fixed
-// butterfly over the wave and the four waves in order -- and lse = M + log(sum), as THNN's LogSoftMax forms max + log(sum).
-// log p(target) = tlogit - lse is added to the row's double sum (one term per step, in step order).  The row then takes the
-// LSTM step of lstm_step_tail_kernel with its target word fed (teacher forcing), unless the target is END (its last term).
+// then lse as lse_wave_sums / lse_finish form it.  log p(target) = tlogit - lse is added to the row's double sum (one term
+// per step, in step order).  The row then takes the LSTM step of lstm_step_tail_kernel with its target word fed (teacher
+// forcing), unless the target is END (its last term).
 __global__ __launch_bounds__(256) void lse_step_tail_kernel(const float* __restrict__ part, int nslots, int ld,
                                                             const int32_t* __restrict__ tgt, int end_tok,
                                                             const float* __restrict__ xg,
@@ -328,20 +350,10 @@ __global__ __launch_bounds__(256) void lse_step_tail_kernel(const float* __restr
   // the point-wise operands of the first pass are requested first: they travel while the log-sum-exp is being reduced
   const int tok = tgt[m];
   const bool feed = tok != end_tok && gates_pre != nullptr;
-  constexpr int UPT = 2;                            // hidden units per thread and pass (Hd = 512: one pass)
-  float gpre[UPT][4], cprev[UPT];
+  TailRegs r;
   const float* g = feed ? gates_pre + (size_t)m * 4 * Hd : nullptr;
-  if (feed) {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = tid + u * 256;
-      if (j < Hd) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-        cprev[u] = c[(size_t)m * Hd + j];
-      }
-    }
-  }
+  float* c_row = c + (size_t)m * Hd;
+  if (feed) tail_load(r, g, c_row, Hd, 0, tid, 0);
   const float* p = part + (size_t)m * ld;
   float mx = -INFINITY;
   for (int s = tid; s < nslots; s += 256) { const float v = p[2 * s]; mx = v > mx ? v : mx; }
@@ -350,54 +362,17 @@ __global__ __launch_bounds__(256) void lse_step_tail_kernel(const float* __restr
   if (lane == 0) smx[wid] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-  double sum = 0.0;
-  for (int s = tid; s < nslots; s += 256) {
-    const float pm = p[2 * s];
-    if (pm != -INFINITY) sum += (double)p[2 * s + 1] * exp((double)pm - (double)mx);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) ssum[wid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    const double lse = (double)mx + log(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
-    acc[m] += (double)p[ld - 1] - lse;
-  }
+  lse_wave_sums(p, 2, nslots, mx, ssum, tid);
+  if (tid == 0) acc[m] += (double)p[ld - 1] - lse_finish(mx, ssum);
   if (!feed) return;
-  const float* x = xg + (size_t)(tok - 1) * 4 * Hd;
-  for (int j0 = 0; j0 < Hd; j0 += 256 * UPT) {
-    if (j0 > 0) {                                   // Hd > 512: further passes load in place
-#pragma unroll
-      for (int u = 0; u < UPT; ++u) {
-        const int j = j0 + tid + u * 256;
-        if (j < Hd) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-          cprev[u] = c[(size_t)m * Hd + j];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = j0 + tid + u * 256;
-      if (j >= Hd) continue;
-      const float gi = x[j] + gpre[u][0], gf = x[Hd + j] + gpre[u][1], go = x[2 * Hd + j] + gpre[u][2],
-                  gg = x[3 * Hd + j] + gpre[u][3];
-      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
-      const float gt = th_tanhf(gg);
-      const size_t i = (size_t)m * Hd + j;
-      const float cn = fg * cprev[u] + ig * gt;
-      c[i] = cn;
-      h[i] = og * th_tanhf(cn);
-    }
-  }
+  tail_update(r, g, xg + (size_t)(tok - 1) * 4 * Hd, c_row, h + (size_t)m * Hd, Hd, tid, 0);
 }
 
 // ---- sampling step tail (densecap.hip::lm_sample_n), one workgroup (256 threads) per row -----------------------------------
 // The row's partials come from the sampling epilogue of the step GEMM, five floats per 32-column slot: (max, sum exp) as the
 // scorer's, then the slot's best perturbed entry (score, column, logit at that column).  The word drawn is the best entry over
-// the slots -- every thread its slots tid, tid + 256, ... in ascending order, then the butterfly of lstm_step_tail_kernel, lower
-// column on ties -- and its log-probability is logit - lse with lse formed exactly as in lse_step_tail_kernel: a row that ends in
+// the slots -- every thread its slots tid, tid + 256, ... in ascending order, then the merge of lstm_step_tail_kernel, lower
+// column on ties -- and its log-probability is logit - lse, lse from the same two helpers as the scorer's: a row that ends in
 // END therefore carries the number the scorer returns for that caption.  A finished row (END drawn at an earlier step) writes
 // zeros and adds nothing, but still takes the LSTM step with the word drawn: all T steps run for every row, as in LM:sample.
 __global__ __launch_bounds__(256) void sample_step_tail_kernel(const float* __restrict__ part, int nslots, int ld, int end_tok,
@@ -411,101 +386,53 @@ __global__ __launch_bounds__(256) void sample_step_tail_kernel(const float* __re
   __shared__ float smx[4], sv[4], sl[4];
   __shared__ int si[4];
   __shared__ double ssum[4];
-  constexpr int UPT = 2;                            // hidden units per thread and pass (Hd = 512: one pass)
-  float gpre[UPT][4], cprev[UPT];
+  TailRegs r;
   const float* g = gates_pre ? gates_pre + (size_t)m * 4 * Hd : nullptr;
-  if (g != nullptr) {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = tid + u * 256;
-      if (j < Hd) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-        cprev[u] = c[(size_t)m * Hd + j];
-      }
-    }
-  }
+  float* c_row = c + (size_t)m * Hd;
+  if (g != nullptr) tail_load(r, g, c_row, Hd, 0, tid, 0);
+  // the row max of the log-sum-exp shares its slot loop, its butterfly and its barrier with the arg-best reduction
   const float* p = part + (size_t)m * ld;
   float mx = -INFINITY, best = -INFINITY, bl = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = kNoCol;
   for (int s = tid; s < nslots; s += 256) {
     const float v = p[5 * s];
     mx = v > mx ? v : mx;
     const float pv = p[5 * s + 2];
     const int i = __builtin_bit_cast(int, p[5 * s + 3]);
-    if (i != 0x7fffffff && (bi == 0x7fffffff || pv > best)) { best = pv; bi = i; bl = p[5 * s + 4]; }   // ascending slot = ascending column
+    if (i != kNoCol && (bi == kNoCol || pv > best)) { best = pv; bi = i; bl = p[5 * s + 4]; }   // ascending slot = ascending column
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(mx, o, 64);
     mx = om > mx ? om : mx;
-    const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bl, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; bl = ol; }
+    const float ol = __shfl_xor(bl, o, 64);
+    if (argbest_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64))) bl = ol;
   }
   if (lane == 0) { smx[wid] = mx; sv[wid] = best; si[wid] = bi; sl[wid] = bl; }
   __syncthreads();
   mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
   best = sv[0]; bi = si[0]; bl = sl[0];
 #pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const float ov = sv[w], ol = sl[w];
-    const int oi = si[w];
-    if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; bl = ol; }
-  }
+  for (int w = 1; w < 4; ++w)
+    if (argbest_merge(best, bi, sv[w], si[w])) bl = sl[w];
   // No entry at all (bi still the sentinel): every perturbed score of the row is NaN -- a NaN or Inf in the caller's codes.  The
   // row then has no word: it writes 0, ends, its log-probability becomes NaN, and like lstm_step_tail_kernel with tok == 0 it
   // takes the LSTM step without an embedding row.  A column from the epilogue is below amax_n; anything else is treated alike,
   // so no address is ever formed from a value that was not checked.
   const bool none = bi < 0 || bi >= end_tok;
   const int tok = none ? 0 : bi + 1;
-  double sum = 0.0;
-  for (int s = tid; s < nslots; s += 256) {
-    const float pm = p[5 * s];
-    if (pm != -INFINITY) sum += (double)p[5 * s + 1] * exp((double)pm - (double)mx);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) ssum[wid] = sum;
-  __syncthreads();
+  lse_wave_sums(p, 5, nslots, mx, ssum, tid);
   if (tid == 0) {
     const bool done = fin[m] != 0;
     seq[(size_t)m * T + t] = done ? 0 : tok;
     if (!done) {
-      const double lse = (double)mx + log(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
       if (none) acc[m] = (double)NAN;
-      else acc[m] += (double)bl - lse;
+      else acc[m] += (double)bl - lse_finish(mx, ssum);
       if (none || tok == end_tok) fin[m] = 1;
     }
   }
   if (g == nullptr) return;
-  const float* x = tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr;
-  for (int j0 = 0; j0 < Hd; j0 += 256 * UPT) {
-    if (j0 > 0) {                                   // Hd > 512: further passes load in place
-#pragma unroll
-      for (int u = 0; u < UPT; ++u) {
-        const int j = j0 + tid + u * 256;
-        if (j < Hd) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gpre[u][q] = g[q * Hd + j];
-          cprev[u] = c[(size_t)m * Hd + j];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int j = j0 + tid + u * 256;
-      if (j >= Hd) continue;
-      float gi = gpre[u][0], gf = gpre[u][1], go = gpre[u][2], gg = gpre[u][3];
-      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
-      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
-      const float gt = th_tanhf(gg);
-      const size_t i = (size_t)m * Hd + j;
-      const float cn = fg * cprev[u] + ig * gt;
-      c[i] = cn;
-      h[i] = og * th_tanhf(cn);
-    }
-  }
+  tail_update(r, g, tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr, c_row, h + (size_t)m * Hd, Hd, tid, 0);
 }
 
 // dst_a / dst_b = `copies` back-to-back repeats of src_a / src_b (len floats each; len % 4 == 0): the START state of every
