@@ -1401,9 +1401,18 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   if (!ctx || !w) return DC_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->have_weights) return ctx->fail(DC_E_STATE, "weights already loaded; create a new ctx");
-  if (w->num_anchors <= 0 || w->rpn_hidden % 32 || w->fc_dim % 256 || w->enc_size % 32 || w->rnn_size % 32 ||
-      w->vocab_size <= 0 || w->seq_length <= 0)
-    return ctx->fail(DC_E_INVALID, "dc_load_weights: unsupported dimensions");
+  // the supported family (docs/SEMANTICS.md, "Supported model dimensions"): every contraction walks K in 32-wide tiles, the
+  // recognition heads walk fc_dim 256 columns at a time -- refused here, by field, so that no forward can fail on a dimension
+  {
+    const struct { const char* name; int v, mult; } dims[] = {
+        {"num_anchors", w->num_anchors, 1}, {"rpn_hidden", w->rpn_hidden, 32}, {"fc_dim", w->fc_dim, 256},
+        {"enc_size", w->enc_size, 32},      {"rnn_size", w->rnn_size, 32},     {"vocab_size", w->vocab_size, 1},
+        {"seq_length", w->seq_length, 1}};
+    for (const auto& f : dims)
+      if (f.v <= 0 || f.v % f.mult)
+        return ctx->fail(DC_E_INVALID, "dc_load_weights: unsupported dimensions: %s = %d must be a positive multiple of %d", f.name,
+                         f.v, f.mult);
+  }
   ctx->k = w->num_anchors; ctx->R = w->rpn_hidden; ctx->V = w->vocab_size; ctx->T = w->seq_length;
   ctx->E = w->enc_size; ctx->Hd = w->rnn_size; ctx->D = w->fc_dim;
   memcpy(ctx->fc, w->field_centers, sizeof ctx->fc);

@@ -27,7 +27,12 @@ FEAT_RMS = 226.8
 
 
 def make_synthetic_weights(seed=1234, vocab_size=10497, seq_length=15, rpn_hidden=256,
-                           enc_size=512, rnn_size=512, fc_dim=4096, feat_rms=None):
+                           enc_size=512, rnn_size=512, fc_dim=4096, feat_rms=None, anchors=None):
+    """anchors: (2, k) widths / heights (LocalizationLayer.lua:611-621: opt.anchors or the default table times
+    anchor_scale); the RPN head tensors are sized from it.  None = DEFAULT_ANCHORS, same random stream as ever."""
+    anchors = DEFAULT_ANCHORS if anchors is None else np.ascontiguousarray(anchors, dtype=np.float32)
+    if anchors.ndim != 2 or anchors.shape[0] != 2 or anchors.shape[1] < 1:
+        raise ValueError("anchors has shape %s, need (2, k)" % (anchors.shape,))
     g = torch.Generator().manual_seed(seed)
 
     def randn(*shape, std=1.0):
@@ -45,7 +50,7 @@ def make_synthetic_weights(seed=1234, vocab_size=10497, seq_length=15, rpn_hidde
             b = b / feat_rms
         conv_w.append(w.contiguous()); conv_b.append(b.contiguous())
     W["conv_w"], W["conv_b"] = conv_w, conv_b
-    k = DEFAULT_ANCHORS.shape[1]
+    k = anchors.shape[1]
     W["rpn_conv_w"] = randn(rpn_hidden, 512, 3, 3, std=math.sqrt(2.0 / (9 * 512)))
     W["rpn_conv_b"] = randn(rpn_hidden, std=0.05)
     W["rpn_box_w"] = randn(4 * k, rpn_hidden, 1, 1, std=0.02)
@@ -69,7 +74,7 @@ def make_synthetic_weights(seed=1234, vocab_size=10497, seq_length=15, rpn_hidde
     W["lstm_b"] = lb.contiguous()
     W["lm_out_w"] = randn(vocab_size + 1, rnn_size, std=3.0 / math.sqrt(rnn_size))
     W["lm_out_b"] = randn(vocab_size + 1, std=0.1)
-    W["anchors"] = torch.from_numpy(DEFAULT_ANCHORS.copy())
+    W["anchors"] = torch.from_numpy(anchors.copy())
     W["field_centers"] = (8.5, 8.5, 16.0, 16.0)  # net_utils.compute_field_centers for VGG-16 layers 1..30
     W["vocab_size"] = vocab_size
     W["seq_length"] = seq_length

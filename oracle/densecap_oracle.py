@@ -443,9 +443,10 @@ def lstm_step(x_gates, h, c, Wh):
     return h2, c2
 
 
-def lm_sample(codes, Wt, T, return_logits=False):
+def lm_sample(codes, Wt, T, return_logits=False, return_state=False):
     """LM:sample with sample_argmax (LanguageModel.lua:293-348).
     codes: torch (N,4096).  Returns int64 (N,T) tokens, 1-based, START=END=V+1.
+    return_state: the result is followed by dict(enc, h, c) -- the image encoder's output and the LSTM state after step T.
     Wt: lm_enc_w (512,4096), lm_enc_b, lm_emb (V+2,512), lstm_w (1024,2048)
     [rows 0..511 = Wx, 512..1023 = Wh], lstm_b (2048), lm_out_w (V+1,512), lm_out_b."""
     import torch
@@ -468,9 +469,10 @@ def lm_sample(codes, Wt, T, return_logits=False):
         seq[:, t] = tok
         if return_logits:
             all_logits.append(logits)
-    if return_logits:
-        return seq.numpy(), all_logits
-    return seq.numpy()
+    out = (seq.numpy(), all_logits) if return_logits else (seq.numpy(),)
+    if return_state:
+        out = out + (dict(enc=enc.numpy(), h=h.numpy(), c=c.numpy()),)
+    return out if len(out) > 1 else out[0]
 
 
 def _log_softmax_thnn(x):
@@ -658,7 +660,8 @@ def forward_test(img, Wt, rpn_nms_thresh=0.7, final_nms_thresh=0.3, num_proposal
     st["feat"] = feat[0].numpy()
     box_head, score_head = rpn_heads(feat, Wt)
     st["box_head"] = box_head; st["score_head"] = score_head
-    d = rpn_decode(box_head, score_head, H, W, clip_boxes=clip_boxes)
+    anchors = np.asarray(Wt["anchors"], F32) if "anchors" in Wt else DEFAULT_ANCHORS   # (2,k), LocalizationLayer.lua:611-621
+    d = rpn_decode(box_head, score_head, H, W, anchors=anchors, clip_boxes=clip_boxes)
     st["rpn"] = d
     b5 = np.concatenate([d["x1y1x2y2"], d["p"][:, None]], 1)
     idx = nms_fn(b5, rpn_nms_thresh, None if num_proposals == -1 else num_proposals)

@@ -324,7 +324,7 @@ def strict_check(model, weights, img, P, rpn_thr=0.7, final_thr=0.3, T=None, sta
 def _strict_check_stages(model, weights, img, P, rpn_thr, final_thr, T, O, torch, hip, ora, st, report):
     H, W = img.shape[1:]
     fh, fw = st["feat"].shape[1:]
-    k = O.DEFAULT_ANCHORS.shape[1]
+    k = int(np.asarray(weights["anchors"]).shape[1])
     A = k * fh * fw
     # ---- (1) continuous: trunk, RPN ---------------------------------------------------------------------
     feat, _ = model.debug_fetch("feat_hwc", (fh, fw, 512))

@@ -203,3 +203,75 @@ def test_bad_arguments_are_refused():
     assert L.dc_debug_plan_gemm(64, 64, 576, 0, 32, 0, 0, o) < 0               # K != 9 * Cin
     assert L.dc_debug_plan_gemm(64, 64, 64, 65, 0, 0, 0, o) < 0                # plan_M > M
     assert L.dc_debug_plan_gemm(64, 64, 64, 0, 0, 0, 0, None) < 0
+
+
+# ---- model dimensions other than the defaults (tests/test_gpu_dims.py runs the same five sets on the GPU) ---------------------
+#            R    E     Hd    D     V      k
+DIM_SETS = {
+    "minimal": (32, 32, 32, 256, 5, 1),
+    "e_lt_h": (128, 256, 768, 512, 777, 9),
+    "e_gt_h": (512, 768, 256, 1024, 1500, 12),
+    "odd32": (96, 544, 1056, 768, 70, 5),
+    "big_vocab": (256, 512, 512, 256, 20000, 15),
+}
+
+
+def contractions_of(R, E, Hd, D, V, k):
+    """(name, M, N, K, conv Cin, arg-max) of every contraction whose shape depends on the model's dimensions, at 1 .. 1000 RoI
+    rows and on the conv5_3 maps of 224x288 and 600x720 images."""
+    v1pad = (V + 1 + 63) // 64 * 64
+    out = []
+    for P in (1, 50, 64, 100, 300, 1000):
+        out += [("lm_encoder", P, E, D, 0, 0), ("gates_x", P, 4 * Hd, E, 0, 0), ("gates_h", P, 4 * Hd, Hd, 0, 0),
+                ("decode_step", P, v1pad + 4 * Hd, Hd, 0, 1), ("last_step", P, V + 1, Hd, 0, 1),
+                ("fc6", P, D, 25088, 0, 0), ("fc7", P, D, D, 0, 0)]
+    out.append(("xg_table", V + 2, 4 * Hd, E, 0, 0))                     # dc_load_weights: b + Emb.Wx for every token
+    for H, W in ((224, 288), (600, 720)):
+        rows = conv_rows(H, W, 4)
+        out += [("rpn_conv", rows, R, 4608, 512, 0), ("rpn_heads", rows, 6 * k, R, 0, 0)]
+    return out
+
+
+@pytest.mark.parametrize("cus", [256, 104])
+@pytest.mark.parametrize("name", list(DIM_SETS))
+def test_plans_of_other_model_dimensions_satisfy_the_launchers(name, cus, cu_count):
+    """dc_load_weights admits K = E, Hd, R that are odd multiples of 32; the K-split kernel walks K two tiles at a time
+    (K % 64 == 0 per slice) and so do the stream-K and tail plans.  Every plan of every contraction of the five sets must
+    satisfy the preconditions of the launcher it names: a violation would be a launch refused in the middle of a forward."""
+    cu_count(cus)
+    ws_floats = 6400 * 128 * 128
+    for what, M, N, K, cin, amax in contractions_of(*DIM_SETS[name]):
+        for serial in (0, 1):
+            p = plan(M, N, K, 0, cin, amax, serial)                      # plan() asserts DC_OK
+            why = (name, cus, what, M, N, K, serial, p)
+            nkt = K // 32
+            assert K % 32 == 0, why
+            if p["kind"] == "splitk":
+                sp = p["splitk"]
+                assert sp > 1 and nkt % sp == 0 and (nkt // sp) % 2 == 0 and p["route"] == "ks", why
+                assert sp * M * N <= ws_floats and not amax, why
+            elif p["kind"] == "streamk":
+                assert K % 64 == 0 and 0 < p["sk_wgs"] <= cus and p["sk_np"] == nkt // 2 and serial and not amax, why
+            elif p["kind"] == "tail":
+                sp = p["tail_splitk"]
+                assert K % 64 == 0 and sp > 1 and nkt % sp == 0 and (nkt // sp) % 2 == 0, why
+                assert 0 < p["m_split"] < M and p["m_split"] % 128 == 0 and serial and not amax, why
+            else:
+                assert p["kind"] == "plain" and p["splitk"] == 1, why
+                if p["route"] == "ks":
+                    assert K % 64 == 0 and not amax, why                 # the K-split kernel steps two K-tiles at a time
+            if amax:
+                assert p["kind"] == "plain" and p["route"] in ("v2_128x64", "v2_64x64"), why   # the arg-max epilogue's tiles
+            if p["route"] == "v2_128x64":
+                assert p["stages"] in (2, 3), why
+
+
+def test_an_odd_number_of_k_tiles_never_reaches_the_k_split_kernel():
+    """K = 32 * odd for every shape class the planner distinguishes: few tiles (split-K territory), one partial round
+    (stream-K), full rounds and a remainder (tail plan), many tiles (the unsplit K-split kernel)."""
+    for K in (544, 1056, 1120, 2080, 4128, 25120):
+        for M in (1, 100, 300, 1000, 1710, 6750, 16000, 27000, 40000):
+            for N in (128, 256, 512, 4096):
+                for serial in (0, 1):
+                    p = plan(M, N, K, serial=serial)
+                    assert p["kind"] == "plain" and p["route"] != "ks", (M, N, K, serial, p)
