@@ -46,6 +46,12 @@ class DcSampleOpts(C.Structure):
     _fields_ = [("num_samples", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class DcBeamState(C.Structure):
+    """dc_beam_state (include/densecap_debug.h): device pointers to the nprop x beam state rows of the beam search."""
+    _fields_ = [("h", C.c_void_p), ("c", C.c_void_p), ("beam_lp", C.c_void_p), ("beams", C.c_void_p), ("tok", C.c_void_p),
+                ("parent", C.c_void_p), ("fin", C.c_void_p)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -86,6 +92,13 @@ _SIGS = {
     "dc_debug_fetch": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "dc_debug_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "dc_debug_plan_gemm": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, c_int32_p]),
+    "dc_debug_beam_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
+    "dc_debug_beam_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_debug_beam_start": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(DcBeamState), C.c_void_p, C.c_void_p]),
+    "dc_debug_beam_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(DcBeamState), C.POINTER(DcBeamState), C.c_void_p,
+                                     C.c_void_p]),
     "dc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "dc_comm_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),

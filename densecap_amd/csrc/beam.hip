@@ -6,15 +6,22 @@
 // advances together (rows = proposals x beams), which computes the same numbers row by row.
 // Tie rule (torch.topk's order on equal values is unspecified): the LOWER index first, everywhere.  It matters only for
 // finished beams, whose next-word log-probabilities the reference zeroes (:243-247) -- all V+1 candidates tie.
+//
+// No word (docs/SEMANTICS.md, "Rows without a word"): a NaN is never a candidate, so a row or a merge whose values are all NaN
+// -- a non-finite code of the caller -- selects nothing.  Every selection is checked before it indexes anything: such a row
+// gets word 0 (no word, as the sampler's `none`), is marked finished, and feeds word 1 to the next step (its state is NaN
+// already, so which valid id it feeds does not matter).  No address is ever formed from a value that was not checked.
 #include "common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+// (v, i) replaces (bv, bi) when it is a candidate at all (an index, a value that is not NaN) and the better one
 __device__ __forceinline__ void arg_better(float& bv, int& bi, float v, int i) {
-  if (i >= 0 && (bi < 0 || v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+  if (i >= 0 && v == v && (bi < 0 || v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
 }
+constexpr int kFeedWord = 1;      // the valid id a row without a word feeds to the next step
 
 // block-wide arg-max with lowest-index ties over values supplied per thread; returns (value, index) to all threads
 __device__ void block_argmax(float& bv, int& bi, float* sv, int* si) {
@@ -34,7 +41,7 @@ __device__ void block_argmax(float& bv, int& bi, float* sv, int* si) {
 
 // One workgroup per row: nn.LogSoftMax (THNN, FloatTensor on the CPU: exp and the running sum in double,
 // logsum = max + log(sum), output = float(x - logsum)), the finished-beam mask (:243-247), torch.topk(k, sorted).
-// top_idx is 1-based (Lua word ids).
+// top_idx is 1-based (Lua word ids); a selection without a candidate (an all-NaN row) is (NaN, 0).
 __global__ __launch_bounds__(256) void beam_logsoftmax_topk_kernel(const float* __restrict__ logits, int V1, int ld,
                                                                    const uint8_t* __restrict__ finished, int k,
                                                                    float* __restrict__ top_lp,
@@ -72,33 +79,39 @@ __global__ __launch_bounds__(256) void beam_logsoftmax_topk_kernel(const float* 
     for (int j = tid; j < V1; j += 256) arg_better(bv, bi, row[j], j);
     block_argmax(bv, bi, sv, si);
     if (tid == 0) {
-      top_lp[(size_t)r * k + q] = bv;
-      top_idx[(size_t)r * k + q] = bi + 1;
-      row[bi] = -INFINITY;
+      const bool none = bi < 0 || bi >= V1;
+      top_lp[(size_t)r * k + q] = none ? NAN : bv;
+      top_idx[(size_t)r * k + q] = none ? 0 : bi + 1;
+      if (!none) row[bi] = -INFINITY;
     }
     __syncthreads();
   }
 }
 
 // First expansion (t = 1, :207-214): one state row per proposal; beams(beam,T) filled with 1, column 1 = the top-k words.
+// A top_idx outside [1, END] is no word: column 1 = 0, the beam is finished.
 __global__ void beam_init_kernel(const float* __restrict__ top_lp, const int32_t* __restrict__ top_idx, int nprop,
                                  int beam, int T, int END, float* __restrict__ beam_lp, int32_t* __restrict__ beams,
                                  int32_t* __restrict__ parent, int32_t* __restrict__ cur_tok,
                                  uint8_t* __restrict__ finished) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;        // (proposal, beam)
   if (i >= nprop * beam) return;
-  const int w = top_idx[i];
+  const int w0 = top_idx[i];
+  const bool none = w0 < 1 || w0 > END;
+  const int w = none ? 0 : w0;
   beam_lp[i] = top_lp[i];
   int32_t* row = beams + (size_t)i * T;
   row[0] = w;
   for (int t = 1; t < T; ++t) row[t] = 1;
   parent[i] = 0;
-  cur_tok[i] = w;
-  finished[i] = (w == END) ? 1 : 0;
+  cur_tok[i] = none ? kFeedWord : w;
+  finished[i] = (none || w == END) ? 1 : 0;
 }
 
 // One workgroup per proposal (:249-264): all_next = top_next_word_logprobs + beam_logprobs (beam x beam candidates),
 // torch.topk(beam, sorted) over them, beams re-indexed by parent with column t set to the chosen word.
+// A rank without a candidate (every remaining sum NaN) keeps its own beam as parent and gets no word: column t = 0, NaN
+// log-probability, finished.  A top_idx outside [1, END] is no word either.
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ top_lp,
                                                          const int32_t* __restrict__ top_idx,
                                                          const float* __restrict__ beam_lp_in,
@@ -120,25 +133,30 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
     for (int j = tid; j < nc; j += 256) arg_better(bv, bi, cand[j], j);
     block_argmax(bv, bi, sv, si);
     if (tid == 0) {
-      pick[q] = bi;
-      beam_lp_out[(size_t)p * beam + q] = bv;
-      cand[bi] = -INFINITY;
+      const bool none = bi < 0 || bi >= nc;
+      pick[q] = none ? -1 : bi;
+      beam_lp_out[(size_t)p * beam + q] = none ? NAN : bv;
+      if (!none) cand[bi] = -INFINITY;
     }
     __syncthreads();
   }
   for (int q = tid; q < beam; q += 256) {
-    const int b = pick[q] / beam;
-    const int w = top_idx[(size_t)p * nc + pick[q]];
+    const int pk = pick[q];
+    const bool picked = pk >= 0 && pk < nc;
+    const int b = picked ? pk / beam : q;
+    const int w0 = picked ? top_idx[(size_t)p * nc + pk] : 0;
+    const bool none = w0 < 1 || w0 > END;
+    const int w = none ? 0 : w0;
     const int32_t* src = beams_in + ((size_t)p * beam + b) * T;
     int32_t* dst = beams_out + ((size_t)p * beam + q) * T;
-    bool fin = false;
+    bool fin = none;
     for (int u = 0; u < T; ++u) {
       const int v = u == t ? w : src[u];
       dst[u] = v;
       fin |= v == END;
     }
     parent[(size_t)p * beam + q] = b;
-    cur_tok[(size_t)p * beam + q] = w;
+    cur_tok[(size_t)p * beam + q] = none ? kFeedWord : w;
     finished[(size_t)p * beam + q] = fin ? 1 : 0;   // torch.eq(beams, END):sum(2) ~= 0 (:243)
   }
 }
@@ -151,7 +169,8 @@ __global__ void beam_gather_state_kernel(const float* __restrict__ h_in, const f
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int r = (int)(i / (Hd / 4)), j4 = (int)(i % (Hd / 4));
     const int p = r / beam;
-    const size_t src = (size_t)p * src_per_prop + parent[r];
+    const int b = parent[r];
+    const size_t src = (size_t)p * src_per_prop + (b >= 0 && b < src_per_prop ? b : 0);
     reinterpret_cast<f32x4*>(h_out)[(size_t)r * (Hd / 4) + j4] = reinterpret_cast<const f32x4*>(h_in)[src * (Hd / 4) + j4];
     reinterpret_cast<f32x4*>(c_out)[(size_t)r * (Hd / 4) + j4] = reinterpret_cast<const f32x4*>(c_in)[src * (Hd / 4) + j4];
   }

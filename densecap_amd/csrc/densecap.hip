@@ -673,47 +673,66 @@ int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
   return DC_OK;
 }
 
+// One LSTM step of the beam search on the words in bm_tok, in place on (h, c)
+static int beam_lstm_step(dc_ctx* ctx, Lane& L, float* h, float* c, int rows, hipStream_t s) {
+  const int Hd = ctx->Hd;
+  GemmDesc d;
+  d.A = h; d.W = ctx->whT; d.C = L.bm_gates; d.M = rows; d.N = 4 * Hd; d.K = Hd; d.ldc = 4 * Hd;
+  d.rowterm = ctx->xg; d.rowidx = L.bm_tok; d.rowterm_ld = 4 * Hd;      // bm_tok: always a valid id (beam.hip, "No word")
+  DCCHK(run_gemm(ctx, d, s));
+  KCHK(launch_lstm_pointwise(L.bm_gates, c, h, rows, nullptr, Hd, 0, s));
+  return DC_OK;
+}
+
+// The beam search keeps its state in two ping-pong sets: iteration t (1 <= t < T) reads the LSTM state in bm_h / bm_c[t & 1] and
+// the beams in bm_lp / bm_beams[(t & 1) ^ 1], and writes the other set of each.  beam_start leaves what t = 1 reads.
+static int beam_state_set(int t) { return t & 1; }
+static int beam_beams_set(int t) { return (t & 1) ^ 1; }
+
+// Everything before the t loop for the c proposals of one chunk: image step (:198-201), START step (:203-206), one state row per
+// proposal, then the first expansion to c x beam rows (top-k lists of the first step in bm_top_lp / bm_top_idx, c x beam).
+int beam_start(dc_ctx* ctx, Lane& L, const float* codes, int c, hipStream_t s) {
+  const int beam = ctx->cfg.beam_size, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
+  DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, L.bm_enc, c, E, D, 1));
+  DCCHK(linear(ctx, s, L.bm_enc, ctx->wxT, ctx->lstm_b, L.bm_gates, c, 4 * Hd, E, 0));
+  KCHK(launch_lstm_pointwise(L.bm_gates, L.bm_c[0], L.bm_h[0], c, nullptr, Hd, 1, s));
+  KCHK(launch_fill_i32(L.bm_tok, V1, c, s));
+  DCCHK(beam_lstm_step(ctx, L, L.bm_h[0], L.bm_c[0], c, s));
+  DCCHK(linear(ctx, s, L.bm_h[0], ctx->out_w, ctx->out_b, L.bm_logits, c, V1, Hd, 0));
+  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, c, V1, V1, nullptr, beam, L.bm_top_lp, L.bm_top_idx, s));
+  KCHK(launch_beam_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bm_parent, L.bm_tok,
+                        L.bm_fin, s));
+  // LanguageModel.lua:221-226 duplicates the states for the beams with `layer.output = layer.cell:expand(...):clone()`:
+  // BOTH the cell and the hidden state of every beam start from the CELL state of the START step (torch-rnn's
+  // nn.LSTM with remember_states reads h0 from self.output).  Replicated as written: h rows := c rows.
+  KCHK(launch_beam_gather_state(L.bm_c[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1], L.bm_c[1], s));
+  return DC_OK;
+}
+
+// Iteration t of the loop (:228-278) on the c x beam rows of one chunk: LSTM step on bm_tok, vocabulary projection, LogSoftMax +
+// top-k per row with the finished mask (lists in bm_top_lp / bm_top_idx, rows x beam), beam x beam merge, states by parent.
+int beam_iter(dc_ctx* ctx, Lane& L, int c, int t, hipStream_t s) {
+  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, rows = c * beam;
+  const int cur = beam_state_set(t), bcur = beam_beams_set(t);
+  DCCHK(beam_lstm_step(ctx, L, L.bm_h[cur], L.bm_c[cur], rows, s));
+  DCCHK(linear(ctx, s, L.bm_h[cur], ctx->out_w, ctx->out_b, L.bm_logits, rows, V1, Hd, 0));
+  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, rows, V1, V1, L.bm_fin, beam, L.bm_top_lp, L.bm_top_idx, s));
+  KCHK(launch_beam_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], c, beam, T, t, V1,
+                         L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
+  KCHK(launch_beam_gather_state(L.bm_h[cur], L.bm_c[cur], L.bm_parent, rows, beam, beam, Hd, L.bm_h[cur ^ 1],
+                                L.bm_c[cur ^ 1], s));
+  return DC_OK;
+}
+
 int lm_beamsearch(dc_ctx* ctx, Lane& L, const float* codes, int n, int32_t* seq_out, hipStream_t s) {
   const int kBeamChunk = beam_chunk(ctx, n);
   DCCHK(beam_prepare(ctx, L, kBeamChunk));
-  const int beam = ctx->cfg.beam_size, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
-  auto step = [&](float* h, float* c, int rows) -> int {        // one LSTM step on the words in bm_tok, in place
-    GemmDesc d;
-    d.A = h; d.W = ctx->whT; d.C = L.bm_gates; d.M = rows; d.N = 4 * Hd; d.K = Hd; d.ldc = 4 * Hd;
-    d.rowterm = ctx->xg; d.rowidx = L.bm_tok; d.rowterm_ld = 4 * Hd;
-    DCCHK(run_gemm(ctx, d, s));
-    KCHK(launch_lstm_pointwise(L.bm_gates, c, h, rows, nullptr, Hd, 0, s));
-    return DC_OK;
-  };
+  const int beam = ctx->cfg.beam_size, T = ctx->T, D = ctx->D;
   for (int p0 = 0; p0 < n; p0 += kBeamChunk) {
     const int c = std::min(kBeamChunk, n - p0);
-    // image step (:198-201) and START step (:203-206), one state row per proposal
-    DCCHK(linear(ctx, s, codes + (size_t)p0 * D, ctx->enc_w, ctx->enc_b, L.bm_enc, c, E, D, 1));
-    DCCHK(linear(ctx, s, L.bm_enc, ctx->wxT, ctx->lstm_b, L.bm_gates, c, 4 * Hd, E, 0));
-    KCHK(launch_lstm_pointwise(L.bm_gates, L.bm_c[0], L.bm_h[0], c, nullptr, Hd, 1, s));
-    KCHK(launch_fill_i32(L.bm_tok, V1, c, s));
-    DCCHK(step(L.bm_h[0], L.bm_c[0], c));
-    DCCHK(linear(ctx, s, L.bm_h[0], ctx->out_w, ctx->out_b, L.bm_logits, c, V1, Hd, 0));
-    KCHK(launch_beam_logsoftmax_topk(L.bm_logits, c, V1, V1, nullptr, beam, L.bm_top_lp, L.bm_top_idx, s));
-    KCHK(launch_beam_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bm_parent, L.bm_tok,
-                          L.bm_fin, s));
-    // LanguageModel.lua:221-226 duplicates the states for the beams with `layer.output = layer.cell:expand(...):clone()`:
-    // BOTH the cell and the hidden state of every beam start from the CELL state of the START step (torch-rnn's
-    // nn.LSTM with remember_states reads h0 from self.output).  Replicated as written: h rows := c rows.
-    KCHK(launch_beam_gather_state(L.bm_c[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1], L.bm_c[1], s));
-    int cur = 1, bcur = 0;
-    const int rows = c * beam;
-    for (int t = 1; t < T; ++t) {
-      DCCHK(step(L.bm_h[cur], L.bm_c[cur], rows));
-      DCCHK(linear(ctx, s, L.bm_h[cur], ctx->out_w, ctx->out_b, L.bm_logits, rows, V1, Hd, 0));
-      KCHK(launch_beam_logsoftmax_topk(L.bm_logits, rows, V1, V1, L.bm_fin, beam, L.bm_top_lp, L.bm_top_idx, s));
-      KCHK(launch_beam_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], c, beam, T, t, V1,
-                             L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
-      KCHK(launch_beam_gather_state(L.bm_h[cur], L.bm_c[cur], L.bm_parent, rows, beam, beam, Hd, L.bm_h[cur ^ 1],
-                                    L.bm_c[cur ^ 1], s));
-      cur ^= 1; bcur ^= 1;
-    }
-    KCHK(launch_beam_best(L.bm_beams[bcur], c, beam, T, seq_out + (size_t)p0 * T, s));
+    DCCHK(beam_start(ctx, L, codes + (size_t)p0 * D, c, s));
+    for (int t = 1; t < T; ++t) DCCHK(beam_iter(ctx, L, c, t, s));
+    KCHK(launch_beam_best(L.bm_beams[beam_beams_set(T)], c, beam, T, seq_out + (size_t)p0 * T, s));
   }
   return DC_OK;
 }
@@ -2267,6 +2286,88 @@ int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_
   if (K == 0) return DC_OK;
   Lane& L = lane0(ctx);
   return lm_sample_n(ctx, L.stream, L.out_feats, K, nullptr, *opts, samples, logprob);      // r = output row
+}
+
+// ---- beam search test hooks (densecap_debug.h) ---------------------------------------------------------------------------------
+int dc_debug_beam_topk(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const uint8_t* finished_or_null, int k,
+                       float* top_lp, int32_t* top_idx) {
+  OP_PROLOGUE();
+  if (!logits || !top_lp || !top_idx || rows < 0 || V1 < 1 || ld < V1)
+    return ctx->fail(DC_E_INVALID, "dc_debug_beam_topk: bad argument");
+  KCHK(launch_beam_logsoftmax_topk(logits, rows, V1, ld, finished_or_null, k, top_lp, top_idx, s));
+  OP_EPILOGUE();
+}
+int dc_debug_beam_merge(dc_ctx* ctx, const float* top_lp, const int32_t* top_idx, const float* beam_lp_in, const int32_t* beams_in,
+                        int nprop, int beam, int T, int t, int END, float* beam_lp_out, int32_t* beams_out, int32_t* parent,
+                        int32_t* cur_tok, uint8_t* finished) {
+  OP_PROLOGUE();
+  if (!top_lp || !top_idx || !beam_lp_in || !beams_in || !beam_lp_out || !beams_out || !parent || !cur_tok || !finished ||
+      nprop < 1 || T < 1 || t < 0 || t >= T || END < 1)
+    return ctx->fail(DC_E_INVALID, "dc_debug_beam_merge: bad argument");
+  KCHK(launch_beam_merge(top_lp, top_idx, beam_lp_in, beams_in, nprop, beam, T, t, END, beam_lp_out, beams_out, parent, cur_tok,
+                         finished, s));
+  OP_EPILOGUE();
+}
+
+// what the two state hooks check first; on DC_OK the lane's beam scratch holds nprop proposals
+static int beam_hook_prepare(dc_ctx* ctx, int nprop, const dc_beam_state* st, const char* who) {
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (ctx->cfg.beam_size < 1) return ctx->fail(DC_E_STATE, "%s: dc_set_beam_size first", who);
+  if (!st || !st->h || !st->c || !st->beam_lp || !st->beams || !st->tok || !st->parent || !st->fin)
+    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (nprop < 1 || beam_chunk(ctx, nprop) < nprop)
+    return ctx->fail(DC_E_INVALID, "%s: %d proposals are not one chunk (the hook does not chunk)", who, nprop);
+  return beam_prepare(ctx, lane0(ctx), nprop);
+}
+// the lane's beam state, sets (hs, bs), to or from the caller's buffers (rows = nprop x beam), and the top-k lists out
+static int beam_hook_copy(dc_ctx* ctx, Lane& L, int rows, int hs, int bs, const dc_beam_state& st, bool out, hipStream_t s) {
+  const size_t Hd = ctx->Hd, T = ctx->T;
+  const struct { void* lane; void* user; size_t bytes; } parts[] = {
+      {L.bm_h[hs], st.h, rows * Hd * 4}, {L.bm_c[hs], st.c, rows * Hd * 4},   {L.bm_lp[bs], st.beam_lp, (size_t)rows * 4},
+      {L.bm_beams[bs], st.beams, rows * T * 4}, {L.bm_tok, st.tok, (size_t)rows * 4}, {L.bm_parent, st.parent, (size_t)rows * 4},
+      {L.bm_fin, st.fin, (size_t)rows}};
+  for (const auto& p : parts)
+    HIPCHK(hipMemcpyAsync(out ? p.user : p.lane, out ? p.lane : p.user, p.bytes, hipMemcpyDeviceToDevice, s));
+  return DC_OK;
+}
+static int beam_hook_lists(dc_ctx* ctx, Lane& L, size_t n, float* top_lp, int32_t* top_idx, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(top_lp, L.bm_top_lp, n * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(top_idx, L.bm_top_idx, n * 4, hipMemcpyDeviceToDevice, s));
+  return DC_OK;
+}
+
+int dc_debug_beam_start(dc_ctx* ctx, const float* codes, int nprop, const dc_beam_state* state_out, float* top_lp,
+                        int32_t* top_idx) {
+  OP_PROLOGUE();
+  if (!codes || !top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "dc_debug_beam_start: null pointer");
+  DCCHK(beam_hook_prepare(ctx, nprop, state_out, "dc_debug_beam_start"));
+  Lane& L = lane0(ctx);
+  const int beam = ctx->cfg.beam_size;
+  DCCHK(beam_start(ctx, L, codes, nprop, s));
+  DCCHK(beam_hook_copy(ctx, L, nprop * beam, beam_state_set(1), beam_beams_set(1), *state_out, true, s));
+  DCCHK(beam_hook_lists(ctx, L, (size_t)nprop * beam, top_lp, top_idx, s));
+  OP_EPILOGUE();
+}
+int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state_in, const dc_beam_state* state_out,
+                       float* top_lp, int32_t* top_idx) {
+  OP_PROLOGUE();
+  if (!top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: null pointer");
+  DCCHK(beam_hook_prepare(ctx, nprop, state_in, "dc_debug_beam_step"));
+  DCCHK(beam_hook_prepare(ctx, nprop, state_out, "dc_debug_beam_step"));
+  if (t < 1 || t >= ctx->T) return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: t = %d is not in [1, %d)", t, ctx->T);
+  Lane& L = lane0(ctx);
+  const int beam = ctx->cfg.beam_size, rows = nprop * beam;
+  // the word of a row selects an xg row by address in the step GEMM: the caller's are checked here, as the kernels check their own
+  std::vector<int32_t> tok(rows);
+  HIPCHK(hipMemcpy(tok.data(), state_in->tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < rows; ++i)
+    if (tok[i] < 1 || tok[i] > ctx->V + 1)
+      return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: tok[%d] = %d is not a word id in [1, %d]", i, (int)tok[i], ctx->V + 1);
+  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *state_in, false, s));
+  DCCHK(beam_iter(ctx, L, nprop, t, s));
+  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
+  DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
+  OP_EPILOGUE();
 }
 
 }  // extern "C"

@@ -326,7 +326,9 @@ __global__ __launch_bounds__(256) void lstm_step_tail_kernel(const float* __rest
     best = sv[0]; bi = si[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w) argbest_merge(best, bi, sv[w], si[w]);
-    tok = bi + 1;
+    // every partial at the sentinel: all scores of the row are NaN (a non-finite code of the caller).  The row has no word:
+    // it writes 0 and, as tok == 0 below, takes the LSTM step without an embedding row (docs/SEMANTICS.md)
+    tok = (bi < 0 || bi == kNoCol) ? 0 : bi + 1;
     if (tid == 0) seq[(size_t)m * T + t] = tok;
   }
   if (g == nullptr) return;

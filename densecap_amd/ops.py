@@ -332,3 +332,78 @@ def lm_sample_n(ctx, codes, num_samples, temperature=1.0, seed=0, row_ids=None, 
     check(ctx.h, ctx.lib.dc_op_lm_sample_n(ctx.h, xd.ptr, n, idd.ptr if idd is not None else None, C.byref(opts), tok.ptr,
                                            lp.ptr), "dc_op_lm_sample_n")
     return tok.numpy(), lp.numpy()
+
+
+# ---- beam search test hooks (include/densecap_debug.h) ----------------------------------------------------------------------
+BEAM_STATE_FIELDS = ("h", "c", "beam_lp", "beams", "tok", "parent", "fin")
+
+
+def beam_topk(ctx, logits, k, finished=None, ld=None):
+    """dc_debug_beam_topk: LogSoftMax + top-k of every row of logits (rows, V1) -> (top_lp (rows, k) float32, top_idx (rows, k)
+    int32, 1-based).  finished: (rows,) flags or None; ld: row stride in floats the logits are laid out with (>= V1)."""
+    x = _f32(logits)
+    rows, V1 = x.shape
+    ld = V1 if ld is None else int(ld)
+    if ld > V1:
+        x = np.concatenate([x, np.full((rows, ld - V1), np.float32(7e37))], 1)      # never read: a huge value would show
+    xd = ctx.to_device(x)
+    fd = ctx.to_device(np.ascontiguousarray(finished, dtype=np.uint8)) if finished is not None else None
+    lp = ctx.empty((rows, k), np.float32); idx = ctx.empty((rows, k), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_beam_topk(ctx.h, xd.ptr, rows, V1, ld, fd.ptr if fd is not None else None, int(k), lp.ptr,
+                                            idx.ptr), "dc_debug_beam_topk")
+    return lp.numpy(), idx.numpy()
+
+
+def beam_merge(ctx, top_lp, top_idx, beam_lp, beams, t, END):
+    """dc_debug_beam_merge: top_lp / top_idx (nprop, beam, beam), beam_lp (nprop, beam), beams (nprop, beam, T), 0-based column
+    t -> dict(beam_lp, beams, parent, tok, fin)."""
+    tl = _f32(top_lp); ti = np.ascontiguousarray(top_idx, dtype=np.int32)
+    bl = _f32(beam_lp); bm = np.ascontiguousarray(beams, dtype=np.int32)
+    nprop, beam, T = bm.shape
+    assert tl.shape == ti.shape == (nprop, beam, beam) and bl.shape == (nprop, beam)
+    d = [ctx.to_device(a) for a in (tl, ti, bl, bm)]
+    o = dict(beam_lp=ctx.empty((nprop, beam), np.float32), beams=ctx.empty((nprop, beam, T), np.int32),
+             parent=ctx.empty((nprop, beam), np.int32), tok=ctx.empty((nprop, beam), np.int32),
+             fin=ctx.empty((nprop, beam), np.uint8))
+    check(ctx.h, ctx.lib.dc_debug_beam_merge(ctx.h, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, nprop, beam, T, int(t), int(END),
+                                             o["beam_lp"].ptr, o["beams"].ptr, o["parent"].ptr, o["tok"].ptr, o["fin"].ptr),
+          "dc_debug_beam_merge")
+    return {k: v.numpy() for k, v in o.items()}
+
+
+def _beam_state_buffers(ctx, nprop, beam, Hd, T):
+    shapes = dict(h=((nprop, beam, Hd), np.float32), c=((nprop, beam, Hd), np.float32), beam_lp=((nprop, beam), np.float32),
+                  beams=((nprop, beam, T), np.int32), tok=((nprop, beam), np.int32), parent=((nprop, beam), np.int32),
+                  fin=((nprop, beam), np.uint8))
+    bufs = {k: ctx.empty(*v) for k, v in shapes.items()}
+    return bufs, _lib.DcBeamState(*[bufs[k].ptr for k in BEAM_STATE_FIELDS]), shapes
+
+
+def beam_start(ctx, codes, beam, rnn_size, seq_length):
+    """dc_debug_beam_start at the ctx's beam size `beam` (dc_set_beam_size): codes (nprop, fc_dim) -> (state dict of
+    BEAM_STATE_FIELDS, nprop x beam rows; top_lp, top_idx (nprop, beam) of the first step)."""
+    x = _f32(codes)
+    nprop = x.shape[0]
+    xd = ctx.to_device(x)
+    bufs, st, _ = _beam_state_buffers(ctx, nprop, beam, rnn_size, seq_length)
+    lp = ctx.empty((nprop, beam), np.float32); idx = ctx.empty((nprop, beam), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_beam_start(ctx.h, xd.ptr, nprop, C.byref(st), lp.ptr, idx.ptr), "dc_debug_beam_start")
+    return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()
+
+
+def beam_step(ctx, state, t):
+    """dc_debug_beam_step: iteration t (1 <= t < T) of the search from `state` (a dict as beam_start returns it; `parent` may
+    be missing) -> (new state, top_lp, top_idx (nprop, beam, beam): the lists the merge consumed)."""
+    nprop, beam, Hd = np.shape(state["h"])
+    T = np.shape(state["beams"])[2]
+    bufs_in, st_in, shapes = _beam_state_buffers(ctx, nprop, beam, Hd, T)
+    for k in BEAM_STATE_FIELDS:
+        if k in state:
+            a = np.ascontiguousarray(state[k], dtype=shapes[k][1])
+            assert a.shape == shapes[k][0], (k, a.shape)
+            check(ctx.h, ctx.lib.dc_memcpy_h2d(ctx.h, bufs_in[k].ptr, a.ctypes.data, a.nbytes), "dc_memcpy_h2d")
+    bufs, st, _ = _beam_state_buffers(ctx, nprop, beam, Hd, T)
+    lp = ctx.empty((nprop, beam, beam), np.float32); idx = ctx.empty((nprop, beam, beam), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_beam_step(ctx.h, nprop, int(t), C.byref(st_in), C.byref(st), lp.ptr, idx.ptr),
+          "dc_debug_beam_step")
+    return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()

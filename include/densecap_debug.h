@@ -82,6 +82,44 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value);
 int dc_debug_plan_gemm(int64_t M, int64_t N, int64_t K, int64_t plan_M, int conv_cin, int argmax, int serial_mode,
                        int32_t* out8);
 
+/* ---- beam search test hooks (tests/test_gpu_beam.py) ---------------------------------------------------------------------
+ * The row kernels of LM:beamsearch one at a time, and the production loop one step at a time.  All pointers are device
+ * pointers; every hook synchronises before it returns DC_OK or a negative code (dc_last_error has the text). */
+
+/* LogSoftMax + top-k of `rows` rows of V1 logits, `ld` floats apart (finished_or_null[r] != 0: k zeros, indices 1..k) ->
+ * top_lp, top_idx (rows x k; 1-based word ids, lower index first among equal values; a row of NaNs gives NaN / 0).
+ * V1 beyond the kernel's LDS row on this device or k outside [1, V1]: refused, nothing is launched. */
+int dc_debug_beam_topk(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const uint8_t* finished_or_null, int k,
+                       float* top_lp, int32_t* top_idx);
+/* The beam x beam merge of step t (0-based column t of the T-column beams): candidates top_lp (nprop x beam x beam) +
+ * beam_lp_in (nprop x beam), the best `beam` of them (lower flat index first among equal sums) -> beam_lp_out, beams_out (the
+ * parent's row with column t = the word), parent, cur_tok, finished (the row contains END).  beam in [1, 32]. */
+int dc_debug_beam_merge(dc_ctx* ctx, const float* top_lp, const int32_t* top_idx, const float* beam_lp_in, const int32_t* beams_in,
+                        int nprop, int beam, int T, int t, int END, float* beam_lp_out, int32_t* beams_out, int32_t* parent,
+                        int32_t* cur_tok, uint8_t* finished);
+/* The state of nprop proposals between two steps of the search, nprop x beam rows at the ctx's beam size (dc_set_beam_size):
+ * LSTM state h, c (rnn_size floats a row), beam_lp, beams (seq_length ids a row), tok (the word every row feeds to the next
+ * step), parent (the beam of the previous step a row continues) and fin (the row contains END or has no word). */
+typedef struct dc_beam_state {
+  float* h;
+  float* c;
+  float* beam_lp;
+  int32_t* beams;
+  int32_t* tok;
+  int32_t* parent;
+  uint8_t* fin;
+} dc_beam_state;
+/* The search up to its loop for nprop rows of codes: image step, START step, first expansion -> the state the iteration t = 1
+ * reads, and the top-k lists of the first step (top_lp, top_idx: nprop x beam).  Runs the code dc_op_lm_sample runs at that beam
+ * size, on lane 0's scratch.  nprop must fit one chunk (see "beam_chunk_floats"): the hook does not chunk. */
+int dc_debug_beam_start(dc_ctx* ctx, const float* codes, int nprop, const dc_beam_state* state_out, float* top_lp,
+                        int32_t* top_idx);
+/* Iteration t (1 <= t < seq_length) of the loop from the caller's state: LSTM step on tok, vocabulary projection, LogSoftMax +
+ * top-k under the finished mask, merge, states by parent -> the state the iteration t + 1 reads and the top-k lists the merge
+ * consumed (top_lp, top_idx: nprop x beam x beam).  state_in->parent is not read; state_in->tok must hold ids in [1, V+1]. */
+int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state_in, const dc_beam_state* state_out,
+                       float* top_lp, int32_t* top_idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ def _declared_symbols(header="densecap.h"):
     return sorted(set(re.findall(r"\b(dc_[a-z0-9_]+)\s*\(", src)))
 
 
-DEBUG_SYMBOLS = ["dc_debug_fetch", "dc_debug_plan_gemm", "dc_debug_set", "dc_mfma_profile"]
+DEBUG_SYMBOLS = ["dc_debug_beam_merge", "dc_debug_beam_start", "dc_debug_beam_step", "dc_debug_beam_topk", "dc_debug_fetch",
+                 "dc_debug_plan_gemm", "dc_debug_set", "dc_mfma_profile"]
 
 
 def _reference_facts():
