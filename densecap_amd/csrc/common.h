@@ -235,6 +235,33 @@ hipError_t launch_iota_count(int32_t* idx, int32_t* count_out, const int32_t* co
 hipError_t launch_lstm_step_tail(const float* pval, const int32_t* pidx, int ntiles, int ld, int fixed_tok,
                                  const float* xg, const float* gates_pre, float* c, float* h, int n,
                                  const int32_t* n_dev, int Hd, int zero_c, int32_t* seq, int T, int t, hipStream_t s);
+// ---- screened greedy decode (Settings::decode_screen) ----
+// Screen (decode_screen.hip): scores[m*V1pad + j] = fp16(bias[j] + sum_k hb[m][k] * wb[j][k]) in bf16 MFMA arithmetic, for rows
+// below the live count (m_dev as in GemmDesc) and columns j < V1.  hb: (M, Kp) bf16, wb: (V1pad, Kp) bf16, Kp % 64 == 0.
+hipError_t launch_decode_screen(const uint16_t* hb, const uint16_t* wb, const float* bias, void* scores, int M,
+                                const int32_t* m_dev, int V1, int V1pad, int Kp, hipStream_t s);
+// hb[m] = bf16(h[m]) (zero from Hd to Kp), hnorm[m] >= |h[m]|_2, for the rows below the live count
+hipError_t launch_screen_operands(const float* h, int n, const int32_t* n_dev, int Hd, int Kp, uint16_t* hb, float* hnorm,
+                                  hipStream_t s);
+// The step tail of the screened route, one workgroup per row: tok = 1 + the arg-max of the fp32 logits h.W^T + bias exactly as
+// the fused step forms them, found among the columns the scores cannot rule out (or among all: see the kernel);
+// seq[m*T + t] = tok; cand[m*T + t] = the row's candidate count (-1: a non-finite score or bound); bestv[m] = the winner's
+// logit.  Then, gates_pre != null, the LSTM update of launch_lstm_step_tail with tok fed, and hb / hnorm of the new h.
+struct RescoreTail {
+  const _Float16* scores; int ld;                 // (n, ld) fp16
+  const _Float16* wnorm;                          // |W_j|_2 rounded up to fp16 (ld of them, zero past V1)
+  const float *W, *bias; int V1;                  // W (V1, Hd) fp32; bias (V1)
+  float cbound;                                   // c of the bound b_j = c |h| |W_j| + ...
+  const float *xg, *gates_pre;
+  float *c, *h; int n; const int32_t* n_dev; int Hd;
+  int32_t* seq; int T, t;
+  uint16_t* hb; int Kp; float* hnorm;             // hnorm: read for this step, rewritten for the next
+  int32_t* cand; float* bestv;
+};
+hipError_t launch_lstm_rescore_tail(const RescoreTail& a, hipStream_t s);
+// dynamic LDS the tail needs for rows of Hd and ld scores; the route exists where it fits kScreenTailMaxLds
+size_t screen_tail_lds_bytes(int Hd, int ld);
+constexpr size_t kScreenTailMaxLds = 64 * 1024;
 // Teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup per row m < n: lse = log-sum-exp of the row's
 // `nslots` partials (part[m*ld + 2s], part[m*ld + 2s + 1]: max, sum), combined in double in a fixed order; the target logit
 // part[m*ld + ld - 1]; acc[m] += (double)tlogit - lse.  Then, if the row's target tgt[m] is not `end_tok` and gates_pre != null,

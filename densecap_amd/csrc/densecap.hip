@@ -62,10 +62,11 @@ struct Settings {
   int bf3_all = 0;                  // 1 = math mode 1 takes EVERY contraction, not only those mfma_gemm_bf3_pays names (test
                                     // hook: small and ragged problems then exercise the split-bf16 kernels)
   int nms_band = 1;                 // launch_nms `band`; dc_create reads the default from DC_NMS_BAND
+  int decode_screen = -1;           // greedy decode step: 0 = fused fp32 step, 1 = bf16 screen + exact re-score, -1 = by row count (screen_pays)
   // contractions planned for one image alone (stream-K / tail plans over partial last rounds): images then travel alone
   bool serial_planning() const { return plan_mode < 0 ? serial_mode != 0 : plan_mode == 1; }
 };
-static_assert(sizeof(Settings) == 18 * 4, "Settings has 4-byte fields only (GraphKey compares it bytewise); a new field updates this count");
+static_assert(sizeof(Settings) == 19 * 4, "Settings has 4-byte fields only (GraphKey compares it bytewise); a new field updates this count");
 
 // Everything a captured forward bakes in: workspace pointers (carve epoch, arena, staging), weights, shape and the settings.
 // Bytewise equality up to the end of `set`: 8-byte fields first, then 4-byte ones, so nothing in between is padding.
@@ -120,6 +121,9 @@ struct Lane {
   float *roi_boxes = nullptr, *roi_feats = nullptr, *fc6_out = nullptr, *codes = nullptr;
   float *obj = nullptr, *final_trans = nullptr, *final_boxes = nullptr, *final_xyxy = nullptr;
   float *enc = nullptr, *gates = nullptr, *hstate = nullptr, *cstate = nullptr, *logits = nullptr;
+  uint16_t* scr_hb = nullptr;         // screened decode: bf16 h rows, their norms, candidate counts (row x step), winners' logits
+  float *scr_hnorm = nullptr, *scr_best = nullptr;
+  int32_t* scr_cand = nullptr;
   int32_t *tok = nullptr, *seq = nullptr;
   int32_t* surv_total = nullptr;   // captions after the final NMS: rows the group's final NMS runs kept, all images together
   float* out_feats = nullptr;
@@ -188,6 +192,19 @@ struct dc_ctx {
   float *out_w = nullptr, *out_b = nullptr, *anchors = nullptr;
   float* dec_w = nullptr;   // (V1pad + 4Hd, Hd): rows [0,V+1) = lm_out_w, zero rows up to V1pad (multiple of 64), then Wh^T
   int V1pad = 0;
+  // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
+  // rounded up to fp16 (V1pad of them), the constant c of the bound.  Part of the weights, made with dec_w.
+  uint16_t* scr_w = nullptr;
+  uint16_t* scr_wnorm = nullptr;
+  float scr_c = 0.f;
+  int scr_Kp = 0;
+  // dc_debug_set "lm_op_keep": dc_op_lm_sample keeps its final state on the host for dc_debug_fetch "lm_op_*"
+  bool lm_op_keep = false;
+  std::vector<char> lm_op_h, lm_op_c, lm_op_scores, lm_op_cand, lm_op_best;
+  // the last lm_sample_parts enqueued: its parts and which of them (bit i = part i) took the screened step;
+  // dc_debug_fetch "decode_screen_routes".  A replayed graph keeps the routes of its capture.
+  int lm_parts = 0;
+  uint32_t lm_screened = 0;
   std::vector<std::unique_ptr<Lane>> lanes;
   // split-bf16 mode: weight matrices that can take it, and their bf16 planes (made when the mode is first switched on)
   struct PlaneEnt { const float* W; size_t rows; int K; uint16_t* planes; };
@@ -460,6 +477,9 @@ size_t carve(const std::vector<Carve>& cv, void* base) {
   return total;
 }
 
+// floats per row of the buffer that holds, by route, a row's full logits, its arg-max partials or its fp16 screen scores
+size_t lm_amax_floats(const dc_ctx* ctx) { return (size_t)std::max(std::max(ctx->V + 1, ctx->V1pad / 16), ctx->V1pad / 2); }
+
 // (Re)build a lane's workspace for G images of size (H,W) side by side and proposal capacity P each.
 int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
   DCCHK(lane_streams(ctx, L));
@@ -468,7 +488,7 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
   for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
     if (kVgg[i].pool_after) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
   const int A = ctx->k * fh * fw;
-  const int Tn = ctx->T, V1 = ctx->V + 1, Dm = ctx->D, E = ctx->E, Hd = ctx->Hd;
+  const int Tn = ctx->T, Dm = ctx->D, E = ctx->E, Hd = ctx->Hd;
   const int nms_n = std::max(A, P);
   const size_t act_bytes = (size_t)G * H * W * 64 * sizeof(float);
   const size_t GP = (size_t)G * P;          // rows of the per-RoI tensors: image i owns rows [i*P, (i+1)*P)
@@ -503,7 +523,11 @@ int lane_prepare(dc_ctx* ctx, Lane& L, int H, int W, int P, int G) {
       {(void**)&L.gates, GP * 4 * Hd * 4},
       {(void**)&L.hstate, GP * Hd * 4},
       {(void**)&L.cstate, GP * Hd * 4},
-      {(void**)&L.logits, GP * (size_t)std::max(V1, ctx->V1pad / 16) * 4},   // full logits (beam) or 2 x V1pad/32 arg-max partials per row
+      {(void**)&L.logits, GP * lm_amax_floats(ctx) * 4},   // full logits (beam), 2 x V1pad/32 arg-max partials or V1pad fp16 scores per row
+      {(void**)&L.scr_hb, GP * (size_t)ctx->scr_Kp * 2},
+      {(void**)&L.scr_hnorm, GP * 4},
+      {(void**)&L.scr_best, GP * 4},
+      {(void**)&L.scr_cand, GP * Tn * 4},
       {(void**)&L.tok, GP * 4},
       {(void**)&L.seq, GP * Tn * 4},
       {(void**)&L.out_pack, (size_t)G * host_stage_stride(ctx, P)},   // packed result records of the group (either kind)
@@ -545,8 +569,22 @@ struct LmPart { hipStream_t s; int r0, n; Ws ws; };
 
 // The buffers of one greedy decode, one row per code row: encoder output (E), gate pre-activations (4 Hd), LSTM state (Hd
 // each) and the step GEMM's arg-max partials (2 x V1pad/32).  The forward passes its lane's, dc_op_lm_sample a carve of its own.
-struct LmBufs { float *enc, *gates, *h, *c, *amax; };
-LmBufs lane_lm_bufs(const Lane& L) { return LmBufs{L.enc, L.gates, L.hstate, L.cstate, L.logits}; }
+// Screened route: amax holds the rows' fp16 scores instead (V1pad each); hb, hnorm, cand, best as in RescoreTail.
+// A part that starts at row r0 owns amax from r0 * lm_part_stride floats on BOTH routes: the route is chosen per part, and
+// parts on different streams run at the same time, so a screened and a fused part must not share a byte.
+struct LmBufs { float *enc, *gates, *h, *c, *amax; uint16_t* hb; float* hnorm; int32_t* cand; float* best; };
+LmBufs lane_lm_bufs(const Lane& L) { return LmBufs{L.enc, L.gates, L.hstate, L.cstate, L.logits, L.scr_hb, L.scr_hnorm, L.scr_cand, L.scr_best}; }
+
+// Whether `rows` decode rows of one launch take the screened step (Settings::decode_screen).  Greedy decode in fp32 mode only;
+// the row tail keeps a row of h in LDS.  The rule of -1 is measured: the screen wins from a few hundred rows.
+size_t lm_part_stride(const dc_ctx* ctx) { return (size_t)ctx->V1pad / 2; }   // floats per row: V1pad fp16 scores >= 2 x V1pad/32 partials
+static_assert(sizeof(_Float16) * 2 == sizeof(float), "lm_part_stride counts a row of fp16 scores in floats");
+constexpr int kScreenMinRows = 400;
+bool screen_pays(const dc_ctx* ctx, int rows) {
+  const Settings& c = ctx->cfg;
+  if (c.math_mode != 0 || c.decode_screen == 0 || screen_tail_lds_bytes(ctx->Hd, ctx->V1pad) > kScreenTailMaxLds) return false;
+  return c.decode_screen == 1 || rows >= kScreenMinRows;
+}
 
 // From fc7 codes to the state after the START token: the first five launches of the schedule in lm_sample_parts (there is the
 // description), for n rows.  Every schedule of the language model but the beam search starts here.  Only enqueues (capture-safe).
@@ -599,13 +637,21 @@ int lm_sample_parts(dc_ctx* ctx, const LmBufs& b, const float* codes, const LmPa
   //   for t = 1..T-1:  [arg-max partials of h_t.Wout^T + b | G = h_t.Wh]   ONE GEMM launch (W = [Wout; pad; Wh])
   //                    tail: tok_t = arg-max; h_{t+1} from xg[tok_t] + G   row kernel
   //   arg-max partials of h_T.Wout^T + b                GEMM;  tail: tok_T
-  // i.e. 2 launches per step.  The h.Wh product of the NEXT step rides in the vocabulary projection's launch (both
+  // Launches of screen_pays() rows run the screened step instead, 3 launches:
+  //                    s = fp16(bf16(h_t).bf16(Wout)^T + b)                  bf16 screen, every column
+  //                    G = h_t.Wh                                            GEMM (not after the last step)
+  //                    tail: tok_t = arg-max of the EXACT fp32 logits of the columns s cannot rule out; h_{t+1}; bf16(h_{t+1}), |h_{t+1}|
+  // Otherwise 2 launches per step.  The h.Wh product of the NEXT step rides in the vocabulary projection's launch (both
   // only need h_t) and fills its partial last round of tiles; the token-dependent half of the gates (a row of the
   // precomputed xg = b + Emb.Wx table) is added where the token is produced.  Per element the arithmetic and its order
   // are those of torch-rnn's nn.LSTM: (b + x.Wx) + h.Wh, sigmoid/tanh, c' = f*c + i*g, h' = o*tanh(c').
   // The first five lines are lm_start_state, the GEMM of a step is decode_step_desc: lm_score and lm_sample_n share both.
   const int E = ctx->E, Hd = ctx->Hd, T = ctx->T, D = ctx->D;
   const int ntn = ctx->V1pad / 32;       // arg-max partials per row: one (value, column) per 32-column half of a 64-column tile
+  if (nparts > 32) return ctx->fail(DC_E_INVALID, "lm_sample_parts: at most 32 parts");
+  ctx->lm_parts = nparts; ctx->lm_screened = 0;
+  for (int pi = 0; pi < nparts; ++pi)
+    if (screen_pays(ctx, parts[pi].n)) ctx->lm_screened |= 1u << pi;
   for (int pi = 0; pi < nparts; ++pi) {
     const LmPart& p = parts[pi];
     const size_t r0 = p.r0;
@@ -619,9 +665,31 @@ int lm_sample_parts(dc_ctx* ctx, const LmBufs& b, const float* codes, const LmPa
       const size_t r0 = p.r0;
       float* gates = b.gates + r0 * 4 * Hd;
       float* hstate = b.h + r0 * Hd;
+      float* amax = b.amax + r0 * lm_part_stride(ctx);      // the part's own region, whichever route it takes
+      if (ctx->lm_screened >> pi & 1) {
+        // screened step: bf16 scores of every column, h_t.Wh on the fp32 family (as lm_start_state forms h_0.Wh: the same bits
+        // as the fused launch's, the K order of an element does not depend on the launch), then the re-scoring tail
+        const int Kp = ctx->scr_Kp, V1pad = ctx->V1pad;
+        uint16_t* hb = b.hb + r0 * Kp;
+        _Float16* scores = reinterpret_cast<_Float16*>(amax);
+        if (t == 0) KCHK(launch_screen_operands(hstate, p.n, n_dev, Hd, Kp, hb, b.hnorm + r0, p.s));
+        KCHK(launch_decode_screen(hb, ctx->scr_w, ctx->out_b, scores, p.n, n_dev, ctx->V + 1, V1pad, Kp, p.s));
+        if (!last) {
+          GemmDesc g;
+          g.A = hstate; g.W = ctx->whT; g.C = gates; g.M = p.n; g.N = 4 * Hd; g.K = Hd; g.ldc = 4 * Hd; g.m_dev = n_dev; g.plan_M = plan;
+          DCCHK(run_gemm(ctx, g, p.s));
+        }
+        RescoreTail a{};
+        a.scores = scores; a.ld = V1pad; a.wnorm = reinterpret_cast<const _Float16*>(ctx->scr_wnorm); a.W = ctx->out_w; a.bias = ctx->out_b; a.V1 = ctx->V + 1;
+        a.cbound = ctx->scr_c; a.xg = ctx->xg; a.gates_pre = last ? nullptr : gates; a.c = b.c + r0 * Hd; a.h = hstate;
+        a.n = p.n; a.n_dev = n_dev; a.Hd = Hd; a.seq = seq_out + r0 * T; a.T = T; a.t = t;
+        a.hb = hb; a.Kp = Kp; a.hnorm = b.hnorm + r0; a.cand = b.cand + r0 * T; a.bestv = b.best + r0;
+        KCHK(launch_lstm_rescore_tail(a, p.s));
+        continue;
+      }
       GemmDesc v = decode_step_desc(ctx, hstate, p.n, plan, last, gates);     // epilogue: the row arg-max
       v.m_dev = n_dev;
-      v.amax_val = b.amax + r0 * 2 * ntn;
+      v.amax_val = amax;
       v.amax_idx = reinterpret_cast<int32_t*>(v.amax_val + (size_t)p.n * ntn);
       v.amax_ld = ntn;
       DCCHK(run_gemm(ctx, v, p.s));
@@ -1416,6 +1484,25 @@ int dc_set_caption_order(dc_ctx* ctx, int after_final_nms) {
   return DC_OK;
 }
 
+// the fp16 bit pattern of the smallest fp16 value not below x >= 0 (inf past 65504; NaN stays NaN)
+static uint16_t half_bits_up(double x) {
+  _Float16 h = (_Float16)x;
+  uint16_t u;
+  memcpy(&u, &h, 2);
+  if ((double)h < x) u += 1;                         // x >= 0: the next pattern up (0x7bff + 1 = inf)
+  return u;
+}
+// The constant c of the screen's bound |s_j - z_j| <= c |h|_2 |W_j|_2 + 2^-10 |s_j| + ... for K = Hd terms:
+//   2u + u^2, u = 2^-8        both factors of a product rounded to bf16
+//   (K/16) 2^-18 (1 + u)^2    the bf16 MFMA chain: K/16 instructions, each off by less than 2^-18 of the sum of magnitudes
+//   K 2^-24 / (1 - K 2^-24)   the fp32 fmaf chain the score is compared with
+// times 1 + 2^-8 for the fp32 evaluation of the bound itself; rounded up.
+static float screen_bound_c(int K) {
+  const double u = 0x1p-8, g = K * 0x1p-24;
+  const double c = ((2 * u + u * u) + (K / 16.0) * 0x1p-18 * (1 + u) * (1 + u) + g / (1 - g)) * (1 + 0x1p-8);
+  return nextafterf((float)c, INFINITY);
+}
+
 int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   if (!ctx || !w) return DC_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1526,6 +1613,28 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
     HIPCHK(hipMemcpy(ctx->dec_w, w->lm_out_w, (size_t)(V + 1) * Hd * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->dec_w + (size_t)ctx->V1pad * Hd, ctx->whT, (size_t)4 * Hd * Hd * 4, hipMemcpyDeviceToDevice));
     ctx->out_w = ctx->dec_w;
+    // the screen's operands (Settings::decode_screen): Wout in bf16 (round to nearest even), rows padded with zeros to a
+    // multiple of 64 columns and to V1pad rows; |Wout_j|_2 in double, rounded up to fp16; the bound's constant
+    const int Kp = (Hd + 63) / 64 * 64;
+    std::vector<uint16_t> wb((size_t)ctx->V1pad * Kp, 0);
+    std::vector<uint16_t> wn((size_t)ctx->V1pad, 0);
+    for (int j = 0; j <= V; ++j) {
+      double ss = 0.0;
+      for (int kk = 0; kk < Hd; ++kk) {
+        const float x = w->lm_out_w[(size_t)j * Hd + kk];
+        ss += (double)x * (double)x;
+        uint32_t u;
+        memcpy(&u, &x, 4);
+        wb[(size_t)j * Kp + kk] = (u & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((u >> 16) | 0x40) : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+      }
+      wn[j] = half_bits_up(sqrt(ss) * (1.0 + 1e-9));   // (NaN / inf stay what they are: the row tail then scans exactly)
+    }
+    DCCHK(dev_alloc(ctx, (void**)&ctx->scr_w, wb.size() * 2));
+    HIPCHK(hipMemcpy(ctx->scr_w, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
+    DCCHK(dev_alloc(ctx, (void**)&ctx->scr_wnorm, wn.size() * 2));
+    HIPCHK(hipMemcpy(ctx->scr_wnorm, wn.data(), wn.size() * 2, hipMemcpyHostToDevice));
+    ctx->scr_Kp = Kp;
+    ctx->scr_c = screen_bound_c(Hd);
   }
   DCCHK(upload(ctx, &ctx->out_b, w->lm_out_b, (size_t)V + 1));
   DCCHK(upload(ctx, &ctx->anchors, w->anchors, (size_t)2 * k));
@@ -1869,6 +1978,25 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     std::vector<int32_t> coords(static_cast<const int32_t*>(host_buf), static_cast<const int32_t*>(host_buf) + count * 4);
     return sample_noise_debug(ctx, 1, val, coords.data(), 0, count, host_buf);
   }
+  if (strcmp(name, "decode_screen_routes") == 0) {
+    if (capacity_bytes < 8) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    static_cast<int32_t*>(host_buf)[0] = ctx->lm_parts;
+    static_cast<int32_t*>(host_buf)[1] = (int32_t)ctx->lm_screened;
+    return 2;
+  }
+  if (strncmp(name, "lm_op_", 6) == 0) {            // what the last dc_op_lm_sample kept (dc_debug_set "lm_op_keep")
+    const struct { const char* n; const std::vector<char>* v; int esize; } kept[] = {
+        {"lm_op_h", &ctx->lm_op_h, 4}, {"lm_op_c", &ctx->lm_op_c, 4}, {"lm_op_scores", &ctx->lm_op_scores, 2},
+        {"lm_op_cand", &ctx->lm_op_cand, 4}, {"lm_op_best", &ctx->lm_op_best, 4}};
+    for (const auto& e : kept) {
+      if (strcmp(name, e.n) != 0) continue;
+      if (e.v->empty()) return ctx->fail(DC_E_STATE, "dc_debug_fetch: %s: nothing kept (lm_op_keep, then dc_op_lm_sample)", name);
+      if ((int64_t)e.v->size() > capacity_bytes) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small (%lld needed)", (long long)e.v->size());
+      memcpy(host_buf, e.v->data(), e.v->size());
+      return (int64_t)(e.v->size() / e.esize);
+    }
+    return ctx->fail(DC_E_INVALID, "dc_debug_fetch: unknown name '%s'", name);
+  }
   if (ctx->lanes.empty() || !ctx->lanes[0]->arena.p) return ctx->fail(DC_E_STATE, "no forward has run yet");
   Lane& L = *ctx->lanes[0];
   const int P = L.P;
@@ -1895,6 +2023,8 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
       {"lm_enc", L.enc, (int64_t)P * ctx->E, 4},
       {"lm_h", L.hstate, (int64_t)P * ctx->Hd, 4},
       {"lm_c", L.cstate, (int64_t)P * ctx->Hd, 4},
+      // screened decode: candidate count of every (row, step) of the lane's whole group (-1: non-finite; > 64: scanned exactly)
+      {"decode_screen_cand", L.scr_cand, (int64_t)L.G * P * ctx->T, 4},
       {"survivor_rows", L.surv_total, 1, 4},
       {"box_src", L.box_src, (int64_t)P, 4},
   };
@@ -1985,6 +2115,11 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value) {
     ctx->score_rows_cap = value;
     return DC_OK;
   }
+  if (strcmp(name, "lm_op_keep") == 0) {
+    if (value != 0 && value != 1) return ctx->fail(DC_E_INVALID, "dc_debug_set: lm_op_keep must be 0 or 1");
+    ctx->lm_op_keep = value != 0;
+    return DC_OK;
+  }
   // the knobs kept in Settings: accepted values lo..hi, except `hole`
   struct Knob { const char* name; int Settings::*field; int lo, hi; const char* accepted; int hole = INT_MIN; };
   static const Knob kKnobs[] = {
@@ -1998,6 +2133,7 @@ int dc_debug_set(dc_ctx* ctx, const char* name, int64_t value) {
       {"bf3_all", &Settings::bf3_all, 0, 1, "0 or 1"},
       {"bf3_presplit", &Settings::bf3_presplit, 0, 1, "0 or 1"},
       {"tail_mode", &Settings::tail_mode, 0, 2, "0, 1 or 2"},
+      {"decode_screen", &Settings::decode_screen, -1, 1, "-1, 0 or 1"},
   };
   for (const Knob& k : kKnobs) {
     if (strcmp(name, k.name) != 0) continue;
@@ -2193,7 +2329,8 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   LmBufs b{};               // sized as lane_prepare sizes the lane's
   const std::vector<Carve> cv = {
       {(void**)&b.enc, rows * E * 4},  {(void**)&b.gates, rows * 4 * Hd * 4},       {(void**)&b.h, rows * Hd * 4},
-      {(void**)&b.c, rows * Hd * 4},   {(void**)&b.amax, rows * std::max(ctx->V + 1, ctx->V1pad / 16) * 4},
+      {(void**)&b.c, rows * Hd * 4},   {(void**)&b.amax, rows * lm_amax_floats(ctx) * 4},
+      {(void**)&b.hb, rows * ctx->scr_Kp * 2}, {(void**)&b.hnorm, rows * 4}, {(void**)&b.cand, rows * ctx->T * 4}, {(void**)&b.best, rows * 4},
   };
   void* base = nullptr;
   HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
@@ -2201,6 +2338,17 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   int rc = ctx->cfg.beam_size > 0 ? lm_beamsearch(ctx, lane0(ctx), codes, n, tokens, s)
                                   : lm_sample(ctx, s, b, lane_ws(lane0(ctx)), codes, n, 0, nullptr, tokens);
   hipError_t e2 = hipStreamSynchronize(s);
+  if (ctx->lm_op_keep && rc == DC_OK && e2 == hipSuccess && ctx->cfg.beam_size == 0) {
+    const bool scr = ctx->lm_screened & 1;      // lm_sample: one part
+    const struct { std::vector<char>* v; const void* p; size_t bytes; } keep[] = {
+        {&ctx->lm_op_h, b.h, rows * Hd * 4}, {&ctx->lm_op_c, b.c, rows * Hd * 4},
+        {&ctx->lm_op_scores, b.amax, scr ? rows * ctx->V1pad * 2 : 0}, {&ctx->lm_op_cand, b.cand, scr ? rows * ctx->T * 4 : 0},
+        {&ctx->lm_op_best, b.best, scr ? rows * 4 : 0}};
+    for (const auto& k : keep) {
+      k.v->resize(k.bytes);
+      if (k.bytes && e2 == hipSuccess) e2 = hipMemcpy(k.v->data(), k.p, k.bytes, hipMemcpyDeviceToHost);
+    }
+  }
   hipFree(base);
   prof_collect(ctx);
   if (rc != DC_OK) return rc;

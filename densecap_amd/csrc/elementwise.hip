@@ -335,6 +335,193 @@ __global__ __launch_bounds__(256) void lstm_step_tail_kernel(const float* __rest
   tail_update(r, g, tok > 0 ? xg + (size_t)(tok - 1) * 4 * Hd : nullptr, c_row, h + (size_t)m * Hd, Hd, tid, zero_c);
 }
 
+// ---- decode step tail of the screened route (Settings::decode_screen), one workgroup per row -----------
+// The row's bf16 scores s_j (decode_screen.hip) carry a proven bound |s_j - z_j| <= b_j on the fp32 logit z_j the fused step
+// forms.  With L = max_j (s_j - b_j), only columns with s_j + b_j >= L can hold the fp32 arg-max (the winner and every column
+// tied with it are among them); their z_j are re-computed exactly and merged under argbest_merge.  A row with more than
+// kScreenMaxCand such columns, or with a non-finite score or bound, scans every real column exactly instead.
+//
+// The exact logit: the fp32 MFMA family's fmaf chain (mfma_gemm.hip header: k-pair (8g + j, 8g + 4 + j), groups and 32-tiles
+// ascending, i.e. k in the order 0 4 1 5 2 6 3 7 inside every block of eight) from a zero accumulator, then + bias.
+constexpr int kScreenMaxCand = 64;
+__device__ __forceinline__ float screen_exact_logit(const float* __restrict__ w, const float* hs, int K, float bias) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = 0; k < K; k += 8) {
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + k), w1 = *reinterpret_cast<const f32x4*>(w + k + 4);
+    const f32x4 h0 = *reinterpret_cast<const f32x4*>(hs + k), h1 = *reinterpret_cast<const f32x4*>(hs + k + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc = __builtin_fmaf(h0[j], w0[j], acc);
+      acc = __builtin_fmaf(h1[j], w1[j], acc);
+    }
+  }
+  return acc + bias;
+}
+// b_j for a score s of a column whose weight row has norm wn (rounded up); ch = c * |h| (rounded up)
+__device__ __forceinline__ float screen_bound(float ch, float wn, float s) {
+  return __builtin_fmaf(ch, wn, __builtin_fmaf(0x1p-10f, fabsf(s), __builtin_fmaf(0x1p-100f, wn, 0x1p-24f)));
+}
+// the screen's operands of a row of h (Hd floats): hb = bf16(h) (round to nearest even), zero up to Kp; *hnorm >= |h|_2
+// (a non-finite h gives a non-finite norm).  Every thread of the workgroup calls it; sred: four floats of LDS.
+__device__ __forceinline__ void screen_row_operands(const float* h_row, int Hd, int Kp, uint16_t* __restrict__ hb_row,
+                                                    float* __restrict__ hnorm, float* sred, int tid) {
+  float ss = 0.f;
+  for (int j = tid; j < Kp; j += 256) {
+    const float x = j < Hd ? h_row[j] : 0.f;
+    ss = __builtin_fmaf(x, x, ss);
+    hb_row[j] = __builtin_bit_cast(uint16_t, (__bf16)x);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  __syncthreads();                                   // sred may still be read from an earlier reduction
+  if ((tid & 63) == 0) sred[tid >> 6] = ss;
+  __syncthreads();
+  if (tid == 0) *hnorm = sqrtf((sred[0] + sred[1]) + (sred[2] + sred[3])) * 1.001f;     // rounding of the sum and the root: < 1e-4
+}
+__global__ __launch_bounds__(256) void screen_operands_kernel(const float* __restrict__ h, int n, const int32_t* __restrict__ n_dev,
+                                                              int Hd, int Kp, uint16_t* __restrict__ hb, float* __restrict__ hnorm) {
+  if (n_dev) n = min(n, *n_dev);
+  const int m = blockIdx.x;
+  if (m >= n) return;
+  __shared__ float sred[4];
+  screen_row_operands(h + (size_t)m * Hd, Hd, Kp, hb + (size_t)m * Kp, hnorm + m, sred, threadIdx.x);
+}
+
+// an fp16 not below x: x moved up by 2^-10 |x| + 2^-24 before the round to nearest (which moves it by at most 2^-11 of its
+// magnitude, 2^-25 among the subnormals); +inf past the fp16 range, a NaN stays a NaN
+__device__ __forceinline__ _Float16 half_up(float x) {
+  return (_Float16)(x + __builtin_fmaf(fabsf(x), 0x1p-10f, 0x1p-24f));
+}
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+constexpr int kScreenChunk = 8;                       // candidate rows of W staged in LDS at a time
+
+__global__ __launch_bounds__(256) void lstm_rescore_tail_kernel(RescoreTail a) {
+  int n = a.n;
+  if (a.n_dev) n = min(n, *a.n_dev);
+  const int m = blockIdx.x;
+  if (m >= n) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, Hd = a.Hd, V1 = a.V1;
+  extern __shared__ __attribute__((aligned(16))) float sh_h[];           // the row's h (Hd floats), then the shared region
+  _Float16* sh_hi = reinterpret_cast<_Float16*>(sh_h + Hd);
+  float* sh_w = sh_h + Hd;
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ int s_cnt;
+  __shared__ int s_col[kScreenMaxCand];
+  TailRegs r;
+  const float* g = a.gates_pre ? a.gates_pre + (size_t)m * 4 * Hd : nullptr;
+  float* c_row = a.c + (size_t)m * Hd;
+  float* h_row = a.h + (size_t)m * Hd;
+  if (g != nullptr) tail_load(r, g, c_row, Hd, 0, tid, 0);
+  for (int j = tid; j < Hd; j += 256) sh_h[j] = h_row[j];
+  if (tid == 0) s_cnt = 0;
+  const _Float16* sc = a.scores + (size_t)m * a.ld;
+  const float ch = a.cbound * a.hnorm[m];
+  // pass 1: L = max (s - b), the upper ends s + b (rounded up to fp16) to LDS, and whether every score and bound is finite
+  float L = -INFINITY;
+  int bad = !(ch < INFINITY);
+  for (int j0 = 4 * tid; j0 < a.ld; j0 += 4096) {      // ld % 64 == 0: four columns per 8-byte load, four loads in flight
+    f16x4 s4[4], w4[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = min(j0 + 1024 * u, a.ld - 4);      // (past the row: a load that is not used)
+      s4[u] = *reinterpret_cast<const f16x4*>(sc + j);
+      w4[u] = *reinterpret_cast<const f16x4*>(a.wnorm + j);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + 1024 * u;
+      if (j >= a.ld) break;
+      f16x4 hi4;
+      if (j + 4 <= V1) {                               // (b carries |s|: a non-finite score makes it non-finite)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float s = (float)s4[u][e], b = screen_bound(ch, (float)w4[u][e], s);
+          bad |= !(b < INFINITY);
+          L = fmaxf(L, s - b);
+          hi4[e] = half_up(s + b);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          hi4[e] = (_Float16)(-INFINITY);
+          if (j + e < V1) {
+            const float s = (float)s4[u][e], b = screen_bound(ch, (float)w4[u][e], s);
+            bad |= !(b < INFINITY);
+            L = fmaxf(L, s - b);
+            hi4[e] = half_up(s + b);
+          }
+        }
+      }
+      *reinterpret_cast<f16x4*>(sh_hi + j) = hi4;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) L = fmaxf(L, __shfl_xor(L, o, 64));
+  if (lane == 0) sv[wid] = L;
+  bad = __syncthreads_or(bad);                       // (also publishes sv, s_cnt, sh_h and sh_hi)
+  L = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+  // pass 2: the columns that can still win
+  if (!bad)
+    for (int j = 4 * tid; j < a.ld; j += 1024) {
+      const f16x4 hi4 = *reinterpret_cast<const f16x4*>(sh_hi + j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((float)hi4[e] >= L) {
+          const int k = atomicAdd(&s_cnt, 1);
+          if (k < kScreenMaxCand) s_col[k] = j + e;
+        }
+    }
+  __syncthreads();                                   // sh_hi is dead from here on: the region becomes sh_w
+  const int ncand = s_cnt;
+  const bool full = bad || ncand > kScreenMaxCand;
+  // exact logits: of the candidates -- their rows of W staged in LDS kScreenChunk at a time, one lane per row --, or of every
+  // real column; entries as in the fused step's epilogue (v > -inf: a NaN or -inf is never an entry), merged as there
+  float best = -INFINITY;
+  int bi = kNoCol;
+  if (!full) {
+    const int Hs = Hd + 4;
+    for (int c0 = 0; c0 < ncand; c0 += kScreenChunk) {
+      const int nc = min(kScreenChunk, ncand - c0);
+      for (int i = tid; i < nc * (Hd / 4); i += 256) {
+        const int q = i / (Hd / 4), k4 = i - q * (Hd / 4);
+        *reinterpret_cast<f32x4*>(sh_w + q * Hs + 4 * k4) = *reinterpret_cast<const f32x4*>(a.W + (size_t)s_col[c0 + q] * Hd + 4 * k4);
+      }
+      __syncthreads();
+      if (tid < nc) {
+        const int col = s_col[c0 + tid];
+        const float v = screen_exact_logit(sh_w + tid * Hs, sh_h, Hd, a.bias[col]);
+        if (v > -INFINITY) argbest_merge(best, bi, v, col);
+      }
+      __syncthreads();
+    }
+  } else {
+    for (int col = tid; col < V1; col += 256) {
+      const float v = screen_exact_logit(a.W + (size_t)col * Hd, sh_h, Hd, a.bias[col]);
+      if (v > -INFINITY) argbest_merge(best, bi, v, col);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) argbest_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+  __syncthreads();                                   // sv was read above
+  if (lane == 0) { sv[wid] = best; si[wid] = bi; }
+  __syncthreads();
+  best = sv[0]; bi = si[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) argbest_merge(best, bi, sv[w], si[w]);
+  const int tok = bi == kNoCol ? 0 : bi + 1;         // no entry: the row has no word (docs/SEMANTICS.md)
+  if (tid == 0) {
+    a.seq[(size_t)m * a.T + a.t] = tok;
+    a.cand[(size_t)m * a.T + a.t] = bad ? -1 : ncand;
+    a.bestv[m] = best;
+  }
+  if (g == nullptr) return;
+  tail_update(r, g, tok > 0 ? a.xg + (size_t)(tok - 1) * 4 * Hd : nullptr, c_row, h_row, Hd, tid, 0);
+  __syncthreads();                                   // every thread re-reads only what it wrote itself (j = tid mod 256)
+  screen_row_operands(h_row, Hd, a.Kp, a.hb + (size_t)m * a.Kp, a.hnorm + m, sv, tid);
+}
+
 // ---- teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup (256 threads) per row -------------------
 // The row's log-sum-exp from the GEMM's partials (max, sum exp(v - max)) per 32-column slot: the row max M over the slots,
 // then lse as lse_wave_sums / lse_finish form it.  log p(target) = tlogit - lse is added to the row's double sum (one term
@@ -626,6 +813,25 @@ hipError_t launch_lstm_step_tail(const float* pval, const int32_t* pidx, int nti
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(lstm_step_tail_kernel, dim3(n), dim3(256), 0, s, pval, pidx, ntiles, ld, fixed_tok, xg, gates_pre,
                      c, h, n, n_dev, Hd, zero_c, seq, T, t);
+  return hipGetLastError();
+}
+// dynamic LDS of the kernel: the row's h (Hd floats), then one region that first holds the row's upper ends s + b as fp16
+// (ld of them) and then the staged candidate rows of W (kScreenChunk rows of Hd + 4 floats: the pad spreads the rows' banks)
+size_t screen_tail_lds_bytes(int Hd, int ld) {
+  return (size_t)Hd * 4 + std::max((size_t)ld * 2, (size_t)kScreenChunk * (Hd + 4) * 4);
+}
+hipError_t launch_screen_operands(const float* h, int n, const int32_t* n_dev, int Hd, int Kp, uint16_t* hb, float* hnorm,
+                                  hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (Kp < Hd) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(screen_operands_kernel, dim3(n), dim3(256), 0, s, h, n, n_dev, Hd, Kp, hb, hnorm);
+  return hipGetLastError();
+}
+hipError_t launch_lstm_rescore_tail(const RescoreTail& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  const size_t lds = screen_tail_lds_bytes(a.Hd, a.ld);
+  if (a.Hd % 8 || a.Kp < a.Hd || a.V1 > a.ld || a.ld % 64 || a.t < 0 || a.t >= a.T || lds > kScreenTailMaxLds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lstm_rescore_tail_kernel, dim3(a.n), dim3(256), lds, s, a);
   return hipGetLastError();
 }
 hipError_t launch_repeat_rows2(const float* src_a, const float* src_b, size_t len, int copies, float* dst_a, float* dst_b,

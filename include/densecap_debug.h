@@ -31,6 +31,14 @@ int dc_mfma_profile(dc_ctx* ctx, int reset, int64_t* launches, double* total_ms,
  * packed result carries -- 0 after a clean forward, -1 if it does not exist), or
  * "arena_allocs" (int32: how many times a lane workspace has been (re)allocated -- it only grows), or
  * "host_enqueue_us" (int32: host microseconds per image spent enqueueing in the last dc_forward_batch).
+ * "decode_screen_cand" (int32, group x P x T: the screened greedy decode's candidate count of every (row, step) of lane 0's
+ * last group -- -1 = a non-finite score or bound, above 64 = the row scanned every column exactly; rows the route did not
+ * decode are undefined), "decode_screen_routes" (2 x int32: the parts of the last greedy decode that was enqueued -- 2 when
+ * a single-image forward cuts its rows over two streams, else 1 -- and a mask, bit i set if part i took the screened step;
+ * a replayed graph keeps the routes of its capture), or, after a dc_op_lm_sample under "lm_op_keep" (no forward needed), what that call left behind:
+ * "lm_op_h", "lm_op_c" (final LSTM state, n x rnn_size), and on the screened route "lm_op_scores" (fp16, n x V1pad: the last
+ * step's screen scores, V1pad = V + 1 rounded up to 64; columns past V are undefined), "lm_op_cand" (int32, n x T, as above),
+ * "lm_op_best" (n: the last step's winning fp32 logit).
  * The noise of caption sampling as the device computes it (docs/SEMANTICS.md, "Sampling captions"; no forward needed):
  * "sample_gumbel@<first>" fills host_buf with capacity_bytes / 4 floats, g = -log(-log(u)) of the 23-bit indices first, first + 1,
  * ... (u = (index + 0.5) * 2^-23; at most 2^23 values a call); "sample_bits@<seed>" reads capacity_bytes / 16 rows of int32
@@ -65,6 +73,13 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
  *   "v2_stages"          LDS ring depth of the 128x64-tile contraction kernel: 0 = by tile count (default: two stages, three
  *                        workgroups per CU, once a launch has >= 3 tiles per CU; three stages otherwise), 2 or 3 forced.
  *                        Same K order either way: bit-identical results.
+ *   "decode_screen"      greedy decode step (fp32 math mode): 0 = the fused fp32 step (vocabulary projection with its row
+ *                        arg-max in the epilogue), 1 = screen + re-score wherever the row tail's LDS fits: bf16 scores of every
+ *                        column, then the exact fp32 logits of the few columns a proven error bound cannot rule out
+ *                        (DESIGN.md 4.1c), -1 (default) = by the row count of the launch (measured crossover).  Tokens and
+ *                        LSTM state are bit-identical on both routes (tests/test_gpu_decode_screen.py).
+ *   "lm_op_keep"         1 / 0 (default): dc_op_lm_sample (greedy) copies its final state to the host before it frees its
+ *                        scratch, for dc_debug_fetch "lm_op_*".  Not a setting of the forward.
  *   "nms_band"           1 (default) / 0, per context: NMS windows of <= 4096 sorted rows are scanned by nms_scan_band_kernel (the
  *                        near-diagonal words of the suppression mask resident in LDS) / every window by nms_scan_kernel (one
  *                        memory round trip per 64-row chunk).  Identical picks (tests/test_gpu_ops.py); A/B measurement only.

@@ -1,5 +1,5 @@
 """Greedy decode alone (LanguageModel:sample through dc_op_lm_sample) at the path's row counts: wall time per call on one
-stream, and the MFMA family's share.   usage (GPU box): python tools/decode_bench.py [reps] [rows ...]"""
+stream, and the MFMA family's share.   usage (GPU box): python tools/decode_bench.py [reps] [rows ...] [--decode-screen=0|1|-1]"""
 import os
 import sys
 import time
@@ -22,6 +22,8 @@ for a in sys.argv:
         check(ctx.h, ctx.lib.dc_debug_set(ctx.h, b"v2_stages", int(a.split("=")[1])))
     if a.startswith("--force-cfg="):      # measurement hook: 2 = 128x64 tiles, 3 = 64x64 tiles for the step GEMM
         check(ctx.h, ctx.lib.dc_debug_set(ctx.h, b"force_cfg", int(a.split("=")[1])))
+    if a.startswith("--decode-screen="):  # greedy step: 0 = fused fp32 step, 1 = bf16 screen + exact re-score, -1 = by row count
+        check(ctx.h, ctx.lib.dc_debug_set(ctx.h, b"decode_screen", int(a.split("=")[1])))
     if a.startswith("--beam="):          # LM:beamsearch with that many beams instead of the greedy LM:sample
         beam = int(a.split("=")[1])
         m.setBeamSize(beam)
