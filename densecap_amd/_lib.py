@@ -99,6 +99,10 @@ _SIGS = {
     "dc_debug_beam_start": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(DcBeamState), C.c_void_p, C.c_void_p]),
     "dc_debug_beam_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(DcBeamState), C.POINTER(DcBeamState), C.c_void_p,
                                      C.c_void_p]),
+    "dc_debug_screen_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_debug_rescore_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "dc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "dc_comm_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),

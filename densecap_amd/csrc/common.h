@@ -259,7 +259,8 @@ struct RescoreTail {
   int32_t* cand; float* bestv;
 };
 hipError_t launch_lstm_rescore_tail(const RescoreTail& a, hipStream_t s);
-// dynamic LDS the tail needs for rows of Hd and ld scores; the route exists where it fits kScreenTailMaxLds
+// dynamic LDS the tail needs for rows of Hd and ld scores; the route exists where it fits kScreenTailMaxLds (the kernel's 560
+// bytes of static LDS come on top: 66,096 bytes at the edge launch on gfx950 as they are -- DESIGN.md §4.1c, test set lds_last)
 size_t screen_tail_lds_bytes(int Hd, int ld);
 constexpr size_t kScreenTailMaxLds = 64 * 1024;
 // Teacher-forced scoring step tail (densecap.hip::lm_score), one workgroup per row m < n: lse = log-sum-exp of the row's

@@ -580,9 +580,11 @@ LmBufs lane_lm_bufs(const Lane& L) { return LmBufs{L.enc, L.gates, L.hstate, L.c
 size_t lm_part_stride(const dc_ctx* ctx) { return (size_t)ctx->V1pad / 2; }   // floats per row: V1pad fp16 scores >= 2 x V1pad/32 partials
 static_assert(sizeof(_Float16) * 2 == sizeof(float), "lm_part_stride counts a row of fp16 scores in floats");
 constexpr int kScreenMinRows = 400;
+// (the part of the rule that depends on the loaded dimensions alone: the test hooks of the route's kernels ask for it)
+bool screen_fits(const dc_ctx* ctx) { return screen_tail_lds_bytes(ctx->Hd, ctx->V1pad) <= kScreenTailMaxLds; }
 bool screen_pays(const dc_ctx* ctx, int rows) {
   const Settings& c = ctx->cfg;
-  if (c.math_mode != 0 || c.decode_screen == 0 || screen_tail_lds_bytes(ctx->Hd, ctx->V1pad) > kScreenTailMaxLds) return false;
+  if (c.math_mode != 0 || c.decode_screen == 0 || !screen_fits(ctx)) return false;
   return c.decode_screen == 1 || rows >= kScreenMinRows;
 }
 
@@ -2516,6 +2518,71 @@ int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state
   DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
   DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
   OP_EPILOGUE();
+}
+
+// ---- screened greedy decode test hooks (densecap_debug.h) ------------------------------------------------------------------------
+static int screen_hook_check(dc_ctx* ctx, int n, const char* who) {
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!screen_fits(ctx))
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: no screened route at rnn_size %d, V + 1 = %d (the row tail's LDS does not fit)", who,
+                     ctx->Hd, ctx->V + 1);
+  if (n < 1) return ctx->fail(DC_E_INVALID, "%s: n must be > 0", who);
+  return DC_OK;
+}
+int dc_debug_screen_scores(dc_ctx* ctx, const float* h, int n, const int32_t* n_dev_or_null, uint16_t* hb_out, float* hnorm_out,
+                           void* scores_out) {
+  OP_PROLOGUE();
+  DCCHK(screen_hook_check(ctx, n, "dc_debug_screen_scores"));
+  if (!h || !hb_out || !hnorm_out || !scores_out) return ctx->fail(DC_E_INVALID, "dc_debug_screen_scores: null pointer");
+  KCHK(launch_screen_operands(h, n, n_dev_or_null, ctx->Hd, ctx->scr_Kp, hb_out, hnorm_out, s));
+  KCHK(launch_decode_screen(hb_out, ctx->scr_w, ctx->out_b, scores_out, n, n_dev_or_null, ctx->V + 1, ctx->V1pad, ctx->scr_Kp, s));
+  OP_EPILOGUE();
+}
+int dc_debug_rescore_tail(dc_ctx* ctx, const void* scores, const float* h, const float* c, const float* hnorm,
+                          const float* gates_pre_or_null, int n, const int32_t* n_dev_or_null, int32_t* tok_out,
+                          int32_t* cand_out, float* best_out, float* h_out, float* c_out, uint16_t* hb_out, float* hnorm_out) {
+  OP_PROLOGUE();
+  DCCHK(screen_hook_check(ctx, n, "dc_debug_rescore_tail"));
+  const bool step = gates_pre_or_null != nullptr;
+  if (!scores || !h || !hnorm || !tok_out || !cand_out || !best_out || (step && (!c || !h_out || !c_out || !hb_out || !hnorm_out)))
+    return ctx->fail(DC_E_INVALID, "dc_debug_rescore_tail: null pointer");
+  // the tail updates h, c and hnorm in place: with gates it runs on copies, and the live rows of the copies go to the caller
+  const size_t Hd = ctx->Hd, rows = n;
+  float *hs = nullptr, *cs = nullptr, *ns = nullptr;
+  const std::vector<Carve> cv = {{(void**)&hs, rows * Hd * 4}, {(void**)&cs, rows * Hd * 4}, {(void**)&ns, rows * 4}};
+  void* base = nullptr;
+  int live = n;
+  if (step) {
+    if (n_dev_or_null) {
+      HIPCHK(hipMemcpy(&live, n_dev_or_null, 4, hipMemcpyDeviceToHost));
+      live = std::max(0, std::min(n, live));
+    }
+    HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+    carve(cv, base);
+  }
+  RescoreTail a{};
+  a.scores = static_cast<const _Float16*>(scores); a.ld = ctx->V1pad; a.wnorm = reinterpret_cast<const _Float16*>(ctx->scr_wnorm);
+  a.W = ctx->out_w; a.bias = ctx->out_b; a.V1 = ctx->V + 1; a.cbound = ctx->scr_c; a.xg = ctx->xg; a.gates_pre = gates_pre_or_null;
+  a.h = step ? hs : const_cast<float*>(h); a.c = step ? cs : const_cast<float*>(h);       // (selection only: c is not touched)
+  a.hnorm = step ? ns : const_cast<float*>(hnorm);
+  a.n = n; a.n_dev = n_dev_or_null; a.Hd = ctx->Hd; a.seq = tok_out; a.T = 1; a.t = 0; a.hb = hb_out; a.Kp = ctx->scr_Kp;
+  a.cand = cand_out; a.bestv = best_out;
+  hipError_t e = hipSuccess;
+  const struct { void* scratch; const void* in; void* out; size_t row; } st[] = {
+      {hs, h, h_out, Hd * 4}, {cs, c, c_out, Hd * 4}, {ns, hnorm, hnorm_out, 4}};
+  if (step)
+    for (const auto& p : st)
+      if (e == hipSuccess) e = hipMemcpyAsync(p.scratch, p.in, rows * p.row, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = launch_lstm_rescore_tail(a, s);
+  if (step && live > 0)
+    for (const auto& p : st)
+      if (e == hipSuccess) e = hipMemcpyAsync(p.out, p.scratch, (size_t)live * p.row, hipMemcpyDeviceToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (base) hipFree(base);
+  prof_collect(ctx);
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_rescore_tail: %s", hipGetErrorString(e));
+  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_rescore_tail sync: %s", hipGetErrorString(e2));
+  return DC_OK;
 }
 
 }  // extern "C"

@@ -407,3 +407,64 @@ def beam_step(ctx, state, t):
     check(ctx.h, ctx.lib.dc_debug_beam_step(ctx.h, nprop, int(t), C.byref(st_in), C.byref(st), lp.ptr, idx.ptr),
           "dc_debug_beam_step")
     return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()
+
+
+# ---- screened greedy decode test hooks (include/densecap_debug.h) ------------------------------------------------------------
+DEBUG_FILL = 0xA5            # the byte every output buffer of the two hooks below holds before the call
+
+
+def screen_pads(rnn_size, vocab_size):
+    """(Kp, V1pad) of a loaded model: the bf16 row length and the score row length of the screened route."""
+    return (int(rnn_size) + 63) // 64 * 64, (int(vocab_size) + 1 + 63) // 64 * 64
+
+
+def _filled(ctx, shape, dtype):
+    return ctx.to_device(np.full(shape, DEBUG_FILL, np.uint8).view(dtype))
+
+
+def _count(ctx, n_dev):
+    return ctx.to_device(np.array([n_dev], np.int32)) if n_dev is not None else None
+
+
+def screen_scores(ctx, h, vocab_size, n_dev=None, guard_rows=2):
+    """dc_debug_screen_scores on the ctx's loaded model: h (n, rnn_size) -> (hb (n + g, Kp) uint16 bf16 patterns, hnorm (n + g,)
+    float32, scores (n + g, V1pad) float16) with g = guard_rows rows the call must not touch after the n it may.  Every byte of
+    the outputs is DEBUG_FILL before the call; n_dev: a device-side row count."""
+    x = _f32(h)
+    n, Hd = x.shape
+    Kp, V1pad = screen_pads(Hd, vocab_size)
+    g = int(guard_rows)
+    xd = ctx.to_device(x); nd = _count(ctx, n_dev)
+    hb = _filled(ctx, (n + g, 2 * Kp), np.uint16); hn = _filled(ctx, ((n + g) * 4,), np.float32)
+    sc = _filled(ctx, (n + g, 2 * V1pad), np.float16)
+    check(ctx.h, ctx.lib.dc_debug_screen_scores(ctx.h, xd.ptr, n, nd.ptr if nd is not None else None, hb.ptr, hn.ptr, sc.ptr),
+          "dc_debug_screen_scores")
+    return hb.numpy(), hn.numpy(), sc.numpy()
+
+
+def rescore_tail(ctx, scores, h, hnorm, c=None, gates_pre=None, n_dev=None, guard_rows=2):
+    """dc_debug_rescore_tail: scores (n, V1pad) float16, h (n, rnn_size), hnorm (n,) -> dict(tok, cand (int32), best (float32)),
+    n + guard_rows rows each; with gates_pre (n, 4 rnn_size) and c (n, rnn_size) also h, c, hb (uint16 bf16 patterns), hnorm of
+    the LSTM update.  Every byte of the outputs is DEBUG_FILL before the call; n_dev: a device-side row count."""
+    s = np.ascontiguousarray(scores, dtype=np.float16)
+    x = _f32(h); hn = _f32(hnorm)
+    n, Hd = x.shape
+    Kp = screen_pads(Hd, 0)[0]
+    assert s.shape[0] == n and s.shape[1] % 64 == 0 and hn.shape == (n,)
+    g = int(guard_rows)
+    sd = ctx.to_device(s); xd = ctx.to_device(x); hd = ctx.to_device(hn); nd = _count(ctx, n_dev)
+    o = dict(tok=_filled(ctx, ((n + g) * 4,), np.int32), cand=_filled(ctx, ((n + g) * 4,), np.int32),
+             best=_filled(ctx, ((n + g) * 4,), np.float32))
+    cd = gd = None
+    if gates_pre is not None:
+        cc = _f32(c); gp = _f32(gates_pre)
+        assert cc.shape == (n, Hd) and gp.shape == (n, 4 * Hd)
+        cd = ctx.to_device(cc); gd = ctx.to_device(gp)
+        o.update(h=_filled(ctx, (n + g, 4 * Hd), np.float32), c=_filled(ctx, (n + g, 4 * Hd), np.float32),
+                 hb=_filled(ctx, (n + g, 2 * Kp), np.uint16), hnorm=_filled(ctx, ((n + g) * 4,), np.float32))
+    ptr = lambda k: o[k].ptr if k in o else None
+    check(ctx.h, ctx.lib.dc_debug_rescore_tail(ctx.h, sd.ptr, xd.ptr, cd.ptr if cd is not None else None, hd.ptr,
+                                               gd.ptr if gd is not None else None, n, nd.ptr if nd is not None else None,
+                                               o["tok"].ptr, o["cand"].ptr, o["best"].ptr, ptr("h"), ptr("c"), ptr("hb"),
+                                               ptr("hnorm")), "dc_debug_rescore_tail")
+    return {k: v.numpy() for k, v in o.items()}

@@ -135,6 +135,30 @@ int dc_debug_beam_start(dc_ctx* ctx, const float* codes, int nprop, const dc_bea
 int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state_in, const dc_beam_state* state_out,
                        float* top_lp, int32_t* top_idx);
 
+/* ---- screened greedy decode test hooks (tests/test_gpu_decode_screen_kernels.py) -----------------------------
+ * The three kernels of the screened step one at a time, through the launchers the decode itself calls, on the loaded weights
+ * (Wout in bf16, its row norms, bias, the bound's constant, the xg table).  All pointers are device pointers; both hooks
+ * synchronise before they return.  DC_E_STATE without weights, DC_E_UNSUPPORTED where the route does not exist for the loaded
+ * dimensions (the row tail's LDS does not fit: the decode then never takes it); nothing is launched in either case.
+ * n_dev_or_null: a device-side row count, as the packed survivor decode passes one; rows from min(n, *n_dev) on are not
+ * computed and every output row of theirs keeps what the caller put there.  Kp = rnn_size rounded up to 64, V1pad = V + 1
+ * rounded up to 64. */
+
+/* h (n x rnn_size fp32) -> what the operand kernel writes: hb_out (n x Kp bf16 bit patterns, zero from rnn_size on), hnorm_out
+ * (n floats, >= |h|_2) -- and what the screen kernel then writes from them: scores_out (n x V1pad fp16; columns past V are
+ * not written). */
+int dc_debug_screen_scores(dc_ctx* ctx, const float* h, int n, const int32_t* n_dev_or_null, uint16_t* hb_out, float* hnorm_out,
+                           void* scores_out);
+/* One launch of the row tail on the caller's scores (n x V1pad fp16), state h (n x rnn_size) and norms hnorm (n) ->
+ * tok_out (n: 1-based word, 0 = no word), cand_out (n: the candidate count, -1 = a non-finite score or bound), best_out (n:
+ * the winner's fp32 logit).  gates_pre_or_null == null is the last step: selection only, c and the four outputs below are
+ * not used and may be null.  Otherwise gates_pre (n x 4 rnn_size: h.Wh, to which the tail adds the word's xg row) and c
+ * (n x rnn_size) give the LSTM update: h_out, c_out (n x rnn_size) and the operands of the next step hb_out (n x Kp),
+ * hnorm_out (n).  The caller's h, c and hnorm are not modified (the tail updates copies in scratch of the hook's own). */
+int dc_debug_rescore_tail(dc_ctx* ctx, const void* scores, const float* h, const float* c, const float* hnorm,
+                          const float* gates_pre_or_null, int n, const int32_t* n_dev_or_null, int32_t* tok_out,
+                          int32_t* cand_out, float* best_out, float* h_out, float* c_out, uint16_t* hb_out, float* hnorm_out);
+
 #ifdef __cplusplus
 }
 #endif

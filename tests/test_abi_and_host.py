@@ -16,7 +16,7 @@ def _declared_symbols(header="densecap.h"):
 
 
 DEBUG_SYMBOLS = ["dc_debug_beam_merge", "dc_debug_beam_start", "dc_debug_beam_step", "dc_debug_beam_topk", "dc_debug_fetch",
-                 "dc_debug_plan_gemm", "dc_debug_set", "dc_mfma_profile"]
+                 "dc_debug_plan_gemm", "dc_debug_rescore_tail", "dc_debug_screen_scores", "dc_debug_set", "dc_mfma_profile"]
 
 
 def _reference_facts():

@@ -9,7 +9,10 @@ and the live rows' LSTM state is compared as well as the outputs.
 
 The shipped default (-1) chooses the route per launch from its row count, from SCREEN_MIN_ROWS rows on; which route ran is read
 back through dc_debug_fetch "decode_screen_routes".  A single-image forward at one lane cuts its rows into two parts on two
-streams, and between 769 and 911 rows the first part is screened and the second is not: both run at once on one buffer."""
+streams, and between 769 and 911 rows the first part is screened and the second is not: both run at once on one buffer.
+
+The dimension sets come from tests/test_gpu_dims.py and tests/test_gpu_decode_screen_kernels.py (lds_last / lds_out: the last
+vocabulary the row tail's LDS rule admits and the first it declines); that module tests the kernels underneath one at a time."""
 import math
 
 import numpy as np
@@ -116,6 +119,50 @@ def test_tokens_and_state_identical_at_other_dimensions(name):
         codes = _codes(129, SETS[name]["D"], 4)
         for n in (1, 65, 129):
             _same(m, codes[:n], "%s rows=%d" % (name, n))
+    finally:
+        m.ctx.close()
+
+
+def _set_model(name):
+    """(model, fc_dim) of a set of tests/test_gpu_decode_screen_kernels.py: the five of test_gpu_dims.py, lds_last, lds_out."""
+    from tests.test_gpu_decode_screen_kernels import screen_set_weights
+    W = screen_set_weights(name)
+    return _model(W), W["lm_enc_w"].shape[1]
+
+
+@pytest.mark.parametrize("name,rows", [("minimal", (1, 129)), ("e_lt_h", (1, 129)), ("big_vocab", (1, 129)), ("lds_last", (1, 129)),
+                                       ("e_gt_h", (1025,))])
+def test_tokens_and_state_identical_on_every_dimension_set(name, rows):
+    """The sets the route had never run at: minimal (Kp = 64: one K step of the screen, V + 1 = 6), e_lt_h (Hd = 768: twelve
+    K steps, two tail passes), big_vocab (five outer rounds of the tail's first pass, 40 KB of upper ends in LDS), lds_last (the
+    largest vocabulary the row tail's LDS rule admits at Hd = 512: 64 KiB of dynamic LDS beside the kernel's static LDS) -- and
+    e_gt_h at 1025 rows: nine row tiles, two per XCD with seven slots empty."""
+    m, D = _set_model(name)
+    try:
+        codes = _codes(max(rows), D, 4)
+        for n in rows:
+            _same(m, codes[:n], "%s rows=%d" % (name, n))
+            assert _routes(m) == (1, 1), (name, n, _routes(m))
+            cand = _kept(m, n)[0]
+            assert cand.min() >= 1, (name, n, cand.min())
+    finally:
+        m.ctx.close()
+
+
+def test_route_declined_past_the_lds_rule():
+    """lds_out: one more 64-column group of vocabulary than lds_last and the row tail's LDS no longer fits.  The loader admits
+    the model, so nothing may fail later: decode_screen = 1 and the default rule at 400 rows both decode on the fused step."""
+    m, D = _set_model("lds_out")
+    try:
+        codes = _codes(SCREEN_MIN_ROWS, D, 4)
+        t0 = _decode(m, codes[:65], 0)
+        t1 = _decode(m, codes[:65], 1)
+        assert _routes(m) == (1, 0)
+        for x, y in zip(t1, t0):
+            np.testing.assert_array_equal(x, y)
+        tok = _decode(m, codes, -1)[0]
+        assert _routes(m) == (1, 0)
+        assert tok.shape == (SCREEN_MIN_ROWS, m.seq_length) and tok.min() >= 1
     finally:
         m.ctx.close()
 
@@ -301,4 +348,37 @@ def test_forward_identical(model, order, lanes):
             assert model.debug_fetch("graph_launches", (1,), np.int32)[0][0] >= 1
     finally:
         model.setGraphReplay(False); model.setLanes(3); model.setCaptionOrder(False); model.setTestArgs()
+        _set(model, "decode_screen", -1)
+
+
+def test_packed_survivor_decode_on_the_xcd_map(model):
+    """A group of four images at 300 proposals, captions after the final NMS: ONE decode launch of 1200 rows (ten row tiles, two
+    per XCD, six slots empty) with a device-side row count below that.  The default rule screens it; outputs of every image and
+    the LSTM state of the live rows of the first 300 against route 0, bit for bit.
+    (Last in the module: a lane keeps its group capacity for an image size, and "decode_screen_cand" is sized by it.)"""
+    from densecap_amd.weights import make_synthetic_image
+    P, G = 300, 4
+    imgs = np.stack([np.ascontiguousarray(make_synthetic_image(240, 320, 30 + i), np.float32) for i in range(G)])
+    model.setTestArgs(rpn_nms_thresh=0.7, final_nms_thresh=0.5, num_proposals=P)
+    model.setLanes(2); model.setGroup(G); model.setCaptionOrder(True)
+    try:
+        got = {}
+        for route in (0, -1):
+            _set(model, "decode_screen", route)
+            outs = model.forward_batch(imgs)
+            surv = int(model.debug_fetch("survivor_rows", (1,), np.int32)[0][0])
+            got[route] = (outs, _lm_state(model, P), _routes(model), surv)
+        surv = got[0][3]
+        print("survivor rows %d of %d launched, routes %s" % (surv, G * P, got[-1][2]))
+        assert got[-1][3] == surv and 128 < surv < G * P, surv
+        assert got[0][2] == (1, 0) and got[-1][2] == (1, 1), (got[0][2], got[-1][2])
+        assert len(got[0][0]) == G and sum(len(o[0]) for o in got[0][0]) == surv
+        for a, b in zip(got[-1][0], got[0][0]):
+            for x, y in zip(a, b):
+                np.testing.assert_array_equal(x, y)
+        live = min(P, surv)
+        for x, y in zip(got[-1][1], got[0][1]):
+            np.testing.assert_array_equal(x[:live], y[:live])
+    finally:
+        model.setLanes(3); model.setGroup(0); model.setCaptionOrder(False); model.setTestArgs()
         _set(model, "decode_screen", -1)
