@@ -46,6 +46,11 @@ class DcSampleOpts(C.Structure):
     _fields_ = [("num_samples", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class DcSampleTrunc(C.Structure):
+    """dc_sample_trunc: {0, 1.0} = no truncation."""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class DcBeamState(C.Structure):
     """dc_beam_state (include/densecap_debug.h): device pointers to the nprop x beam state rows of the beam search."""
     _fields_ = [("h", C.c_void_p), ("c", C.c_void_p), ("beam_lp", C.c_void_p), ("beams", C.c_void_p), ("tok", C.c_void_p),
@@ -149,6 +154,16 @@ _SIGS = {
                                      C.POINTER(DcResult), C.c_void_p, C.c_void_p]),
     "dc_op_lm_sample_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DcSampleOpts), C.c_void_p,
                                     C.c_void_p]),
+    "dc_sample_captions_trunc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcSampleOpts),
+                                           C.POINTER(DcSampleTrunc), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_op_lm_sample_n_trunc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DcSampleOpts),
+                                          C.POINTER(DcSampleTrunc), C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+# the hook of include/densecap_debug_sample.h (bound like the others; the two lists above mirror densecap.h / densecap_debug.h)
+_SAMPLE_HOOK_SIGS = {
+    "dc_debug_sample_trunc_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint64,
+                                             C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -164,7 +179,7 @@ def lib():
                 "libdensecap_hip.so not built at %s -- run `make -C densecap_amd/csrc` "
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -8,6 +8,7 @@
 
 #include "../../include/densecap.h"
 #include "../../include/densecap_debug.h"
+#include "../../include/densecap_debug_sample.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -42,6 +43,46 @@ __device__ __forceinline__ float gumbel_from_bits(uint32_t bits) {
   const uint32_t k = bits >> 9;
   const float w = ((float)((1u << 23) - k) - 0.5f) * 0x1p-23f;
   return -logf(-log1pf(-w));
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return th_sigmoidf(x); }
+// ---- what the decode step tails share (elementwise.hip, sample_trunc.hip) ------------------------------------------------------
+// The LSTM point-wise half: thread tid owns hidden units j0 + tid + u * 256 (u < kTailUPT) of its row in the pass that starts
+// at j0.  tail_load requests a pass's token-independent operands (the h.Wh gates, c); the kernels call it for j0 = 0 before
+// their reduction, so the operands travel while the word is being found.  tail_update then runs every pass -- the ones past
+// the first (Hd > 512) load in place -- with the word's xg row `x` (null: no embedding row) added: per element
+// (x + gates_pre), sigmoid/tanh, c' = f*c + i*g, h' = o*tanh(c'), c and h in place.
+constexpr int kTailUPT = 2;                         // hidden units per thread and pass (Hd = 512: one pass)
+struct TailRegs { float gpre[kTailUPT][4], cprev[kTailUPT]; };
+__device__ __forceinline__ void tail_load(TailRegs& r, const float* __restrict__ g, const float* __restrict__ c_row, int Hd,
+                                          int j0, int tid, int zero_c) {
+#pragma unroll
+  for (int u = 0; u < kTailUPT; ++u) {
+    const int j = j0 + tid + u * 256;
+    if (j < Hd) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.gpre[u][q] = g[q * Hd + j];
+      r.cprev[u] = zero_c ? 0.f : c_row[j];
+    }
+  }
+}
+__device__ __forceinline__ void tail_update(TailRegs& r, const float* __restrict__ g, const float* __restrict__ x,
+                                            float* __restrict__ c_row, float* __restrict__ h_row, int Hd, int tid, int zero_c) {
+  for (int j0 = 0; j0 < Hd; j0 += 256 * kTailUPT) {
+    if (j0 > 0) tail_load(r, g, c_row, Hd, j0, tid, zero_c);
+#pragma unroll
+    for (int u = 0; u < kTailUPT; ++u) {
+      const int j = j0 + tid + u * 256;
+      if (j >= Hd) continue;
+      float gi = r.gpre[u][0], gf = r.gpre[u][1], go = r.gpre[u][2], gg = r.gpre[u][3];
+      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
+      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
+      const float gt = th_tanhf(gg);
+      const float cn = fg * r.cprev[u] + ig * gt;
+      c_row[j] = cn;
+      h_row[j] = og * th_tanhf(cn);
+    }
+  }
 }
 
 // (shared by boxes.hip and the recognition heads: one definition of the conversion every NMS input goes through)
@@ -280,6 +321,26 @@ hipError_t launch_lse_step_tail(const float* part, int nslots, int ld, const int
 hipError_t launch_sample_step_tail(const float* part, int nslots, int ld, int end_tok, const float* xg, const float* gates_pre,
                                    float* c, float* h, double* acc, uint8_t* fin, int32_t* seq, int T, int t, int n, int Hd,
                                    hipStream_t s);
+// ---- truncated sampling (sample_trunc.hip; docs/SEMANTICS.md, "Truncation: top-k and nucleus") ----
+// One workgroup per row m < rows on the row's V1 logits (logits + m*ld) held in LDS: the kept set of (top_k, top_p) at 1/inv_temp,
+// tok = 1 + the Gumbel-max over it with the noise of (seed, keys[2m + 1] = s, keys[2m] = r, t), lower column on ties; then, as
+// launch_sample_step_tail: with fin[m] == 0 seq[m*T + tpos] = tok, acc[m] += log p(tok) (temperature 1, untruncated), acc_q[m] +=
+// log q(tok) (under the truncated distribution), fin[m] = 1 at end_tok; with fin[m] != 0 seq = 0.  A row without a word writes 0,
+// NaN to both sums and ends.  gates_pre != null: the LSTM point-wise update with tok fed, finished or not.  acc, acc_q, fin and
+// the four per-row outputs of the test hook (kept: words kept, -1 = no word; theta: raw score of the last kept rank; lp, lq: this
+// step's two terms) may each be null.
+struct SampleTruncArgs {
+  const float* logits; int ld, V1;
+  const int32_t* keys; int t; uint32_t seed_lo, seed_hi;
+  float inv_temp; int top_k; float top_p;
+  int end_tok;
+  const float *xg, *gates_pre; float *c, *h; int Hd;
+  double *acc, *acc_q; uint8_t* fin;
+  int32_t* seq; int T, tpos;
+  int32_t* kept_out; float* theta_out; double *lp_out, *lq_out;
+};
+size_t sample_trunc_max_vocab();    // largest V+1 whose row and the kernel's workspace fit the LDS of the current device
+hipError_t launch_sample_trunc_rows(const SampleTruncArgs& a, int rows, hipStream_t s);
 // test hooks of the sampling noise (mfma_gemm.hip, so that the build that draws the words is the one tested; dc_debug_fetch): out[i] = gumbel_from_bits((first + i) << 9), i < count;
 // bits[i] = the Philox word of the coordinates srtv[4i..4i+3] = (s, r, t, v) under `seed`
 hipError_t launch_sample_noise_gumbel(uint32_t first, size_t count, float* out, hipStream_t s);

@@ -956,6 +956,28 @@ int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
   return DC_OK;
 }
 
+// ... and for a dc_sample_trunc beside it.  *route = the truncation the row route runs with, or null: the call is the fused one.
+int check_sample_trunc(dc_ctx* ctx, const dc_sample_opts* o, const dc_sample_trunc* tr, bool want_q, const char* who,
+                       const dc_sample_trunc** route) {
+  static const dc_sample_trunc kOff = {0, 1.f};
+  *route = nullptr;
+  const dc_sample_trunc* t = tr ? tr : &kOff;
+  const int V1 = ctx->V + 1;
+  if (t->top_k < 0 || t->top_k > V1)
+    return ctx->fail(DC_E_INVALID, "%s: top_k must be 0 (off) or in 1..%d (got %d)", who, V1, (int)t->top_k);
+  if (!(t->top_p > 0.f && t->top_p <= 1.f))
+    return ctx->fail(DC_E_INVALID, "%s: top_p must be in (0, 1] (got %g)", who, (double)t->top_p);
+  const bool on = t->top_k != 0 || t->top_p != 1.f;
+  if (!on && !want_q) return DC_OK;
+  if (o->temperature == 0.f)
+    return ctx->fail(DC_E_INVALID, "%s: temperature 0 is the greedy rule: no top_k / top_p / sample_logprob with it", who);
+  if ((size_t)V1 > sample_trunc_max_vocab())
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a vocabulary of %d words does not fit the truncation kernel's LDS row on this device (max %zu)",
+                     who, V1, sample_trunc_max_vocab());
+  *route = t;
+  return DC_OK;
+}
+
 // Sampling captions: LanguageModel:sample with sample_argmax = false (LanguageModel.lua:40-41,328-333) -- S draws per region, each
 // word drawn from SoftMax(scores / temperature) by the Gumbel-max rule with counter-based noise, and the model's own
 // log-probability of every draw (definition: docs/SEMANTICS.md, "Sampling captions").
@@ -968,21 +990,33 @@ int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
 // Planned like lm_score (min(n, kScorePlanRows) rows, no split-K workspace), noise a function of (seed, s, r, t, column) alone
 // with r = row_ids[i] (or i): a draw does not depend on S, the chunking, or the other regions in the call.
 // row_ids: host (n) or null; samples (n, S, T) and logprob (n, S): host.
+//
+// The row route (truncation, or a caller who wants sample_logprob): the epilogue's five floats per slot cannot
+// carry a top-k or nucleus cut, which needs the whole row before the choice.  Per step then: the logits h.Wout^T + b through
+// linear() into rows x (V+1) floats of scratch (w.part: lm_rows_plan counts them in row_bytes, so the 512 MiB chunk rule and
+// "sample_rows_cap" hold), G = h.Wh as lm_start_state forms it, and sample_trunc_rows (sample_trunc.hip) in the place of
+// sample_step_tail.  The same shared pieces, the same planning, the same noise coordinates: the bit-identities above hold here
+// too.  trunc == null and lq == null: the fused route, untouched.
 int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts& o,
-                int32_t* samples, float* logprob) {
+                int32_t* samples, float* logprob, const dc_sample_trunc* trunc = nullptr, float* sample_logprob = nullptr) {
   const int Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, S = o.num_samples;
-  const int nslots = ctx->V1pad / 32, ld = 5 * nslots;
+  const bool by_rows = trunc != nullptr || sample_logprob != nullptr;
+  const int nslots = ctx->V1pad / 32, ld = by_rows ? V1 : 5 * nslots;
   Fp32Guard fp32(ctx->cfg);
   LmRows w;
-  lm_rows_plan(w, n, S, ctx->sample_rows_cap, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1);
+  lm_rows_plan(w, n, S, ctx->sample_rows_cap,
+               (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1 + (by_rows ? 8 : 0));
   if (w.rmax > (size_t)INT32_MAX / (size_t)std::max(ld, 4 * Hd))
     return ctx->fail(DC_E_INVALID, "lm_sample_n: %d regions are too many rows for one launch", n);
   int32_t *seq = nullptr, *keys = nullptr;      // the rows' words; their (row id, draw) noise keys
   uint8_t* fin = nullptr;                       // END drawn at an earlier step
-  DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&seq, w.rmax * T * 4}, {(void**)&keys, w.rmax * 8}, {(void**)&fin, w.rmax}}));
+  double* acc_q = nullptr;                      // row route: the sum of the draws' log-probabilities under the truncated distribution
+  DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&seq, w.rmax * T * 4}, {(void**)&keys, w.rmax * 8}, {(void**)&fin, w.rmax},
+                                   {(void**)&acc_q, by_rows ? w.rmax * 8 : 0}}));
   auto body = [&]() -> int {
     DCCHK(lm_start_state(ctx, s, codes, n, w.enc, w.g0, w.c0, w.h0, w.plan, nullptr, Ws()));
     std::vector<int32_t> kh, sh;
+    std::vector<double> qh;
     for (int a = 0; a < S; a += w.chunk) {
       const int nd = std::min(w.chunk, S - a);
       const size_t rows = (size_t)nd * n;
@@ -993,7 +1027,24 @@ int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int
           kh[2 * ((size_t)i * n + r) + 1] = a + i;
         }
       DCCHK(lm_chunk_begin(ctx, s, w, nd, keys, kh, fin));
-      for (int t = 1; t <= T; ++t) {
+      if (by_rows) HIPCHK(hipMemsetAsync(acc_q, 0, rows * 8, s));
+      for (int t = 1; by_rows && t <= T; ++t) {
+        const bool last = t == T;
+        DCCHK(linear(ctx, s, w.h, ctx->out_w, ctx->out_b, w.part, (int)rows, V1, Hd, 0, Ws(), w.plan));
+        if (!last) {
+          GemmDesc g;              // h_t.Wh for the next step's gates, as lm_start_state forms h_0.Wh
+          g.A = w.h; g.W = ctx->whT; g.C = w.gates; g.M = (int)rows; g.N = 4 * Hd; g.K = Hd; g.ldc = 4 * Hd; g.plan_M = w.plan;
+          DCCHK(run_gemm(ctx, g, s));
+        }
+        SampleTruncArgs a = {};
+        a.logits = w.part; a.ld = ld; a.V1 = V1; a.keys = keys; a.t = t;
+        a.seed_lo = (uint32_t)(o.seed & 0xffffffffu); a.seed_hi = (uint32_t)(o.seed >> 32);
+        a.inv_temp = 1.f / o.temperature; a.top_k = trunc ? trunc->top_k : 0; a.top_p = trunc ? trunc->top_p : 1.f;
+        a.end_tok = V1; a.xg = ctx->xg; a.gates_pre = last ? nullptr : w.gates; a.c = w.c; a.h = w.h; a.Hd = Hd;
+        a.acc = w.acc; a.acc_q = acc_q; a.fin = fin; a.seq = seq; a.T = T; a.tpos = t - 1;
+        KCHK(launch_sample_trunc_rows(a, (int)rows, s));
+      }
+      for (int t = 1; !by_rows && t <= T; ++t) {
         const bool last = t == T;
         GemmDesc v = decode_step_desc(ctx, w.h, (int)rows, w.plan, last, w.gates);     // epilogue: the sampling partials
         v.amax_val = w.part; v.amax_ld = ld; v.rowidx = keys;
@@ -1005,10 +1056,15 @@ int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int
       }
       sh.resize(rows * T);
       HIPCHK(hipMemcpyAsync(sh.data(), seq, rows * T * 4, hipMemcpyDeviceToHost, s));
+      if (by_rows) {
+        qh.resize(rows);
+        HIPCHK(hipMemcpyAsync(qh.data(), acc_q, rows * 8, hipMemcpyDeviceToHost, s));
+      }
       DCCHK(lm_chunk_end(ctx, s, w, nd));
       for (int i = 0; i < nd; ++i)
         for (int r = 0; r < n; ++r) {
           logprob[(size_t)r * S + a + i] = (float)w.acc_host[(size_t)i * n + r];
+          if (sample_logprob != nullptr) sample_logprob[(size_t)r * S + a + i] = (float)qh[(size_t)i * n + r];
           memcpy(samples + ((size_t)r * S + a + i) * T, sh.data() + ((size_t)i * n + r) * T, (size_t)T * 4);
         }
     }
@@ -2402,40 +2458,93 @@ int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   return lm_score(ctx, L.stream, L.out_feats, K, queries, Q, Tq, loglik, Q);
 }
 
-int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
-                      int32_t* samples, float* logprob) {
+static int op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                          const dc_sample_trunc* trunc, int32_t* samples, float* logprob, float* sample_logprob, const char* who) {
   OP_PROLOGUE();
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_op_lm_sample_n: weights not loaded");
-  if (!codes || !samples || !logprob) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: null pointer");
-  if (n <= 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: n must be > 0");
-  DCCHK(check_sample_opts(ctx, opts, "dc_op_lm_sample_n"));
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!codes || !samples || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n <= 0) return ctx->fail(DC_E_INVALID, "%s: n must be > 0", who);
+  DCCHK(check_sample_opts(ctx, opts, who));
+  const dc_sample_trunc* route = nullptr;
+  DCCHK(check_sample_trunc(ctx, opts, trunc, sample_logprob != nullptr, who, &route));
   std::vector<int32_t> ids;
   if (row_ids != nullptr) {
     ids.resize(n);
     HIPCHK(hipMemcpy(ids.data(), row_ids, (size_t)n * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i)
-      if (ids[i] < 0) return ctx->fail(DC_E_INVALID, "dc_op_lm_sample_n: row_ids[%d] = %d is negative", i, (int)ids[i]);
+      if (ids[i] < 0) return ctx->fail(DC_E_INVALID, "%s: row_ids[%d] = %d is negative", who, i, (int)ids[i]);
   }
   const size_t S = (size_t)opts->num_samples;
   std::vector<int32_t> tok((size_t)n * S * ctx->T);
-  std::vector<float> lp((size_t)n * S);
-  DCCHK(lm_sample_n(ctx, s, codes, n, row_ids ? ids.data() : nullptr, *opts, tok.data(), lp.data()));
+  std::vector<float> lp((size_t)n * S), lq(sample_logprob ? (size_t)n * S : 0);
+  DCCHK(lm_sample_n(ctx, s, codes, n, row_ids ? ids.data() : nullptr, *opts, tok.data(), lp.data(), route,
+                    sample_logprob ? lq.data() : nullptr));
   HIPCHK(hipMemcpy(samples, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(logprob, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+  if (sample_logprob) HIPCHK(hipMemcpy(sample_logprob, lq.data(), lq.size() * 4, hipMemcpyHostToDevice));
   OP_EPILOGUE();
 }
+int dc_op_lm_sample_n_trunc(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                            const dc_sample_trunc* trunc_or_null, int32_t* samples, float* logprob,
+                            float* sample_logprob_or_null) {
+  return op_lm_sample_n(ctx, codes, n, row_ids, opts, trunc_or_null, samples, logprob, sample_logprob_or_null,
+                        "dc_op_lm_sample_n_trunc");
+}
+int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                      int32_t* samples, float* logprob) {
+  return op_lm_sample_n(ctx, codes, n, row_ids, opts, nullptr, samples, logprob, nullptr, "dc_op_lm_sample_n");
+}
 
-int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
-                       dc_result* out, int32_t* samples, float* logprob) {
+static int sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                           const dc_sample_trunc* trunc, dc_result* out, int32_t* samples, float* logprob, float* sample_logprob,
+                           const char* who) {
   if (!ctx) return DC_E_INVALID;
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "dc_sample_captions: weights not loaded");
-  if (!img_chw || !out || !samples || !logprob) return ctx->fail(DC_E_INVALID, "dc_sample_captions: null pointer");
-  DCCHK(check_sample_opts(ctx, opts, "dc_sample_captions"));
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!img_chw || !out || !samples || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_sample_opts(ctx, opts, who));
+  const dc_sample_trunc* route = nullptr;
+  DCCHK(check_sample_trunc(ctx, opts, trunc, sample_logprob != nullptr, who, &route));
   int K = 0;
-  DCCHK(forward_kept_codes(ctx, img_chw, H, W, img_on_device, out, "dc_sample_captions", &K));
+  DCCHK(forward_kept_codes(ctx, img_chw, H, W, img_on_device, out, who, &K));
   if (K == 0) return DC_OK;
   Lane& L = lane0(ctx);
-  return lm_sample_n(ctx, L.stream, L.out_feats, K, nullptr, *opts, samples, logprob);      // r = output row
+  return lm_sample_n(ctx, L.stream, L.out_feats, K, nullptr, *opts, samples, logprob, route, sample_logprob);      // r = output row
+}
+int dc_sample_captions_trunc(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                             const dc_sample_trunc* trunc_or_null, dc_result* out, int32_t* samples, float* logprob,
+                             float* sample_logprob_or_null) {
+  return sample_captions(ctx, img_chw, H, W, img_on_device, opts, trunc_or_null, out, samples, logprob, sample_logprob_or_null,
+                         "dc_sample_captions_trunc");
+}
+int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                       dc_result* out, int32_t* samples, float* logprob) {
+  return sample_captions(ctx, img_chw, H, W, img_on_device, opts, nullptr, out, samples, logprob, nullptr, "dc_sample_captions");
+}
+
+// ---- the truncated sampler's test hook (densecap_debug_sample.h) ----------------------------------------------------------------
+int dc_debug_sample_trunc_rows(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const int32_t* keys, int t,
+                               uint64_t seed, float temperature, int top_k, float top_p, int32_t* tok_out, int32_t* kept_out,
+                               float* theta_out, double* lp_out, double* lq_out) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_sample_trunc_rows";
+  if (!logits || !keys || !tok_out || !kept_out || !theta_out || !lp_out || !lq_out)
+    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (rows < 1 || V1 < 1 || ld < V1 || t < 1) return ctx->fail(DC_E_INVALID, "%s: rows, V1 >= 1, ld >= V1 and t >= 1 wanted", who);
+  if (!(temperature >= 0.01f && temperature <= 100.f))
+    return ctx->fail(DC_E_INVALID, "%s: temperature must be in [0.01, 100] (got %g)", who, (double)temperature);
+  if (top_k < 0 || top_k > V1) return ctx->fail(DC_E_INVALID, "%s: top_k must be 0 (off) or in 1..%d (got %d)", who, V1, top_k);
+  if (!(top_p > 0.f && top_p <= 1.f)) return ctx->fail(DC_E_INVALID, "%s: top_p must be in (0, 1] (got %g)", who, (double)top_p);
+  if ((size_t)V1 > sample_trunc_max_vocab())
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a row of %d words does not fit the truncation kernel's LDS row on this device (max %zu)", who,
+                     V1, sample_trunc_max_vocab());
+  SampleTruncArgs a = {};
+  a.logits = logits; a.ld = ld; a.V1 = V1; a.keys = keys; a.t = t;
+  a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
+  a.inv_temp = 1.f / temperature; a.top_k = top_k; a.top_p = top_p; a.end_tok = V1;
+  a.seq = tok_out; a.T = 1; a.tpos = 0;
+  a.kept_out = kept_out; a.theta_out = theta_out; a.lp_out = lp_out; a.lq_out = lq_out;
+  KCHK(launch_sample_trunc_rows(a, rows, s));
+  OP_EPILOGUE();
 }
 
 // ---- beam search test hooks (densecap_debug.h) ---------------------------------------------------------------------------------

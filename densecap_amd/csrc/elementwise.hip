@@ -203,7 +203,6 @@ __global__ void maxpool2x2_ceil_kernel(const float* __restrict__ in, float* __re
 }
 
 // ---- LSTM point-wise (torch-rnn nn.LSTM step; gate order i,f,o,g) ----------------------------
-__device__ __forceinline__ float sigmoidf_(float x) { return th_sigmoidf(x); }
 __global__ void lstm_pointwise_kernel(const float* __restrict__ gates, float* __restrict__ c, float* __restrict__ h,
                                       int n, const int32_t* __restrict__ n_dev, int Hd, int zero_c) {
   if (n_dev) n = min(n, *n_dev);
@@ -221,44 +220,8 @@ __global__ void lstm_pointwise_kernel(const float* __restrict__ gates, float* __
   }
 }
 
-// ---- what the three decode step tails below share --------------------------------------------------------------------------
-// The LSTM point-wise half: thread tid owns hidden units j0 + tid + u * 256 (u < kTailUPT) of its row in the pass that starts
-// at j0.  tail_load requests a pass's token-independent operands (the h.Wh gates, c); the kernels call it for j0 = 0 before
-// their reduction, so the operands travel while the word is being found.  tail_update then runs every pass -- the ones past
-// the first (Hd > 512) load in place -- with the word's xg row `x` (null: no embedding row) added: per element
-// (x + gates_pre), sigmoid/tanh, c' = f*c + i*g, h' = o*tanh(c'), c and h in place.
-constexpr int kTailUPT = 2;                         // hidden units per thread and pass (Hd = 512: one pass)
-struct TailRegs { float gpre[kTailUPT][4], cprev[kTailUPT]; };
-__device__ __forceinline__ void tail_load(TailRegs& r, const float* __restrict__ g, const float* __restrict__ c_row, int Hd,
-                                          int j0, int tid, int zero_c) {
-#pragma unroll
-  for (int u = 0; u < kTailUPT; ++u) {
-    const int j = j0 + tid + u * 256;
-    if (j < Hd) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r.gpre[u][q] = g[q * Hd + j];
-      r.cprev[u] = zero_c ? 0.f : c_row[j];
-    }
-  }
-}
-__device__ __forceinline__ void tail_update(TailRegs& r, const float* __restrict__ g, const float* __restrict__ x,
-                                            float* __restrict__ c_row, float* __restrict__ h_row, int Hd, int tid, int zero_c) {
-  for (int j0 = 0; j0 < Hd; j0 += 256 * kTailUPT) {
-    if (j0 > 0) tail_load(r, g, c_row, Hd, j0, tid, zero_c);
-#pragma unroll
-    for (int u = 0; u < kTailUPT; ++u) {
-      const int j = j0 + tid + u * 256;
-      if (j >= Hd) continue;
-      float gi = r.gpre[u][0], gf = r.gpre[u][1], go = r.gpre[u][2], gg = r.gpre[u][3];
-      if (x != nullptr) { gi = x[j] + gi; gf = x[Hd + j] + gf; go = x[2 * Hd + j] + go; gg = x[3 * Hd + j] + gg; }
-      const float ig = sigmoidf_(gi), fg = sigmoidf_(gf), og = sigmoidf_(go);
-      const float gt = th_tanhf(gg);
-      const float cn = fg * r.cprev[u] + ig * gt;
-      c_row[j] = cn;
-      h_row[j] = og * th_tanhf(cn);
-    }
-  }
-}
+// (the LSTM point-wise half the decode step tails share -- TailRegs, tail_load, tail_update -- lives in common.h: sample_trunc.hip
+// runs it too)
 
 // Arg-best merge: (ov, oi) replaces (best, bi) -- true is returned, for a caller that carries more with the entry -- when it
 // is an entry at all and the larger one, the lower column on ties.  kNoCol: no entry yet.

@@ -569,14 +569,19 @@ class DenseCapModel:
             res = res + (self.decodeSequence(tokens[:K]),)
         return res
 
-    def sampleCaptions(self, img, num_samples, temperature=1.0, seed=0, want_tokens=True):
+    def sampleCaptions(self, img, num_samples, temperature=1.0, seed=0, want_tokens=True, top_k=0, top_p=1.0,
+                       want_sample_logprob=False):
         """Sample captions for the image's regions (dc_sample_captions; LM:sample with sample_argmax = false,
         LanguageModel.lua:40-41,328-333): the regions forward_test returns, each with num_samples draws whose words come from
         SoftMax(scores / temperature), and the model's log-probability of every draw.  temperature 0 (num_samples 1) is the
         greedy rule.  Returns (boxes (K,4) xcycwh, scores (K,), tokens (K,T) -- the greedy captions, or None without
-        want_tokens --, samples (K,S,T) int32, logprob (K,S)); decodeSequence(samples[:, s]) gives the strings of draw s."""
-        from .ops import DeviceArray, check_sample_args
-        opts = check_sample_args(num_samples, temperature, seed)
+        want_tokens --, samples (K,S,T) int32, logprob (K,S)); decodeSequence(samples[:, s]) gives the strings of draw s.
+        top_k (0 = off) / top_p (1.0 = off) truncate the distribution of every step (dc_sample_captions_trunc;
+        docs/SEMANTICS.md, "Truncation: top-k and nucleus"); want_sample_logprob appends sample_logprob (K,S) -- the
+        log-probability of every draw under the distribution it was drawn from -- as a sixth element."""
+        from .ops import DeviceArray, check_sample_args, sample_trunc_arg
+        opts = check_sample_args(num_samples, temperature, seed, top_k, top_p, want_sample_logprob)
+        trunc = sample_trunc_arg(temperature, top_k, top_p, want_sample_logprob, vocab_size=self.vocab_size)
         self._push_test_args()
         on_device = isinstance(img, DeviceArray)       # a (3,H,W) float32 image already on the device (ops.preprocess_u8)
         if on_device:
@@ -593,12 +598,21 @@ class DenseCapModel:
         S = opts.num_samples
         samples = np.zeros((P, S, self.seq_length), np.int32)
         logprob = np.zeros((P, S), np.float32)
-        check(self.ctx.h, self.lib.dc_sample_captions(self.ctx.h, ptr, img.shape[1], img.shape[2], int(on_device),
-                                                      C.byref(opts), C.byref(r), samples.ctypes.data, logprob.ctypes.data),
-              "dc_sample_captions")
+        if trunc is None:
+            check(self.ctx.h, self.lib.dc_sample_captions(self.ctx.h, ptr, img.shape[1], img.shape[2], int(on_device),
+                                                          C.byref(opts), C.byref(r), samples.ctypes.data, logprob.ctypes.data),
+                  "dc_sample_captions")
+        else:
+            slp = np.zeros((P, S), np.float32) if want_sample_logprob else None
+            check(self.ctx.h, self.lib.dc_sample_captions_trunc(self.ctx.h, ptr, img.shape[1], img.shape[2], int(on_device),
+                                                                C.byref(opts), C.byref(trunc), C.byref(r), samples.ctypes.data,
+                                                                logprob.ctypes.data,
+                                                                slp.ctypes.data if slp is not None else None),
+                  "dc_sample_captions_trunc")
         K = r.K
-        return (boxes[:K].copy(), scores[:K].copy(), tokens[:K].copy() if want_tokens else None, samples[:K].copy(),
-                logprob[:K].copy())
+        res = (boxes[:K].copy(), scores[:K].copy(), tokens[:K].copy() if want_tokens else None, samples[:K].copy(),
+               logprob[:K].copy())
+        return res + (slp[:K].copy(),) if want_sample_logprob else res
 
     def decodeSequence(self, seq):
         """LanguageModel:decodeSequence (LanguageModel.lua:86-103)."""

@@ -288,9 +288,10 @@ def lm_score(ctx, codes, queries):
     return o.numpy()
 
 
-def check_sample_args(num_samples, temperature, seed):
-    """The rules of dc_sample_opts (docs/SEMANTICS.md, "Sampling captions"), checked before the library is called.
-    Returns the filled DcSampleOpts."""
+def check_sample_args(num_samples, temperature, seed, top_k=0, top_p=1.0, want_sample_logprob=False, vocab_size=None):
+    """The rules of dc_sample_opts and dc_sample_trunc (docs/SEMANTICS.md, "Sampling captions"), checked before the library is
+    called.  Returns the filled DcSampleOpts (the DcSampleTrunc beside it: sample_trunc_arg).  vocab_size (V): top_k's upper
+    end V + 1 is checked here when given, by the library otherwise."""
     S = int(num_samples)
     if S != num_samples or not 1 <= S <= 256:
         raise ValueError("num_samples must be an integer in 1..256 (got %r)" % (num_samples,))
@@ -302,17 +303,41 @@ def check_sample_args(num_samples, temperature, seed):
     sd = int(seed)
     if sd != seed or not 0 <= sd < 1 << 64:
         raise ValueError("seed must be an integer in 0..2^64-1 (got %r)" % (seed,))
+    sample_trunc_arg(t, top_k, top_p, want_sample_logprob, vocab_size)
     return _lib.DcSampleOpts(S, t, sd)
 
 
-def lm_sample_n(ctx, codes, num_samples, temperature=1.0, seed=0, row_ids=None, seq_length=None):
+def sample_trunc_arg(temperature, top_k=0, top_p=1.0, want_sample_logprob=False, vocab_size=None):
+    """The DcSampleTrunc of a call, or None when the call is the untruncated one (top_k 0, top_p 1.0, no sample_logprob wanted);
+    ValueError where dc_sample_trunc's rules do not hold."""
+    try:
+        k = int(top_k)
+    except (TypeError, ValueError, OverflowError):
+        k = -1
+    if k != top_k or k < 0 or k >= 1 << 31 or (vocab_size is not None and k > vocab_size + 1):
+        raise ValueError("top_k must be 0 (off) or an integer in 1..V+1 (got %r)" % (top_k,))
+    p = float(np.float32(top_p))
+    if not 0.0 < p <= 1.0:                           # NaN fails
+        raise ValueError("top_p must be in (0, 1] (got %r)" % (top_p,))
+    on = k != 0 or p != 1.0
+    if (on or want_sample_logprob) and float(np.float32(temperature)) == 0.0:
+        raise ValueError("temperature 0 is the greedy rule: no top_k / top_p / sample_logprob with it")
+    return _lib.DcSampleTrunc(k, p) if on or want_sample_logprob else None
+
+
+def lm_sample_n(ctx, codes, num_samples, temperature=1.0, seed=0, row_ids=None, seq_length=None, top_k=0, top_p=1.0,
+                want_sample_logprob=False):
     """num_samples draws per code row from the ctx's loaded language model (dc_op_lm_sample_n): every word drawn from
     SoftMax(scores / temperature) (temperature 0, num_samples 1: the greedy rule), noise a function of (seed, draw, row id,
     step, word) alone.  codes (n, fc_dim); row_ids (n) ints >= 0 or None (= 0..n-1).  Returns (samples (n, S, T) int32 --
     word ids up to and including the first END, zeros after it --, logprob (n, S) float32: the model's log-probability of
     the words written; NaN, with an all-zero row from that step on, for a row whose scores became NaN -- non-finite codes).
-    seq_length: the loaded model's T; needed only when the weights were not loaded through DenseCapModel."""
-    opts = check_sample_args(num_samples, temperature, seed)
+    seq_length: the loaded model's T; needed only when the weights were not loaded through DenseCapModel.
+    top_k (0 = off) / top_p (1.0 = off) truncate the distribution of every step (dc_op_lm_sample_n_trunc; docs/SEMANTICS.md,
+    "Truncation: top-k and nucleus"); want_sample_logprob appends sample_logprob (n, S) float32 -- the log-probability of
+    every draw under the distribution it was drawn from -- to the result.  With neither, the call is the untruncated one."""
+    opts = check_sample_args(num_samples, temperature, seed, top_k, top_p, want_sample_logprob)
+    trunc = sample_trunc_arg(temperature, top_k, top_p, want_sample_logprob)
     x = _f32(codes)
     if x.ndim != 2 or x.shape[0] < 1:
         raise ValueError("codes must be (n, fc_dim) with n >= 1")
@@ -329,9 +354,32 @@ def lm_sample_n(ctx, codes, num_samples, temperature=1.0, seed=0, row_ids=None, 
     xd = ctx.to_device(x)
     idd = ctx.to_device(ids) if ids is not None else None
     tok = ctx.empty((n, S, T), np.int32); lp = ctx.empty((n, S), np.float32)
-    check(ctx.h, ctx.lib.dc_op_lm_sample_n(ctx.h, xd.ptr, n, idd.ptr if idd is not None else None, C.byref(opts), tok.ptr,
-                                           lp.ptr), "dc_op_lm_sample_n")
-    return tok.numpy(), lp.numpy()
+    if trunc is None:
+        check(ctx.h, ctx.lib.dc_op_lm_sample_n(ctx.h, xd.ptr, n, idd.ptr if idd is not None else None, C.byref(opts), tok.ptr,
+                                               lp.ptr), "dc_op_lm_sample_n")
+        return tok.numpy(), lp.numpy()
+    lq = ctx.empty((n, S), np.float32) if want_sample_logprob else None
+    check(ctx.h, ctx.lib.dc_op_lm_sample_n_trunc(ctx.h, xd.ptr, n, idd.ptr if idd is not None else None, C.byref(opts),
+                                                 C.byref(trunc), tok.ptr, lp.ptr, lq.ptr if lq is not None else None),
+          "dc_op_lm_sample_n_trunc")
+    return (tok.numpy(), lp.numpy(), lq.numpy()) if want_sample_logprob else (tok.numpy(), lp.numpy())
+
+
+def sample_trunc_rows(ctx, logits, keys, t, seed, temperature, top_k=0, top_p=1.0):
+    """The selection of the truncated sampler alone (dc_debug_sample_trunc_rows): logits (rows, V1) float32, keys (rows, 2)
+    int32 (r, s).  Returns dict(tok, kept, theta, lp, lq) of per-row arrays."""
+    x = _f32(logits)
+    k = np.ascontiguousarray(keys, dtype=np.int32)
+    rows, V1 = x.shape
+    if k.shape != (rows, 2):
+        raise ValueError("keys must be (rows, 2)")
+    xd = ctx.to_device(x); kd = ctx.to_device(k)
+    tok = ctx.empty((rows,), np.int32); kept = ctx.empty((rows,), np.int32); theta = ctx.empty((rows,), np.float32)
+    lp = ctx.empty((rows,), np.float64); lq = ctx.empty((rows,), np.float64)
+    check(ctx.h, ctx.lib.dc_debug_sample_trunc_rows(ctx.h, xd.ptr, rows, V1, V1, kd.ptr, int(t), int(seed), float(temperature),
+                                                    int(top_k), float(top_p), tok.ptr, kept.ptr, theta.ptr, lp.ptr, lq.ptr),
+          "dc_debug_sample_trunc_rows")
+    return dict(tok=tok.numpy(), kept=kept.numpy(), theta=theta.numpy(), lp=lp.numpy(), lq=lq.numpy())
 
 
 # ---- beam search test hooks (include/densecap_debug.h) ----------------------------------------------------------------------

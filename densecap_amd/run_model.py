@@ -77,10 +77,15 @@ def build_parser():
            "0 (default): output as without the flag")
     a("-temperature", type=float, default=1.0, help="temperature of -num_samples: 0.01..100, or 0 with -num_samples 1 (the greedy rule)")
     a("-sample_seed", type=int, default=0, help="seed of -num_samples: image i of the run uses seed + i")
+    a("-top_k", type=int, default=0, help="with -num_samples: draw every word from the top_k best-scoring words only (0 = off)")
+    a("-top_p", type=float, default=1.0,
+      help="with -num_samples: nucleus truncation -- the smallest set of best-scoring words (among the top_k) whose probability "
+           "reaches top_p (1 = off).  With either, results.json also carries `sampled_sample_logprobs`: every draw's "
+           "log-probability under the truncated distribution it was drawn from")
     return p
 
 
-SAMPLING_FLAGS = ("num_samples", "temperature", "sample_seed")
+SAMPLING_FLAGS = ("num_samples", "temperature", "sample_seed", "top_k", "top_p")
 
 
 def _scale_linear_axis(src, dst_len, axis):
@@ -419,12 +424,13 @@ def main(argv=None):
         weights = t7.weights_from_checkpoint(ck)
     if opt.num_samples:
         try:                               # at start-up, not at the image whose seed would leave the range
-            ops.check_sample_args(opt.num_samples, opt.temperature, opt.sample_seed)
+            ops.check_sample_args(opt.num_samples, opt.temperature, opt.sample_seed, opt.top_k, opt.top_p)
         except ValueError as e:
-            raise SystemExit("-num_samples / -temperature / -sample_seed: %s" % e)
+            raise SystemExit("-num_samples / -temperature / -sample_seed / -top_k / -top_p: %s" % e)
         if opt.input_boxes:
             raise SystemExit("-num_samples with -input_boxes: sample on the boxes' codes instead (extract_features_boxes, then "
                              "ops.lm_sample_n)")
+    truncated = bool(opt.num_samples) and (opt.top_k != 0 or opt.top_p != 1.0)
     paths = get_input_images(opt)
     num = min(len(paths), opt.max_images)
     if opt.num_samples and opt.sample_seed + max(num, 1) - 1 >= 1 << 64:
@@ -474,6 +480,8 @@ def main(argv=None):
                 samples, logprob = out[3], out[4]
                 rj["sampled_captions"] = [model.decodeSequence(samples[k]) for k in range(len(samples))]
                 rj["sampled_logprobs"] = [[float(v) for v in row] for row in logprob]
+                if truncated:
+                    rj["sampled_sample_logprobs"] = [[float(v) for v in row] for row in out[5]]
             results[i] = rj
 
     try:
@@ -482,7 +490,11 @@ def main(argv=None):
                 print("%d/%d processing image %s" % (i + 1, num, paths[i]))
             if opt.num_samples:
                 # image by image: dc_sample_captions runs the forward itself (lane 0), then the draws -- same boxes, scores, captions
-                outs = [model.sampleCaptions(d, opt.num_samples, opt.temperature, opt.sample_seed + i) for i, d, _ in chunk]
+                if truncated:
+                    outs = [model.sampleCaptions(d, opt.num_samples, opt.temperature, opt.sample_seed + i, top_k=opt.top_k,
+                                                 top_p=opt.top_p, want_sample_logprob=True) for i, d, _ in chunk]
+                else:
+                    outs = [model.sampleCaptions(d, opt.num_samples, opt.temperature, opt.sample_seed + i) for i, d, _ in chunk]
             elif in_boxes is None:
                 outs = model.forward_images_device([d for _, d, _ in chunk])
             else:

@@ -152,6 +152,22 @@ typedef struct dc_sample_opts {
  * outside the ranges above are refused with DC_E_INVALID before anything is enqueued; K > out->capacity is refused. */
 int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
                        dc_result* out, int32_t* samples, float* logprob);
+/* Truncation of the sampling distribution, at every step of every draw (docs/SEMANTICS.md, "Truncation: top-k and nucleus"):
+ * top_k = 0 (off) or 1..V+1 keeps the top_k best-scoring words; top_p = 1 (off) or in (0, 1) then keeps the smallest prefix of
+ * those, best first, whose renormalised probability at the call's temperature reaches top_p.  {0, 1.0f} = no truncation.
+ * Ties: the lower word id first.  Any truncation needs temperature > 0. */
+typedef struct dc_sample_trunc { int32_t top_k; float top_p; } dc_sample_trunc;
+/* dc_sample_captions with truncation.  trunc == NULL or {0, 1.0f} together with sample_logprob == NULL IS dc_sample_captions
+ * (the same code path, the same bits); anything else runs on the row route (full logits per step, one row kernel), whose words
+ * follow the same definition but may differ from the fused route's at near-ties.  logprob keeps its meaning (the model's own
+ * probability at temperature 1, untruncated; on the row route within the stage bound of dc_op_lm_score, not bit-equal).
+ * sample_logprob: NULL, or host (out->capacity, S): the natural-log probability of the draw under the distribution it was
+ * drawn from (temperature and truncation applied).  A top_k outside 0..V+1, a top_p outside (0, 1] or truncation at
+ * temperature 0 is refused with DC_E_INVALID, a vocabulary whose row does not fit a workgroup's LDS with DC_E_UNSUPPORTED, both
+ * before anything is enqueued. */
+int dc_sample_captions_trunc(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
+                             const dc_sample_trunc* trunc_or_null, dc_result* out, int32_t* samples, float* logprob,
+                             float* sample_logprob_or_null);
 /* run_model.lua:160-180 host loop over images, n images of identical size laid out
  * back to back; images are software-pipelined over the ctx's lanes (streams). */
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device,
@@ -391,6 +407,11 @@ int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* querie
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */
 int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
                       int32_t* samples, float* logprob);
+/* The sampling of dc_sample_captions_trunc on given fc7 codes: as dc_op_lm_sample_n, with sample_logprob (n, S) or NULL.
+ * Device pointers throughout; synchronous. */
+int dc_op_lm_sample_n_trunc(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
+                            const dc_sample_trunc* trunc_or_null, int32_t* samples, float* logprob,
+                            float* sample_logprob_or_null);
 
 #ifdef __cplusplus
 }

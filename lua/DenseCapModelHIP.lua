@@ -293,7 +293,10 @@ end
 -- Returns boxes, scores, the greedy captions, samples: IntTensor (K, S, T) of word ids (up to and including the first END,
 -- zeros after it; self:decodeSequence(samples[{{}, s}]:long()) gives the strings of draw s) and logprob (K, S), the model's
 -- log-probability of every draw.
-function Model:sampleCaptions(input, num_samples, temperature, seed)
+-- top_k (nil or 0 = off) / top_p (nil or 1 = off): truncation of every step's distribution (dc_sample_captions_trunc;
+-- docs/SEMANTICS.md, "Truncation: top-k and nucleus").  With either, a sixth value is returned: sample_logprob (K, S), the
+-- log-probability of every draw under the truncated distribution it was drawn from.
+function Model:sampleCaptions(input, num_samples, temperature, seed, top_k, top_p)
   self:_push_test_args()
   assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
   local img = input:float():contiguous()
@@ -310,13 +313,26 @@ function Model:sampleCaptions(input, num_samples, temperature, seed)
   r.capacity = P
   r.boxes, r.scores = torch.data(boxes), torch.data(scores)
   r.tokens = torch.data(tokens)
-  hip.check(self.ctx, C.dc_sample_captions(self.ctx, fptr(img), H, W, 0, o, r, torch.data(samples), torch.data(logprob)),
-            'dc_sample_captions')
+  local truncated = (top_k ~= nil and top_k ~= 0) or (top_p ~= nil and top_p ~= 1)
+  local slp
+  if truncated then
+    local tr = ffi.new('dc_sample_trunc')
+    tr.top_k, tr.top_p = top_k or 0, top_p or 1
+    slp = torch.FloatTensor(P, S):zero()
+    hip.check(self.ctx, C.dc_sample_captions_trunc(self.ctx, fptr(img), H, W, 0, o, tr, r, torch.data(samples),
+                                                   torch.data(logprob), torch.data(slp)), 'dc_sample_captions_trunc')
+  else
+    hip.check(self.ctx, C.dc_sample_captions(self.ctx, fptr(img), H, W, 0, o, r, torch.data(samples), torch.data(logprob)),
+              'dc_sample_captions')
+  end
   local K = r.K
-  if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, torch.IntTensor(), torch.FloatTensor() end
+  if K == 0 then
+    return torch.FloatTensor(), torch.FloatTensor(), {}, torch.IntTensor(), torch.FloatTensor(),
+           truncated and torch.FloatTensor() or nil
+  end
   local seq = tokens[{{1, K}}]:long()
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), samples[{{1, K}}]:clone(),
-         logprob[{{1, K}}]:clone()
+         logprob[{{1, K}}]:clone(), truncated and slp[{{1, K}}]:clone() or nil
 end
 
 -- The model after the RPN on the caller's boxes (dc_forward_boxes; DenseCapModel.lua:242-275 with `boxes` in the place of

@@ -6,7 +6,11 @@ epilogue -- dc_op_lm_score with Q = S queries of T-1 words (K x S rows, T step G
 same run: their ratio is what the noise generation costs a step.  Also temperature 0 / S = 1 against the greedy decode
 (dc_op_lm_sample) on the same K rows: the price of carrying the log-probability.  Prints one JSON line per measurement.
 --only S: just that draw count, a few repetitions of the two ops (for a kernel trace).
-usage: python tools/sample_bench.py [--reps 5] [--samples 1,8,32,128] [--only S] [--out FILE]"""
+--top_k K --top_p P (several pairs: --top_k 40,0 --top_p 1,0.9; K = -1 stands for V + 1): the truncated sampler instead --
+for every S, dc_op_lm_sample_n_trunc at each pair beside the fused dc_op_lm_sample_n on the same rows in the same run, and
+their ratio (the row route writes the logits and runs two more launches per step).  With --only: a few repetitions of
+the first pair and of the fused op.
+usage: python tools/sample_bench.py [--reps 5] [--samples 1,8,32,128] [--only S] [--top_k K,.. --top_p P,..] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +30,8 @@ def main():
     ap.add_argument("--samples", default="1,8,32,128")
     ap.add_argument("--only", type=int, default=0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--top_k", default="")
+    ap.add_argument("--top_p", default="")
     a = ap.parse_args()
     from densecap_amd import DenseCapModel, _lib
     from densecap_amd.weights import make_synthetic_image, make_synthetic_weights
@@ -68,6 +74,38 @@ def main():
             _lib.check(m.ctx.h, m.lib.dc_op_lm_score(m.ctx.h, codes_d.ptr, K, qd.ptr, S, T, out.ptr), "dc_op_lm_score")
         return sample, score, opts
 
+    def trunc_op(S, top_k, top_p):
+        opts = _lib.DcSampleOpts(S, 1.0, 1)
+        tr = _lib.DcSampleTrunc(top_k, top_p)
+        tok = m.ctx.empty((K, S, T), np.int32); lp = m.ctx.empty((K, S)); lq = m.ctx.empty((K, S))
+
+        def sample():
+            _lib.check(m.ctx.h, m.lib.dc_op_lm_sample_n_trunc(m.ctx.h, codes_d.ptr, K, None, C.byref(opts), C.byref(tr), tok.ptr,
+                                                              lp.ptr, lq.ptr), "dc_op_lm_sample_n_trunc")
+        return sample
+
+    if a.top_k or a.top_p:
+        ks = [V + 1 if int(x) < 0 else int(x) for x in (a.top_k or "0").split(",")]
+        ps = [float(x) for x in (a.top_p or "1").split(",")]
+        if len(ks) != len(ps):
+            raise SystemExit("--top_k and --top_p take the same number of values")
+        if a.only:
+            fused, _, _ = ops_for(a.only)
+            emit(dict(what="trunc_trace", S=a.only, K=K, rows=K * a.only, top_k=ks[0], top_p=ps[0],
+                      op_lm_sample_n_trunc_ms=timed(trunc_op(a.only, ks[0], ps[0]), 3), op_lm_sample_n_ms=timed(fused, 3)))
+        else:
+            for S in [int(x) for x in a.samples.split(",")]:
+                fused, _, _ = ops_for(S)
+                f_ms = timed(fused)
+                for k, p in zip(ks, ps):
+                    t_ms = timed(trunc_op(S, k, p))
+                    emit(dict(what="sample_trunc", S=S, K=K, rows=K * S, V1=V + 1, temperature=1.0, top_k=k, top_p=p,
+                              op_lm_sample_n_trunc_ms=t_ms, op_lm_sample_n_ms=f_ms, trunc_over_fused=t_ms / f_ms))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(json.dumps(x) for x in lines) + "\n")
+        m.ctx.close()
+        return
     if a.only:
         sample, score, _ = ops_for(a.only)
         emit(dict(what="trace", S=a.only, K=K, rows=K * a.only, op_lm_sample_n_ms=timed(sample, 3), op_lm_score_ms=timed(score, 3)))
