@@ -57,6 +57,16 @@ class DcBeamState(C.Structure):
                 ("parent", C.c_void_p), ("fin", C.c_void_p)]
 
 
+class DcBeamOpts(C.Structure):
+    """dc_beam_opts: the standard beam search of dc_beam_captions / dc_op_lm_beam_n."""
+    _fields_ = [("beam_size", C.c_int32), ("n_best", C.c_int32), ("length_alpha", C.c_float)]
+
+
+class DcBeamStdState(C.Structure):
+    """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
+    _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -158,12 +168,25 @@ _SIGS = {
                                            C.POINTER(DcSampleTrunc), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p]),
     "dc_op_lm_sample_n_trunc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DcSampleOpts),
                                           C.POINTER(DcSampleTrunc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_beam_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcBeamOpts), C.POINTER(DcResult),
+                                   C.c_void_p, C.c_void_p]),
+    "dc_op_lm_beam_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(DcBeamOpts), C.c_void_p, C.c_void_p]),
 }
 # the hook of include/densecap_debug_sample.h (bound like the others; the two lists above mirror densecap.h / densecap_debug.h)
 _SAMPLE_HOOK_SIGS = {
     "dc_debug_sample_trunc_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint64,
                                              C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+}
+# the hooks of include/densecap_debug_beam.h (the standard beam search; bound like the others)
+_BEAM_STD_HOOK_SIGS = {
+    "dc_debug_beam_std_merge": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 6),
+    "dc_debug_beam_std_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_float, C.c_void_p, C.c_void_p]),
+    "dc_debug_beam_std_start": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DcBeamStdState), C.c_void_p,
+                                          C.c_void_p]),
+    "dc_debug_beam_std_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcBeamStdState),
+                                         C.POINTER(DcBeamStdState), C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -179,7 +202,7 @@ def lib():
                 "libdensecap_hip.so not built at %s -- run `make -C densecap_amd/csrc` "
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

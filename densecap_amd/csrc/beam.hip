@@ -184,6 +184,139 @@ __global__ void beam_best_kernel(const int32_t* __restrict__ beams, int nprop, i
   seq[(size_t)p * T + u] = beams[((size_t)p * beam) * T + u];
 }
 
+// ---- the standard search (docs/SEMANTICS.md, "Standard beam search") ----------------------------------------------------------
+// The same lists and the same state re-indexing as above; what differs is the bookkeeping between them.  A finished hypothesis is
+// set aside: it stays in the selection as ONE candidate with its score unchanged, so it neither floods the beam with copies of
+// itself nor loses its place to a worse live one.  Rows hold 0 where there is no word (the sampler's row format), and every
+// hypothesis carries the number of words it holds for the length penalty of the final ranking.
+
+// First expansion: beam_init_kernel plus len; columns 1..T-1 hold 0.
+__global__ void beam_std_init_kernel(const float* __restrict__ top_lp, const int32_t* __restrict__ top_idx, int nprop, int beam,
+                                     int T, int END, float* __restrict__ beam_lp, int32_t* __restrict__ beams,
+                                     int32_t* __restrict__ len, int32_t* __restrict__ parent, int32_t* __restrict__ cur_tok,
+                                     uint8_t* __restrict__ finished) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;        // (proposal, hypothesis)
+  if (i >= nprop * beam) return;
+  const int w0 = top_idx[i];
+  const bool none = w0 < 1 || w0 > END;
+  const int w = none ? 0 : w0;
+  beam_lp[i] = top_lp[i];
+  int32_t* row = beams + (size_t)i * T;
+  row[0] = w;
+  for (int t = 1; t < T; ++t) row[t] = 0;
+  len[i] = none ? 0 : 1;
+  parent[i] = 0;
+  cur_tok[i] = none ? kFeedWord : w;
+  finished[i] = (none || w == END) ? 1 : 0;
+}
+
+// One workgroup per proposal.  Candidates: (b, j) with top_lp[b][j] + lp[b] under a live parent b; (b, 0) alone, with lp[b] itself
+// (the same bits), under a finished one -- its (b, j > 0) are not candidates at all (`live` below, not a sentinel sum).  The best
+// `beam` of them, lower flat index first among equal sums; a rank without a candidate keeps its own row, with no word, NaN and
+// finished.  fin_in is staged in LDS before anything is written, so fin_in and fin_out may be the same buffer.
+__global__ __launch_bounds__(256) void beam_std_merge_kernel(const float* __restrict__ top_lp,
+                                                             const int32_t* __restrict__ top_idx,
+                                                             const float* __restrict__ beam_lp_in,
+                                                             const int32_t* __restrict__ beams_in,
+                                                             const int32_t* __restrict__ len_in, const uint8_t* fin_in, int beam,
+                                                             int T, int t, int END, float* __restrict__ beam_lp_out,
+                                                             int32_t* __restrict__ beams_out, int32_t* __restrict__ len_out,
+                                                             int32_t* __restrict__ parent, int32_t* __restrict__ cur_tok,
+                                                             uint8_t* fin_out) {
+  __shared__ float cand[1024];
+  __shared__ uint8_t live[1024];          // the candidate exists and has not been picked
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ int pick[32];
+  __shared__ uint8_t pfin[32];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nc = beam * beam;
+  if (tid < beam) pfin[tid] = fin_in[(size_t)p * beam + tid] ? 1 : 0;
+  __syncthreads();
+  for (int j = tid; j < nc; j += 256) {
+    const int b = j / beam;
+    const float lp = beam_lp_in[(size_t)p * beam + b];
+    if (pfin[b]) {
+      cand[j] = lp;
+      live[j] = j == b * beam ? 1 : 0;
+    } else {
+      cand[j] = top_lp[(size_t)p * nc + j] + lp;
+      live[j] = 1;
+    }
+  }
+  __syncthreads();
+  for (int q = 0; q < beam; ++q) {
+    float bv = 0.f;
+    int bi = -1;
+    for (int j = tid; j < nc; j += 256) arg_better(bv, bi, cand[j], live[j] ? j : -1);
+    block_argmax(bv, bi, sv, si);
+    if (tid == 0) {
+      const bool none = bi < 0 || bi >= nc;
+      pick[q] = none ? -1 : bi;
+      if (!none) live[bi] = 0;
+    }
+    __syncthreads();
+  }
+  for (int q = tid; q < beam; q += 256) {
+    const int pk = pick[q];
+    const bool picked = pk >= 0 && pk < nc;
+    const int b = picked ? pk / beam : q;
+    const bool set_aside = !picked || pfin[b];                 // no word is added: the parent is finished, or nothing was selected
+    const int w0 = set_aside ? 0 : top_idx[(size_t)p * nc + pk];
+    const bool none = w0 < 1 || w0 > END;
+    const int w = none ? 0 : w0;
+    const int32_t* src = beams_in + ((size_t)p * beam + b) * T;
+    int32_t* dst = beams_out + ((size_t)p * beam + q) * T;
+    for (int u = 0; u < T; ++u) dst[u] = u == t ? w : src[u];
+    const size_t o = (size_t)p * beam + q;
+    beam_lp_out[o] = picked ? cand[pk] : NAN;
+    len_out[o] = len_in[(size_t)p * beam + b] + (none ? 0 : 1);
+    parent[o] = b;
+    cur_tok[o] = none ? kFeedWord : w;
+    fin_out[o] = (none || w == END) ? 1 : 0;                   // none covers the finished parent
+  }
+}
+
+// Final ranking, one wavefront per proposal: lane b holds the score of hypothesis b, lp / pen[len] (one fp32 division; the table
+// comes from the host).  has_pen == 0: no division and no re-ranking, rank = b.  A lane's rank is the number of lanes that come
+// before it: a higher score, or an equal one at a lower lane; NaN after every number, among themselves in lane order.  Ranks below
+// n_best write their row and the UNNORMALISED lp; a NaN lp writes a row of zeros.
+__global__ __launch_bounds__(256) void beam_std_finish_kernel(const float* __restrict__ beam_lp,
+                                                              const int32_t* __restrict__ beams,
+                                                              const int32_t* __restrict__ len, const float* __restrict__ pen,
+                                                              int has_pen, int nprop, int beam, int T, int n_best,
+                                                              int32_t* __restrict__ captions, float* __restrict__ logprob) {
+  const int lane = threadIdx.x & 63;
+  const int p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // uniform over the wavefront
+  if (p >= nprop) return;
+  const bool mine = lane < beam;
+  const size_t i = (size_t)p * beam + (mine ? lane : 0);
+  const float lp = beam_lp[i];
+  float sc = lp;
+  if (has_pen) {
+    int l = len[i];
+    l = l < 0 ? 0 : (l > T ? T : l);
+    sc = lp / pen[l];
+  }
+  int rank = lane;
+  if (has_pen) {
+    rank = 0;
+    const bool nan_me = sc != sc;
+    for (int o = 0; o < beam; ++o) {
+      const float so = __shfl(sc, o, 64);
+      const bool nan_o = so != so;
+      const bool before = nan_o ? (nan_me && o < lane) : (nan_me || so > sc || (so == sc && o < lane));
+      rank += before ? 1 : 0;
+    }
+  }
+  if (!mine || rank >= n_best) return;
+  const int32_t* src = beams + i * T;
+  int32_t* dst = captions + ((size_t)p * n_best + rank) * T;
+  const bool nan_lp = lp != lp;
+  for (int u = 0; u < T; ++u) dst[u] = nan_lp ? 0 : src[u];
+  logprob[(size_t)p * n_best + rank] = lp;
+}
+
 }  // namespace
 
 // The top-k kernel keeps one vocabulary row in dynamic LDS: V+1 floats must fit what the CURRENT device grants a
@@ -238,5 +371,32 @@ hipError_t launch_beam_gather_state(const float* h_in, const float* c_in, const 
 hipError_t launch_beam_best(const int32_t* beams, int nprop, int beam, int T, int32_t* seq, hipStream_t s) {
   const int n = nprop * T;
   hipLaunchKernelGGL(beam_best_kernel, dim3((n + 255) / 256), dim3(256), 0, s, beams, nprop, beam, T, seq);
+  return hipGetLastError();
+}
+hipError_t launch_beam_std_init(const float* top_lp, const int32_t* top_idx, int nprop, int beam, int T, int END, float* beam_lp,
+                                int32_t* beams, int32_t* len, int32_t* parent, int32_t* cur_tok, uint8_t* finished,
+                                hipStream_t s) {
+  const int n = nprop * beam;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(beam_std_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, top_lp, top_idx, nprop, beam, T, END, beam_lp,
+                     beams, len, parent, cur_tok, finished);
+  return hipGetLastError();
+}
+hipError_t launch_beam_std_merge(const float* top_lp, const int32_t* top_idx, const float* beam_lp_in, const int32_t* beams_in,
+                                 const int32_t* len_in, const uint8_t* fin_in, int nprop, int beam, int T, int t, int END,
+                                 float* beam_lp_out, int32_t* beams_out, int32_t* len_out, int32_t* parent, int32_t* cur_tok,
+                                 uint8_t* fin_out, hipStream_t s) {
+  if (beam < 1 || beam > 32 || T < 1 || t < 0 || t >= T) return hipErrorInvalidValue;
+  if (nprop <= 0) return hipSuccess;
+  hipLaunchKernelGGL(beam_std_merge_kernel, dim3(nprop), dim3(256), 0, s, top_lp, top_idx, beam_lp_in, beams_in, len_in, fin_in,
+                     beam, T, t, END, beam_lp_out, beams_out, len_out, parent, cur_tok, fin_out);
+  return hipGetLastError();
+}
+hipError_t launch_beam_std_finish(const float* beam_lp, const int32_t* beams, const int32_t* len, const float* pen, int has_pen,
+                                  int nprop, int beam, int T, int n_best, int32_t* captions, float* logprob, hipStream_t s) {
+  if (beam < 1 || beam > 32 || n_best < 1 || n_best > beam || T < 1 || (has_pen && pen == nullptr)) return hipErrorInvalidValue;
+  if (nprop <= 0) return hipSuccess;
+  hipLaunchKernelGGL(beam_std_finish_kernel, dim3((nprop + 3) / 4), dim3(256), 0, s, beam_lp, beams, len, pen, has_pen, nprop,
+                     beam, T, n_best, captions, logprob);
   return hipGetLastError();
 }

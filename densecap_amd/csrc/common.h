@@ -9,6 +9,7 @@
 #include "../../include/densecap.h"
 #include "../../include/densecap_debug.h"
 #include "../../include/densecap_debug_sample.h"
+#include "../../include/densecap_debug_beam.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -369,6 +370,16 @@ hipError_t launch_beam_merge(const float* top_lp, const int32_t* top_idx, const 
 hipError_t launch_beam_gather_state(const float* h_in, const float* c_in, const int32_t* parent, int rows, int beam,
                                     int src_per_prop, int Hd, float* h_out, float* c_out, hipStream_t s);
 hipError_t launch_beam_best(const int32_t* beams, int nprop, int beam, int T, int32_t* seq, hipStream_t s);
+// the standard search (docs/SEMANTICS.md, "Standard beam search"): first expansion, merge, final ranking
+hipError_t launch_beam_std_init(const float* top_lp, const int32_t* top_idx, int nprop, int beam, int T, int END, float* beam_lp,
+                                int32_t* beams, int32_t* len, int32_t* parent, int32_t* cur_tok, uint8_t* finished,
+                                hipStream_t s);
+hipError_t launch_beam_std_merge(const float* top_lp, const int32_t* top_idx, const float* beam_lp_in, const int32_t* beams_in,
+                                 const int32_t* len_in, const uint8_t* fin_in, int nprop, int beam, int T, int t, int END,
+                                 float* beam_lp_out, int32_t* beams_out, int32_t* len_out, int32_t* parent, int32_t* cur_tok,
+                                 uint8_t* fin_out, hipStream_t s);
+hipError_t launch_beam_std_finish(const float* beam_lp, const int32_t* beams, const int32_t* len, const float* pen, int has_pen,
+                                  int nprop, int beam, int T, int n_best, int32_t* captions, float* logprob, hipStream_t s);
 
 // ---- box pipeline (boxes.hip) ------------------------------------------------------
 hipError_t launch_make_anchors(float* out, int h, int w, float x0, float y0, float sx, float sy,

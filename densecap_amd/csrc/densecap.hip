@@ -146,6 +146,11 @@ struct Lane {
   float *bm_logits = nullptr, *bm_top_lp = nullptr, *bm_lp[2] = {nullptr, nullptr};
   int32_t *bm_top_idx = nullptr, *bm_beams[2] = {nullptr, nullptr}, *bm_parent = nullptr, *bm_tok = nullptr;
   uint8_t* bm_fin = nullptr;
+  // what the standard search (dc_beam_captions) adds to it, in an allocation of its own: the carve above stays the other search's
+  void* bs_base = nullptr;
+  int bs_rows = 0, bs_T = 0;
+  int32_t* bs_len[2] = {nullptr, nullptr};
+  float* bs_pen = nullptr;
   hipStream_t aux = nullptr;            // single-image mode: second half of the decode rows runs here
   hipStream_t aux2 = nullptr;           // single-image mode: the final NMS runs here, beside the decode
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork2 = nullptr, ev_join2 = nullptr;
@@ -458,6 +463,7 @@ int lane_streams(dc_ctx* ctx, Lane& L) {
 void lane_release(Lane& L) {
   if (L.arena.p) (void)hipFree(L.arena.p);
   if (L.beam_base) (void)hipFree(L.beam_base);
+  if (L.bs_base) (void)hipFree(L.bs_base);
   if (L.gexec) (void)hipGraphExecDestroy(L.gexec);
   if (L.host_stage) (void)hipHostFree(L.host_stage);
   for (auto& ev : L.ev) if (ev) (void)hipEventDestroy(ev);
@@ -2521,6 +2527,135 @@ int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_
   return sample_captions(ctx, img_chw, H, W, img_on_device, opts, nullptr, out, samples, logprob, nullptr, "dc_sample_captions");
 }
 
+// ---- standard beam search (docs/SEMANTICS.md, "Standard beam search") ---------------------------------------------
+// The dense steps and the lists are the reference-rule search's (beam_lstm_step, the full-logits projection, the top-k kernel with
+// its finished mask, the state gather); the bookkeeping between them is beam_std_init / beam_std_merge, and beam_std_finish ranks
+// at the end.  It runs on the same scratch (beam_prepare at ITS width: BeamWidthGuard) plus bs_len / bs_pen, in fp32, eagerly.
+struct BeamWidthGuard {   // cfg.beam_size = the call's width while one lives: beam_chunk / beam_prepare / beam_lstm_step read it
+  Settings& c; int saved;
+  BeamWidthGuard(Settings& cfg, int beam) : c(cfg), saved(cfg.beam_size) { c.beam_size = beam; }
+  ~BeamWidthGuard() { c.beam_size = saved; }
+};
+static int check_beam_opts(dc_ctx* ctx, const dc_beam_opts* o, const char* who) {
+  if (!o) return ctx->fail(DC_E_INVALID, "%s: null options", who);
+  if (o->beam_size < 1 || o->beam_size > 32 || o->beam_size > ctx->V + 1)
+    return ctx->fail(DC_E_INVALID, "%s: beam_size must be in 1..32 and at most the %d output words (got %d)", who, ctx->V + 1,
+                     (int)o->beam_size);
+  if (o->n_best < 1 || o->n_best > o->beam_size)
+    return ctx->fail(DC_E_INVALID, "%s: n_best must be in 1..beam_size = %d (got %d)", who, (int)o->beam_size, (int)o->n_best);
+  if (!(o->length_alpha >= 0.f && o->length_alpha <= 2.f))        // NaN fails
+    return ctx->fail(DC_E_INVALID, "%s: length_alpha must be in [0, 2] (got %g)", who, (double)o->length_alpha);
+  return check_beam_fits(ctx, o->beam_size);
+}
+// pen[l] = (float)pow(l, alpha) for l = 0..T (pen[0] = 1: a hypothesis without a word has a NaN score already)
+static std::vector<float> beam_std_pen(int T, float alpha) {
+  std::vector<float> pen((size_t)T + 1, 1.f);
+  for (int l = 1; l <= T; ++l) pen[l] = (float)pow((double)l, (double)alpha);
+  return pen;
+}
+static int beam_std_prepare(dc_ctx* ctx, Lane& L, int chunk) {
+  DCCHK(beam_prepare(ctx, L, chunk));
+  const int rows = chunk * ctx->cfg.beam_size, T = ctx->T;
+  if (L.bs_base && L.bs_rows >= rows && L.bs_T >= T) return DC_OK;
+  if (L.bs_base) { HIPCHK(hipStreamSynchronize(L.stream)); HIPCHK(hipFree(L.bs_base)); L.bs_base = nullptr; }
+  L.bs_rows = L.bs_T = 0;
+  const std::vector<Carve> cv = {{(void**)&L.bs_len[0], (size_t)rows * 4}, {(void**)&L.bs_len[1], (size_t)rows * 4},
+                                 {(void**)&L.bs_pen, ((size_t)T + 1) * 4}};
+  HIPCHK(hipMalloc(&L.bs_base, carve(cv, nullptr)));
+  carve(cv, L.bs_base);
+  L.bs_rows = rows; L.bs_T = T;
+  return DC_OK;
+}
+// Everything before the t loop for the c proposals of one chunk: lm_start_state (h AND c of the START step), the first lists,
+// the first expansion; every hypothesis of a proposal starts from the proposal's (h, c).  Leaves what iteration t = 1 reads.
+static int beam_std_start(dc_ctx* ctx, Lane& L, const float* codes, int c, hipStream_t s) {
+  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T;
+  DCCHK(lm_start_state(ctx, s, codes, c, L.bm_enc, L.bm_gates, L.bm_c[0], L.bm_h[0], 0, nullptr, Ws()));
+  DCCHK(linear(ctx, s, L.bm_h[0], ctx->out_w, ctx->out_b, L.bm_logits, c, V1, Hd, 0));
+  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, c, V1, V1, nullptr, beam, L.bm_top_lp, L.bm_top_idx, s));
+  KCHK(launch_beam_std_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bs_len[0], L.bm_parent,
+                            L.bm_tok, L.bm_fin, s));
+  KCHK(launch_beam_gather_state(L.bm_h[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1], L.bm_c[1], s));
+  return DC_OK;
+}
+// Iteration t on the c x beam rows of one chunk; the ping-pong sets are beam_iter's (len rides with lp and the rows)
+static int beam_std_iter(dc_ctx* ctx, Lane& L, int c, int t, hipStream_t s) {
+  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, rows = c * beam;
+  const int cur = beam_state_set(t), bcur = beam_beams_set(t);
+  DCCHK(beam_lstm_step(ctx, L, L.bm_h[cur], L.bm_c[cur], rows, s));
+  DCCHK(linear(ctx, s, L.bm_h[cur], ctx->out_w, ctx->out_b, L.bm_logits, rows, V1, Hd, 0));
+  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, rows, V1, V1, L.bm_fin, beam, L.bm_top_lp, L.bm_top_idx, s));
+  KCHK(launch_beam_std_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], L.bs_len[bcur], L.bm_fin, c, beam, T, t,
+                             V1, L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bs_len[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
+  KCHK(launch_beam_gather_state(L.bm_h[cur], L.bm_c[cur], L.bm_parent, rows, beam, beam, Hd, L.bm_h[cur ^ 1],
+                                L.bm_c[cur ^ 1], s));
+  return DC_OK;
+}
+// The whole search on n code rows; captions (n, n_best, T) and logprob (n, n_best) are DEVICE buffers.  Only enqueues; `pen` (the
+// host table) must live until the caller has synchronised.
+static int lm_beam_std(dc_ctx* ctx, Lane& L, hipStream_t s, const float* codes, int n, const dc_beam_opts& o,
+                       const std::vector<float>& pen, int32_t* captions, float* logprob) {
+  Fp32Guard fp32(ctx->cfg);
+  BeamWidthGuard width(ctx->cfg, o.beam_size);
+  const int chunk = beam_chunk(ctx, n);
+  DCCHK(beam_std_prepare(ctx, L, chunk));
+  const int beam = o.beam_size, T = ctx->T, D = ctx->D, N = o.n_best;
+  const int has_pen = o.length_alpha != 0.f;
+  if (has_pen) HIPCHK(hipMemcpyAsync(L.bs_pen, pen.data(), pen.size() * 4, hipMemcpyHostToDevice, s));
+  for (int p0 = 0; p0 < n; p0 += chunk) {
+    const int c = std::min(chunk, n - p0);
+    DCCHK(beam_std_start(ctx, L, codes + (size_t)p0 * D, c, s));
+    for (int t = 1; t < T; ++t) DCCHK(beam_std_iter(ctx, L, c, t, s));
+    const int bs = beam_beams_set(T);
+    KCHK(launch_beam_std_finish(L.bm_lp[bs], L.bm_beams[bs], L.bs_len[bs], L.bs_pen, has_pen, c, beam, T, N,
+                                captions + (size_t)p0 * N * T, logprob + (size_t)p0 * N, s));
+  }
+  return DC_OK;
+}
+int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* opts, int32_t* captions, float* logprob) {
+  OP_PROLOGUE();
+  const char* who = "dc_op_lm_beam_n";
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!codes || !captions || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n <= 0) return ctx->fail(DC_E_INVALID, "%s: n must be > 0", who);
+  DCCHK(check_beam_opts(ctx, opts, who));
+  const std::vector<float> pen = beam_std_pen(ctx->T, opts->length_alpha);
+  const int rc = lm_beam_std(ctx, lane0(ctx), s, codes, n, *opts, pen, captions, logprob);
+  const hipError_t e = hipStreamSynchronize(s);        // also after a failure part-way: `pen` may still be in flight
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s sync: %s", who, hipGetErrorString(e));
+  return DC_OK;
+}
+int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_beam_opts* opts, dc_result* out,
+                     int32_t* captions, float* logprob) {
+  if (!ctx) return DC_E_INVALID;
+  const char* who = "dc_beam_captions";
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!img_chw || !out || !captions || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_beam_opts(ctx, opts, who));
+  int K = 0;
+  DCCHK(forward_kept_codes(ctx, img_chw, H, W, img_on_device, out, who, &K));
+  if (K == 0) return DC_OK;
+  Lane& L = lane0(ctx);
+  const size_t N = (size_t)opts->n_best, T = (size_t)ctx->T;
+  int32_t* cap_d = nullptr; float* lp_d = nullptr;
+  const std::vector<Carve> cv = {{(void**)&cap_d, (size_t)K * N * T * 4}, {(void**)&lp_d, (size_t)K * N * 4}};
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+  carve(cv, base);
+  const std::vector<float> pen = beam_std_pen(ctx->T, opts->length_alpha);
+  const int rc = lm_beam_std(ctx, L, L.stream, L.out_feats, K, *opts, pen, cap_d, lp_d);
+  hipError_t e = hipStreamSynchronize(L.stream);
+  if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(captions, cap_d, (size_t)K * N * T * 4, hipMemcpyDeviceToHost);
+  if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(logprob, lp_d, (size_t)K * N * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return DC_OK;
+}
+
 // ---- the truncated sampler's test hook (densecap_debug_sample.h) ----------------------------------------------------------------
 int dc_debug_sample_trunc_rows(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const int32_t* keys, int t,
                                uint64_t seed, float temperature, int top_k, float top_p, int32_t* tok_out, int32_t* kept_out,
@@ -2625,6 +2760,99 @@ int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state
   DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *state_in, false, s));
   DCCHK(beam_iter(ctx, L, nprop, t, s));
   DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
+  DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
+  OP_EPILOGUE();
+}
+
+// ---- standard beam search test hooks (densecap_debug_beam.h) ---------------------------------------------------------------------
+int dc_debug_beam_std_merge(dc_ctx* ctx, const float* top_lp, const int32_t* top_idx, const float* beam_lp_in,
+                            const int32_t* beams_in, const int32_t* len_in, const uint8_t* fin_in, int nprop, int beam, int T, int t,
+                            int END, float* beam_lp_out, int32_t* beams_out, int32_t* len_out, int32_t* parent, int32_t* cur_tok,
+                            uint8_t* fin_out) {
+  OP_PROLOGUE();
+  if (!top_lp || !top_idx || !beam_lp_in || !beams_in || !len_in || !fin_in || !beam_lp_out || !beams_out || !len_out || !parent ||
+      !cur_tok || !fin_out || nprop < 1 || beam < 1 || beam > 32 || T < 1 || t < 0 || t >= T || END < 1)
+    return ctx->fail(DC_E_INVALID, "dc_debug_beam_std_merge: bad argument");
+  KCHK(launch_beam_std_merge(top_lp, top_idx, beam_lp_in, beams_in, len_in, fin_in, nprop, beam, T, t, END, beam_lp_out, beams_out,
+                             len_out, parent, cur_tok, fin_out, s));
+  OP_EPILOGUE();
+}
+int dc_debug_beam_std_finish(dc_ctx* ctx, const float* beam_lp, const int32_t* beams, const int32_t* len, int nprop, int beam, int T,
+                             int n_best, float length_alpha, int32_t* captions, float* logprob) {
+  OP_PROLOGUE();
+  if (!beam_lp || !beams || !len || !captions || !logprob || nprop < 1 || beam < 1 || beam > 32 || T < 1 || n_best < 1 ||
+      n_best > beam || !(length_alpha >= 0.f && length_alpha <= 2.f))
+    return ctx->fail(DC_E_INVALID, "dc_debug_beam_std_finish: bad argument");
+  const std::vector<float> pen = beam_std_pen(T, length_alpha);
+  float* pen_d = nullptr;
+  HIPCHK(hipMalloc((void**)&pen_d, pen.size() * 4));
+  hipError_t e = hipMemcpy(pen_d, pen.data(), pen.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = launch_beam_std_finish(beam_lp, beams, len, pen_d, length_alpha != 0.f, nprop, beam, T, n_best, captions, logprob, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)hipFree(pen_d);
+  prof_collect(ctx);
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_beam_std_finish: %s", hipGetErrorString(e));
+  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_beam_std_finish sync: %s", hipGetErrorString(e2));
+  return DC_OK;
+}
+// what the two state hooks check first (the caller holds a BeamWidthGuard); on DC_OK the lane's scratch holds nprop proposals
+static int beam_std_hook_prepare(dc_ctx* ctx, int nprop, int beam, const dc_beam_std_state* st, const char* who) {
+  if (!st || !st->h || !st->c || !st->beam_lp || !st->beams || !st->tok || !st->parent || !st->fin || !st->len)
+    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (nprop < 1 || beam_chunk(ctx, nprop) < nprop)
+    return ctx->fail(DC_E_INVALID, "%s: %d proposals are not one chunk (the hook does not chunk)", who, nprop);
+  return beam_std_prepare(ctx, lane0(ctx), nprop);
+}
+static int beam_std_hook_copy(dc_ctx* ctx, Lane& L, int rows, int hs, int bs, const dc_beam_std_state& st, bool out, hipStream_t s) {
+  const dc_beam_state base = {st.h, st.c, st.beam_lp, st.beams, st.tok, st.parent, st.fin};
+  DCCHK(beam_hook_copy(ctx, L, rows, hs, bs, base, out, s));
+  HIPCHK(hipMemcpyAsync(out ? (void*)st.len : (void*)L.bs_len[bs], out ? (void*)L.bs_len[bs] : (void*)st.len, (size_t)rows * 4,
+                        hipMemcpyDeviceToDevice, s));
+  return DC_OK;
+}
+static int beam_std_hook_opts(dc_ctx* ctx, int beam, const char* who) {
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  const dc_beam_opts o = {beam, 1, 0.f};
+  return check_beam_opts(ctx, &o, who);
+}
+int dc_debug_beam_std_start(dc_ctx* ctx, const float* codes, int nprop, int beam, const dc_beam_std_state* state_out, float* top_lp,
+                            int32_t* top_idx) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_beam_std_start";
+  if (!codes || !top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(beam_std_hook_opts(ctx, beam, who));
+  Fp32Guard fp32(ctx->cfg);
+  BeamWidthGuard width(ctx->cfg, beam);
+  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_out, who));
+  Lane& L = lane0(ctx);
+  DCCHK(beam_std_start(ctx, L, codes, nprop, s));
+  DCCHK(beam_std_hook_copy(ctx, L, nprop * beam, beam_state_set(1), beam_beams_set(1), *state_out, true, s));
+  DCCHK(beam_hook_lists(ctx, L, (size_t)nprop * beam, top_lp, top_idx, s));
+  OP_EPILOGUE();
+}
+int dc_debug_beam_std_step(dc_ctx* ctx, int nprop, int beam, int t, const dc_beam_std_state* state_in,
+                           const dc_beam_std_state* state_out, float* top_lp, int32_t* top_idx) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_beam_std_step";
+  if (!top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(beam_std_hook_opts(ctx, beam, who));
+  Fp32Guard fp32(ctx->cfg);
+  BeamWidthGuard width(ctx->cfg, beam);
+  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_in, who));
+  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_out, who));
+  if (t < 1 || t >= ctx->T) return ctx->fail(DC_E_INVALID, "%s: t = %d is not in [1, %d)", who, t, ctx->T);
+  Lane& L = lane0(ctx);
+  const int rows = nprop * beam;
+  // the word of a row selects an xg row by address in the step GEMM: the caller's are checked here, as the kernels check their own
+  std::vector<int32_t> tok(rows);
+  HIPCHK(hipMemcpy(tok.data(), state_in->tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < rows; ++i)
+    if (tok[i] < 1 || tok[i] > ctx->V + 1)
+      return ctx->fail(DC_E_INVALID, "%s: tok[%d] = %d is not a word id in [1, %d]", who, i, (int)tok[i], ctx->V + 1);
+  DCCHK(beam_std_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *state_in, false, s));
+  DCCHK(beam_std_iter(ctx, L, nprop, t, s));
+  DCCHK(beam_std_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
   DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
   OP_EPILOGUE();
 }

@@ -614,6 +614,37 @@ class DenseCapModel:
                logprob[:K].copy())
         return res + (slp[:K].copy(),) if want_sample_logprob else res
 
+    def beamCaptions(self, img, beam_size, n_best=None, length_alpha=0.0, want_tokens=True):
+        """The n_best best captions of the image's regions by standard beam search (dc_beam_captions; docs/SEMANTICS.md,
+        "Standard beam search"): the regions forward_test returns, each with its n_best (None = beam_size) best hypotheses of a
+        search of width beam_size -- finished hypotheses set aside, ranked by logprob / len^length_alpha -- and the model's
+        unnormalised log-probability of each.  Independent of setBeamSize.  Returns (boxes (K,4) xcycwh, scores (K,), tokens
+        (K,T) -- the greedy captions, or None without want_tokens --, captions (K,N,T) int32, logprob (K,N));
+        decodeSequence(captions[:, 0]) gives the best strings."""
+        from .ops import DeviceArray, check_beam_args
+        opts = check_beam_args(beam_size, n_best, length_alpha, vocab_size=self.vocab_size)
+        self._push_test_args()
+        on_device = isinstance(img, DeviceArray)       # a (3,H,W) float32 image already on the device (ops.preprocess_u8)
+        if on_device:
+            if img.dtype != np.float32 or len(img.shape) != 3 or img.shape[0] != 3:
+                raise ValueError("beamCaptions wants a (3,H,W) float32 device image")
+            ptr = img.ptr
+        else:
+            img = self._check_input(img)
+            ptr = img.ctypes.data
+        P = self._capacity(img.shape[1], img.shape[2])
+        r, boxes, scores, tokens = self._new_result(P)
+        if not want_tokens:
+            r.tokens = None
+        N = opts.n_best
+        captions = np.zeros((P, N, self.seq_length), np.int32)
+        logprob = np.zeros((P, N), np.float32)
+        check(self.ctx.h, self.lib.dc_beam_captions(self.ctx.h, ptr, img.shape[1], img.shape[2], int(on_device), C.byref(opts),
+                                                    C.byref(r), captions.ctypes.data, logprob.ctypes.data), "dc_beam_captions")
+        K = r.K
+        return (boxes[:K].copy(), scores[:K].copy(), tokens[:K].copy() if want_tokens else None, captions[:K].copy(),
+                logprob[:K].copy())
+
     def decodeSequence(self, seq):
         """LanguageModel:decodeSequence (LanguageModel.lua:86-103)."""
         return decode_sequence(seq, self.idx_to_token, self.vocab_size)

@@ -457,6 +457,125 @@ def beam_step(ctx, state, t):
     return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()
 
 
+# ---- standard beam search (dc_op_lm_beam_n; docs/SEMANTICS.md, "Standard beam search") ---------------------------------------
+def check_beam_args(beam_size, n_best=None, length_alpha=0.0, vocab_size=None):
+    """The DcBeamOpts of a call; ValueError where dc_beam_opts' rules do not hold (what the library answers with DC_E_INVALID):
+    beam_size an integer in 1..32 (and <= V+1 when vocab_size is given), n_best None (= beam_size) or an integer in
+    1..beam_size, length_alpha in [0, 2]."""
+    def as_int(v):
+        try:
+            i = int(v)
+        except (TypeError, ValueError, OverflowError):
+            return None
+        return i if i == v else None
+    B = as_int(beam_size)
+    if B is None or not 1 <= B <= 32 or (vocab_size is not None and B > vocab_size + 1):
+        raise ValueError("beam_size must be an integer in 1..32, at most V+1 (got %r)" % (beam_size,))
+    N = B if n_best is None else as_int(n_best)
+    if N is None or not 1 <= N <= B:
+        raise ValueError("n_best must be an integer in 1..beam_size = %d (got %r)" % (B, n_best))
+    try:
+        a = float(np.float32(length_alpha))
+    except (TypeError, ValueError):
+        a = float("nan")
+    if not 0.0 <= a <= 2.0:                          # NaN fails
+        raise ValueError("length_alpha must be in [0, 2] (got %r)" % (length_alpha,))
+    return _lib.DcBeamOpts(B, N, a)
+
+
+def lm_beam_n(ctx, codes, beam_size, n_best=None, length_alpha=0.0, seq_length=None):
+    """The n_best best captions of every code row by the standard beam search of width beam_size (dc_op_lm_beam_n): finished
+    hypotheses are set aside, ranking by logprob / len^length_alpha.  codes (n, fc_dim).  Returns (captions (n, N, T) int32 --
+    word ids up to and including END, zeros after it, best first --, logprob (n, N) float32: the model's unnormalised
+    log-probability of the words written; NaN, with all-zero rows, for a row whose scores are NaN).  n_best None = beam_size.
+    seq_length: the loaded model's T; needed only when the weights were not loaded through DenseCapModel."""
+    opts = check_beam_args(beam_size, n_best, length_alpha)
+    x = _f32(codes)
+    if x.ndim != 2 or x.shape[0] < 1:
+        raise ValueError("codes must be (n, fc_dim) with n >= 1")
+    T = int(seq_length or getattr(ctx, "seq_length", 0) or 0)
+    if T < 1:
+        raise ValueError("lm_beam_n: pass seq_length= (the loaded model's T) for a ctx that DenseCapModel did not load")
+    n, N = x.shape[0], opts.n_best
+    xd = ctx.to_device(x)
+    cap = ctx.empty((n, N, T), np.int32); lp = ctx.empty((n, N), np.float32)
+    check(ctx.h, ctx.lib.dc_op_lm_beam_n(ctx.h, xd.ptr, n, C.byref(opts), cap.ptr, lp.ptr), "dc_op_lm_beam_n")
+    return cap.numpy(), lp.numpy()
+
+
+# ---- standard beam search test hooks (include/densecap_debug_beam.h) ----------------------------------------------------------
+BEAM_STD_STATE_FIELDS = BEAM_STATE_FIELDS + ("len",)
+BEAM_STD_MERGE_OUT = ("beam_lp", "beams", "len", "parent", "tok", "fin")
+
+
+def beam_std_merge(ctx, top_lp, top_idx, beam_lp, beams, length, fin, t, END):
+    """dc_debug_beam_std_merge: top_lp / top_idx (nprop, beam, beam), beam_lp, length, fin (nprop, beam), beams (nprop, beam, T),
+    0-based column t -> dict(beam_lp, beams, len, parent, tok, fin)."""
+    tl = _f32(top_lp); ti = np.ascontiguousarray(top_idx, dtype=np.int32)
+    bl = _f32(beam_lp); bm = np.ascontiguousarray(beams, dtype=np.int32)
+    ln = np.ascontiguousarray(length, dtype=np.int32); fn = np.ascontiguousarray(fin, dtype=np.uint8)
+    nprop, beam, T = bm.shape
+    assert tl.shape == ti.shape == (nprop, beam, beam) and bl.shape == ln.shape == fn.shape == (nprop, beam)
+    d = [ctx.to_device(a) for a in (tl, ti, bl, bm, ln, fn)]
+    o = dict(beam_lp=ctx.empty((nprop, beam), np.float32), beams=ctx.empty((nprop, beam, T), np.int32),
+             len=ctx.empty((nprop, beam), np.int32), parent=ctx.empty((nprop, beam), np.int32),
+             tok=ctx.empty((nprop, beam), np.int32), fin=ctx.empty((nprop, beam), np.uint8))
+    check(ctx.h, ctx.lib.dc_debug_beam_std_merge(ctx.h, *[a.ptr for a in d], nprop, beam, T, int(t), int(END),
+                                                 *[o[k].ptr for k in BEAM_STD_MERGE_OUT]), "dc_debug_beam_std_merge")
+    return {k: v.numpy() for k, v in o.items()}
+
+
+def beam_std_finish(ctx, beam_lp, beams, length, n_best, length_alpha):
+    """dc_debug_beam_std_finish: beam_lp, length (nprop, beam), beams (nprop, beam, T) -> (captions (nprop, n_best, T) int32,
+    logprob (nprop, n_best) float32)."""
+    bl = _f32(beam_lp); bm = np.ascontiguousarray(beams, dtype=np.int32); ln = np.ascontiguousarray(length, dtype=np.int32)
+    nprop, beam, T = bm.shape
+    assert bl.shape == ln.shape == (nprop, beam)
+    d = [ctx.to_device(a) for a in (bl, bm, ln)]
+    cap = ctx.to_device(np.full((nprop, n_best, T), -7, np.int32)); lp = ctx.to_device(np.full((nprop, n_best), 7.0, np.float32))
+    check(ctx.h, ctx.lib.dc_debug_beam_std_finish(ctx.h, d[0].ptr, d[1].ptr, d[2].ptr, nprop, beam, T, int(n_best),
+                                                  float(length_alpha), cap.ptr, lp.ptr), "dc_debug_beam_std_finish")
+    return cap.numpy(), lp.numpy()
+
+
+def _beam_std_state_buffers(ctx, nprop, beam, Hd, T):
+    bufs, _, shapes = _beam_state_buffers(ctx, nprop, beam, Hd, T)
+    shapes["len"] = ((nprop, beam), np.int32)
+    bufs["len"] = ctx.empty(*shapes["len"])
+    return bufs, _lib.DcBeamStdState(*[bufs[k].ptr for k in BEAM_STD_STATE_FIELDS]), shapes
+
+
+def beam_std_start(ctx, codes, beam, rnn_size, seq_length):
+    """dc_debug_beam_std_start at width `beam`: codes (nprop, fc_dim) -> (state dict of BEAM_STD_STATE_FIELDS, nprop x beam
+    rows; top_lp, top_idx (nprop, beam) of the first step)."""
+    x = _f32(codes)
+    nprop = x.shape[0]
+    xd = ctx.to_device(x)
+    bufs, st, _ = _beam_std_state_buffers(ctx, nprop, beam, rnn_size, seq_length)
+    lp = ctx.empty((nprop, beam), np.float32); idx = ctx.empty((nprop, beam), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_beam_std_start(ctx.h, xd.ptr, nprop, int(beam), C.byref(st), lp.ptr, idx.ptr),
+          "dc_debug_beam_std_start")
+    return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()
+
+
+def beam_std_step(ctx, state, t):
+    """dc_debug_beam_std_step: iteration t (1 <= t < T) from `state` (a dict as beam_std_start returns it; `parent` may be
+    missing) -> (new state, top_lp, top_idx (nprop, beam, beam): the lists of the step)."""
+    nprop, beam, Hd = np.shape(state["h"])
+    T = np.shape(state["beams"])[2]
+    bufs_in, st_in, shapes = _beam_std_state_buffers(ctx, nprop, beam, Hd, T)
+    for k in BEAM_STD_STATE_FIELDS:
+        if k in state:
+            a = np.ascontiguousarray(state[k], dtype=shapes[k][1])
+            assert a.shape == shapes[k][0], (k, a.shape)
+            check(ctx.h, ctx.lib.dc_memcpy_h2d(ctx.h, bufs_in[k].ptr, a.ctypes.data, a.nbytes), "dc_memcpy_h2d")
+    bufs, st, _ = _beam_std_state_buffers(ctx, nprop, beam, Hd, T)
+    lp = ctx.empty((nprop, beam, beam), np.float32); idx = ctx.empty((nprop, beam, beam), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_beam_std_step(ctx.h, nprop, beam, int(t), C.byref(st_in), C.byref(st), lp.ptr, idx.ptr),
+          "dc_debug_beam_std_step")
+    return {k: v.numpy() for k, v in bufs.items()}, lp.numpy(), idx.numpy()
+
+
 # ---- screened greedy decode test hooks (include/densecap_debug.h) ------------------------------------------------------------
 DEBUG_FILL = 0xA5            # the byte every output buffer of the two hooks below holds before the call
 

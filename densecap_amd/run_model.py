@@ -82,10 +82,18 @@ def build_parser():
       help="with -num_samples: nucleus truncation -- the smallest set of best-scoring words (among the top_k) whose probability "
            "reaches top_p (1 = off).  With either, results.json also carries `sampled_sample_logprobs`: every draw's "
            "log-probability under the truncated distribution it was drawn from")
+    a("-num_beams", type=int, default=0,
+      help="B > 0: every image also gets the -n_best best captions per region of a standard beam search of width B "
+           "(dc_beam_captions; finished hypotheses set aside) and their log-probabilities: `beam_captions` / `beam_logprobs` in "
+           "results.json; 0 (default): output as without the flag.  Not together with -num_samples or -input_boxes")
+    a("-n_best", type=int, default=0, help="with -num_beams: hypotheses kept per region, 1..B (0 = B)")
+    a("-length_alpha", type=float, default=0.0,
+      help="with -num_beams: rank the hypotheses by logprob / len^alpha, alpha in [0, 2] (0 = by log-probability)")
     return p
 
 
 SAMPLING_FLAGS = ("num_samples", "temperature", "sample_seed", "top_k", "top_p")
+BEAM_FLAGS = ("num_beams", "n_best", "length_alpha")
 
 
 def _scale_linear_axis(src, dst_len, axis):
@@ -407,6 +415,18 @@ class ImagePipeline:
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     from . import DenseCapModel, ops
+    if opt.num_beams:                      # before the weights are read: a refusal costs nothing
+        try:
+            ops.check_beam_args(opt.num_beams, opt.n_best or None, opt.length_alpha)
+        except ValueError as e:
+            raise SystemExit("-num_beams / -n_best / -length_alpha: %s" % e)
+        if opt.num_samples:
+            raise SystemExit("-num_beams with -num_samples: one run writes either the beam search's captions or the sampler's")
+        if opt.input_boxes:
+            raise SystemExit("-num_beams with -input_boxes: search on the boxes' codes instead (extract_features_boxes, then "
+                             "ops.lm_beam_n)")
+    elif opt.n_best or opt.length_alpha:
+        raise SystemExit("-n_best / -length_alpha belong to -num_beams")
     if opt.synthetic_weights:
         from .weights import make_synthetic_weights
         weights = make_synthetic_weights()
@@ -482,6 +502,10 @@ def main(argv=None):
                 rj["sampled_logprobs"] = [[float(v) for v in row] for row in logprob]
                 if truncated:
                     rj["sampled_sample_logprobs"] = [[float(v) for v in row] for row in out[5]]
+            if opt.num_beams:
+                beams, logprob = out[3], out[4]
+                rj["beam_captions"] = [model.decodeSequence(beams[k]) for k in range(len(beams))]
+                rj["beam_logprobs"] = [[float(v) for v in row] for row in logprob]
             results[i] = rj
 
     try:
@@ -495,6 +519,9 @@ def main(argv=None):
                                                  top_p=opt.top_p, want_sample_logprob=True) for i, d, _ in chunk]
                 else:
                     outs = [model.sampleCaptions(d, opt.num_samples, opt.temperature, opt.sample_seed + i) for i, d, _ in chunk]
+            elif opt.num_beams:
+                # image by image, as the sampler: dc_beam_captions runs the forward itself (lane 0), then the search
+                outs = [model.beamCaptions(d, opt.num_beams, opt.n_best or None, opt.length_alpha) for _, d, _ in chunk]
             elif in_boxes is None:
                 outs = model.forward_images_device([d for _, d, _ in chunk])
             else:
@@ -516,7 +543,9 @@ def main(argv=None):
     results = [r for r in results if r is not None]
     if results:
         # (without -num_samples the file is what it was before the flag existed: the sampling flags are left out of `opt`)
-        out = dict(results=results, opt={k: v for k, v in vars(opt).items() if opt.num_samples or k not in SAMPLING_FLAGS})
+        # (and without -num_beams, what it was before that flag existed)
+        out = dict(results=results, opt={k: v for k, v in vars(opt).items() if (opt.num_samples or k not in SAMPLING_FLAGS)
+                                         and (opt.num_beams or k not in BEAM_FLAGS)})
         with open(os.path.join(opt.output_vis_dir, "results.json"), "w") as f:
             json.dump(out, f)
     return 0

@@ -168,6 +168,22 @@ typedef struct dc_sample_trunc { int32_t top_k; float top_p; } dc_sample_trunc;
 int dc_sample_captions_trunc(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_sample_opts* opts,
                              const dc_sample_trunc* trunc_or_null, dc_result* out, int32_t* samples, float* logprob,
                              float* sample_logprob_or_null);
+/* Standard beam search (docs/SEMANTICS.md, "Standard beam search"): the N best captions of every region with the model's
+ * log-probability of each.  Unlike the reference-rule search of dc_set_beam_size -- which stays what it is -- a finished
+ * hypothesis is set aside (it competes as ONE candidate with its score unchanged, and adds no word), every hypothesis starts from
+ * the true (h, c) of the START step, and all n_best <= beam_size hypotheses leave the library, ranked by
+ * logprob / len^length_alpha (len = words written, END included; length_alpha 0 = by log-probability).
+ * beam_size in 1..32 and <= V+1, n_best in 1..beam_size, length_alpha in [0, 2]: anything else is DC_E_INVALID before any work;
+ * a vocabulary whose row does not fit the top-k kernel's LDS is DC_E_UNSUPPORTED.  Always fp32, never graph-replayed, and
+ * independent of dc_set_beam_size. */
+typedef struct dc_beam_opts { int32_t beam_size; int32_t n_best; float length_alpha; } dc_beam_opts;
+/* The forward of dc_forward_test (out as there; out->tokens == NULL skips the greedy decode), then the search on the K regions it
+ * returns, in its order.  captions: host (out->capacity, n_best, T) int32 -- word ids up to and including END, zeros after it,
+ * best first; logprob: host (out->capacity, n_best) -- the UNNORMALISED natural-log probability of the words written.  Rows
+ * from K on are not written.  K > out->capacity is refused.  A region whose scores are NaN (non-finite codes) has all-zero
+ * rows and NaN log-probabilities. */
+int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_beam_opts* opts, dc_result* out,
+                     int32_t* captions, float* logprob);
 /* run_model.lua:160-180 host loop over images, n images of identical size laid out
  * back to back; images are software-pipelined over the ctx's lanes (streams). */
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device,
@@ -412,6 +428,9 @@ int dc_op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row
 int dc_op_lm_sample_n_trunc(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
                             const dc_sample_trunc* trunc_or_null, int32_t* samples, float* logprob,
                             float* sample_logprob_or_null);
+/* The search of dc_beam_captions on given fc7 codes (n, fc_dim): captions (n, n_best, T), logprob (n, n_best).  Device pointers
+ * throughout (codes, captions, logprob); synchronous.  A row's result does not depend on the other rows. */
+int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* opts, int32_t* captions, float* logprob);
 
 #ifdef __cplusplus
 }

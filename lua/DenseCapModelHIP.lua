@@ -335,6 +335,42 @@ function Model:sampleCaptions(input, num_samples, temperature, seed, top_k, top_
          logprob[{{1, K}}]:clone(), truncated and slp[{{1, K}}]:clone() or nil
 end
 
+-- Standard beam search (dc_beam_captions; docs/SEMANTICS.md, "Standard beam search"): for each region forward_test returns, the
+-- n_best (nil = beam_size) best hypotheses of a search of width beam_size (1..32) in which finished hypotheses are set aside,
+-- ranked by logprob / len^length_alpha (nil or 0 = by log-probability).  Independent of language_model.beam_size.
+-- Returns boxes, scores, the greedy captions, captions: IntTensor (K, N, T) of word ids (up to and including END, zeros after
+-- it, best first; self:decodeSequence(captions[{{}, 1}]:long()) gives the best strings) and logprob (K, N), the model's
+-- unnormalised log-probability of each.
+function Model:beamCaptions(input, beam_size, n_best, length_alpha)
+  self:_push_test_args()
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local H, W, T = img:size(3), img:size(4), self.seq_length
+  local B = beam_size
+  assert(type(B) == 'number' and B >= 1 and B <= 32 and B == math.floor(B), 'beam_size must be an integer in 1..32')
+  local N = n_best or B
+  assert(type(N) == 'number' and N >= 1 and N <= B and N == math.floor(N), 'n_best must be an integer in 1..beam_size')
+  local P = self:_capacity(H, W)
+  local boxes, scores = torch.FloatTensor(P, 4), torch.FloatTensor(P, 1)
+  local tokens = torch.IntTensor(P, T)
+  local captions, logprob = torch.IntTensor(P, N, T):zero(), torch.FloatTensor(P, N):zero()
+  local o = ffi.new('dc_beam_opts')
+  o.beam_size, o.n_best, o.length_alpha = B, N, length_alpha or 0
+  local r = ffi.new('dc_result')
+  r.capacity = P
+  r.boxes, r.scores = torch.data(boxes), torch.data(scores)
+  r.tokens = torch.data(tokens)
+  hip.check(self.ctx, C.dc_beam_captions(self.ctx, fptr(img), H, W, 0, o, r, torch.data(captions), torch.data(logprob)),
+            'dc_beam_captions')
+  local K = r.K
+  if K == 0 then
+    return torch.FloatTensor(), torch.FloatTensor(), {}, torch.IntTensor(), torch.FloatTensor()
+  end
+  local seq = tokens[{{1, K}}]:long()
+  return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), captions[{{1, K}}]:clone(),
+         logprob[{{1, K}}]:clone()
+end
+
 -- The model after the RPN on the caller's boxes (dc_forward_boxes; DenseCapModel.lua:242-275 with `boxes` in the place of
 -- the localisation layer's roi_boxes).  boxes: FloatTensor (n, 4) xc,yc,w,h in the pixel frame of `input` (the frame
 -- forward_test returns), 1 <= n <= num_proposals; clip (optional): box_utils.clip_boxes first, invalid boxes dropped.

@@ -58,6 +58,10 @@ int dc_sample_captions_trunc(dc_ctx* ctx, const float* img_chw, int H, int W, in
 int dc_op_lm_sample_n_trunc(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
                             const dc_sample_trunc* trunc_or_null, int32_t* samples, float* logprob,
                             float* sample_logprob_or_null);
+typedef struct dc_beam_opts { int32_t beam_size; int32_t n_best; float length_alpha; } dc_beam_opts;
+int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_beam_opts* opts, dc_result* out,
+                     int32_t* captions, float* logprob);
+int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* opts, int32_t* captions, float* logprob);
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device, dc_result* outs);
 int dc_forward_images(dc_ctx* ctx, const float* const* imgs, const int* H, const int* W, int n, int imgs_on_device,
                       dc_result* outs);
