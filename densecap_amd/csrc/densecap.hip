@@ -146,9 +146,7 @@ struct Lane {
   float *bm_logits = nullptr, *bm_top_lp = nullptr, *bm_lp[2] = {nullptr, nullptr};
   int32_t *bm_top_idx = nullptr, *bm_beams[2] = {nullptr, nullptr}, *bm_parent = nullptr, *bm_tok = nullptr;
   uint8_t* bm_fin = nullptr;
-  // what the standard search (dc_beam_captions) adds to it, in an allocation of its own: the carve above stays the other search's
-  void* bs_base = nullptr;
-  int bs_rows = 0, bs_T = 0;
+  // what the standard search (dc_beam_captions) adds to it
   int32_t* bs_len[2] = {nullptr, nullptr};
   float* bs_pen = nullptr;
   hipStream_t aux = nullptr;            // single-image mode: second half of the decode rows runs here
@@ -463,7 +461,6 @@ int lane_streams(dc_ctx* ctx, Lane& L) {
 void lane_release(Lane& L) {
   if (L.arena.p) (void)hipFree(L.arena.p);
   if (L.beam_base) (void)hipFree(L.beam_base);
-  if (L.bs_base) (void)hipFree(L.bs_base);
   if (L.gexec) (void)hipGraphExecDestroy(L.gexec);
   if (L.host_stage) (void)hipHostFree(L.host_stage);
   for (auto& ev : L.ev) if (ev) (void)hipEventDestroy(ev);
@@ -595,9 +592,9 @@ bool screen_pays(const dc_ctx* ctx, int rows) {
 }
 
 // From fc7 codes to the state after the START token: the first five launches of the schedule in lm_sample_parts (there is the
-// description), for n rows.  Every schedule of the language model but the beam search starts here.  Only enqueues (capture-safe).
-// `plan`: GemmDesc::plan_M; m_dev: optional device-side row count; enc_ws: scratch of the encoder GEMM (K = 4096), the only one
-// of the three that may take a split-K route.
+// description), for n rows.  Every schedule of the language model but the reference-rule beam search starts here.  Only enqueues
+// (capture-safe).  `plan`: GemmDesc::plan_M; m_dev: optional device-side row count; enc_ws: scratch of the encoder GEMM
+// (K = 4096), the only one of the three that may take a split-K route.
 int lm_start_state(dc_ctx* ctx, hipStream_t s, const float* codes, int n, float* enc, float* gates, float* c, float* h, int plan,
                    const int32_t* m_dev, const Ws& enc_ws) {
   const int E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1;
@@ -714,19 +711,25 @@ int lm_sample(dc_ctx* ctx, hipStream_t s, const LmBufs& b, const Ws& ws, const f
   const LmPart whole{s, 0, n, ws};
   return lm_sample_parts(ctx, b, codes, &whole, 1, n_dev, seq_out, plan);
 }
-// LanguageModel:beamsearch (LanguageModel.lua:170-290), dispatched by LM:updateOutput when self.beam_size is set
+// ---- beam search: both rules ----------------------------------------------------------------------------------------------------
+// Reference rule: LanguageModel:beamsearch (LanguageModel.lua:170-290), dispatched by LM:updateOutput when self.beam_size is set
 // (:129-131; no reference script sets it).  The reference walks the proposals one by one with the beams in the
 // minibatch dimension; here ALL proposals advance together (rows = proposals x beams; beam_chunk), row for row the same
 // arithmetic: LSTM step (MFMA GEMM + point-wise), vocabulary projection (full logits this time), LogSoftMax + top-k per
 // beam, beam x beam merge, states re-indexed by parent.  Ties: lower index first (docs/SEMANTICS.md).
+// Standard search (docs/SEMANTICS.md, "Standard beam search"): the same dense steps, lists and state gather; what
+// differs is how the first state is formed, the bookkeeping kernel between the lists and the gather (beam_std_init /
+// beam_std_merge, which carry a length per hypothesis), and the read-out (beam_std_finish ranks n_best of them).
+// One run's width and rule travel as a BeamRun: no function of the search reads the dc_set_beam_size setting.
+struct BeamRun { int beam; bool standard; };
 // Proposals that advance together: all of them (rows = P x beam, one GEMM per step over every proposal) unless the
 // full-logits buffer rows x (V+1) would pass 2^28 floats (1 GiB) -- e.g. 5,114 proposals at beam 5 / V = 10,497.
-int beam_chunk(const dc_ctx* ctx, int n) {
-  const long cap = (long)(ctx->beam_chunk_floats / ((int64_t)ctx->cfg.beam_size * (ctx->V + 1)));
+int beam_chunk(const dc_ctx* ctx, BeamRun run, int n) {
+  const long cap = (long)(ctx->beam_chunk_floats / ((int64_t)run.beam * (ctx->V + 1)));
   return (int)std::max<long>(1, std::min<long>(n, std::max<long>(64, cap)));
 }
-int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
-  const int beam = ctx->cfg.beam_size, rows = chunk * beam;
+int beam_prepare(dc_ctx* ctx, Lane& L, BeamRun run, int chunk) {
+  const int beam = run.beam, rows = chunk * beam;
   // bm_enc is sized by the chunk, bm_top_lp / bm_top_idx by rows x beam: the scratch is reusable only when NONE of the
   // three grew (beam 2 x 1000 proposals and beam 20 x 100 have the same row count but not the same carve)
   if (L.beam_base && L.beam_rows >= rows && L.beam_chunk >= chunk && L.beam_width >= beam) return DC_OK;
@@ -742,6 +745,9 @@ int beam_prepare(dc_ctx* ctx, Lane& L, int chunk) {
       {(void**)&L.bm_lp[1], (size_t)rows * 4},         {(void**)&L.bm_beams[0], (size_t)rows * T * 4},
       {(void**)&L.bm_beams[1], (size_t)rows * T * 4},  {(void**)&L.bm_parent, (size_t)rows * 4},
       {(void**)&L.bm_tok, (size_t)rows * 4},           {(void**)&L.bm_fin, (size_t)rows},
+      // the standard search's: carved for either rule (a few bytes per row beside the logits' rows x (V+1) x 4)
+      {(void**)&L.bs_len[0], (size_t)rows * 4},        {(void**)&L.bs_len[1], (size_t)rows * 4},
+      {(void**)&L.bs_pen, ((size_t)T + 1) * 4},
   };
   HIPCHK(hipMalloc(&L.beam_base, carve(cv, nullptr)));
   carve(cv, L.beam_base);
@@ -761,54 +767,87 @@ static int beam_lstm_step(dc_ctx* ctx, Lane& L, float* h, float* c, int rows, hi
 }
 
 // The beam search keeps its state in two ping-pong sets: iteration t (1 <= t < T) reads the LSTM state in bm_h / bm_c[t & 1] and
-// the beams in bm_lp / bm_beams[(t & 1) ^ 1], and writes the other set of each.  beam_start leaves what t = 1 reads.
+// the beams in bm_lp / bm_beams[(t & 1) ^ 1], and writes the other set of each (the standard search's bs_len rides with bm_lp and
+// bm_beams).  beam_start leaves what t = 1 reads.
 static int beam_state_set(int t) { return t & 1; }
 static int beam_beams_set(int t) { return (t & 1) ^ 1; }
 
 // Everything before the t loop for the c proposals of one chunk: image step (:198-201), START step (:203-206), one state row per
 // proposal, then the first expansion to c x beam rows (top-k lists of the first step in bm_top_lp / bm_top_idx, c x beam).
-int beam_start(dc_ctx* ctx, Lane& L, const float* codes, int c, hipStream_t s) {
-  const int beam = ctx->cfg.beam_size, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
-  DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, L.bm_enc, c, E, D, 1));
-  DCCHK(linear(ctx, s, L.bm_enc, ctx->wxT, ctx->lstm_b, L.bm_gates, c, 4 * Hd, E, 0));
-  KCHK(launch_lstm_pointwise(L.bm_gates, L.bm_c[0], L.bm_h[0], c, nullptr, Hd, 1, s));
-  KCHK(launch_fill_i32(L.bm_tok, V1, c, s));
-  DCCHK(beam_lstm_step(ctx, L, L.bm_h[0], L.bm_c[0], c, s));
+int beam_start(dc_ctx* ctx, Lane& L, BeamRun run, const float* codes, int c, hipStream_t s) {
+  const int beam = run.beam, E = ctx->E, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, D = ctx->D;
+  if (run.standard) {         // lm_start_state: h AND c of the START step
+    DCCHK(lm_start_state(ctx, s, codes, c, L.bm_enc, L.bm_gates, L.bm_c[0], L.bm_h[0], 0, nullptr, Ws()));
+  } else {
+    DCCHK(linear(ctx, s, codes, ctx->enc_w, ctx->enc_b, L.bm_enc, c, E, D, 1));
+    DCCHK(linear(ctx, s, L.bm_enc, ctx->wxT, ctx->lstm_b, L.bm_gates, c, 4 * Hd, E, 0));
+    KCHK(launch_lstm_pointwise(L.bm_gates, L.bm_c[0], L.bm_h[0], c, nullptr, Hd, 1, s));
+    KCHK(launch_fill_i32(L.bm_tok, V1, c, s));
+    DCCHK(beam_lstm_step(ctx, L, L.bm_h[0], L.bm_c[0], c, s));
+  }
   DCCHK(linear(ctx, s, L.bm_h[0], ctx->out_w, ctx->out_b, L.bm_logits, c, V1, Hd, 0));
   KCHK(launch_beam_logsoftmax_topk(L.bm_logits, c, V1, V1, nullptr, beam, L.bm_top_lp, L.bm_top_idx, s));
-  KCHK(launch_beam_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bm_parent, L.bm_tok,
-                        L.bm_fin, s));
-  // LanguageModel.lua:221-226 duplicates the states for the beams with `layer.output = layer.cell:expand(...):clone()`:
-  // BOTH the cell and the hidden state of every beam start from the CELL state of the START step (torch-rnn's
-  // nn.LSTM with remember_states reads h0 from self.output).  Replicated as written: h rows := c rows.
-  KCHK(launch_beam_gather_state(L.bm_c[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1], L.bm_c[1], s));
+  if (run.standard)
+    KCHK(launch_beam_std_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bs_len[0], L.bm_parent,
+                              L.bm_tok, L.bm_fin, s));
+  else
+    KCHK(launch_beam_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bm_parent, L.bm_tok,
+                          L.bm_fin, s));
+  // Reference rule: LanguageModel.lua:221-226 duplicates the states for the beams with
+  // `layer.output = layer.cell:expand(...):clone()`: BOTH the cell and the hidden state of every beam start from the CELL state
+  // of the START step (torch-rnn's nn.LSTM with remember_states reads h0 from self.output).  Replicated as written: h rows := c rows.
+  // Standard search: every hypothesis of a proposal starts from the proposal's (h, c).
+  KCHK(launch_beam_gather_state(run.standard ? L.bm_h[0] : L.bm_c[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1],
+                                L.bm_c[1], s));
   return DC_OK;
 }
 
 // Iteration t of the loop (:228-278) on the c x beam rows of one chunk: LSTM step on bm_tok, vocabulary projection, LogSoftMax +
 // top-k per row with the finished mask (lists in bm_top_lp / bm_top_idx, rows x beam), beam x beam merge, states by parent.
-int beam_iter(dc_ctx* ctx, Lane& L, int c, int t, hipStream_t s) {
-  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, rows = c * beam;
+int beam_iter(dc_ctx* ctx, Lane& L, BeamRun run, int c, int t, hipStream_t s) {
+  const int beam = run.beam, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, rows = c * beam;
   const int cur = beam_state_set(t), bcur = beam_beams_set(t);
   DCCHK(beam_lstm_step(ctx, L, L.bm_h[cur], L.bm_c[cur], rows, s));
   DCCHK(linear(ctx, s, L.bm_h[cur], ctx->out_w, ctx->out_b, L.bm_logits, rows, V1, Hd, 0));
   KCHK(launch_beam_logsoftmax_topk(L.bm_logits, rows, V1, V1, L.bm_fin, beam, L.bm_top_lp, L.bm_top_idx, s));
-  KCHK(launch_beam_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], c, beam, T, t, V1,
-                         L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
+  if (run.standard)
+    KCHK(launch_beam_std_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], L.bs_len[bcur], L.bm_fin, c, beam, T, t,
+                               V1, L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bs_len[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
+  else
+    KCHK(launch_beam_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], c, beam, T, t, V1,
+                           L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
   KCHK(launch_beam_gather_state(L.bm_h[cur], L.bm_c[cur], L.bm_parent, rows, beam, beam, Hd, L.bm_h[cur ^ 1],
                                 L.bm_c[cur ^ 1], s));
   return DC_OK;
 }
 
-int lm_beamsearch(dc_ctx* ctx, Lane& L, const float* codes, int n, int32_t* seq_out, hipStream_t s) {
-  const int kBeamChunk = beam_chunk(ctx, n);
-  DCCHK(beam_prepare(ctx, L, kBeamChunk));
-  const int beam = ctx->cfg.beam_size, T = ctx->T, D = ctx->D;
-  for (int p0 = 0; p0 < n; p0 += kBeamChunk) {
-    const int c = std::min(kBeamChunk, n - p0);
-    DCCHK(beam_start(ctx, L, codes + (size_t)p0 * D, c, s));
-    for (int t = 1; t < T; ++t) DCCHK(beam_iter(ctx, L, c, t, s));
-    KCHK(launch_beam_best(L.bm_beams[beam_beams_set(T)], c, beam, T, seq_out + (size_t)p0 * T, s));
+// pen[l] = (float)pow(l, alpha) for l = 0..T (pen[0] = 1: a hypothesis without a word has a NaN score already)
+std::vector<float> beam_std_pen(int T, float alpha) {
+  std::vector<float> pen((size_t)T + 1, 1.f);
+  for (int l = 1; l <= T; ++l) pen[l] = (float)pow((double)l, (double)alpha);
+  return pen;
+}
+// Where a search leaves its result (DEVICE buffers).  Reference rule: seq (n, T), the tokens of every proposal's best beam.
+// Standard search: seq (n, n_best, T) and logprob (n, n_best), ranked under length_alpha.
+struct BeamOut { int32_t* seq; float* logprob = nullptr; int n_best = 1; float length_alpha = 0.f; };
+// The whole search on n code rows, chunk by chunk.  Eager: the scratch is allocated on first use, and the length-penalty table goes
+// up with a blocking copy before the first launch (every caller has synchronised its previous call: nothing on the stream still
+// reads bs_pen); the launches themselves are only enqueued.
+int beam_search(dc_ctx* ctx, Lane& L, hipStream_t s, BeamRun run, const float* codes, int n, const BeamOut& out) {
+  const int chunk = beam_chunk(ctx, run, n);
+  DCCHK(beam_prepare(ctx, L, run, chunk));
+  const int beam = run.beam, T = ctx->T, D = ctx->D, N = out.n_best, bs = beam_beams_set(T);
+  const int has_pen = run.standard && out.length_alpha != 0.f;
+  if (has_pen) HIPCHK(hipMemcpy(L.bs_pen, beam_std_pen(T, out.length_alpha).data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice));
+  for (int p0 = 0; p0 < n; p0 += chunk) {
+    const int c = std::min(chunk, n - p0);
+    DCCHK(beam_start(ctx, L, run, codes + (size_t)p0 * D, c, s));
+    for (int t = 1; t < T; ++t) DCCHK(beam_iter(ctx, L, run, c, t, s));
+    if (run.standard)
+      KCHK(launch_beam_std_finish(L.bm_lp[bs], L.bm_beams[bs], L.bs_len[bs], L.bs_pen, has_pen, c, beam, T, N,
+                                  out.seq + (size_t)p0 * N * T, out.logprob + (size_t)p0 * N, s));
+    else
+      KCHK(launch_beam_best(L.bm_beams[bs], c, beam, T, out.seq + (size_t)p0 * T, s));
   }
   return DC_OK;
 }
@@ -1199,7 +1238,7 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
   }
   // ---- language model (reference order: all P proposals, DenseCapModel.lua:127-162) -----------------
   if (!features_only && !survivors_only && !no_decode) {
-    if (cfg.beam_size > 0) DCCHK(lm_beamsearch(ctx, L, L.codes, R, L.seq, s));
+    if (cfg.beam_size > 0) DCCHK(beam_search(ctx, L, s, {cfg.beam_size, false}, L.codes, R, {L.seq}));
     else if (side_streams) DCCHK(lm_sample_two_streams(ctx, L, L.codes, R, P, L.seq));
     else DCCHK(lm_sample(ctx, s, lane_lm_bufs(L), lane_ws(L), L.codes, R, P, nullptr, L.seq));
   }
@@ -1243,7 +1282,8 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
       const size_t r0 = (size_t)i * P;
       const int32_t *pk = L.picks2 + r0, *cnt = L.count2 + i * kCountStride;
       KCHK(launch_gather_rows(L.codes + r0 * ctx->D, pk, cnt, P, ctx->D, L.out_feats + r0 * ctx->D, s));
-      DCCHK(lm_beamsearch(ctx, L, L.out_feats + r0 * ctx->D, P, L.out_tokens + r0 * ctx->T, s));   // rows past K: zero codes, ignored
+      // rows past K: zero codes, ignored
+      DCCHK(beam_search(ctx, L, s, {cfg.beam_size, false}, L.out_feats + r0 * ctx->D, P, {L.out_tokens + r0 * ctx->T}));
     }
   }
   // ---- results: ONE gather launch for the group into packed records, ONE copy to the pinned host staging ---------------
@@ -2399,7 +2439,7 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
   void* base = nullptr;
   HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
   carve(cv, base);
-  int rc = ctx->cfg.beam_size > 0 ? lm_beamsearch(ctx, lane0(ctx), codes, n, tokens, s)
+  int rc = ctx->cfg.beam_size > 0 ? beam_search(ctx, lane0(ctx), s, {ctx->cfg.beam_size, false}, codes, n, {tokens})
                                   : lm_sample(ctx, s, b, lane_ws(lane0(ctx)), codes, n, 0, nullptr, tokens);
   hipError_t e2 = hipStreamSynchronize(s);
   if (ctx->lm_op_keep && rc == DC_OK && e2 == hipSuccess && ctx->cfg.beam_size == 0) {
@@ -2527,15 +2567,7 @@ int dc_sample_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_
   return sample_captions(ctx, img_chw, H, W, img_on_device, opts, nullptr, out, samples, logprob, nullptr, "dc_sample_captions");
 }
 
-// ---- standard beam search (docs/SEMANTICS.md, "Standard beam search") ---------------------------------------------
-// The dense steps and the lists are the reference-rule search's (beam_lstm_step, the full-logits projection, the top-k kernel with
-// its finished mask, the state gather); the bookkeeping between them is beam_std_init / beam_std_merge, and beam_std_finish ranks
-// at the end.  It runs on the same scratch (beam_prepare at ITS width: BeamWidthGuard) plus bs_len / bs_pen, in fp32, eagerly.
-struct BeamWidthGuard {   // cfg.beam_size = the call's width while one lives: beam_chunk / beam_prepare / beam_lstm_step read it
-  Settings& c; int saved;
-  BeamWidthGuard(Settings& cfg, int beam) : c(cfg), saved(cfg.beam_size) { c.beam_size = beam; }
-  ~BeamWidthGuard() { c.beam_size = saved; }
-};
+// The standard search's entry points (the search itself: "beam search: both rules" above).  It always runs in fp32, eagerly.
 static int check_beam_opts(dc_ctx* ctx, const dc_beam_opts* o, const char* who) {
   if (!o) return ctx->fail(DC_E_INVALID, "%s: null options", who);
   if (o->beam_size < 1 || o->beam_size > 32 || o->beam_size > ctx->V + 1)
@@ -2547,70 +2579,11 @@ static int check_beam_opts(dc_ctx* ctx, const dc_beam_opts* o, const char* who) 
     return ctx->fail(DC_E_INVALID, "%s: length_alpha must be in [0, 2] (got %g)", who, (double)o->length_alpha);
   return check_beam_fits(ctx, o->beam_size);
 }
-// pen[l] = (float)pow(l, alpha) for l = 0..T (pen[0] = 1: a hypothesis without a word has a NaN score already)
-static std::vector<float> beam_std_pen(int T, float alpha) {
-  std::vector<float> pen((size_t)T + 1, 1.f);
-  for (int l = 1; l <= T; ++l) pen[l] = (float)pow((double)l, (double)alpha);
-  return pen;
-}
-static int beam_std_prepare(dc_ctx* ctx, Lane& L, int chunk) {
-  DCCHK(beam_prepare(ctx, L, chunk));
-  const int rows = chunk * ctx->cfg.beam_size, T = ctx->T;
-  if (L.bs_base && L.bs_rows >= rows && L.bs_T >= T) return DC_OK;
-  if (L.bs_base) { HIPCHK(hipStreamSynchronize(L.stream)); HIPCHK(hipFree(L.bs_base)); L.bs_base = nullptr; }
-  L.bs_rows = L.bs_T = 0;
-  const std::vector<Carve> cv = {{(void**)&L.bs_len[0], (size_t)rows * 4}, {(void**)&L.bs_len[1], (size_t)rows * 4},
-                                 {(void**)&L.bs_pen, ((size_t)T + 1) * 4}};
-  HIPCHK(hipMalloc(&L.bs_base, carve(cv, nullptr)));
-  carve(cv, L.bs_base);
-  L.bs_rows = rows; L.bs_T = T;
-  return DC_OK;
-}
-// Everything before the t loop for the c proposals of one chunk: lm_start_state (h AND c of the START step), the first lists,
-// the first expansion; every hypothesis of a proposal starts from the proposal's (h, c).  Leaves what iteration t = 1 reads.
-static int beam_std_start(dc_ctx* ctx, Lane& L, const float* codes, int c, hipStream_t s) {
-  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T;
-  DCCHK(lm_start_state(ctx, s, codes, c, L.bm_enc, L.bm_gates, L.bm_c[0], L.bm_h[0], 0, nullptr, Ws()));
-  DCCHK(linear(ctx, s, L.bm_h[0], ctx->out_w, ctx->out_b, L.bm_logits, c, V1, Hd, 0));
-  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, c, V1, V1, nullptr, beam, L.bm_top_lp, L.bm_top_idx, s));
-  KCHK(launch_beam_std_init(L.bm_top_lp, L.bm_top_idx, c, beam, T, V1, L.bm_lp[0], L.bm_beams[0], L.bs_len[0], L.bm_parent,
-                            L.bm_tok, L.bm_fin, s));
-  KCHK(launch_beam_gather_state(L.bm_h[0], L.bm_c[0], L.bm_parent, c * beam, beam, 1, Hd, L.bm_h[1], L.bm_c[1], s));
-  return DC_OK;
-}
-// Iteration t on the c x beam rows of one chunk; the ping-pong sets are beam_iter's (len rides with lp and the rows)
-static int beam_std_iter(dc_ctx* ctx, Lane& L, int c, int t, hipStream_t s) {
-  const int beam = ctx->cfg.beam_size, Hd = ctx->Hd, V1 = ctx->V + 1, T = ctx->T, rows = c * beam;
-  const int cur = beam_state_set(t), bcur = beam_beams_set(t);
-  DCCHK(beam_lstm_step(ctx, L, L.bm_h[cur], L.bm_c[cur], rows, s));
-  DCCHK(linear(ctx, s, L.bm_h[cur], ctx->out_w, ctx->out_b, L.bm_logits, rows, V1, Hd, 0));
-  KCHK(launch_beam_logsoftmax_topk(L.bm_logits, rows, V1, V1, L.bm_fin, beam, L.bm_top_lp, L.bm_top_idx, s));
-  KCHK(launch_beam_std_merge(L.bm_top_lp, L.bm_top_idx, L.bm_lp[bcur], L.bm_beams[bcur], L.bs_len[bcur], L.bm_fin, c, beam, T, t,
-                             V1, L.bm_lp[bcur ^ 1], L.bm_beams[bcur ^ 1], L.bs_len[bcur ^ 1], L.bm_parent, L.bm_tok, L.bm_fin, s));
-  KCHK(launch_beam_gather_state(L.bm_h[cur], L.bm_c[cur], L.bm_parent, rows, beam, beam, Hd, L.bm_h[cur ^ 1],
-                                L.bm_c[cur ^ 1], s));
-  return DC_OK;
-}
-// The whole search on n code rows; captions (n, n_best, T) and logprob (n, n_best) are DEVICE buffers.  Only enqueues; `pen` (the
-// host table) must live until the caller has synchronised.
-static int lm_beam_std(dc_ctx* ctx, Lane& L, hipStream_t s, const float* codes, int n, const dc_beam_opts& o,
-                       const std::vector<float>& pen, int32_t* captions, float* logprob) {
+// captions (n, n_best, T) and logprob (n, n_best): DEVICE buffers.  Only the launches are enqueued: the caller synchronises.
+static int lm_beam_std(dc_ctx* ctx, Lane& L, hipStream_t s, const float* codes, int n, const dc_beam_opts& o, int32_t* captions,
+                       float* logprob) {
   Fp32Guard fp32(ctx->cfg);
-  BeamWidthGuard width(ctx->cfg, o.beam_size);
-  const int chunk = beam_chunk(ctx, n);
-  DCCHK(beam_std_prepare(ctx, L, chunk));
-  const int beam = o.beam_size, T = ctx->T, D = ctx->D, N = o.n_best;
-  const int has_pen = o.length_alpha != 0.f;
-  if (has_pen) HIPCHK(hipMemcpyAsync(L.bs_pen, pen.data(), pen.size() * 4, hipMemcpyHostToDevice, s));
-  for (int p0 = 0; p0 < n; p0 += chunk) {
-    const int c = std::min(chunk, n - p0);
-    DCCHK(beam_std_start(ctx, L, codes + (size_t)p0 * D, c, s));
-    for (int t = 1; t < T; ++t) DCCHK(beam_std_iter(ctx, L, c, t, s));
-    const int bs = beam_beams_set(T);
-    KCHK(launch_beam_std_finish(L.bm_lp[bs], L.bm_beams[bs], L.bs_len[bs], L.bs_pen, has_pen, c, beam, T, N,
-                                captions + (size_t)p0 * N * T, logprob + (size_t)p0 * N, s));
-  }
-  return DC_OK;
+  return beam_search(ctx, L, s, {o.beam_size, true}, codes, n, {captions, logprob, o.n_best, o.length_alpha});
 }
 int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* opts, int32_t* captions, float* logprob) {
   OP_PROLOGUE();
@@ -2619,9 +2592,8 @@ int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* 
   if (!codes || !captions || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
   if (n <= 0) return ctx->fail(DC_E_INVALID, "%s: n must be > 0", who);
   DCCHK(check_beam_opts(ctx, opts, who));
-  const std::vector<float> pen = beam_std_pen(ctx->T, opts->length_alpha);
-  const int rc = lm_beam_std(ctx, lane0(ctx), s, codes, n, *opts, pen, captions, logprob);
-  const hipError_t e = hipStreamSynchronize(s);        // also after a failure part-way: `pen` may still be in flight
+  const int rc = lm_beam_std(ctx, lane0(ctx), s, codes, n, *opts, captions, logprob);
+  const hipError_t e = hipStreamSynchronize(s);
   prof_collect(ctx);
   if (rc != DC_OK) return rc;
   if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s sync: %s", who, hipGetErrorString(e));
@@ -2644,8 +2616,7 @@ int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on
   void* base = nullptr;
   HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
   carve(cv, base);
-  const std::vector<float> pen = beam_std_pen(ctx->T, opts->length_alpha);
-  const int rc = lm_beam_std(ctx, L, L.stream, L.out_feats, K, *opts, pen, cap_d, lp_d);
+  const int rc = lm_beam_std(ctx, L, L.stream, L.out_feats, K, *opts, cap_d, lp_d);
   hipError_t e = hipStreamSynchronize(L.stream);
   if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(captions, cap_d, (size_t)K * N * T * 4, hipMemcpyDeviceToHost);
   if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(logprob, lp_d, (size_t)K * N * 4, hipMemcpyDeviceToHost);
@@ -2682,7 +2653,7 @@ int dc_debug_sample_trunc_rows(dc_ctx* ctx, const float* logits, int rows, int V
   OP_EPILOGUE();
 }
 
-// ---- beam search test hooks (densecap_debug.h) ---------------------------------------------------------------------------------
+// ---- beam search test hooks, both rules (densecap_debug.h, densecap_debug_beam.h) ----------------------------------------------
 int dc_debug_beam_topk(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const uint8_t* finished_or_null, int k,
                        float* top_lp, int32_t* top_idx) {
   OP_PROLOGUE();
@@ -2703,68 +2674,93 @@ int dc_debug_beam_merge(dc_ctx* ctx, const float* top_lp, const int32_t* top_idx
   OP_EPILOGUE();
 }
 
-// what the two state hooks check first; on DC_OK the lane's beam scratch holds nprop proposals
-static int beam_hook_prepare(dc_ctx* ctx, int nprop, const dc_beam_state* st, const char* who) {
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
-  if (ctx->cfg.beam_size < 1) return ctx->fail(DC_E_STATE, "%s: dc_set_beam_size first", who);
-  if (!st || !st->h || !st->c || !st->beam_lp || !st->beams || !st->tok || !st->parent || !st->fin)
-    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
-  if (nprop < 1 || beam_chunk(ctx, nprop) < nprop)
-    return ctx->fail(DC_E_INVALID, "%s: %d proposals are not one chunk (the hook does not chunk)", who, nprop);
-  return beam_prepare(ctx, lane0(ctx), nprop);
+// The four state hooks run one body: the search's own start and iteration on lane 0's scratch under the caller's BeamRun.  A state
+// is a dc_beam_std_state inside, `len` null (and not copied) for the reference rule.
+static dc_beam_std_state beam_hook_state(const dc_beam_state* st) {
+  return st ? dc_beam_std_state{st->h, st->c, st->beam_lp, st->beams, st->tok, st->parent, st->fin, nullptr} : dc_beam_std_state{};
 }
-// the lane's beam state, sets (hs, bs), to or from the caller's buffers (rows = nprop x beam), and the top-k lists out
-static int beam_hook_copy(dc_ctx* ctx, Lane& L, int rows, int hs, int bs, const dc_beam_state& st, bool out, hipStream_t s) {
+// what they check of a state first; on DC_OK the lane's beam scratch holds nprop proposals
+static int beam_hook_prepare(dc_ctx* ctx, BeamRun run, int nprop, const dc_beam_std_state* st, const char* who) {
+  if (!st || !st->h || !st->c || !st->beam_lp || !st->beams || !st->tok || !st->parent || !st->fin || (run.standard && !st->len))
+    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (nprop < 1 || beam_chunk(ctx, run, nprop) < nprop)
+    return ctx->fail(DC_E_INVALID, "%s: %d proposals are not one chunk (the hook does not chunk)", who, nprop);
+  return beam_prepare(ctx, lane0(ctx), run, nprop);
+}
+// the lane's beam state, sets (hs, bs), to or from the caller's buffers (rows = nprop x beam)
+static int beam_hook_copy(dc_ctx* ctx, Lane& L, int rows, int hs, int bs, const dc_beam_std_state& st, bool out, hipStream_t s) {
   const size_t Hd = ctx->Hd, T = ctx->T;
   const struct { void* lane; void* user; size_t bytes; } parts[] = {
       {L.bm_h[hs], st.h, rows * Hd * 4}, {L.bm_c[hs], st.c, rows * Hd * 4},   {L.bm_lp[bs], st.beam_lp, (size_t)rows * 4},
       {L.bm_beams[bs], st.beams, rows * T * 4}, {L.bm_tok, st.tok, (size_t)rows * 4}, {L.bm_parent, st.parent, (size_t)rows * 4},
-      {L.bm_fin, st.fin, (size_t)rows}};
+      {L.bm_fin, st.fin, (size_t)rows}, {L.bs_len[bs], st.len, st.len ? (size_t)rows * 4 : 0}};
   for (const auto& p : parts)
-    HIPCHK(hipMemcpyAsync(out ? p.user : p.lane, out ? p.lane : p.user, p.bytes, hipMemcpyDeviceToDevice, s));
+    if (p.bytes) HIPCHK(hipMemcpyAsync(out ? p.user : p.lane, out ? p.lane : p.user, p.bytes, hipMemcpyDeviceToDevice, s));
   return DC_OK;
 }
+// ... and the top-k lists out
 static int beam_hook_lists(dc_ctx* ctx, Lane& L, size_t n, float* top_lp, int32_t* top_idx, hipStream_t s) {
   HIPCHK(hipMemcpyAsync(top_lp, L.bm_top_lp, n * 4, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(top_idx, L.bm_top_idx, n * 4, hipMemcpyDeviceToDevice, s));
   return DC_OK;
 }
+static int beam_hook_start(dc_ctx* ctx, hipStream_t s, BeamRun run, const float* codes, int nprop, const dc_beam_std_state* out,
+                           float* top_lp, int32_t* top_idx, const char* who) {
+  DCCHK(beam_hook_prepare(ctx, run, nprop, out, who));
+  Lane& L = lane0(ctx);
+  DCCHK(beam_start(ctx, L, run, codes, nprop, s));
+  DCCHK(beam_hook_copy(ctx, L, nprop * run.beam, beam_state_set(1), beam_beams_set(1), *out, true, s));
+  return beam_hook_lists(ctx, L, (size_t)nprop * run.beam, top_lp, top_idx, s);
+}
+static int beam_hook_step(dc_ctx* ctx, hipStream_t s, BeamRun run, int nprop, int t, const dc_beam_std_state* in,
+                          const dc_beam_std_state* out, float* top_lp, int32_t* top_idx, const char* who) {
+  DCCHK(beam_hook_prepare(ctx, run, nprop, in, who));
+  DCCHK(beam_hook_prepare(ctx, run, nprop, out, who));
+  if (t < 1 || t >= ctx->T) return ctx->fail(DC_E_INVALID, "%s: t = %d is not in [1, %d)", who, t, ctx->T);
+  Lane& L = lane0(ctx);
+  const int rows = nprop * run.beam;
+  // the word of a row selects an xg row by address in the step GEMM: the caller's are checked here, as the kernels check their own
+  std::vector<int32_t> tok(rows);
+  HIPCHK(hipMemcpy(tok.data(), in->tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < rows; ++i)
+    if (tok[i] < 1 || tok[i] > ctx->V + 1)
+      return ctx->fail(DC_E_INVALID, "%s: tok[%d] = %d is not a word id in [1, %d]", who, i, (int)tok[i], ctx->V + 1);
+  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *in, false, s));
+  DCCHK(beam_iter(ctx, L, run, nprop, t, s));
+  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *out, true, s));
+  return beam_hook_lists(ctx, L, (size_t)rows * run.beam, top_lp, top_idx, s);
+}
 
+// the reference-rule hooks run at the width dc_set_beam_size set, in the math mode of dc_set_math_mode
+static int beam_ref_hook_run(dc_ctx* ctx, const char* who, BeamRun* run) {
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (ctx->cfg.beam_size < 1) return ctx->fail(DC_E_STATE, "%s: dc_set_beam_size first", who);
+  *run = {ctx->cfg.beam_size, false};
+  return DC_OK;
+}
 int dc_debug_beam_start(dc_ctx* ctx, const float* codes, int nprop, const dc_beam_state* state_out, float* top_lp,
                         int32_t* top_idx) {
   OP_PROLOGUE();
-  if (!codes || !top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "dc_debug_beam_start: null pointer");
-  DCCHK(beam_hook_prepare(ctx, nprop, state_out, "dc_debug_beam_start"));
-  Lane& L = lane0(ctx);
-  const int beam = ctx->cfg.beam_size;
-  DCCHK(beam_start(ctx, L, codes, nprop, s));
-  DCCHK(beam_hook_copy(ctx, L, nprop * beam, beam_state_set(1), beam_beams_set(1), *state_out, true, s));
-  DCCHK(beam_hook_lists(ctx, L, (size_t)nprop * beam, top_lp, top_idx, s));
+  const char* who = "dc_debug_beam_start";
+  if (!codes || !top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  BeamRun run;
+  DCCHK(beam_ref_hook_run(ctx, who, &run));
+  const dc_beam_std_state out = beam_hook_state(state_out);
+  DCCHK(beam_hook_start(ctx, s, run, codes, nprop, &out, top_lp, top_idx, who));
   OP_EPILOGUE();
 }
 int dc_debug_beam_step(dc_ctx* ctx, int nprop, int t, const dc_beam_state* state_in, const dc_beam_state* state_out,
                        float* top_lp, int32_t* top_idx) {
   OP_PROLOGUE();
-  if (!top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: null pointer");
-  DCCHK(beam_hook_prepare(ctx, nprop, state_in, "dc_debug_beam_step"));
-  DCCHK(beam_hook_prepare(ctx, nprop, state_out, "dc_debug_beam_step"));
-  if (t < 1 || t >= ctx->T) return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: t = %d is not in [1, %d)", t, ctx->T);
-  Lane& L = lane0(ctx);
-  const int beam = ctx->cfg.beam_size, rows = nprop * beam;
-  // the word of a row selects an xg row by address in the step GEMM: the caller's are checked here, as the kernels check their own
-  std::vector<int32_t> tok(rows);
-  HIPCHK(hipMemcpy(tok.data(), state_in->tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
-  for (int i = 0; i < rows; ++i)
-    if (tok[i] < 1 || tok[i] > ctx->V + 1)
-      return ctx->fail(DC_E_INVALID, "dc_debug_beam_step: tok[%d] = %d is not a word id in [1, %d]", i, (int)tok[i], ctx->V + 1);
-  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *state_in, false, s));
-  DCCHK(beam_iter(ctx, L, nprop, t, s));
-  DCCHK(beam_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
-  DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
+  const char* who = "dc_debug_beam_step";
+  if (!top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  BeamRun run;
+  DCCHK(beam_ref_hook_run(ctx, who, &run));
+  const dc_beam_std_state in = beam_hook_state(state_in), out = beam_hook_state(state_out);
+  DCCHK(beam_hook_step(ctx, s, run, nprop, t, &in, &out, top_lp, top_idx, who));
   OP_EPILOGUE();
 }
 
-// ---- standard beam search test hooks (densecap_debug_beam.h) ---------------------------------------------------------------------
 int dc_debug_beam_std_merge(dc_ctx* ctx, const float* top_lp, const int32_t* top_idx, const float* beam_lp_in,
                             const int32_t* beams_in, const int32_t* len_in, const uint8_t* fin_in, int nprop, int beam, int T, int t,
                             int END, float* beam_lp_out, int32_t* beams_out, int32_t* len_out, int32_t* parent, int32_t* cur_tok,
@@ -2796,21 +2792,7 @@ int dc_debug_beam_std_finish(dc_ctx* ctx, const float* beam_lp, const int32_t* b
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_beam_std_finish sync: %s", hipGetErrorString(e2));
   return DC_OK;
 }
-// what the two state hooks check first (the caller holds a BeamWidthGuard); on DC_OK the lane's scratch holds nprop proposals
-static int beam_std_hook_prepare(dc_ctx* ctx, int nprop, int beam, const dc_beam_std_state* st, const char* who) {
-  if (!st || !st->h || !st->c || !st->beam_lp || !st->beams || !st->tok || !st->parent || !st->fin || !st->len)
-    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
-  if (nprop < 1 || beam_chunk(ctx, nprop) < nprop)
-    return ctx->fail(DC_E_INVALID, "%s: %d proposals are not one chunk (the hook does not chunk)", who, nprop);
-  return beam_std_prepare(ctx, lane0(ctx), nprop);
-}
-static int beam_std_hook_copy(dc_ctx* ctx, Lane& L, int rows, int hs, int bs, const dc_beam_std_state& st, bool out, hipStream_t s) {
-  const dc_beam_state base = {st.h, st.c, st.beam_lp, st.beams, st.tok, st.parent, st.fin};
-  DCCHK(beam_hook_copy(ctx, L, rows, hs, bs, base, out, s));
-  HIPCHK(hipMemcpyAsync(out ? (void*)st.len : (void*)L.bs_len[bs], out ? (void*)L.bs_len[bs] : (void*)st.len, (size_t)rows * 4,
-                        hipMemcpyDeviceToDevice, s));
-  return DC_OK;
-}
+// the standard hooks take their width as an argument, validated like a call's options, and run in fp32 like the search
 static int beam_std_hook_opts(dc_ctx* ctx, int beam, const char* who) {
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
   const dc_beam_opts o = {beam, 1, 0.f};
@@ -2823,12 +2805,7 @@ int dc_debug_beam_std_start(dc_ctx* ctx, const float* codes, int nprop, int beam
   if (!codes || !top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
   DCCHK(beam_std_hook_opts(ctx, beam, who));
   Fp32Guard fp32(ctx->cfg);
-  BeamWidthGuard width(ctx->cfg, beam);
-  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_out, who));
-  Lane& L = lane0(ctx);
-  DCCHK(beam_std_start(ctx, L, codes, nprop, s));
-  DCCHK(beam_std_hook_copy(ctx, L, nprop * beam, beam_state_set(1), beam_beams_set(1), *state_out, true, s));
-  DCCHK(beam_hook_lists(ctx, L, (size_t)nprop * beam, top_lp, top_idx, s));
+  DCCHK(beam_hook_start(ctx, s, {beam, true}, codes, nprop, state_out, top_lp, top_idx, who));
   OP_EPILOGUE();
 }
 int dc_debug_beam_std_step(dc_ctx* ctx, int nprop, int beam, int t, const dc_beam_std_state* state_in,
@@ -2838,22 +2815,7 @@ int dc_debug_beam_std_step(dc_ctx* ctx, int nprop, int beam, int t, const dc_bea
   if (!top_lp || !top_idx) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
   DCCHK(beam_std_hook_opts(ctx, beam, who));
   Fp32Guard fp32(ctx->cfg);
-  BeamWidthGuard width(ctx->cfg, beam);
-  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_in, who));
-  DCCHK(beam_std_hook_prepare(ctx, nprop, beam, state_out, who));
-  if (t < 1 || t >= ctx->T) return ctx->fail(DC_E_INVALID, "%s: t = %d is not in [1, %d)", who, t, ctx->T);
-  Lane& L = lane0(ctx);
-  const int rows = nprop * beam;
-  // the word of a row selects an xg row by address in the step GEMM: the caller's are checked here, as the kernels check their own
-  std::vector<int32_t> tok(rows);
-  HIPCHK(hipMemcpy(tok.data(), state_in->tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
-  for (int i = 0; i < rows; ++i)
-    if (tok[i] < 1 || tok[i] > ctx->V + 1)
-      return ctx->fail(DC_E_INVALID, "%s: tok[%d] = %d is not a word id in [1, %d]", who, i, (int)tok[i], ctx->V + 1);
-  DCCHK(beam_std_hook_copy(ctx, L, rows, beam_state_set(t), beam_beams_set(t), *state_in, false, s));
-  DCCHK(beam_std_iter(ctx, L, nprop, t, s));
-  DCCHK(beam_std_hook_copy(ctx, L, rows, beam_state_set(t + 1), beam_beams_set(t + 1), *state_out, true, s));
-  DCCHK(beam_hook_lists(ctx, L, (size_t)rows * beam, top_lp, top_idx, s));
+  DCCHK(beam_hook_step(ctx, s, {beam, true}, nprop, t, state_in, state_out, top_lp, top_idx, who));
   OP_EPILOGUE();
 }
 

@@ -339,6 +339,45 @@ def test_invariances_bit_for_bit(model):
     assert _fault_word(m) == 0
 
 
+def test_two_searches_share_one_scratch():
+    """Both searches grow and reuse the lane's one beam scratch: on a ctx whose scratch does not exist yet, the standard search at
+    width 4 and the reference rule at width 3 give the same bits before and after the other search, a wider and a narrower run
+    have carved the scratch again or run on a corner of it."""
+    from densecap_amd import DenseCapModel, ops
+    from densecap_amd.weights import make_synthetic_image
+    from tests.test_gpu_sample import _greedy
+    W, codes = S.fixture()
+    m = DenseCapModel(W, device=0)
+    m.setTestArgs(rpn_nms_thresh=0.7, final_nms_thresh=0.3, num_proposals=50)
+    a = 0.7
+    std = lambda x, B: dict(zip(("captions", "logprob"), ops.lm_beam_n(m.ctx, x, B, None, a)))
+
+    def ref(B):
+        m.setBeamSize(B)
+        try:
+            return _greedy(m, codes)
+        finally:
+            m.setBeamSize(0)
+
+    try:
+        m.forward_raw(make_synthetic_image(96, 128, 0))               # the fault word exists from here on
+        A = std(codes, 4)
+        R3 = ref(3)
+        assert R3.shape == (N, T) and (R3 != R3[0]).any()
+        ref(8)                                                        # the width grows: carved again
+        R.check_same(std(codes, 4), A, "width 4 after the reference rule at 8")
+        wide = std(codes, 32)                                         # ... and again
+        np.testing.assert_array_equal(ref(3), R3)
+        two = std(codes[3:7], 2)                                      # rows, chunk and width shrink: the same carve
+        R.check_same(two, {k: v[3:7] for k, v in std(codes, 2).items()}, "width 2, rows 3..6 alone")
+        R.check_same(std(codes, 4), A, "width 4 at the end")
+        assert wide["captions"].shape == (N, 32, T) and _row_format(A["captions"], END).any()
+        assert _fault_word(m) == 0
+    finally:
+        m.setBeamSize(0)
+        m.ctx.close()
+
+
 # ---- e. the whole image, other shapes, refusals, the CLI -------------------------------------------------------------------------
 def test_whole_image(model):
     from densecap_amd import ops
