@@ -62,6 +62,11 @@ class DcBeamOpts(C.Structure):
     _fields_ = [("beam_size", C.c_int32), ("n_best", C.c_int32), ("length_alpha", C.c_float)]
 
 
+class DcLocalizeOpts(C.Structure):
+    """dc_localize_opts: the per-query NMS of dc_localize_captions."""
+    _fields_ = [("nms_thresh", C.c_float), ("max_regions", C.c_int32), ("min_objectness", C.c_float)]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -171,6 +176,11 @@ _SIGS = {
     "dc_beam_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcBeamOpts), C.POINTER(DcResult),
                                    C.c_void_p, C.c_void_p]),
     "dc_op_lm_beam_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(DcBeamOpts), C.c_void_p, C.c_void_p]),
+    "dc_op_nms_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
+                                  C.c_void_p, C.c_void_p]),
+    "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
 }
 # the hook of include/densecap_debug_sample.h (bound like the others; the two lists above mirror densecap.h / densecap_debug.h)
 _SAMPLE_HOOK_SIGS = {

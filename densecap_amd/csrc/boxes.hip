@@ -721,6 +721,160 @@ __global__ __launch_bounds__(256) void nms_scan_band_kernel(const u64* __restric
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Multi-order NMS (dc_op_nms_multi; docs/SEMANTICS.md, "Localising phrases"): the greedy NMS above on ONE box list under Q score
+// columns at once.  Which box suppresses which does not depend on the column -- only the order of the walk does -- so the
+// suppression bits are computed once, in INDEX space, and the Q walks run side by side, one workgroup each.
+//
+// (a) nms_multi_mask_kernel: S[i][w], n rows of W = ceil(n_cap / 64) words; bit j of word w set <=> nms_suppresses(box i,
+//     box 64w + j) and 64w + j != i (the test is symmetric in its two boxes, so the row of a pick is "what this pick removes").
+//     Words past the last box are written as zero: the scan reads whole rows.
+// (b) nms_multi_scan_kernel, workgroup = column q:
+//     * key = (sort_key(score, candidate) << 32) | index for every row, bitonic-sorted in LDS: decreasing score, the lower index
+//       first among equals, -0 == +0; rows that are no candidates (valid == 0, NaN score) carry the key of an invalid box and
+//       sort behind all ncand candidates (a NaN is NOT ranked first here, the one departure from the single-order NMS).
+//     * wave 0 walks the order 64 positions a chunk, lane = word of the `removed` bit set (n <= 4096 = 64 lanes x 64 bits).
+//       Per chunk every lane fetches the removed-bit of its own position (one ds_bpermute pair + a ballot), so positions that
+//       are dead already cost nothing; the positions still alive are then taken in order by the scalar unit: re-test the bit
+//       (an earlier pick of the same chunk may have removed it), pick, OR the pick's row into `removed`.
+//     * the rows of a chunk are at addresses that depend on the ORDER only, never on the picks: while wave 0 walks chunk c out
+//       of one LDS buffer, waves 1..3 stage the 64 rows of chunk c + 1 into the other -- no dependent global load per pick.
+//       The hand-off is one __syncthreads per chunk; the stop flag alternates between two slots so that a slot is rewritten
+//       only after a further barrier (no wave can read the flag of a later chunk in the place of its own).
+// A column's walk reads its own column and the shared mask only: its picks do not depend on Q, the other columns or their order.
+// ---------------------------------------------------------------------------------------
+constexpr int NMS_MULTI_MAX = 4096;
+
+// (mirrors nms_mask_kernel above -- the same LDS staging, area formula and inner loop, in index space and without the
+// triangle / near-band cases; a change to the IoU staging there belongs here too)
+__global__ __launch_bounds__(256) void nms_multi_mask_kernel(const float* __restrict__ boxes, int n_cap,
+                                                             const int32_t* __restrict__ n_dev, float thresh, int W,
+                                                             u64* __restrict__ S) {
+  const int n = n_dev ? max(0, min(*n_dev, n_cap)) : n_cap;
+  const int rc = blockIdx.y, q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (rc * 64 >= n) return;                                    // (the whole workgroup)
+  const int cc = blockIdx.x * 4 + q;
+  __shared__ float cb[4][64][5];
+  const int cj = cc * 64 + lane;
+  if (cc < W && cj < n) {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(boxes + (size_t)cj * 4);
+    cb[q][lane][0] = b[0]; cb[q][lane][1] = b[1]; cb[q][lane][2] = b[2]; cb[q][lane][3] = b[3];
+    cb[q][lane][4] = __fmul_rn(__fadd_rn(__fsub_rn(b[2], b[0]), 1.f), __fadd_rn(__fsub_rn(b[3], b[1]), 1.f));
+  }
+  __syncthreads();
+  const int row = rc * 64 + lane;
+  if (cc >= W || row >= n) return;
+  const f32x4 bi = *reinterpret_cast<const f32x4*>(boxes + (size_t)row * 4);
+  // box_utils.lua:178-181: area = (x2-x1+1) * (y2-y1+1)
+  const float ai = __fmul_rn(__fadd_rn(__fsub_rn(bi[2], bi[0]), 1.f), __fadd_rn(__fsub_rn(bi[3], bi[1]), 1.f));
+  const int jn = max(0, min(64, n - cc * 64));
+  u64 word = 0;
+  for (int j = 0; j < jn; ++j)
+    if (cc * 64 + j != row)
+      if (nms_suppresses(bi, ai, cb[q][j][0], cb[q][j][1], cb[q][j][2], cb[q][j][3], cb[q][j][4], thresh))
+        word |= (1ull << j);
+  S[(size_t)row * W + cc] = word;
+}
+
+__global__ __launch_bounds__(256) void nms_multi_scan_kernel(const float* __restrict__ scores, int Q,
+                                                             const uint8_t* __restrict__ valid, int n_cap,
+                                                             const int32_t* __restrict__ n_dev, const u64* __restrict__ S,
+                                                             int W, int npad_cap, int M, int32_t* __restrict__ picks,
+                                                             int32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) u64 nmsm_lds[];     // keys [npad_cap] | rows [2][64 * W]
+  u64* keys = nmsm_lds;
+  u64* rows = nmsm_lds + npad_cap;
+  __shared__ int s_ncand, s_cnt, s_done[2];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int n = n_dev ? max(0, min(*n_dev, n_cap)) : n_cap;
+  int npad = 64;
+  while (npad < n) npad <<= 1;                                  // <= npad_cap (launch_nms_multi pads n_cap the same way)
+  if (tid == 0) { s_ncand = 0; s_cnt = 0; s_done[0] = 0; s_done[1] = 0; }
+  __syncthreads();
+  for (int i = tid; i < npad; i += 256) {                       // (npad is a multiple of 64: whole waves)
+    bool cand = false;
+    u64 key = ~0ull;
+    if (i < n) {
+      const float s = scores[(size_t)i * Q + q];
+      cand = (valid == nullptr || valid[i] != 0) && !(s != s);
+      key = ((u64)sort_key(s, cand) << 32) | (u64)(uint32_t)i;
+    }
+    keys[i] = key;
+    const u64 bal = __ballot(cand);
+    if (lane == 0 && bal) atomicAdd(&s_ncand, __builtin_popcountll(bal));
+  }
+  __syncthreads();
+  // bitonic sort, ascending (the keys are distinct but for the padding, which is all ones)
+  for (int k = 2; k <= npad; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (npad >> 1); t += 256) {
+        const int l = ((t & ~(j - 1)) << 1) | (t & (j - 1)), r = l | j;
+        const u64 a = keys[l], b = keys[r];
+        if ((a > b) == ((l & k) == 0)) { keys[l] = b; keys[r] = a; }
+      }
+      __syncthreads();
+    }
+  const int ncand = s_ncand;
+  const int nchunks = (ncand + 63) >> 6;
+  const int rowwords = 64 * W;
+  // rows of the 64 positions of chunk c -> buffer `buf`, by threads first, first + nthr, ...; 8 loads in flight per thread
+  auto stage = [&](int c, int buf, int first, int nthr) {
+    u64* dst = rows + (size_t)buf * rowwords;
+    for (int t0 = first; t0 < rowwords; t0 += nthr * 8) {
+      u64 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int t = t0 + u * nthr;
+        v[u] = 0ull;
+        if (t < rowwords) {
+          const int k = t / W, w = t - k * W, p = c * 64 + k;
+          if (p < ncand) v[u] = S[(size_t)(uint32_t)keys[p] * W + w];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int t = t0 + u * nthr;
+        if (t < rowwords) dst[t] = v[u];
+      }
+    }
+  };
+  if (nchunks > 0) stage(0, 0, tid, 256);
+  __syncthreads();
+  u64 removed = 0ull;                                           // wave 0: lane w holds bits 64w .. 64w + 63
+  int cnt = 0;
+  for (int c = 0; c < nchunks; ++c) {
+    if (wid != 0) {
+      if (c + 1 < nchunks) stage(c + 1, (c + 1) & 1, tid - 64, 192);
+    } else {
+      const int p0 = c * 64, np = min(64, ncand - p0);
+      const int myi = lane < np ? (int)(uint32_t)keys[p0 + lane] : 0;
+      const unsigned rlo = (unsigned)__shfl((int)(unsigned)removed, myi >> 6, 64);
+      const unsigned rhi = (unsigned)__shfl((int)(unsigned)(removed >> 32), myi >> 6, 64);
+      const u64 mine = ((u64)rhi << 32) | rlo;
+      u64 alive = __ballot(lane < np && ((mine >> (myi & 63)) & 1ull) == 0ull);
+      const u64* rb = rows + (size_t)(c & 1) * rowwords;
+      while (alive != 0ull && cnt < M) {
+        const int b = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
+        alive &= alive - 1ull;
+        const int i = __builtin_amdgcn_readlane(myi, b);
+        const u64 cur = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(removed >> 32), i >> 6) << 32) |
+                        (unsigned)__builtin_amdgcn_readlane((int)(unsigned)removed, i >> 6);
+        if (((cur >> (i & 63)) & 1ull) == 0ull) {
+          if (lane == 0) picks[(size_t)q * M + cnt] = i;
+          ++cnt;
+          if (lane < W) removed |= rb[b * W + lane];
+        }
+      }
+      if (lane == 0) { s_cnt = cnt; s_done[c & 1] = cnt >= M ? 1 : 0; }
+    }
+    __syncthreads();
+    if (s_done[c & 1]) break;
+  }
+  const int total = s_cnt;
+  for (int j = total + tid; j < M; j += 256) picks[(size_t)q * M + j] = -1;
+  if (tid == 0) counts[q] = total;
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
                                    const int32_t* __restrict__ count, int cap, int width, float* __restrict__ out) {
   const int total = cap * width;
@@ -994,6 +1148,25 @@ hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores,
                          ws.removed0, picks, ws.pick_pos, st, count);
     }
   }
+  return hipGetLastError();
+}
+
+size_t nms_multi_workspace_bytes(int n) { return align256((size_t)n * (((size_t)n + 63) / 64) * 8); }
+hipError_t launch_nms_multi(void* ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
+                            const int32_t* n_dev, int Q, float thresh, int max_picks, int32_t* picks, int32_t* counts,
+                            hipStream_t s) {
+  if (n < 1 || n > NMS_MULTI_MAX || Q < 1 || max_picks < 1 || max_picks > NMS_MULTI_MAX) return hipErrorInvalidValue;
+  const int W = (n + 63) / 64;
+  int npad = 64;
+  while (npad < n) npad <<= 1;
+  u64* S = static_cast<u64*>(ws);
+  hipLaunchKernelGGL(nms_multi_mask_kernel, dim3((W + 3) / 4, W), dim3(256), 0, s, boxes, n, n_dev, thresh, W, S);
+  const size_t lds = ((size_t)npad + 2 * 64 * (size_t)W) * sizeof(u64);         // <= 96 KiB
+  const void* fn = reinterpret_cast<const void*>(&nms_multi_scan_kernel);
+  hipError_t e = ensure_dyn_lds(fn, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(nms_multi_scan_kernel, dim3(Q), dim3(256), lds, s, scores, Q, valid, n, n_dev, S, W, npad, max_picks,
+                     picks, counts);
   return hipGetLastError();
 }
 

@@ -425,6 +425,14 @@ hipError_t nms_workspace_bind(NmsWorkspace& ws, void* base, int n);
 hipError_t launch_nms(NmsWorkspace& ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
                       const int32_t* n_dev, float thresh, int max_boxes, int32_t* picks, int32_t* count, bool band,
                       hipStream_t s, uint32_t* fault);
+// Multi-order NMS (boxes.hip): the greedy NMS of launch_nms on ONE box list (n <= 4096 rows, x1y1x2y2) under the Q score columns
+// of scores (n, Q), entry r*Q + q, side by side: picks (Q, max_picks) int32, -1 past counts[q].  Rows with valid[r] == 0 (valid
+// may be null) or a NaN score in column q are no candidates of q.  ws: nms_multi_workspace_bytes(n) of device scratch (the shared
+// suppression bit mask).  n_dev (optional device int32) overrides n at run time (n is then the capacity).
+size_t nms_multi_workspace_bytes(int n);
+hipError_t launch_nms_multi(void* ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
+                            const int32_t* n_dev, int Q, float thresh, int max_picks, int32_t* picks, int32_t* counts,
+                            hipStream_t s);
 // out[i] = src[idx[i]] rows of `width` floats for i < *count (rows >= *count zero-filled up to cap)
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, const int32_t* count, int cap, int width,
                               float* out, hipStream_t s);

@@ -2120,6 +2120,7 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
       {"obj", L.obj, (int64_t)P, 4},
       {"final_trans", L.final_trans, (int64_t)P * 4, 4},
       {"final_boxes", L.final_boxes, (int64_t)P * 4, 4},
+      {"final_x1y1x2y2", L.final_xyxy, (int64_t)P * 4, 4},
       {"seq", L.seq, (int64_t)P * ctx->T, 4},
       {"final_nms_idx", L.picks2, (int64_t)P, 4},
       {"final_nms_count", L.count2, 1, 4},
@@ -2417,6 +2418,27 @@ int dc_op_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms sync: %s", hipGetErrorString(e2));
   return check_fault_word(ctx, "dc_op_nms");
 }
+constexpr int kNmsMultiMax = 4096;       // rows and picks of the multi-order NMS (boxes.hip: one 64-bit word of the removed set per lane)
+int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q, float thresh,
+                    int max_picks, int32_t* picks, int32_t* counts) {
+  OP_PROLOGUE();
+  if (!boxes || !scores || !picks || !counts) return ctx->fail(DC_E_INVALID, "dc_op_nms_multi: null pointer");
+  if (n < 1) return ctx->fail(DC_E_INVALID, "dc_op_nms_multi: n must be >= 1 (got %d)", n);
+  if (Q < 1) return ctx->fail(DC_E_INVALID, "dc_op_nms_multi: Q must be >= 1 (got %d)", Q);
+  if (max_picks < 1 || max_picks > kNmsMultiMax)
+    return ctx->fail(DC_E_INVALID, "dc_op_nms_multi: max_picks must be in 1..%d (got %d)", kNmsMultiMax, max_picks);
+  if (n > kNmsMultiMax)
+    return ctx->fail(DC_E_UNSUPPORTED, "dc_op_nms_multi: %d boxes exceed the %d the per-query scan holds", n, kNmsMultiMax);
+  void* ws = nullptr;
+  HIPCHK(hipMalloc(&ws, nms_multi_workspace_bytes(n)));
+  const hipError_t e = launch_nms_multi(ws, boxes, scores, valid_or_null, n, nullptr, Q, thresh, max_picks, picks, counts, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(ws);
+  prof_collect(ctx);
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "nms_multi launch: %s", hipGetErrorString(e));
+  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms_multi sync: %s", hipGetErrorString(e2));
+  return DC_OK;
+}
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B,
                             int img_h, int img_w, int HH, int WW, float* out, int out_layout) {
   OP_PROLOGUE();
@@ -2502,6 +2524,91 @@ int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   if (K == 0) return DC_OK;
   Lane& L = lane0(ctx);
   return lm_score(ctx, L.stream, L.out_feats, K, queries, Q, Tq, loglik, Q);
+}
+
+// Localising phrases (docs/SEMANTICS.md): the forward of dc_forward_test, then ALL count1 proposal rows -- not only the K the
+// final NMS kept -- scored against the queries (lm_score on L.codes: a row's number does not depend on the rows scored with it,
+// so it is the number dc_score_captions gives that proposal under final_nms_thresh = 0), then one NMS per query, ordered by the
+// query's own column, on the lane's final boxes (launch_nms_multi on L.final_xyxy with the device row count L.count1).  The
+// (n, Q) scores reach the host in lm_score and go up again: n * Q floats, next to nothing beside the scoring itself.
+int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const int32_t* queries, int Q, int Tq,
+                         const dc_localize_opts* opts, dc_result* out, int32_t* count, float* boxes, float* loglik,
+                         float* objectness, int32_t* region) {
+  const char* who = "dc_localize_captions";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!img_chw || !queries || !opts || !out || !count || !boxes || !loglik || !objectness || !region)
+    return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (!(opts->nms_thresh >= 0.f && opts->nms_thresh <= 1.f))
+    return ctx->fail(DC_E_INVALID, "%s: nms_thresh must be in [0, 1] (got %g)", who, (double)opts->nms_thresh);
+  if (opts->max_regions < 1 || opts->max_regions > kNmsMultiMax)
+    return ctx->fail(DC_E_INVALID, "%s: max_regions must be in 1..%d (got %d)", who, kNmsMultiMax, (int)opts->max_regions);
+  if (opts->min_objectness != opts->min_objectness) return ctx->fail(DC_E_INVALID, "%s: min_objectness is NaN", who);
+  DCCHK(check_queries(ctx, queries, Q, Tq, who));
+  if (H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
+  const int P = effective_proposals(ctx, H, W);
+  if (P > kNmsMultiMax)
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a forward of %d proposal rows exceeds the %d the per-query NMS holds; cap num_proposals", who,
+                     P, kNmsMultiMax);
+  DCCHK(forward_batch(ctx, img_chw, 1, H, W, img_on_device, out, out->tokens == nullptr ? MODE_NO_DECODE : MODE_RESULTS));
+  Lane& L = lane0(ctx);
+  const int K = *reinterpret_cast<const int32_t*>(static_cast<const char*>(L.host_stage) + kRecK);
+  if (K > out->capacity)
+    return ctx->fail(DC_E_INVALID, "%s: the image has %d regions but out->capacity is %d", who, K, (int)out->capacity);
+  const int M = opts->max_regions;
+  std::fill(count, count + Q, 0);
+  HIPCHK(hipSetDevice(ctx->device));
+  int32_t n1 = 0;
+  HIPCHK(hipMemcpy(&n1, L.count1, 4, hipMemcpyDeviceToHost));
+  const int n = std::max(0, std::min((int)n1, L.P));
+  if (K == 0 || n == 0) return DC_OK;
+  std::vector<float> ll((size_t)n * Q);
+  DCCHK(lm_score(ctx, L.stream, L.codes, n, queries, Q, Tq, ll.data(), Q));
+  std::vector<float> fb((size_t)n * 4), obj(n);
+  std::vector<int32_t> inv(n, -1), p2(K);
+  HIPCHK(hipMemcpy(fb.data(), L.final_boxes, fb.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(obj.data(), L.obj, obj.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(p2.data(), L.picks2, p2.size() * 4, hipMemcpyDeviceToHost));
+  for (int k = 0; k < K; ++k)
+    if (p2[k] >= 0 && p2[k] < n) inv[p2[k]] = k;              // region: the row of `out` that is the same proposal
+  const bool masked = !(std::isinf(opts->min_objectness) && opts->min_objectness < 0.f);
+  std::vector<uint8_t> vh(masked ? n : 0);
+  for (size_t r = 0; r < vh.size(); ++r) vh[r] = obj[r] >= opts->min_objectness ? 1 : 0;      // (a NaN objectness: invalid)
+  float* sc_d = nullptr; uint8_t* valid_d = nullptr; void* mask_d = nullptr; int32_t *picks_d = nullptr, *counts_d = nullptr;
+  const std::vector<Carve> cv = {{(void**)&sc_d, ll.size() * 4}, {(void**)&valid_d, (size_t)L.P},
+                                 {(void**)&mask_d, nms_multi_workspace_bytes(L.P)}, {(void**)&picks_d, (size_t)Q * M * 4},
+                                 {(void**)&counts_d, (size_t)Q * 4}};
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
+  carve(cv, base);
+  std::vector<int32_t> pk((size_t)Q * M);
+  auto body = [&]() -> int {
+    hipStream_t s = L.stream;
+    HIPCHK(hipMemcpyAsync(sc_d, ll.data(), ll.size() * 4, hipMemcpyHostToDevice, s));
+    if (masked) HIPCHK(hipMemcpyAsync(valid_d, vh.data(), vh.size(), hipMemcpyHostToDevice, s));
+    KCHK(launch_nms_multi(mask_d, L.final_xyxy, sc_d, masked ? valid_d : nullptr, L.P, L.count1, Q, opts->nms_thresh, M, picks_d,
+                          counts_d, s));
+    HIPCHK(hipMemcpyAsync(pk.data(), picks_d, pk.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(count, counts_d, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    return DC_OK;
+  };
+  const int rc = body();
+  const hipError_t e = hipStreamSynchronize(L.stream);
+  hipFree(base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  for (int q = 0; q < Q; ++q)
+    for (int j = 0; j < count[q]; ++j) {
+      const int r = j < M ? pk[(size_t)q * M + j] : -1;
+      if (r < 0 || r >= n) return ctx->fail(DC_E_HIP, "%s: query %d: pick %d of %d is row %d of %d", who, q, j, (int)count[q], r, n);
+      const size_t o = (size_t)q * M + j;
+      std::copy(fb.begin() + (size_t)r * 4, fb.begin() + (size_t)r * 4 + 4, boxes + o * 4);
+      loglik[o] = ll[(size_t)r * Q + q];
+      objectness[o] = obj[r];
+      region[o] = inv[r];
+    }
+  return DC_OK;
 }
 
 static int op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,

@@ -547,12 +547,7 @@ class DenseCapModel:
         captions: strings (encoded by encode_captions) or id rows.  Returns (boxes (K,4) xcycwh, scores (K,), loglik (K,Q)),
         plus the regions' own captions when return_captions."""
         self._push_test_args()
-        if isinstance(captions, np.ndarray) and captions.ndim == 2:
-            q = np.ascontiguousarray(captions, dtype=np.int32)
-        else:
-            caps = [captions] if isinstance(captions, str) else list(captions)
-            width = max_len or max([1] + [len(words_preprocess(c)) if isinstance(c, str) else np.asarray(c).size for c in caps])
-            q = encode_captions(caps, self.idx_to_token, max(1, width))
+        q = self._encode_queries(captions, max_len)
         img = self._check_input(img)
         P = self._capacity(img.shape[1], img.shape[2])
         r, boxes, scores, tokens = self._new_result(P)
@@ -568,6 +563,47 @@ class DenseCapModel:
         if return_captions:
             res = res + (self.decodeSequence(tokens[:K]),)
         return res
+
+    def _encode_queries(self, captions, max_len=None):
+        """strings (encode_captions, max_len words wide or as wide as the longest) or ready (Q, Tq) id rows -> (Q, Tq) int32"""
+        if isinstance(captions, np.ndarray) and captions.ndim == 2:
+            return np.ascontiguousarray(captions, dtype=np.int32)
+        caps = [captions] if isinstance(captions, str) else list(captions)
+        width = max_len or max([1] + [len(words_preprocess(c)) if isinstance(c, str) else np.asarray(c).size for c in caps])
+        return encode_captions(caps, self.idx_to_token, max(1, width))
+
+    def localizeCaptions(self, img, captions, nms_thresh=0.3, max_regions=5, min_objectness=None, return_captions=False):
+        """Localise query phrases (dc_localize_captions; docs/SEMANTICS.md, "Localising phrases"): for every query a greedy NMS
+        ordered by the query's own log-likelihood over ALL proposals of the image, not only the regions the objectness-ordered
+        final NMS kept.  captions as in scoreCaptions; nms_thresh in [0, 1]; max_regions in 1..4096 picks per query;
+        min_objectness: proposals below it are no candidates (None: all are).  Returns (boxes, scores[, captions]) as forward_test
+        gives them and a list with one dict per query, best pick first: {"boxes" (c,4) xcycwh, "loglik" (c,), "objectness" (c,),
+        "region" (c,) int32 -- the row of `boxes` that is the same proposal, -1 if the final NMS dropped it}."""
+        from .ops import check_localize_args
+        opts = check_localize_args(nms_thresh, max_regions, min_objectness)
+        q = self._encode_queries(captions)
+        self._push_test_args()
+        img = self._check_input(img)
+        P = self._capacity(img.shape[1], img.shape[2])
+        r, boxes, scores, tokens = self._new_result(P)
+        if not return_captions:
+            r.tokens = None
+        Q, Tq = q.shape
+        M = opts.max_regions
+        cnt = np.zeros((max(Q, 1),), np.int32)
+        lb = np.zeros((max(Q, 1), M, 4), np.float32); ll = np.zeros((max(Q, 1), M), np.float32)
+        lo = np.zeros((max(Q, 1), M), np.float32); reg = np.full((max(Q, 1), M), -1, np.int32)
+        check(self.ctx.h, self.lib.dc_localize_captions(self.ctx.h, img.ctypes.data, img.shape[1], img.shape[2], 0, q.ctypes.data,
+                                                        Q, Tq, C.byref(opts), C.byref(r), cnt.ctypes.data, lb.ctypes.data,
+                                                        ll.ctypes.data, lo.ctypes.data, reg.ctypes.data),
+              "dc_localize_captions")
+        K = r.K
+        found = [{"boxes": lb[i, :cnt[i]].copy(), "loglik": ll[i, :cnt[i]].copy(), "objectness": lo[i, :cnt[i]].copy(),
+                  "region": reg[i, :cnt[i]].copy()} for i in range(Q)]
+        res = (boxes[:K].copy(), scores[:K].copy())
+        if return_captions:
+            res = res + (self.decodeSequence(tokens[:K]),)
+        return res + (found,)
 
     def sampleCaptions(self, img, num_samples, temperature=1.0, seed=0, want_tokens=True, top_k=0, top_p=1.0,
                        want_sample_logprob=False):

@@ -260,6 +260,44 @@ def nms(ctx, boxes5, overlap, max_boxes=None, valid=None):
     return picks.numpy()[:kk].astype(np.int64)
 
 
+def nms_multi(ctx, boxes, scores, thresh, max_picks, valid=None):
+    """The NMS of `nms` on one box list under Q score columns at once (dc_op_nms_multi): boxes (n,4) x1y1x2y2, scores (n,Q),
+    valid (n) or None.  Column q's candidates are the valid rows whose score in q is not NaN; a row that is no candidate is never
+    picked and never suppresses.  Returns (picks (Q, max_picks) int32 0-based, -1 past the count, counts (Q) int32)."""
+    b = _f32(boxes).reshape(-1, 4)
+    s = _f32(scores)
+    if s.ndim == 1:
+        s = s[:, None]
+    n, Q = s.shape
+    if b.shape[0] != n:
+        raise ValueError("nms_multi: %d boxes but %d score rows" % (b.shape[0], n))
+    M = int(max_picks)
+    bd = ctx.to_device(b); sd = ctx.to_device(s)
+    vd = ctx.to_device(np.ascontiguousarray(valid, dtype=np.uint8)) if valid is not None else None
+    if vd is not None and vd.shape != (n,):
+        raise ValueError("nms_multi: valid must have one entry per box")
+    picks = ctx.empty((max(Q, 1), min(max(M, 1), 4096)), np.int32); cnt = ctx.empty((max(Q, 1),), np.int32)
+    check(ctx.h, ctx.lib.dc_op_nms_multi(ctx.h, bd.ptr, sd.ptr, vd.ptr if vd else None, n, Q, C.c_float(float(np.float32(thresh))),
+                                         M, picks.ptr, cnt.ptr), "dc_op_nms_multi")
+    return picks.numpy(), cnt.numpy()
+
+
+def check_localize_args(nms_thresh, max_regions, min_objectness):
+    """The rules of dc_localize_opts (docs/SEMANTICS.md, "Localising phrases"), checked before the library is called: nms_thresh
+    in [0, 1], max_regions an integer in 1..4096, min_objectness None (= every proposal) or a number that is not NaN.  Returns
+    the filled DcLocalizeOpts."""
+    t = float(np.float32(nms_thresh))
+    if not 0.0 <= t <= 1.0:                                   # NaN fails
+        raise ValueError("nms_thresh must be in [0, 1] (got %r)" % (nms_thresh,))
+    M = int(max_regions)
+    if M != max_regions or not 1 <= M <= 4096:
+        raise ValueError("max_regions must be an integer in 1..4096 (got %r)" % (max_regions,))
+    lo = float("-inf") if min_objectness is None else float(np.float32(min_objectness))
+    if lo != lo:
+        raise ValueError("min_objectness must not be NaN")
+    return _lib.DcLocalizeOpts(t, M, lo)
+
+
 def bilinear_roi_pool(ctx, feat_chw, boxes, img_h, img_w, HH=7, WW=7, out_layout=0):
     """nn.BilinearRoiPooling forward: (C,h,w)+(B,4) -> (B,C,HH,WW) [layout 0] or (B,HH,WW,C) [1]."""
     f = _f32(feat_chw); b = _f32(boxes)

@@ -136,6 +136,24 @@ int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_
  * never graph-replayed; results do not depend on Q, the query order or the chunking.  K > out->capacity is refused. */
 int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
                       const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
+/* Localise phrases (docs/SEMANTICS.md, "Localising phrases"): for every query, the best-fitting boxes among ALL proposals of the
+ * image -- not only the rows the objectness-ordered final NMS kept.  nms_thresh in [0, 1]: the IoU threshold of the per-query
+ * NMS; max_regions = M in 1..4096: picks returned per query; min_objectness: proposals whose raw objectness is below it (or NaN)
+ * are no candidates, -INFINITY = all are.  Anything else (a NaN included) is DC_E_INVALID before any work. */
+typedef struct dc_localize_opts { float nms_thresh; int32_t max_regions; float min_objectness; } dc_localize_opts;
+/* The forward of dc_forward_test (`out` as there; out->tokens == NULL skips the caption decode), then every proposal row is
+ * scored against the queries (rules of dc_score_captions) and, per query, a greedy NMS ordered by that query's log-likelihood
+ * (decreasing; ties: the lower proposal row; a NaN log-likelihood is no candidate) runs over the final boxes of all proposals.
+ * Host outputs, query q's j-th pick (best first) at q*M + j: count (Q); boxes (Q, M, 4) xcycwh in the frame of dc_result.boxes;
+ * loglik (Q, M): the number dc_score_captions returns for that proposal and query under final_nms_thresh = 0, bit for bit;
+ * objectness (Q, M): the raw score; region (Q, M): the row of `out` that is the same proposal, -1 if the final NMS dropped it.
+ * Entries from count[q] on are not written.  The result does not depend on final_nms_thresh, the caption order, lanes or
+ * groups, nor a query's rows on the other queries.  fp32 language model whatever dc_set_math_mode says, never graph-replayed.
+ * DC_E_UNSUPPORTED when a forward of this size has more than 4096 proposal rows (num_proposals = -1 on a large image);
+ * K > out->capacity is refused.  No proposals: every count is 0. */
+int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
+                         const int32_t* queries, int Q, int Tq, const dc_localize_opts* opts, dc_result* out,
+                         int32_t* count, float* boxes, float* loglik, float* objectness, int32_t* region);
 /* Sample captions: LanguageModel:sample with sample_argmax = false (LanguageModel.lua:40-41,328-333).  num_samples = S draws
  * per region (1..256); every word is drawn from SoftMax(scores / temperature), temperature in [0.01, 100], or with
  * temperature 0 (S must then be 1) taken by the greedy rule; seed selects the noise, which is counter-based: a draw depends on
@@ -408,6 +426,14 @@ int dc_op_rpn_decode(dc_ctx* ctx, const float* heads_hwc, int h, int w, int k, c
  * in decreasing score order (ties: lower index first) and their count (device int32). */
 int dc_op_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid, int n,
               float thresh, int max_boxes, int32_t* picks, int32_t* count);
+/* The per-query NMS of dc_localize_captions: dc_op_nms on ONE box list under Q score columns in one pass.  boxes (n,4)
+ * x1y1x2y2, scores (n, Q) entry r*Q + q (the layout dc_op_lm_score writes), valid (n) or NULL.  For every column q the picks of
+ * dc_op_nms with max_boxes = max_picks on the candidates of q -- the rows with valid[r] != 0 whose score in column q is not
+ * NaN; a row that is no candidate is never picked and never suppresses (dc_op_nms ranks a NaN first instead).  picks
+ * (Q, max_picks) int32 0-based, -1 past counts[q]; counts (Q).  1 <= n <= 4096 (more: DC_E_UNSUPPORTED), 1 <= max_picks <= 4096,
+ * Q >= 1.  A column's result does not depend on Q, the other columns or their order.  Device pointers; synchronous. */
+int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q,
+                    float thresh, int max_picks, int32_t* picks, int32_t* counts);
 /* nn.BilinearRoiPooling forward (BilinearRoiPooling.lua:42-60): feat (h,w,C) HWC, boxes (B,4)
  * xcycwh image px -> out.  out_layout 0: (B,C,HH,WW) as the reference; 1: (B,HH,WW,C). */
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes,

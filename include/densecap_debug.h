@@ -22,6 +22,7 @@ int dc_mfma_profile(dc_ctx* ctx, int reset, int64_t* launches, double* total_ms,
 /* Copy an intermediate of the most recent forward to the host for stage-wise parity:
  * name in {"feat_hwc","rpn_heads","rpn_boxes","rpn_x1y1x2y2","rpn_p","rpn_valid",
  * "rpn_nms_idx","rpn_nms_count","roi_boxes","roi_feats","codes","obj","final_trans","final_boxes",
+ * "final_x1y1x2y2" (the corners of "final_boxes" as the final NMS and dc_localize_captions read them),
  * "seq","final_nms_idx","final_nms_count"} (lane 0; "seq" is only filled in the reference caption order),
  * "box_src" (int32, P: after a forward on caller-supplied boxes, the caller's row behind every row of "roi_boxes", -1 past
  * "rpn_nms_count" -- the map before the final NMS),

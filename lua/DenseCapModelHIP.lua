@@ -287,6 +287,44 @@ function Model:scoreCaptions(input, queries)
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), loglik[{{1, K}}]:clone()
 end
 
+-- Localise query phrases (dc_localize_captions; docs/SEMANTICS.md, "Localising phrases"): per query a greedy NMS ordered by the
+-- query's own log-likelihood over ALL proposals of the image.  queries as in scoreCaptions; nms_thresh (default 0.3) in [0, 1];
+-- max_regions (default 5) in 1..4096; min_objectness (nil = every proposal is a candidate).
+-- Returns the boxes, scores and captions forward_test returns, and count: IntTensor (Q); lboxes (Q, M, 4) xcycwh; loglik (Q, M);
+-- objectness (Q, M); region: LongTensor (Q, M), the 1-based row of `boxes` that is the same proposal, 0 if the final NMS
+-- dropped it.  Entries from count[q] on are zero.
+function Model:localizeCaptions(input, queries, nms_thresh, max_regions, min_objectness)
+  self:_push_test_args()
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local o = ffi.new('dc_localize_opts')
+  o.nms_thresh, o.max_regions, o.min_objectness = nms_thresh or 0.3, max_regions or 5, min_objectness or -math.huge
+  local M = o.max_regions
+  assert(o.nms_thresh >= 0 and o.nms_thresh <= 1, 'nms_thresh must be in [0, 1]')
+  assert(M >= 1 and M <= 4096 and M == (max_regions or 5), 'max_regions must be an integer in 1..4096')
+  assert(o.min_objectness == o.min_objectness, 'min_objectness must not be NaN')
+  local img = input:float():contiguous()
+  local q = queries:int():contiguous()
+  local H, W, T = img:size(3), img:size(4), self.seq_length
+  local Q, Tq = q:size(1), q:size(2)
+  local P = self:_capacity(H, W)
+  local boxes, scores = torch.FloatTensor(P, 4), torch.FloatTensor(P, 1)
+  local tokens = torch.IntTensor(P, T)
+  local count, region = torch.IntTensor(Q):zero(), torch.IntTensor(Q, M):fill(-1)
+  local lboxes, loglik, obj = torch.FloatTensor(Q, M, 4):zero(), torch.FloatTensor(Q, M):zero(), torch.FloatTensor(Q, M):zero()
+  local r = ffi.new('dc_result')
+  r.capacity = P
+  r.boxes, r.scores = torch.data(boxes), torch.data(scores)
+  r.tokens = torch.data(tokens)
+  hip.check(self.ctx, C.dc_localize_captions(self.ctx, fptr(img), H, W, 0, torch.data(q), Q, Tq, o, r, torch.data(count),
+                                             torch.data(lboxes), torch.data(loglik), torch.data(obj), torch.data(region)),
+            'dc_localize_captions')
+  local K = r.K
+  local reg1 = region:long():add(1)
+  if K == 0 then return torch.FloatTensor(), torch.FloatTensor(), {}, count, lboxes, loglik, obj, reg1 end
+  local seq = tokens[{{1, K}}]:long()
+  return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq), count, lboxes, loglik, obj, reg1
+end
+
 -- Sample captions (LanguageModel:sample with sample_argmax = false, LanguageModel.lua:40-41,328-333): num_samples draws for
 -- each region forward_test returns, every word drawn from SoftMax(scores / temperature) (temperature default 1; 0 with
 -- num_samples 1 is the greedy rule), noise selected by `seed` (default 0, a non-negative integer below 2^53 from Lua).

@@ -44,6 +44,12 @@ int dc_set_group(dc_ctx* ctx, int images);
 int dc_forward_test(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, dc_result* out);
 int dc_score_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
                       const int32_t* queries, int Q, int Tq, dc_result* out, float* loglik);
+typedef struct dc_localize_opts { float nms_thresh; int32_t max_regions; float min_objectness; } dc_localize_opts;
+int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device,
+                         const int32_t* queries, int Q, int Tq, const dc_localize_opts* opts, dc_result* out,
+                         int32_t* count, float* boxes, float* loglik, float* objectness, int32_t* region);
+int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q,
+                    float thresh, int max_picks, int32_t* picks, int32_t* counts);
 typedef struct dc_sample_opts {
   int32_t num_samples; float temperature; uint64_t seed;
 } dc_sample_opts;
