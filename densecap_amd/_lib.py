@@ -178,6 +178,7 @@ _SIGS = {
     "dc_op_lm_beam_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(DcBeamOpts), C.c_void_p, C.c_void_p]),
     "dc_op_nms_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.c_void_p]),
+    "dc_op_eval_match": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 7),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),

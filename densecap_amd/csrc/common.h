@@ -433,6 +433,13 @@ size_t nms_multi_workspace_bytes(int n);
 hipError_t launch_nms_multi(void* ws, const float* boxes, const float* scores, const uint8_t* valid, int n,
                             const int32_t* n_dev, int Q, float thresh, int max_picks, int32_t* picks, int32_t* counts,
                             hipStream_t s);
+// Evaluation (eval_match.hip): per image, the detections in score order against the merged ground truth; one workgroup an image.
+// max_b / max_m: the largest detection / ground-truth count of any image (<= 4096 / 512), which size the dynamic LDS.  thr: the
+// merge threshold as the double it is compared in.  Outputs are ragged like the inputs (see dc_op_eval_match).
+hipError_t launch_eval_match(const float* det_boxes, const float* det_scores, const int32_t* det_off, const float* gt_boxes,
+                             const int32_t* gt_off, int n_images, int max_b, int max_m, double thr, int claim_last,
+                             int32_t* order, double* ov, int32_t* group, uint8_t* ok, int32_t* gt_group, int32_t* n_groups,
+                             double* merged_boxes, hipStream_t s);
 // out[i] = src[idx[i]] rows of `width` floats for i < *count (rows >= *count zero-filled up to cap)
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, const int32_t* count, int cap, int width,
                               float* out, hipStream_t s);

@@ -2439,6 +2439,54 @@ int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const 
   if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms_multi sync: %s", hipGetErrorString(e2));
   return DC_OK;
 }
+constexpr int kEvalMaxDet = 4096, kEvalMaxGt = 512;   // per image (eval_match.hip: the sort keys and the M x M bit mask live in LDS)
+// The ABI carries the merge threshold as a float, the reference compares doubles against the literal 0.7: the double with the
+// shortest decimal form that reads back as the float (0.7f -> 0.7; docs/SEMANTICS.md, "Evaluation").
+static double eval_merge_threshold(float t) {
+  char buf[40];
+  for (int p = 1; p <= 9; ++p) {
+    snprintf(buf, sizeof buf, "%.*g", p, (double)t);
+    const double d = strtod(buf, nullptr);
+    if ((float)d == t) return d;
+  }
+  return (double)t;
+}
+int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_scores, const int32_t* det_off, const float* gt_boxes,
+                     const int32_t* gt_off, int n_images, float merge_thresh, int flags, int32_t* order, double* ov, int32_t* group,
+                     uint8_t* ok, int32_t* gt_group, int32_t* n_groups, double* merged_boxes) {
+  OP_PROLOGUE();
+  if (!det_boxes || !det_scores || !det_off || !gt_boxes || !gt_off || !order || !ov || !group || !ok || !gt_group || !n_groups ||
+      !merged_boxes)
+    return ctx->fail(DC_E_INVALID, "dc_op_eval_match: null pointer");
+  if (n_images < 1) return ctx->fail(DC_E_INVALID, "dc_op_eval_match: n_images must be >= 1 (got %d)", n_images);
+  if (!(merge_thresh > 0.f && merge_thresh <= 1.f))
+    return ctx->fail(DC_E_INVALID, "dc_op_eval_match: merge_thresh must be in (0, 1] (got %g)", (double)merge_thresh);
+  if (flags & ~DC_EVAL_CLAIM_LAST) return ctx->fail(DC_E_INVALID, "dc_op_eval_match: unknown flag bits 0x%x", flags);
+  // the offsets decide the launch: read them back first (the call is synchronous anyway)
+  std::vector<int32_t> off(2 * ((size_t)n_images + 1));
+  HIPCHK(hipMemcpyAsync(off.data(), det_off, ((size_t)n_images + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(off.data() + n_images + 1, gt_off, ((size_t)n_images + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int max_b = 0, max_m = 0;
+  for (int which = 0; which < 2; ++which) {
+    const int32_t* o = off.data() + (size_t)which * (n_images + 1);
+    if (o[0] < 0) return ctx->fail(DC_E_INVALID, "dc_op_eval_match: %s[0] is negative", which ? "gt_off" : "det_off");
+    for (int i = 0; i < n_images; ++i) {
+      if (o[i + 1] < o[i])
+        return ctx->fail(DC_E_INVALID, "dc_op_eval_match: %s decreases at image %d", which ? "gt_off" : "det_off", i);
+      int& mx = which ? max_m : max_b;
+      mx = std::max(mx, (int)(o[i + 1] - o[i]));
+    }
+  }
+  if (max_b > kEvalMaxDet)
+    return ctx->fail(DC_E_UNSUPPORTED, "dc_op_eval_match: %d detections in one image exceed the %d the sort holds", max_b, kEvalMaxDet);
+  if (max_m > kEvalMaxGt)
+    return ctx->fail(DC_E_UNSUPPORTED, "dc_op_eval_match: %d ground-truth boxes in one image exceed the %d the merge holds", max_m,
+                     kEvalMaxGt);
+  KCHK(launch_eval_match(det_boxes, det_scores, det_off, gt_boxes, gt_off, n_images, max_b, max_m, eval_merge_threshold(merge_thresh),
+                         (flags & DC_EVAL_CLAIM_LAST) ? 1 : 0, order, ov, group, ok, gt_group, n_groups, merged_boxes, s));
+  OP_EPILOGUE();
+}
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B,
                             int img_h, int img_w, int HH, int WW, float* out, int out_layout) {
   OP_PROLOGUE();

@@ -2,8 +2,8 @@
 extract_features.lua:92-96) -- the image has no h5py.
 
 Writes the classic, universally readable layout of the HDF5 file-format specification (version 1.8 "III. Disk Format"):
-superblock v0; root group = v1 object header with a Symbol Table message -> v1 B-tree (one leaf) -> one symbol-table
-node (SNOD) + local heap with the link names; every dataset = v1 object header {Dataspace v1, Datatype (IEEE little
+superblock v0; root group = v1 object header with a Symbol Table message -> v1 B-tree (one leaf) -> symbol-table
+nodes (SNOD, eight names each) + local heap with the link names; every dataset = v1 object header {Dataspace v1, Datatype (IEEE little
 endian float / fixed-point), Fill Value v2, Data Layout v3 contiguous} followed by its raw data, C order.  No chunking,
 compression, attributes or nested groups.  Files are checked against libhdf5 itself in tests/test_hdf5.py when the
 library is present (it is in this image, under /opt/conda/lib), and with the small reader below everywhere.
@@ -51,8 +51,10 @@ def _object_header(messages):
 def write_hdf5(path, datasets):
     """datasets: {name: ndarray} (float32/float64/ints), written as contiguous datasets of the root group."""
     names = sorted(datasets)                    # symbol-table entries are ordered by name
-    if not names or len(names) > 2 * LEAF_K:
-        raise ValueError("hdf5_min: between 1 and %d datasets" % (2 * LEAF_K))
+    if not names or len(names) > 2 * LEAF_K * 2 * INTERNAL_K:
+        raise ValueError("hdf5_min: between 1 and %d datasets" % (2 * LEAF_K * 2 * INTERNAL_K))
+    # one symbol-table node holds 2 * LEAF_K entries; the B-tree leaf points at up to 2 * INTERNAL_K nodes
+    nodes = [names[i:i + 2 * LEAF_K] for i in range(0, len(names), 2 * LEAF_K)]
     arrays = {}
     for n in names:
         if "/" in n or not n:
@@ -77,7 +79,7 @@ def write_hdf5(path, datasets):
     addr_heap_data = addr_heap + 32
     addr_snod = addr_heap_data + len(heap)
     snod_size = 8 + 2 * LEAF_K * 40
-    cur = addr_snod + snod_size
+    cur = addr_snod + snod_size * len(nodes)
     ds_headers, ds_addr = {}, {}
     for n in names:
         a = arrays[n]
@@ -98,14 +100,18 @@ def write_hdf5(path, datasets):
                   struct.pack("<QQQQ", 0, UNDEF, eof, UNDEF) + root_entry)
     assert len(superblock) == sb_size
     root_oh = _object_header([_message(0x0011, struct.pack("<QQ", addr_btree, addr_heap))])
-    # B-tree leaf: node type 0 (group), level 0, one child; key0 = "" (heap offset 0), key1 = the largest name in the child
-    btree = b"TREE" + struct.pack("<BBHQQ", 0, 0, 1, UNDEF, UNDEF) + struct.pack("<QQQ", 0, addr_snod, name_off[names[-1]])
+    # B-tree leaf: node type 0 (group), level 0; key0 = "" (heap offset 0), then per child its address and the largest name in it
+    btree = b"TREE" + struct.pack("<BBHQQ", 0, 0, len(nodes), UNDEF, UNDEF) + struct.pack("<Q", 0)
+    for k, node in enumerate(nodes):
+        btree += struct.pack("<QQ", addr_snod + k * snod_size, name_off[node[-1]])
     btree += b"\x00" * (btree_size - len(btree))
     heap_hdr = b"HEAP" + struct.pack("<B3xQQQ", 0, len(heap), free_off, addr_heap_data)
-    snod = b"SNOD" + struct.pack("<BBH", 1, 0, len(names))
-    for n in names:
-        snod += struct.pack("<QQII16x", name_off[n], ds_addr[n][0], 0, 0)
-    snod += b"\x00" * (snod_size - len(snod))
+    snod = b""
+    for node in nodes:
+        one = b"SNOD" + struct.pack("<BBH", 1, 0, len(node))
+        for n in node:
+            one += struct.pack("<QQII16x", name_off[n], ds_addr[n][0], 0, 0)
+        snod += one + b"\x00" * (snod_size - len(one))
     with open(path, "wb") as f:
         f.write(superblock); f.write(root_oh); f.write(btree); f.write(heap_hdr); f.write(bytes(heap)); f.write(snod)
         for n in names:
@@ -117,44 +123,63 @@ def write_hdf5(path, datasets):
     return path
 
 
-def read_hdf5(path):
-    """Reads back files of the layout above (superblock v0, one symbol-table node, contiguous datasets) -> {name: ndarray}."""
-    buf = open(path, "rb").read()
-    if buf[:8] != SIGNATURE or buf[8] != 0:
-        raise ValueError("hdf5_min: not a superblock-v0 HDF5 file")
-    addr_btree, addr_heap = struct.unpack_from("<QQ", buf, 56 + 24)
-    if buf[addr_btree:addr_btree + 4] != b"TREE" or buf[addr_heap:addr_heap + 4] != b"HEAP":
-        raise ValueError("hdf5_min: bad root group")
-    _, _, heap_data = struct.unpack_from("<QQQ", buf, addr_heap + 8)
-    level, nent = struct.unpack_from("<BH", buf, addr_btree + 5)
-    if level != 0:
-        raise ValueError("hdf5_min: multi-level group B-tree not supported")
-    out = {}
-    for c in range(nent):
-        snod = struct.unpack_from("<Q", buf, addr_btree + 24 + 8 + c * 16)[0]
-        if buf[snod:snod + 4] != b"SNOD":
-            raise ValueError("hdf5_min: bad symbol table node")
-        nsym = struct.unpack_from("<H", buf, snod + 6)[0]
-        for i in range(nsym):
-            noff, oh = struct.unpack_from("<QQ", buf, snod + 8 + i * 40)
-            name = buf[heap_data + noff:buf.index(b"\x00", heap_data + noff)].decode("ascii")
-            nmsg, = struct.unpack_from("<H", buf, oh + 2)
-            p = oh + 16
-            shape = dtype = addr = nbytes = None
-            for _ in range(nmsg):
-                mtype, msize = struct.unpack_from("<HH", buf, p)
-                d = p + 8
-                if mtype == 0x0001:
-                    rank = buf[d + 1]
-                    shape = struct.unpack_from("<%dQ" % rank, buf, d + 8)
-                elif mtype == 0x0003:
-                    cls, bits0 = buf[d] & 0x0F, buf[d + 1]
-                    size = struct.unpack_from("<I", buf, d + 4)[0]
-                    dtype = np.dtype("<f%d" % size) if cls == 1 else np.dtype("<%s%d" % ("i" if bits0 & 0x08 else "u", size))
-                elif mtype == 0x0008:
-                    if buf[d] != 3 or buf[d + 1] != 1:
-                        raise ValueError("hdf5_min: only contiguous v3 layouts")
-                    addr, nbytes = struct.unpack_from("<QQ", buf, d + 2)
-                p = d + msize
-            out[name] = np.frombuffer(buf, dtype, count=nbytes // dtype.itemsize, offset=addr).reshape(shape).copy()
-    return out
+def read_hdf5(path, names=None):
+    """Reads back files of the layout above (superblock v0, a one-level group B-tree, contiguous datasets) -> {name: ndarray}.
+    names: only these datasets (a missing one is a KeyError); the file is then not loaded whole -- the metadata is read where it
+    lies and the reader seeks to each dataset asked for (a dataset file's `/images` can be tens of gigabytes)."""
+    with open(path, "rb") as f:
+        def at(addr, n):
+            f.seek(addr)
+            b = f.read(n)
+            if len(b) != n:
+                raise ValueError("hdf5_min: file ends inside a structure")
+            return b
+        sb = at(0, 96)
+        if sb[:8] != SIGNATURE or sb[8] != 0:
+            raise ValueError("hdf5_min: not a superblock-v0 HDF5 file")
+        addr_btree, addr_heap = struct.unpack_from("<QQ", sb, 56 + 24)
+        if at(addr_btree, 4) != b"TREE" or at(addr_heap, 4) != b"HEAP":
+            raise ValueError("hdf5_min: bad root group")
+        heap_size, _, heap_data = struct.unpack("<QQQ", at(addr_heap + 8, 24))
+        heap = at(heap_data, heap_size)
+        level, nent = struct.unpack("<BH", at(addr_btree + 5, 3))
+        if level != 0:
+            raise ValueError("hdf5_min: multi-level group B-tree not supported")
+        want = None if names is None else set(names)
+        out = {}
+        for c in range(nent):
+            snod = struct.unpack("<Q", at(addr_btree + 24 + 8 + c * 16, 8))[0]
+            head = at(snod, 8)
+            if head[:4] != b"SNOD":
+                raise ValueError("hdf5_min: bad symbol table node")
+            nsym = struct.unpack_from("<H", head, 6)[0]
+            entries = at(snod + 8, nsym * 40)
+            for i in range(nsym):
+                noff, oh = struct.unpack_from("<QQ", entries, i * 40)
+                name = heap[noff:heap.index(b"\x00", noff)].decode("ascii")
+                if want is not None and name not in want:
+                    continue
+                nmsg, = struct.unpack("<H", at(oh + 2, 2))
+                hsize, = struct.unpack("<I", at(oh + 8, 4))
+                buf = at(oh + 16, hsize)
+                p = 0
+                shape = dtype = addr = nbytes = None
+                for _ in range(nmsg):
+                    mtype, msize = struct.unpack_from("<HH", buf, p)
+                    d = p + 8
+                    if mtype == 0x0001:
+                        rank = buf[d + 1]
+                        shape = struct.unpack_from("<%dQ" % rank, buf, d + 8)
+                    elif mtype == 0x0003:
+                        cls, bits0 = buf[d] & 0x0F, buf[d + 1]
+                        size = struct.unpack_from("<I", buf, d + 4)[0]
+                        dtype = np.dtype("<f%d" % size) if cls == 1 else np.dtype("<%s%d" % ("i" if bits0 & 0x08 else "u", size))
+                    elif mtype == 0x0008:
+                        if buf[d] != 3 or buf[d + 1] != 1:
+                            raise ValueError("hdf5_min: only contiguous v3 layouts")
+                        addr, nbytes = struct.unpack_from("<QQ", buf, d + 2)
+                    p = d + msize
+                out[name] = np.frombuffer(at(addr, nbytes), dtype, count=nbytes // dtype.itemsize).reshape(shape).copy()
+        if want is not None and want - set(out):
+            raise KeyError("hdf5_min: %s has no dataset %s" % (path, ", ".join(sorted(want - set(out)))))
+        return out

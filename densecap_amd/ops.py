@@ -282,6 +282,46 @@ def nms_multi(ctx, boxes, scores, thresh, max_picks, valid=None):
     return picks.numpy(), cnt.numpy()
 
 
+DC_EVAL_CLAIM_LAST = 1
+
+
+def eval_match(ctx, det_boxes, det_scores, gt_boxes, merge_thresh=0.7, claim_last=True):
+    """DenseCaptioningEvaluator:addResult's matching for a list of images in one launch (dc_op_eval_match; docs/SEMANTICS.md,
+    "Evaluation").  det_boxes[i] (B_i,4) xcycwh, det_scores[i] (B_i), gt_boxes[i] (M_i,4) xcycwh, one entry per image.  Returns
+    one dict per image: order (B) int32 -- the detection at every rank of the score order --, ov (B) float64, group (B) int32
+    (-1 = overlaps nothing), ok (B) uint8, all by rank; gt_group (M) int32, n_groups, merged (n_groups,4) float64 x1y1x2y2."""
+    n = len(det_boxes)
+    if len(det_scores) != n or len(gt_boxes) != n:
+        raise ValueError("eval_match: one box list, score list and ground-truth list per image")
+    db = [_f32(b).reshape(-1, 4) for b in det_boxes]
+    ds = [_f32(s).reshape(-1) for s in det_scores]
+    gb = [_f32(b).reshape(-1, 4) for b in gt_boxes]
+    for i in range(n):
+        if len(db[i]) != len(ds[i]):
+            raise ValueError("eval_match: image %d has %d boxes but %d scores" % (i, len(db[i]), len(ds[i])))
+    doff = np.concatenate([[0], np.cumsum([len(b) for b in db])]).astype(np.int32)
+    goff = np.concatenate([[0], np.cumsum([len(b) for b in gb])]).astype(np.int32)
+    BT, MT = int(doff[-1]), int(goff[-1])
+    cat = lambda lst, shape: np.concatenate(lst, 0) if lst else np.zeros(shape, np.float32)
+    dbd = ctx.to_device(cat(db, (0, 4))); dsd = ctx.to_device(cat(ds, (0,))); gbd = ctx.to_device(cat(gb, (0, 4)))
+    doffd = ctx.to_device(doff); goffd = ctx.to_device(goff)
+    order = ctx.empty((BT,), np.int32); ov = ctx.empty((BT,), np.float64); group = ctx.empty((BT,), np.int32)
+    ok = ctx.empty((BT,), np.uint8); gt_group = ctx.empty((MT,), np.int32); ng = ctx.empty((max(n, 1),), np.int32)
+    merged = ctx.empty((MT, 4), np.float64)
+    flags = DC_EVAL_CLAIM_LAST if claim_last else 0
+    check(ctx.h, ctx.lib.dc_op_eval_match(ctx.h, dbd.ptr, dsd.ptr, doffd.ptr, gbd.ptr, goffd.ptr, n,
+                                          C.c_float(float(np.float32(merge_thresh))), flags, order.ptr, ov.ptr, group.ptr, ok.ptr,
+                                          gt_group.ptr, ng.ptr, merged.ptr), "dc_op_eval_match")
+    order, ov, group, ok, gt_group, ng, merged = (a.numpy() for a in (order, ov, group, ok, gt_group, ng, merged))
+    out = []
+    for i in range(n):
+        d0, d1, g0, g1 = int(doff[i]), int(doff[i + 1]), int(goff[i]), int(goff[i + 1])
+        G = int(ng[i])
+        out.append(dict(order=order[d0:d1], ov=ov[d0:d1], group=group[d0:d1], ok=ok[d0:d1], gt_group=gt_group[g0:g1], n_groups=G,
+                        merged=merged[g0:g0 + G], merged_tail=merged[g0 + G:g1]))
+    return out
+
+
 def check_localize_args(nms_thresh, max_regions, min_objectness):
     """The rules of dc_localize_opts (docs/SEMANTICS.md, "Localising phrases"), checked before the library is called: nms_thresh
     in [0, 1], max_regions an integer in 1..4096, min_objectness None (= every proposal) or a number that is not NaN.  Returns

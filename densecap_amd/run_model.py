@@ -412,6 +412,24 @@ class ImagePipeline:
         return False
 
 
+def load_weights(opt):
+    """-synthetic_weights / -checkpoint -> the weights dict DenseCapModel takes (shared with evaluate_model)."""
+    if opt.synthetic_weights:
+        from .weights import make_synthetic_weights
+        return make_synthetic_weights()
+    from . import t7
+    if not os.path.exists(opt.checkpoint):
+        raise SystemExit("checkpoint %s not found (use -synthetic_weights 1 for random weights)" % opt.checkpoint)
+    try:
+        ck = t7.load(opt.checkpoint)
+    except t7.T7FormatError as e:
+        # the two checks that rest on torch.save's habits (object numbering, nothing after the object) must not lock a
+        # user out of an unusual but well-formed file: say so and read it again with only the bounds checks on
+        print("warning: %s -- reading %s again without the writer-habit checks" % (e, opt.checkpoint), file=sys.stderr)
+        ck = t7.load(opt.checkpoint, strict=False)
+    return t7.weights_from_checkpoint(ck)
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     from . import DenseCapModel, ops
@@ -427,21 +445,7 @@ def main(argv=None):
                              "ops.lm_beam_n)")
     elif opt.n_best or opt.length_alpha:
         raise SystemExit("-n_best / -length_alpha belong to -num_beams")
-    if opt.synthetic_weights:
-        from .weights import make_synthetic_weights
-        weights = make_synthetic_weights()
-    else:
-        from . import t7
-        if not os.path.exists(opt.checkpoint):
-            raise SystemExit("checkpoint %s not found (use -synthetic_weights 1 for random weights)" % opt.checkpoint)
-        try:
-            ck = t7.load(opt.checkpoint)
-        except t7.T7FormatError as e:
-            # the two checks that rest on torch.save's habits (object numbering, nothing after the object) must not lock a
-            # user out of an unusual but well-formed file: say so and read it again with only the bounds checks on
-            print("warning: %s -- reading %s again without the writer-habit checks" % (e, opt.checkpoint), file=sys.stderr)
-            ck = t7.load(opt.checkpoint, strict=False)
-        weights = t7.weights_from_checkpoint(ck)
+    weights = load_weights(opt)
     if opt.num_samples:
         try:                               # at start-up, not at the image whose seed would leave the range
             ops.check_sample_args(opt.num_samples, opt.temperature, opt.sample_seed, opt.top_k, opt.top_p)

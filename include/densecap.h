@@ -434,6 +434,23 @@ int dc_op_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_
  * Q >= 1.  A column's result does not depend on Q, the other columns or their order.  Device pointers; synchronous. */
 int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q,
                     float thresh, int max_picks, int32_t* picks, int32_t* counts);
+/* DenseCaptioningEvaluator:addResult (eval/eval_utils.lua:148-221) for n_images images in one launch; rules in docs/SEMANTICS.md,
+ * "Evaluation".  Ragged: image i's detections are rows det_off[i] .. det_off[i+1]-1 of det_boxes (xcycwh) / det_scores, its
+ * ground truth rows gt_off[i] .. gt_off[i+1]-1 of gt_boxes (xcycwh); both offset lists have n_images + 1 entries, start at >= 0
+ * and do not decrease.  The ground truth is merged (IoU >= merge_thresh, the reference's 0.7), the detections are taken in
+ * decreasing score (ties: lower index; NaN last) and claim the merged box they overlap most.  Per image, d = rank in score
+ * order, at det_off[i] + d: order (the detection's index within the image), ov (float64), group (0-based merged box, -1 = none),
+ * ok (1 = the claimed group was still free).  At gt_off[i] + j: gt_group (the group of ground-truth box j); at gt_off[i] + g:
+ * merged_boxes (4 float64 x1y1x2y2 of group g; rows from n_groups[i] on are zero).  n_groups (n_images).
+ * flags: DC_EVAL_CLAIM_LAST = a detection that overlaps nothing claims the LAST group (the reference's used[-1]); without it
+ * such a detection claims nothing and has ok = 0.  <= 4096 detections and <= 512 ground-truth boxes per image
+ * (DC_E_UNSUPPORTED beyond); n_images < 1, merge_thresh NaN or outside (0, 1], unknown flag bits, offsets that are negative or
+ * decrease: DC_E_INVALID.  All refusals come before any launch.  Device pointers; synchronous. */
+#define DC_EVAL_CLAIM_LAST 1
+int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_scores, const int32_t* det_off,
+                     const float* gt_boxes, const int32_t* gt_off, int n_images, float merge_thresh, int flags,
+                     int32_t* order, double* ov, int32_t* group, uint8_t* ok,
+                     int32_t* gt_group, int32_t* n_groups, double* merged_boxes);
 /* nn.BilinearRoiPooling forward (BilinearRoiPooling.lua:42-60): feat (h,w,C) HWC, boxes (B,4)
  * xcycwh image px -> out.  out_layout 0: (B,C,HH,WW) as the reference; 1: (B,HH,WW,C). */
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes,

@@ -50,6 +50,10 @@ int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int im
                          int32_t* count, float* boxes, float* loglik, float* objectness, int32_t* region);
 int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q,
                     float thresh, int max_picks, int32_t* picks, int32_t* counts);
+int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_scores, const int32_t* det_off,
+                     const float* gt_boxes, const int32_t* gt_off, int n_images, float merge_thresh, int flags,
+                     int32_t* order, double* ov, int32_t* group, uint8_t* ok,
+                     int32_t* gt_group, int32_t* n_groups, double* merged_boxes);
 typedef struct dc_sample_opts {
   int32_t num_samples; float temperature; uint64_t seed;
 } dc_sample_opts;
