@@ -67,6 +67,30 @@ class DcLocalizeOpts(C.Structure):
     _fields_ = [("nms_thresh", C.c_float), ("max_regions", C.c_int32), ("min_objectness", C.c_float)]
 
 
+class DcLossOpts(C.Structure):
+    """dc_loss_opts: the settings of the training forward (the sampler's and the five loss weights)."""
+    _fields_ = [("batch_size", C.c_int32), ("high_thresh", C.c_float), ("low_thresh", C.c_float), ("remove_outbounds", C.c_int32),
+                ("mid_box_reg_weight", C.c_float), ("mid_objectness_weight", C.c_float), ("end_box_reg_weight", C.c_float),
+                ("end_objectness_weight", C.c_float), ("captioning_weight", C.c_float), ("seed", C.c_uint64)]
+
+
+class DcSamplerForced(C.Structure):
+    """dc_sampler_forced: host lists of ranks that take the place of the sampler's draws."""
+    _fields_ = [("pos_sample_idx", c_int32_p), ("num_pos", C.c_int32), ("neg_sample_idx", c_int32_p), ("num_neg", C.c_int32)]
+
+
+class DcLosses(C.Structure):
+    """dc_losses: the six validation losses of one image and the sampler's counts."""
+    _fields_ = ([(n, C.c_double) for n in ("mid_objectness_loss", "mid_box_reg_loss", "end_objectness_loss", "end_box_reg_loss",
+                                           "captioning_loss", "total_loss")] +
+                [(n, C.c_int32) for n in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")])
+
+
+class DcLossDump(C.Structure):
+    """dc_loss_dump: host buffers (batch_size int32 each) for the sampler's three lists."""
+    _fields_ = [("pos_input_idx", c_int32_p), ("pos_target_idx", c_int32_p), ("neg_input_idx", c_int32_p)]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -179,6 +203,10 @@ _SIGS = {
     "dc_op_nms_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "dc_op_eval_match": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 7),
+    "dc_op_box_sampler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DcLossOpts),
+                                    C.POINTER(DcSamplerForced)] + [C.c_void_p] * 6),
+    "dc_forward_losses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump)]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),

@@ -440,6 +440,37 @@ hipError_t launch_eval_match(const float* det_boxes, const float* det_scores, co
                              const int32_t* gt_off, int n_images, int max_b, int max_m, double thr, int claim_last,
                              int32_t* order, double* ov, int32_t* group, uint8_t* ok, int32_t* gt_group, int32_t* n_groups,
                              double* merged_boxes, hipStream_t s);
+// nn.BoxSampler (train_losses.hip; docs/SEMANTICS.md, "Validation losses"): match the A inputs against the G <= 512 ground-truth
+// boxes, assign positives and negatives, draw.  Outputs as dc_op_box_sampler documents them; ws: box_sampler_ws_bytes(A, G) of
+// device scratch.  forced_pos / forced_neg: device lists of 0-based ranks in the class's ascending candidate list, or null.
+struct BoxSamplerArgs {
+  const float* boxes; const float* gt; int A, G;
+  float x_max, y_max; int bounds;
+  float high, low; int batch; uint32_t seed_lo, seed_hi;
+  const int32_t* forced_pos; int n_forced_pos;
+  const int32_t* forced_neg; int n_forced_neg;
+  int32_t *pos_input_idx, *pos_target_idx, *neg_input_idx, *counts;
+  float* max_iou_user; int32_t* arg_user;
+  void* ws;
+};
+size_t box_sampler_ws_bytes(int A, int G);
+hipError_t launch_box_sampler(const BoxSamplerArgs& a, hipStream_t s);
+// The RPN's raw two-class scores as (k*h*w, 2) rows in ReshapeBoxFeatures order, read from the heads buffer (channel 4k + 2a + d)
+hipError_t launch_rpn_score_rows(const float* heads, int h, int w, int k, float* out, hipStream_t s);
+// The five criteria and their total (train_losses.hip), one workgroup, every sum a fixed tree of doubles over the sampled rows:
+// scores (A,2), anchors / trans (A,4) of the RPN; the sampler's lists; gt (G,4); roi_boxes / final_trans (n,4) and obj (n) of the
+// n = num_pos + num_neg <= 1024 sampled rows, positives first; rowlik (num_pos) the rows' caption log-likelihoods; L the label
+// width.  out: six doubles (mid objectness, mid box, end objectness, end box, captioning, total); out_masked: rows masked in the
+// two box terms.
+struct LossTermArgs {
+  const float *scores, *anchors, *trans, *gt, *roi_boxes, *final_trans, *obj;
+  const int32_t *pos_input_idx, *pos_target_idx, *neg_input_idx;
+  const double* rowlik;
+  int num_pos, num_neg, L;
+  float w_mid_box, w_mid_obj, w_end_box, w_end_obj, w_cap;
+  double* out; int32_t* out_masked;
+};
+hipError_t launch_loss_terms(const LossTermArgs& a, hipStream_t s);
 // out[i] = src[idx[i]] rows of `width` floats for i < *count (rows >= *count zero-filled up to cap)
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, const int32_t* count, int cap, int width,
                               float* out, hipStream_t s);

@@ -216,6 +216,14 @@ struct dc_ctx {
   DevBuf pre_taps;                  // ... and the tap tables of the sizes in pre_key, kept while the sizes repeat (webcam frames)
   std::vector<char> pre_taps_host;  // (the host copy outlives its asynchronous upload)
   int pre_key[4] = {0, 0, 0, 0};    // H0, W0, oh, ow the tables were made for
+  // dc_forward_losses: its scratch (grow only) and what the last call left there for dc_debug_fetch "loss_*"
+  DevBuf loss_ws;
+  struct LossKeep {
+    const float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr;
+    const double* rowlik = nullptr;
+    int A = 0, n = 0, num_pos = 0;
+    float stage_ms[5] = {0, 0, 0, 0, 0};
+  } loss_keep;
   // MFMA profile
   bool prof = false;
   std::vector<ProfEvt> prof_pending;
@@ -988,6 +996,61 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
   return lm_rows_finish(ctx, s, w, body(), "lm_score");
 }
 
+// Paired teacher-forced scoring (dc_forward_losses): n rows, row r scored against ITS OWN label row lab[r*L .. r*L+L) (words, then
+// zeros), out[r] = the row's double sum -- the number lm_score forms for that (code, caption) pair, from the same pieces: the rows
+// are permuted by caption length, longest first (stable), their codes gathered in that order, so that the rows still alive at a
+// step are a prefix as lm_score's queries are; one item of n rows, tgt[(j-1)*n + row] the row's own target.  `plan`: the rows
+// every GEMM is planned on (<= kScorePlanRows: the sequential-K kernels, see lm_rows_plan).  `lab` host, validated.
+int lm_score_paired(dc_ctx* ctx, hipStream_t s, const float* codes, int n, int plan, const int32_t* lab, int L, double* out) {
+  const int Hd = ctx->Hd, V1 = ctx->V + 1, D = ctx->D;
+  const int nslots = ctx->V1pad / 32, ld = 2 * nslots + 1;
+  std::vector<int> len(n), order(n);
+  for (int r = 0; r < n; ++r) {
+    int l = 0;
+    while (l < L && lab[(size_t)r * L + l] != 0) ++l;
+    len[r] = l;
+    order[r] = r;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+  const int steps = len[order[0]] + 1;
+  Fp32Guard fp32(ctx->cfg);
+  LmRows w;
+  lm_rows_plan(w, n, 1, 0, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps * 4);
+  w.plan = std::min(plan, kScorePlanRows);
+  int32_t* ints = nullptr;      // the rows' targets step by step, then the permutation and the row count
+  float* gcodes = nullptr;
+  const size_t n_tgt = (size_t)n * steps;
+  DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&ints, (n_tgt + n + 1) * 4}, {(void**)&gcodes, (size_t)n * D * 4}}));
+  std::vector<int32_t> th(n_tgt + n + 1, 0);
+  auto body = [&]() -> int {
+    for (int j = 1; j <= steps; ++j)
+      for (int i = 0; i < n; ++i) {
+        const int r = order[i];
+        if (len[r] + 1 < j) break;
+        th[(size_t)(j - 1) * n + i] = j <= len[r] ? lab[(size_t)r * L + j - 1] : V1;
+      }
+    for (int i = 0; i < n; ++i) th[n_tgt + i] = order[i];
+    th[n_tgt + n] = n;
+    HIPCHK(hipMemcpyAsync(ints, th.data(), th.size() * 4, hipMemcpyHostToDevice, s));
+    KCHK(launch_gather_rows(codes, ints + n_tgt, ints + n_tgt + n, n, D, gcodes, s));
+    DCCHK(lm_start_state(ctx, s, gcodes, n, w.enc, w.g0, w.c0, w.h0, w.plan, nullptr, Ws()));
+    DCCHK(lm_chunk_begin(ctx, s, w, 1, ints, th));
+    int alive = n;
+    for (int j = 1; j <= steps; ++j) {
+      while (alive > 0 && len[order[alive - 1]] + 1 < j) --alive;
+      const bool last = j == steps;
+      GemmDesc v = decode_step_desc(ctx, w.h, alive, w.plan, last, w.gates);
+      v.amax_val = w.part; v.amax_ld = ld; v.rowidx = ints + (size_t)(j - 1) * n;
+      DCCHK(run_gemm(ctx, v, s));
+      KCHK(launch_lse_step_tail(w.part, nslots, ld, v.rowidx, V1, ctx->xg, last ? nullptr : w.gates, w.c, w.h, w.acc, alive, Hd, s));
+    }
+    DCCHK(lm_chunk_end(ctx, s, w, 1));
+    for (int i = 0; i < n; ++i) out[order[i]] = w.acc_host[i];
+    return DC_OK;
+  };
+  return lm_rows_finish(ctx, s, w, body(), "lm_score_paired");
+}
+
 // the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
 int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
   if (o == nullptr) return ctx->fail(DC_E_INVALID, "%s: null options", who);
@@ -1154,6 +1217,29 @@ int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int p
   return DC_OK;
 }
 
+// The VGG-16 trunk (DenseCapModel.lua:73-76) of the g images at L.img, on the lane's stream: L.feat = conv5_3's map, (*fh, *fw)
+// its size.  Shared by the test-time forward (enqueue_body) and the training forward of dc_forward_losses.
+int enqueue_trunk(dc_ctx* ctx, Lane& L, int g, int* fh, int* fw) {
+  hipStream_t s = L.stream;
+  int h = L.H, w = L.W, cur = 0;
+  KCHK(launch_conv3x3_c3(L.img, ctx->conv_w[0], ctx->conv_b[0], L.act[0], g, h, w, 64, 1, s));
+  for (int i = 1; i < DC_NUM_VGG_CONVS; ++i) {
+    if (kVgg[i].pool_after) {
+      // conv + ReLU + ceil-mode 2x2 pool in one launch
+      DCCHK(conv3x3_pool(ctx, s, L.act[cur], ctx->conv_w[i], ctx->conv_b[i], L.act[cur ^ 1], g, h, w, kVgg[i].cin,
+                         kVgg[i].cout, 1, lane_ws(L)));
+      h = (h + 1) / 2; w = (w + 1) / 2;
+    } else {
+      DCCHK(conv3x3(ctx, s, L.act[cur], ctx->conv_w[i], ctx->conv_b[i], L.act[cur ^ 1], g, h, w, kVgg[i].cin,
+                    kVgg[i].cout, 1, lane_ws(L)));
+    }
+    cur ^= 1;
+  }
+  L.feat = L.act[cur];
+  *fh = h; *fw = w;
+  return DC_OK;
+}
+
 // Enqueue the whole forward of a GROUP of g images (laid out back to back at `img`) on the lane's stream (no host
 // sync).  The dense stages run once for the whole group -- the convolutions over g images, fc6/fc7, heads and the
 // decode over g*P RoI rows -- so their launches carry g times the tiles (fuller last rounds, half the launches per
@@ -1173,21 +1259,8 @@ int enqueue_body(dc_ctx* ctx, Lane& L, int g, bool features_only, bool events, b
 #define STAGE_EVENT(i) do { if (events) HIPCHK(hipEventRecord(L.ev[i], s)); } while (0)
   STAGE_EVENT(0);
   // ---- VGG-16 trunk (DenseCapModel.lua:73-76) -------------------------------------------
-  int h = H, w = W, cur = 0;
-  KCHK(launch_conv3x3_c3(L.img, ctx->conv_w[0], ctx->conv_b[0], L.act[0], g, H, W, 64, 1, s));
-  for (int i = 1; i < DC_NUM_VGG_CONVS; ++i) {
-    if (kVgg[i].pool_after) {
-      // conv + ReLU + ceil-mode 2x2 pool in one launch
-      DCCHK(conv3x3_pool(ctx, s, L.act[cur], ctx->conv_w[i], ctx->conv_b[i], L.act[cur ^ 1], g, h, w, kVgg[i].cin,
-                         kVgg[i].cout, 1, lane_ws(L)));
-      h = (h + 1) / 2; w = (w + 1) / 2;
-    } else {
-      DCCHK(conv3x3(ctx, s, L.act[cur], ctx->conv_w[i], ctx->conv_b[i], L.act[cur ^ 1], g, h, w, kVgg[i].cin,
-                    kVgg[i].cout, 1, lane_ws(L)));
-    }
-    cur ^= 1;
-  }
-  L.feat = L.act[cur];
+  int h = H, w = W;
+  DCCHK(enqueue_trunk(ctx, L, g, &h, &w));
   const size_t feat_elems = (size_t)h * w * 512;
   STAGE_EVENT(1);
   ensure_fault_word(ctx);            // every forward has an NMS and a final pack that report through it: made before any capture
@@ -1490,6 +1563,7 @@ void dc_destroy(dc_ctx* ctx) {
   if (ctx->pre_src.p) hipFree(ctx->pre_src.p);
   if (ctx->pre_scratch.p) hipFree(ctx->pre_scratch.p);
   if (ctx->pre_taps.p) hipFree(ctx->pre_taps.p);
+  if (ctx->loss_ws.p) hipFree(ctx->loss_ws.p);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
   delete ctx;
 }
@@ -2104,6 +2178,31 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
   if (ctx->lanes.empty() || !ctx->lanes[0]->arena.p) return ctx->fail(DC_E_STATE, "no forward has run yet");
   Lane& L = *ctx->lanes[0];
   const int P = L.P;
+  if (strncmp(name, "loss_", 5) == 0) {             // what the last dc_forward_losses left (include/densecap.h, at that function)
+    const dc_ctx::LossKeep& k = ctx->loss_keep;
+    if (k.boxes == nullptr) return ctx->fail(DC_E_STATE, "dc_debug_fetch: %s: no dc_forward_losses call has got that far", name);
+    if (strcmp(name, "loss_stage_ms") == 0) {
+      if (capacity_bytes < 20) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+      memcpy(host_buf, k.stage_ms, 20);
+      return 5;
+    }
+    const struct { const char* n; const void* p; int64_t elems; int esize; } kept[] = {
+        {"loss_rpn_boxes", k.boxes, (int64_t)k.A * 4, 4},     {"loss_rpn_anchors", k.anchors, (int64_t)k.A * 4, 4},
+        {"loss_rpn_trans", k.trans, (int64_t)k.A * 4, 4},     {"loss_rpn_scores", k.scores, (int64_t)k.A * 2, 4},
+        {"loss_obj", L.obj, (int64_t)k.n, 4},                 {"loss_final_trans", L.final_trans, (int64_t)k.n * 4, 4},
+        {"loss_roi_boxes", L.roi_boxes, (int64_t)k.n * 4, 4}, {"loss_codes", L.codes, (int64_t)k.n * ctx->D, 4},
+        {"loss_rowlik", k.rowlik, (int64_t)k.num_pos, 8}};
+    for (const auto& e : kept) {
+      if (strcmp(name, e.n) != 0) continue;
+      const int64_t bytes = e.elems * e.esize;
+      if (bytes > capacity_bytes) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small (%lld needed)", (long long)bytes);
+      HIPCHK(hipSetDevice(ctx->device));
+      HIPCHK(hipStreamSynchronize(L.stream));
+      if (bytes > 0) HIPCHK(hipMemcpy(host_buf, e.p, bytes, hipMemcpyDeviceToHost));
+      return e.elems;
+    }
+    return ctx->fail(DC_E_INVALID, "dc_debug_fetch: unknown name '%s'", name);
+  }
   struct Ent { const char* n; const void* p; int64_t elems; int esize; };
   const Ent tab[] = {
       {"feat_hwc", L.feat, (int64_t)L.fh * L.fw * 512, 4},
@@ -2487,6 +2586,62 @@ int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_score
                          (flags & DC_EVAL_CLAIM_LAST) ? 1 : 0, order, ov, group, ok, gt_group, n_groups, merged_boxes, s));
   OP_EPILOGUE();
 }
+// The sampler's settings, checked before anything is enqueued (docs/SEMANTICS.md, "Validation losses")
+static int check_sampler_opts(dc_ctx* ctx, const dc_loss_opts* o, const char* who) {
+  if (o->batch_size < 2 || o->batch_size > 1024 || (o->batch_size & 1))
+    return ctx->fail(DC_E_INVALID, "%s: batch_size must be even and in 2..1024 (got %d)", who, o->batch_size);
+  if (!(o->low_thresh >= 0.f && o->low_thresh <= 1.f) || !(o->high_thresh >= 0.f && o->high_thresh <= 1.f) ||
+      o->low_thresh > o->high_thresh)
+    return ctx->fail(DC_E_INVALID, "%s: thresholds must satisfy 0 <= low <= high <= 1 (got low %g, high %g)", who,
+                     (double)o->low_thresh, (double)o->high_thresh);
+  if (o->remove_outbounds != 0 && o->remove_outbounds != 1)
+    return ctx->fail(DC_E_INVALID, "%s: remove_outbounds must be 0 or 1 (got %d)", who, o->remove_outbounds);
+  return DC_OK;
+}
+int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w, const dc_loss_opts* opts,
+                      const dc_sampler_forced* forced, int32_t* pos_input_idx, int32_t* pos_target_idx, int32_t* neg_input_idx,
+                      int32_t* counts, float* max_iou, int32_t* arg) {
+  OP_PROLOGUE();
+  if (!boxes || !gt || !opts || !pos_input_idx || !pos_target_idx || !neg_input_idx || !counts)
+    return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: null pointer");
+  if (A < 1) return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: A must be >= 1 (got %d)", A);
+  if (G < 1 || G > 512) return ctx->fail(DC_E_UNSUPPORTED, "dc_op_box_sampler: G must be in 1..512 (got %d)", G);
+  if (img_h < 1 || img_w < 1) return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: image size %dx%d", img_w, img_h);
+  DCCHK(check_sampler_opts(ctx, opts, "dc_op_box_sampler"));
+  const int np = forced && forced->pos_sample_idx ? forced->num_pos : 0, nn = forced && forced->neg_sample_idx ? forced->num_neg : 0;
+  if (np < 0 || np > opts->batch_size || nn < 0 || nn > opts->batch_size)
+    return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: a forced list holds 0..batch_size entries (got %d, %d)", np, nn);
+  const size_t ws_bytes = box_sampler_ws_bytes(A, G), forced_bytes = (size_t)2048 * 4;
+  char* ws = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&ws), ws_bytes + forced_bytes));
+  int32_t* fdev = reinterpret_cast<int32_t*>(ws + ws_bytes);
+  BoxSamplerArgs a{};
+  a.boxes = boxes; a.gt = gt; a.A = A; a.G = G;
+  a.x_max = (float)img_w; a.y_max = (float)img_h; a.bounds = opts->remove_outbounds;
+  a.high = opts->high_thresh; a.low = opts->low_thresh; a.batch = opts->batch_size;
+  a.seed_lo = (uint32_t)(opts->seed & 0xffffffffull); a.seed_hi = (uint32_t)(opts->seed >> 32);
+  hipError_t e = hipSuccess;
+  if (forced && forced->pos_sample_idx) {
+    if (np > 0) e = hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)np * 4, hipMemcpyHostToDevice, s);
+    a.forced_pos = fdev; a.n_forced_pos = np;
+  }
+  if (e == hipSuccess && forced && forced->neg_sample_idx) {
+    if (nn > 0) e = hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)nn * 4, hipMemcpyHostToDevice, s);
+    a.forced_neg = fdev + 1024; a.n_forced_neg = nn;
+  }
+  a.pos_input_idx = pos_input_idx; a.pos_target_idx = pos_target_idx; a.neg_input_idx = neg_input_idx; a.counts = counts;
+  a.max_iou_user = max_iou; a.arg_user = arg; a.ws = ws;
+  if (e == hipSuccess) e = launch_box_sampler(a, s);
+  int32_t c[8] = {0};
+  if (e == hipSuccess) e = hipMemcpyAsync(c, counts, sizeof c, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_box_sampler: %s", hipGetErrorString(e));
+  if (c[5] || c[6])
+    return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: %d forced positive and %d forced negative ranks lie outside the candidate lists (%d, %d)",
+                     c[5], c[6], c[2], c[3]);
+  OP_EPILOGUE();
+}
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B,
                             int img_h, int img_w, int HH, int WW, float* out, int out_layout) {
   OP_PROLOGUE();
@@ -2656,6 +2811,186 @@ int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int im
       objectness[o] = obj[r];
       region[o] = inv[r];
     }
+  return DC_OK;
+}
+
+// ---- validation losses (docs/SEMANTICS.md, "Validation losses") -----------------------------------------------------------------
+// The settings a losses call runs under, whatever the ctx holds: fp32 MFMA and multi-lane planning (single-image planning shares a
+// layer's last tile round along K, another summation order), so that the numbers depend on neither dc_set_math_mode nor
+// dc_set_lanes.  The ctx's own settings come back when the guard dies.
+struct LossCfgGuard {
+  Settings& c; Settings saved;
+  explicit LossCfgGuard(Settings& cfg) : c(cfg), saved(cfg) { c.math_mode = 0; c.serial_mode = 0; c.plan_mode = 0; }
+  ~LossCfgGuard() { c = saved; }
+};
+static const dc_loss_opts kLossDefaults = {256, 0.7f, 0.3f, 1, 0.05f, 0.1f, 0.1f, 0.1f, 1.0f, 0};
+
+// The training forward of one image and its five criteria: LocalizationLayer:_forward_train (LocalizationLayer.lua:383-527) and
+// DenseCapModel:forward_backward's forward half (DenseCapModel.lua:401-459).  Launch list (lane 0's stream, eager):
+//   image copy; the trunk (enqueue_trunk); RPN conv; heads; rpn_decode with clip = 0 (boxes, anchors, trans); rpn_score_rows
+//   memset + box_sampler_match + box_sampler_draw; the counts and lists come back (the host sizes the rest by them)
+//   bilinear RoI pooling of the n = num_pos + num_neg sampled boxes (gathered by the kernel); fc6; fc7; recog_heads
+//   lm_score_paired on the num_pos positive rows (its own scratch; the row sums come back and go up again: num_pos doubles)
+//   loss_terms (one workgroup); six doubles and two counts come back
+int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int Lw, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump) {
+  const char* who = "dc_forward_losses";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!img_chw || !gt_boxes || !gt_labels || !out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
+  DCCHK(check_image_size(ctx, H, W, who));
+  if (G < 1 || G > 512) return ctx->fail(DC_E_UNSUPPORTED, "%s: G must be in 1..512 (got %d)", who, G);
+  DCCHK(check_queries(ctx, gt_labels, G, Lw, who));
+  for (int j = 0; j < G; ++j) {
+    const float* b = gt_boxes + (size_t)j * 4;
+    if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3])) || !(b[2] > 0.f) || !(b[3] > 0.f))
+      return ctx->fail(DC_E_INVALID, "%s: ground-truth box %d (%g, %g, %g, %g) is not finite with w > 0 and h > 0", who, j, (double)b[0],
+                       (double)b[1], (double)b[2], (double)b[3]);
+  }
+  const dc_loss_opts o = opts ? *opts : kLossDefaults;
+  DCCHK(check_sampler_opts(ctx, &o, who));
+  const int batch = o.batch_size;
+  const int fnp = forced && forced->pos_sample_idx ? forced->num_pos : 0, fnn = forced && forced->neg_sample_idx ? forced->num_neg : 0;
+  if (fnp < 0 || fnp > batch || fnn < 0 || fnn > batch || fnp + fnn > batch)
+    return ctx->fail(DC_E_INVALID, "%s: forced lists hold 0..batch_size entries, batch_size in all (got %d, %d)", who, fnp, fnn);
+  if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
+    return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  Lane& L = lane0(ctx);
+  DCCHK(lane_prepare(ctx, L, H, W, batch, 1));
+  hipStream_t s = L.stream;
+  const int A = L.A, k = ctx->k, D = ctx->D;
+  // ---- scratch: what the lane does not hold (kept for dc_debug_fetch "loss_*" until the next call) ----
+  float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr, *gt_dev = nullptr;
+  void* samp_ws = nullptr;
+  int32_t *fdev = nullptr, *pos_idx = nullptr, *pos_tgt = nullptr, *neg_idx = nullptr, *counts = nullptr, *sel = nullptr, *masked = nullptr;
+  double *rowlik = nullptr, *terms = nullptr;
+  const std::vector<Carve> cv = {
+      {(void**)&boxes, (size_t)A * 16},   {(void**)&anchors, (size_t)A * 16}, {(void**)&trans, (size_t)A * 16},
+      {(void**)&scores, (size_t)A * 8},   {(void**)&gt_dev, (size_t)G * 16},  {(void**)&samp_ws, box_sampler_ws_bytes(A, G)},
+      {(void**)&fdev, 2048 * 4},          {(void**)&pos_idx, 1024 * 4},       {(void**)&pos_tgt, 1024 * 4},
+      {(void**)&neg_idx, 1024 * 4},       {(void**)&counts, 8 * 4},           {(void**)&sel, 1024 * 4},
+      {(void**)&rowlik, 1024 * 8},        {(void**)&terms, 6 * 8},            {(void**)&masked, 2 * 4},
+  };
+  const size_t total = carve(cv, nullptr);
+  ctx->loss_keep = dc_ctx::LossKeep();
+  if (ctx->loss_ws.p == nullptr || total > ctx->loss_ws.bytes) {
+    if (ctx->loss_ws.p) HIPCHK(hipFree(ctx->loss_ws.p));
+    ctx->loss_ws = DevBuf();
+    HIPCHK(hipMalloc(&ctx->loss_ws.p, total));
+    ctx->loss_ws.bytes = total;
+  }
+  carve(cv, ctx->loss_ws.p);
+  int32_t c8[8] = {0};
+  std::vector<int32_t> lists(3 * 1024);
+  std::vector<double> rl;
+  double terms_h[6] = {0};
+  int32_t masked_h[2] = {0, 0};
+  int np = 0, nn = 0;
+  auto body = [&]() -> int {
+    HIPCHK(hipEventRecord(L.ev[0], s));
+    HIPCHK(hipMemcpyAsync(L.img, img_chw, (size_t)3 * H * W * 4, img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    int h = 0, w = 0;
+    DCCHK(enqueue_trunk(ctx, L, 1, &h, &w));
+    ensure_fault_word(ctx);
+    // ---- RPN in training form (LocalizationLayer.lua:405-412): all A rows, not clipped, raw scores ----
+    DCCHK(conv3x3(ctx, s, L.feat, ctx->rpn_w, ctx->rpn_b, L.rpn_hidden, 1, h, w, 512, ctx->R, 1, lane_ws(L)));
+    DCCHK(linear(ctx, s, L.rpn_hidden, ctx->heads_w, ctx->heads_b, L.heads, h * w, 6 * k, ctx->R, 0, Ws(), h * w));
+    KCHK(launch_rpn_decode(L.heads, 1, h, w, k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], H, W, boxes, anchors, trans,
+                           nullptr, nullptr, nullptr, 0, s));
+    KCHK(launch_rpn_score_rows(L.heads, h, w, k, scores, s));
+    HIPCHK(hipEventRecord(L.ev[1], s));
+    // ---- the sampler ----
+    HIPCHK(hipMemcpyAsync(gt_dev, gt_boxes, (size_t)G * 16, hipMemcpyHostToDevice, s));
+    BoxSamplerArgs a{};
+    a.boxes = boxes; a.gt = gt_dev; a.A = A; a.G = G;
+    a.x_max = (float)W; a.y_max = (float)H; a.bounds = o.remove_outbounds;
+    a.high = o.high_thresh; a.low = o.low_thresh; a.batch = batch;
+    a.seed_lo = (uint32_t)(o.seed & 0xffffffffull); a.seed_hi = (uint32_t)(o.seed >> 32);
+    if (forced && forced->pos_sample_idx) {
+      if (fnp > 0) HIPCHK(hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)fnp * 4, hipMemcpyHostToDevice, s));
+      a.forced_pos = fdev; a.n_forced_pos = fnp;
+    }
+    if (forced && forced->neg_sample_idx) {
+      if (fnn > 0) HIPCHK(hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)fnn * 4, hipMemcpyHostToDevice, s));
+      a.forced_neg = fdev + 1024; a.n_forced_neg = fnn;
+    }
+    a.pos_input_idx = pos_idx; a.pos_target_idx = pos_tgt; a.neg_input_idx = neg_idx; a.counts = counts; a.ws = samp_ws;
+    KCHK(launch_box_sampler(a, s));
+    HIPCHK(hipMemcpyAsync(c8, counts, sizeof c8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists.data(), pos_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists.data() + 1024, pos_tgt, 1024 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists.data() + 2048, neg_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(L.ev[2], s));
+    HIPCHK(hipStreamSynchronize(s));
+    np = c8[0]; nn = c8[1];
+    if (c8[5] || c8[6])
+      return ctx->fail(DC_E_INVALID, "%s: %d forced positive and %d forced negative ranks lie outside the candidate lists (%d, %d)", who,
+                       c8[5], c8[6], c8[2], c8[3]);
+    const int n = np + nn;
+    if (np < 0 || nn < 0 || n > batch)
+      return ctx->fail(DC_E_INVALID, "%s: the forced lists give %d + %d sampled rows, more than batch_size = %d", who, np, nn, batch);
+    for (int r = 0; r < np; ++r)
+      if (lists[r] < 0 || lists[r] >= A || lists[1024 + r] < 0 || lists[1024 + r] >= G)
+        return ctx->fail(DC_E_HIP, "%s: sampler row %d names input %d, ground-truth box %d", who, r, lists[r], lists[1024 + r]);
+    for (int r = 0; r < nn; ++r)
+      if (lists[2048 + r] < 0 || lists[2048 + r] >= A) return ctx->fail(DC_E_HIP, "%s: sampler negative %d names input %d", who, r, lists[2048 + r]);
+    ctx->loss_keep.boxes = boxes; ctx->loss_keep.anchors = anchors; ctx->loss_keep.trans = trans; ctx->loss_keep.scores = scores;
+    ctx->loss_keep.rowlik = rowlik; ctx->loss_keep.A = A; ctx->loss_keep.n = n; ctx->loss_keep.num_pos = np;
+    if (n > 0) {
+      // ---- RoI pooling, fc6 / fc7, recognition heads on the sampled rows, positives first (LocalizationLayer.lua:443-452) ----
+      HIPCHK(hipMemcpyAsync(sel, pos_idx, (size_t)np * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(sel + np, neg_idx, (size_t)nn * 4, hipMemcpyDeviceToDevice, s));
+      KCHK(launch_bilinear_roi_pool_group(L.feat, 0, 1, h, w, 512, L.roi_boxes, n, nullptr, 0, sel, boxes, 0, H, W, 7, 7, L.roi_feats, 1, s));
+      DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, 49 * 512, 1, lane_ws(L), batch));
+      DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), batch));
+      KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
+    }
+    HIPCHK(hipEventRecord(L.ev[3], s));
+    // ---- captioning: every positive row against the labels of its ground-truth box ----
+    rl.assign(std::max(np, 1), 0.0);
+    if (np > 0) {
+      std::vector<int32_t> lab((size_t)np * Lw);
+      for (int r = 0; r < np; ++r)
+        std::copy(gt_labels + (size_t)lists[1024 + r] * Lw, gt_labels + (size_t)(lists[1024 + r] + 1) * Lw, lab.begin() + (size_t)r * Lw);
+      DCCHK(lm_score_paired(ctx, s, L.codes, np, batch, lab.data(), Lw, rl.data()));
+      HIPCHK(hipMemcpyAsync(rowlik, rl.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipEventRecord(L.ev[4], s));
+    // ---- the five criteria ----
+    LossTermArgs t{};
+    t.scores = scores; t.anchors = anchors; t.trans = trans; t.gt = gt_dev; t.roi_boxes = L.roi_boxes; t.final_trans = L.final_trans;
+    t.obj = L.obj; t.pos_input_idx = pos_idx; t.pos_target_idx = pos_tgt; t.neg_input_idx = neg_idx; t.rowlik = rowlik;
+    t.num_pos = np; t.num_neg = nn; t.L = Lw;
+    t.w_mid_box = o.mid_box_reg_weight; t.w_mid_obj = o.mid_objectness_weight; t.w_end_box = o.end_box_reg_weight;
+    t.w_end_obj = o.end_objectness_weight; t.w_cap = o.captioning_weight;
+    t.out = terms; t.out_masked = masked;
+    KCHK(launch_loss_terms(t, s));
+    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(masked_h, masked, sizeof masked_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(L.ev[5], s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DC_OK;
+  };
+  const int rc = body();
+  if (rc != DC_OK) { drain_lanes(ctx); prof_collect(ctx); return rc; }
+  prof_collect(ctx);
+  for (int i = 0; i < 5; ++i) (void)hipEventElapsedTime(&ctx->loss_keep.stage_ms[i], L.ev[i], L.ev[i + 1]);
+  L.have_times = false;                       // the lane's stage events no longer time a dc_forward_test
+  DCCHK(check_fault_word(ctx, who));
+  out->mid_objectness_loss = terms_h[0]; out->mid_box_reg_loss = terms_h[1]; out->end_objectness_loss = terms_h[2];
+  out->end_box_reg_loss = terms_h[3]; out->captioning_loss = terms_h[4]; out->total_loss = terms_h[5];
+  out->num_pos = np; out->num_neg = nn; out->total_pos = c8[2]; out->total_neg = c8[3];
+  out->masked_mid = masked_h[0]; out->masked_end = masked_h[1]; out->flags = c8[4];
+  if (dump) {
+    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
+    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
+    std::copy(lists.begin() + 2048, lists.begin() + 2048 + nn, dump->neg_input_idx);
+  }
   return DC_OK;
 }
 

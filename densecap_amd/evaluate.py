@@ -144,13 +144,25 @@ class DenseCaptioningEvaluator:
 
 
 # ---- the file protocol of eval/meteor_bridge.py --------------------------------------------------------------------------------
-def write_records(directory, evaluator):
-    """input.json (the records, what meteor_bridge.py reads) and eval_state.json (the state above) into `directory`."""
+def write_records(directory, evaluator, loss_results=None):
+    """input.json (the records, what meteor_bridge.py reads) and eval_state.json (the state above) into `directory`.
+    loss_results: the averaged validation losses of the run, kept in the state under that key so that the second phase reports
+    them again; None: the state is what it was without them."""
     os.makedirs(directory, exist_ok=True)
     with open(os.path.join(directory, "input.json"), "w") as f:
         json.dump(evaluator.records(), f)
+    st = evaluator.state()
+    if loss_results is not None:
+        st["loss_results"] = loss_results
     with open(os.path.join(directory, "eval_state.json"), "w") as f:
-        json.dump(evaluator.state(), f)       # (Python's json writes and reads NaN / Infinity, which a score may be)
+        json.dump(st, f)                      # (Python's json writes and reads NaN / Infinity, which a score may be)
+
+
+def dict_average(dicts):
+    """utils.dict_average (densecap/utils.lua): the mean of every key over a list of dicts with the same keys."""
+    if not dicts:
+        return {}
+    return {k: sum(float(d[k]) for d in dicts) / len(dicts) for k in dicts[0]}
 
 
 def evaluate_from_files(directory, caption_scores_path=None):
@@ -164,4 +176,7 @@ def evaluate_from_files(directory, caption_scores_path=None):
             cs = json.load(f)["scores"]
         if len(cs) != len(st["ok"]):
             raise ValueError("%s holds %d scores, %s has %d records" % (caption_scores_path, len(cs), directory, len(st["ok"])))
-    return evaluate_records([float(v) for v in st["scores"]], st["ok"], st["ov"], st["npos"], cs)
+    res = evaluate_records([float(v) for v in st["scores"]], st["ok"], st["ov"], st["npos"], cs)
+    if "loss_results" in st:
+        res["loss_results"] = st["loss_results"]
+    return res

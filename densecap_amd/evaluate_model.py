@@ -14,7 +14,13 @@ way the image itself is scaled, then read like run_model's -input_boxes), or the
 (`boxes` xcycwh already in the -image_size frame, `labels`, `img_to_first_box`, `img_to_last_box`, `split`; `/images` is never
 read: the pixels come from -image_dir through idx_to_filename).  The HDF5 reader is the project's minimal one: it reads files of
 hdf5_min.write_hdf5's layout (classic superblock, contiguous datasets); files written by h5py itself have not been read with it.
-The validation losses of eval_split need the training forward and are not computed.
+
+-losses 1 adds eval_split's validation losses (eval/eval_utils.lua:54-59,78-81): every image also runs the training forward
+(DenseCapModel.forward_losses; docs/SEMANTICS.md, "Validation losses") against its ground truth -- the dataset's label rows as
+they are with -data_h5, the -gt_json captions tokenised like query_regions' queries (unknown words become <UNK>), cut to the
+model's seq_length and zero-padded -- and the six losses, averaged over the images, are printed as `loss_results`, added to the
+result under that key and kept in eval_state.json, so that the second phase reports them again.  The sampler's settings and the
+five weights are train_opts.lua's, with its defaults; -loss_seed selects the sampler's draws.
 """
 from __future__ import annotations
 
@@ -55,7 +61,42 @@ def build_parser():
     a("-math_mode", type=int, default=0, choices=[0, 1])
     a("-caption_order", type=int, default=1, choices=[0, 1])
     a("-synthetic_weights", type=int, default=0, help="1: random weights in checkpoint shapes")
+    # ---- validation losses: train_opts.lua:18-40, with its defaults ----
+    a("-losses", type=int, default=0, choices=[0, 1], help="1: also compute eval_split's validation losses (a second forward per image)")
+    a("-sampler_batch_size", type=int, default=256)
+    a("-sampler_high_thresh", type=float, default=0.7)
+    a("-sampler_low_thresh", type=float, default=0.3)
+    a("-train_remove_outbounds_boxes", type=int, default=1, choices=[0, 1])
+    a("-mid_box_reg_weight", type=float, default=0.05)
+    a("-mid_objectness_weight", type=float, default=0.1)
+    a("-end_box_reg_weight", type=float, default=0.1)
+    a("-end_objectness_weight", type=float, default=0.1)
+    a("-captioning_weight", type=float, default=1.0)
+    a("-loss_seed", type=int, default=0, help="seed of the box sampler's draws")
     return p
+
+
+def loss_options(opt):
+    """The flags above as the keyword arguments of DenseCapModel.forward_losses."""
+    return dict(batch_size=opt.sampler_batch_size, high_thresh=opt.sampler_high_thresh, low_thresh=opt.sampler_low_thresh,
+                remove_outbounds=opt.train_remove_outbounds_boxes, mid_box_reg_weight=opt.mid_box_reg_weight,
+                mid_objectness_weight=opt.mid_objectness_weight, end_box_reg_weight=opt.end_box_reg_weight,
+                end_objectness_weight=opt.end_objectness_weight, captioning_weight=opt.captioning_weight, seed=opt.loss_seed)
+
+
+def encode_gt_captions(captions, idx_to_token, seq_length):
+    """-gt_json captions -> (M, seq_length) int32 label rows: tokenised the way query_regions tokenises queries (words_preprocess;
+    a word the vocabulary lacks becomes <UNK>), cut to seq_length words, zero-padded."""
+    from .model import encode_captions, words_preprocess
+    token_to_idx = {str(v): int(k) for k, v in (idx_to_token or {}).items()}
+    rows = []
+    for c in captions:
+        words = words_preprocess(c)[:seq_length]
+        unknown = [w for w in words if w not in token_to_idx]
+        if unknown and "<UNK>" not in token_to_idx:
+            raise ValueError("caption %r: word %r is not in the vocabulary (and it has no <UNK>)" % (c, unknown[0]))
+        rows.append([token_to_idx.get(w, token_to_idx.get("<UNK>")) for w in words])
+    return encode_captions(rows, idx_to_token, seq_length) if rows else np.zeros((0, seq_length), np.int32)
 
 
 def scaled_size(h0, w0, image_size):
@@ -104,6 +145,10 @@ def read_dataset(data_h5, data_json, split, max_images):
 
 
 def print_results(res):
+    if res.get("loss_results"):
+        print("loss_results:")
+        for k in sorted(res["loss_results"]):
+            print("%s: %f" % (k, res["loss_results"][k]))
     if res["map"] is not None:
         for k in sorted(res["ap_breakdown"]):
             print("%s: %f" % (k, res["ap_breakdown"][k]))
@@ -167,15 +212,31 @@ def main(argv=None):
     model.evaluate()
     if labels is not None:
         gt_caps = {n: model.decodeSequence(labels[n]) for n in names}
+    all_losses = []
+    if opt.losses:
+        from . import ops
+        from .evaluate import dict_average
+        try:
+            gt_labels = labels if labels is not None else {n: encode_gt_captions(gt_caps[n], model.idx_to_token, model.seq_length) for n in names}
+        except ValueError as e:
+            raise SystemExit(str(e))
     ev = E.DenseCaptioningEvaluator(model.ctx, claim_last=bool(opt.claim_last))
     pipe = ImagePipeline(paths, opt.image_size, opt.gpu, model.ctx, io_threads=opt.io_threads,
                          chunk=max(1, opt.lanes) * max(1, opt.group) * 2, want_rgb=False)
     try:
         for chunk in pipe:
             outs = model.forward_images_device([d for _, d, _ in chunk])
+            ns = [names[i] for i, _, _ in chunk]
+            if opt.losses:
+                # eval_split calls forward_backward on every image (eval/eval_utils.lua:54-59): the training forward, one image a call
+                for (_, dev, _), n in zip(chunk, ns):
+                    if len(gt_boxes[n]) == 0:
+                        print("Image %s has no ground truth: no losses" % n)
+                        continue
+                    lo = ops.forward_losses(model.ctx, dev, gt_boxes[n], gt_labels[n], on_device=True, **loss_options(opt))
+                    all_losses.append({k: lo[k] for k in ops.LOSS_KEYS})
             for _, dev, _ in chunk:
                 pipe.recycle(dev)
-            ns = [names[i] for i, _, _ in chunk]
             # one dc_op_eval_match call for the chunk
             ev.add_result([o[1] for o in outs], [o[0] for o in outs], [model.decodeSequence(o[2]) for o in outs],
                           [gt_boxes[n] for n in ns], [gt_caps[n] for n in ns])
@@ -183,8 +244,11 @@ def main(argv=None):
                 print("Processed image %s (%d / %d), detected %d regions" % (names[i], i + 1, num, len(o[0])))
     finally:
         pipe.close()
-    E.write_records(opt.output_records, ev)
+    loss_results = dict_average(all_losses) if opt.losses else None
+    E.write_records(opt.output_records, ev, loss_results)
     res = ev.evaluate()
+    if opt.losses:
+        res["loss_results"] = loss_results
     print_results(res)
     print(json.dumps(res))
     return 0

@@ -564,6 +564,16 @@ class DenseCapModel:
             res = res + (self.decodeSequence(tokens[:K]),)
         return res
 
+    def forward_losses(self, img, gt_boxes, gt_labels, **opts):
+        """The validation losses of one image: what DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474) and
+        eval_utils.eval_split averages -- mid_objectness_loss, mid_box_reg_loss, end_objectness_loss, end_box_reg_loss,
+        captioning_loss, total_loss -- from the forward half alone, every Dropout the identity (docs/SEMANTICS.md, "Validation
+        losses").  gt_boxes (G,4) xcycwh in the frame of the image passed, gt_labels (G,L) word ids padded with zeros.  opts: the
+        sampler's settings and the five weights (ops.LOSS_DEFAULTS), forced_pos / forced_neg, dump.  The test arguments
+        (setTestArgs) play no part."""
+        from . import ops
+        return ops.forward_losses(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
+
     def _encode_queries(self, captions, max_len=None):
         """strings (encode_captions, max_len words wide or as wide as the longest) or ready (Q, Tq) id rows -> (Q, Tq) int32"""
         if isinstance(captions, np.ndarray) and captions.ndim == 2:

@@ -322,6 +322,98 @@ def eval_match(ctx, det_boxes, det_scores, gt_boxes, merge_thresh=0.7, claim_las
     return out
 
 
+LOSS_DEFAULTS = dict(batch_size=256, high_thresh=0.7, low_thresh=0.3, remove_outbounds=1, mid_box_reg_weight=0.05,
+                     mid_objectness_weight=0.1, end_box_reg_weight=0.1, end_objectness_weight=0.1, captioning_weight=1.0, seed=0)
+LOSS_KEYS = ("mid_objectness_loss", "mid_box_reg_loss", "end_objectness_loss", "end_box_reg_loss", "captioning_loss", "total_loss")
+
+
+def loss_opts(**kw):
+    """A filled DcLossOpts (train_opts.lua:18-40 defaults; docs/SEMANTICS.md, "Validation losses").  Unknown keys raise; the
+    library checks the values."""
+    unknown = set(kw) - set(LOSS_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown loss option(s): %s" % ", ".join(sorted(unknown)))
+    o = dict(LOSS_DEFAULTS, **kw)
+    return _lib.DcLossOpts(int(o["batch_size"]), float(o["high_thresh"]), float(o["low_thresh"]), int(o["remove_outbounds"]),
+                           float(o["mid_box_reg_weight"]), float(o["mid_objectness_weight"]), float(o["end_box_reg_weight"]),
+                           float(o["end_objectness_weight"]), float(o["captioning_weight"]), int(o["seed"]) & (2 ** 64 - 1))
+
+
+def _forced_lists(forced_pos, forced_neg):
+    """(DcSamplerForced or None, the arrays it points into)"""
+    if forced_pos is None and forced_neg is None:
+        return None, ()
+    f = _lib.DcSamplerForced()
+    keep = []
+    for name, lst in (("pos", forced_pos), ("neg", forced_neg)):
+        if lst is None:
+            continue
+        a = np.ascontiguousarray(np.asarray(lst, dtype=np.int64).reshape(-1), dtype=np.int32)
+        a = a if a.size else np.zeros(1, np.int32)          # a valid pointer for an empty list
+        keep.append(a)
+        setattr(f, name + "_sample_idx", a.ctypes.data_as(_lib.c_int32_p))
+        setattr(f, "num_" + name, int(np.asarray(lst).size))
+    return f, keep
+
+
+def box_sampler(ctx, boxes, gt, img_h, img_w, forced_pos=None, forced_neg=None, want_iou=True, **opts):
+    """nn.BoxSampler (dc_op_box_sampler; docs/SEMANTICS.md, "Validation losses"): boxes (A,4), gt (G,4) xcycwh.  Returns a dict:
+    pos_input_idx, pos_target_idx (num_pos), neg_input_idx (num_neg) int32 0-based; num_pos, num_neg, total_pos, total_neg,
+    flags; with want_iou max_iou (A) float32 and arg (A) int32.  forced_pos / forced_neg: ranks in the class's ascending candidate
+    list that take the place of the draws.  opts: the keys of LOSS_DEFAULTS."""
+    b = _f32(boxes).reshape(-1, 4); g = _f32(gt).reshape(-1, 4)
+    A, G = len(b), len(g)
+    o = loss_opts(**opts)
+    f, keep = _forced_lists(forced_pos, forced_neg)
+    cap = max(int(o.batch_size), 1)
+    bd = ctx.to_device(b); gd = ctx.to_device(g)
+    pi = ctx.empty((cap,), np.int32); pt = ctx.empty((cap,), np.int32); ni = ctx.empty((cap,), np.int32)
+    counts = ctx.empty((8,), np.int32)
+    mi = ctx.empty((max(A, 1),), np.float32) if want_iou else None
+    ar = ctx.empty((max(A, 1),), np.int32) if want_iou else None
+    check(ctx.h, ctx.lib.dc_op_box_sampler(ctx.h, bd.ptr, gd.ptr, A, G, int(img_h), int(img_w), C.byref(o),
+                                           C.byref(f) if f is not None else None, pi.ptr, pt.ptr, ni.ptr, counts.ptr,
+                                           mi.ptr if want_iou else None, ar.ptr if want_iou else None), "dc_op_box_sampler")
+    c = counts.numpy()
+    out = dict(pos_input_idx=pi.numpy()[:c[0]], pos_target_idx=pt.numpy()[:c[0]], neg_input_idx=ni.numpy()[:c[1]],
+               num_pos=int(c[0]), num_neg=int(c[1]), total_pos=int(c[2]), total_neg=int(c[3]), flags=int(c[4]))
+    if want_iou:
+        out.update(max_iou=mi.numpy()[:A], arg=ar.numpy()[:A])
+    return out
+
+
+def forward_losses(ctx, img, gt_boxes, gt_labels, forced_pos=None, forced_neg=None, dump=False, on_device=False, **opts):
+    """The validation losses of one image (dc_forward_losses; docs/SEMANTICS.md, "Validation losses") on a ctx with weights
+    loaded.  img: (3,H,W) float32 host array, or with on_device an ops.DeviceArray; gt_boxes (G,4) xcycwh in the resized frame;
+    gt_labels (G,L) int32, words then zeros.  Returns a dict with the reference's six keys (float), the sampler's counts
+    (num_pos, num_neg, total_pos, total_neg, masked_mid, masked_end, flags) and, with dump, its three index lists."""
+    g = _f32(gt_boxes).reshape(-1, 4)
+    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
+    if lab.ndim != 2 or len(lab) != len(g):
+        raise ValueError("forward_losses: gt_labels must be (G, L) with one row per ground-truth box")
+    o = loss_opts(**opts)
+    f, keep = _forced_lists(forced_pos, forced_neg)
+    out = _lib.DcLosses()
+    d = None
+    if dump:
+        lists = [np.zeros(int(o.batch_size), np.int32) for _ in range(3)]
+        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
+    if on_device:
+        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
+    else:
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
+    check(ctx.h, ctx.lib.dc_forward_losses(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
+                                           len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
+                                           C.byref(out), C.byref(d) if d is not None else None), "dc_forward_losses")
+    res = {k: float(getattr(out, k)) for k in LOSS_KEYS}
+    res.update({k: int(getattr(out, k)) for k in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
+    if dump:
+        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
+                   neg_input_idx=lists[2][:out.num_neg].copy())
+    return res
+
+
 def check_localize_args(nms_thresh, max_regions, min_objectness):
     """The rules of dc_localize_opts (docs/SEMANTICS.md, "Localising phrases"), checked before the library is called: nms_thresh
     in [0, 1], max_regions an integer in 1..4096, min_objectness None (= every proposal) or a number that is not NaN.  Returns

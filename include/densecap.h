@@ -202,6 +202,55 @@ typedef struct dc_beam_opts { int32_t beam_size; int32_t n_best; float length_al
  * rows and NaN log-probabilities. */
 int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_beam_opts* opts, dc_result* out,
                      int32_t* captions, float* logprob);
+/* ---- validation losses (docs/SEMANTICS.md, "Validation losses") ----
+ * The six numbers DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474, LocalizationLayer.lua:383-527) and
+ * eval_utils.eval_split averages (eval/eval_utils.lua:54-59,78-81): the forward half only, every Dropout the identity.
+ * The sampler's rules: see dc_op_box_sampler. */
+/* Settings of the training forward (train_opts.lua:18-40).  The sampler reads batch_size (even, 2..1024), high_thresh and
+ * low_thresh (numbers in [0, 1], low <= high), remove_outbounds (0 / 1) and seed; the five weights belong to the loss terms.
+ * Defaults of the reference: 256, 0.7, 0.3, 1, mid_box_reg 0.05, mid_objectness 0.1, end_box_reg 0.1, end_objectness 0.1,
+ * captioning 1.0. */
+typedef struct dc_loss_opts {
+  int32_t batch_size; float high_thresh; float low_thresh; int32_t remove_outbounds;
+  float mid_box_reg_weight; float mid_objectness_weight; float end_box_reg_weight; float end_objectness_weight;
+  float captioning_weight; uint64_t seed;
+} dc_loss_opts;
+/* The reference's debug_pos_sample_idx / debug_neg_sample_idx (BoxSampler.lua:154-159): HOST lists that take the place of a
+ * class's draws.  Entry q is the 0-based rank, in the class's ascending list of candidates, of the q-th sampled row; a non-NULL
+ * list sets that class's count to its length (0 .. batch_size), a NULL list leaves the class to the rule. */
+typedef struct dc_sampler_forced {
+  const int32_t* pos_sample_idx; int32_t num_pos;
+  const int32_t* neg_sample_idx; int32_t num_neg;
+} dc_sampler_forced;
+#define DC_SAMPLER_NO_NEGATIVES 1       /* flags: no input was negative, the negatives are the non-positives            */
+#define DC_SAMPLER_NEG_REPLACEMENT 2    /*        fewer negatives than wanted: they were drawn with replacement         */
+typedef struct dc_losses {
+  double mid_objectness_loss; double mid_box_reg_loss; double end_objectness_loss; double end_box_reg_loss;
+  double captioning_loss; double total_loss;
+  int32_t num_pos; int32_t num_neg; int32_t total_pos; int32_t total_neg;
+  int32_t masked_mid; int32_t masked_end;   /* positive rows whose box-regression target exceeded 10 (zeroed, still counted) */
+  int32_t flags;                            /* DC_SAMPLER_NO_NEGATIVES | DC_SAMPLER_NEG_REPLACEMENT */
+} dc_losses;
+/* The sampler's three lists of a dc_forward_losses call (the reference's dump_vars): HOST buffers of batch_size int32 each,
+ * 0-based; num_pos / num_pos / num_neg entries are written. */
+typedef struct dc_loss_dump { int32_t* pos_input_idx; int32_t* pos_target_idx; int32_t* neg_input_idx; } dc_loss_dump;
+/* One image (3,H,W) as dc_forward_test takes it.  gt_boxes: HOST (G,4) xc,yc,w,h in the frame of the resized image, finite,
+ * w > 0, h > 0; gt_labels: HOST (G,L) int32, each row words in [1, V] followed by zeros; 1 <= G <= 512, 1 <= L <= 64.
+ * opts_or_null: NULL = the reference's defaults with seed 0.  forced_or_null: caller-forced sample lists.
+ * RPN in training form (all k*h*w rows, boxes not clipped, raw two-class scores), the sampler, RoI pooling + fc6 / fc7 + the
+ * recognition heads on the num_pos + num_neg sampled rows (positives first), the language model teacher-forced on every
+ * positive row against the labels of its ground-truth box, then the five criteria in double and their sum.
+ * Eager, on lane 0, fp32 whatever dc_set_math_mode says, never graph-replayed; the dense GEMMs are planned on batch_size rows.
+ * The result does not depend on num_proposals, lanes, groups, caption order or beam size, and the call leaves every setting
+ * as it found it.  Anything outside the ranges above is refused (DC_E_INVALID; G > 512: DC_E_UNSUPPORTED) before anything is
+ * enqueued; forced lists that give more than batch_size rows in all are DC_E_INVALID.
+ * Stage-wise test hooks, read with dc_debug_fetch after a call: "loss_rpn_boxes", "loss_rpn_anchors", "loss_rpn_trans" (A,4),
+ * "loss_rpn_scores" (A,2) float; "loss_obj" (n), "loss_final_trans" (n,4), "loss_roi_boxes" (n,4), "loss_codes" (n,fc_dim)
+ * float of the n sampled rows; "loss_rowlik" (num_pos) double, every positive row's caption log-likelihood; "loss_stage_ms" 5 float: trunk + RPN, match + assign + draw,
+ * RoI pool + fc, paired scoring, loss terms. */
+int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts_or_null,
+                      const dc_sampler_forced* forced_or_null, dc_losses* out, const dc_loss_dump* dump_or_null);
 /* run_model.lua:160-180 host loop over images, n images of identical size laid out
  * back to back; images are software-pipelined over the ctx's lanes (streams). */
 int dc_forward_batch(dc_ctx* ctx, const float* imgs, int n, int H, int W, int imgs_on_device,
@@ -451,6 +500,26 @@ int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_score
                      const float* gt_boxes, const int32_t* gt_off, int n_images, float merge_thresh, int flags,
                      int32_t* order, double* ov, int32_t* group, uint8_t* ok,
                      int32_t* gt_group, int32_t* n_groups, double* merged_boxes);
+/* nn.BoxSampler:updateOutput (BoxSampler.lua:64-167) for one image: boxes (A,4) xcycwh against gt (G,4) xcycwh, IoU in the
+ * DC_IOU_BOXIOU_MODULE convention, bit for bit what dc_op_box_iou writes.  max / arg-max per input over the ground truth and per
+ * ground-truth box over the inputs (ties: the lower index; a NaN never wins; an input whose IoUs are all NaN is neither positive
+ * nor negative); positive = max > high_thresh, negative = max < low_thresh; with remove_outbounds both are cleared for inputs
+ * whose (w-1)/2 corners leave [1, img_w] x [1, img_h]; every ground-truth box's best input is then positive whatever its IoU or
+ * bounds; no negatives left: the negatives are the non-positives (DC_SAMPLER_NO_NEGATIVES).  num_pos = min(batch_size / 2,
+ * total_pos), num_neg = batch_size - num_pos (0 if there is no candidate at all, where the reference stops with an error).
+ * Draws are counter-based: candidate i of class c (0 positive, 1 negative) has the key philox4x32_10(i, 0, c, 0, seed).w[0]; the
+ * num smallest (key, i) are taken, in that order; with fewer negatives than num_neg (DC_SAMPLER_NEG_REPLACEMENT) draw j takes
+ * entry (philox4x32_10(j, 1, 1, 0, seed).w[0] * total_neg) >> 32 of the ascending list.
+ * Outputs (device, int32, 0-based): pos_input_idx, pos_target_idx (the arg-max ground-truth box of the sampled input),
+ * neg_input_idx, each with room for batch_size entries; counts (8): num_pos, num_neg, total_pos, total_neg, flags, then the number
+ * of forced positive / negative ranks outside the candidate list (their rows hold -1 and the call returns DC_E_INVALID), 0.
+ * max_iou_or_null (A) float and arg_or_null (A) int32: the per-input max (NaN: no number seen) and arg-max.
+ * A < 1, a bad batch size or threshold (NaN included), a forced list longer than batch_size: DC_E_INVALID; G < 1 or G > 512:
+ * DC_E_UNSUPPORTED; all before any launch.  Device pointers but for opts and forced; synchronous. */
+int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
+                      const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
+                      int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
+                      int32_t* arg_or_null);
 /* nn.BilinearRoiPooling forward (BilinearRoiPooling.lua:42-60): feat (h,w,C) HWC, boxes (B,4)
  * xcycwh image px -> out.  out_layout 0: (B,C,HH,WW) as the reference; 1: (B,HH,WW,C). */
 int dc_op_bilinear_roi_pool(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes,

@@ -261,6 +261,41 @@ function Model:forward_test(input)
   return boxes[{{1, K}}]:clone(), scores[{{1, K}}]:clone(), self:decodeSequence(seq)
 end
 
+-- The validation losses of one image: what DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474) and
+-- eval_utils.eval_split averages, from the forward half alone, every Dropout the identity (docs/SEMANTICS.md, "Validation losses").
+-- data.image (1, 3, H, W), data.gt_boxes (1, G, 4) or (G, 4) xcycwh in the frame of the image, data.gt_labels (1, G, L) or (G, L) word
+-- ids padded with zeros.  opts (optional): sampler_batch_size, sampler_high_thresh, sampler_low_thresh,
+-- train_remove_outbounds_boxes, the five *_weight keys of train_opts.lua and loss_seed; absent keys take train_opts' defaults.
+-- Returns the same table keys as forward_backward.
+function Model:forward_losses(data, opts)
+  opts = opts or {}
+  local input = data.image
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local gb, gl = data.gt_boxes, data.gt_labels
+  if gb:dim() == 3 then gb = gb[1] end
+  if gl:dim() == 3 then gl = gl[1] end
+  gb, gl = gb:float():contiguous(), gl:int():contiguous()
+  assert(gb:dim() == 2 and gb:size(2) == 4 and gl:dim() == 2 and gl:size(1) == gb:size(1), 'gt_boxes (G,4), gt_labels (G,L)')
+  local function get(k, d) if opts[k] == nil then return d end return opts[k] end
+  local o = ffi.new('dc_loss_opts')
+  o.batch_size = get('sampler_batch_size', 256)
+  o.high_thresh, o.low_thresh = get('sampler_high_thresh', 0.7), get('sampler_low_thresh', 0.3)
+  o.remove_outbounds = get('train_remove_outbounds_boxes', 1)
+  o.mid_box_reg_weight, o.mid_objectness_weight = get('mid_box_reg_weight', 0.05), get('mid_objectness_weight', 0.1)
+  o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
+  o.captioning_weight = get('captioning_weight', 1.0)
+  o.seed = get('loss_seed', 0)
+  local out = ffi.new('dc_losses')
+  hip.check(self.ctx, C.dc_forward_losses(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),
+                                          gb:size(1), gl:size(2), o, nil, out, nil), 'dc_forward_losses')
+  return {
+    mid_objectness_loss = out.mid_objectness_loss, mid_box_reg_loss = out.mid_box_reg_loss,
+    end_objectness_loss = out.end_objectness_loss, end_box_reg_loss = out.end_box_reg_loss,
+    captioning_loss = out.captioning_loss, total_loss = out.total_loss,
+  }
+end
+
 -- Rank the regions of one image by log p(query | region) (teacher-forced LanguageModel:updateOutput with a gt_sequence,
 -- LanguageModel.lua:106-127, targets of getTarget :148-167).  queries: IntTensor (Q, Tq) of 1-based word ids, zero-padded.
 -- Returns the boxes, scores and captions forward_test returns, and loglik (K, Q).

@@ -54,6 +54,30 @@ int dc_op_eval_match(dc_ctx* ctx, const float* det_boxes, const float* det_score
                      const float* gt_boxes, const int32_t* gt_off, int n_images, float merge_thresh, int flags,
                      int32_t* order, double* ov, int32_t* group, uint8_t* ok,
                      int32_t* gt_group, int32_t* n_groups, double* merged_boxes);
+typedef struct dc_loss_opts {
+  int32_t batch_size; float high_thresh; float low_thresh; int32_t remove_outbounds;
+  float mid_box_reg_weight; float mid_objectness_weight; float end_box_reg_weight; float end_objectness_weight;
+  float captioning_weight; uint64_t seed;
+} dc_loss_opts;
+typedef struct dc_sampler_forced {
+  const int32_t* pos_sample_idx; int32_t num_pos;
+  const int32_t* neg_sample_idx; int32_t num_neg;
+} dc_sampler_forced;
+typedef struct dc_losses {
+  double mid_objectness_loss; double mid_box_reg_loss; double end_objectness_loss; double end_box_reg_loss;
+  double captioning_loss; double total_loss;
+  int32_t num_pos; int32_t num_neg; int32_t total_pos; int32_t total_neg;
+  int32_t masked_mid; int32_t masked_end;
+  int32_t flags;
+} dc_losses;
+typedef struct dc_loss_dump { int32_t* pos_input_idx; int32_t* pos_target_idx; int32_t* neg_input_idx; } dc_loss_dump;
+int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts_or_null,
+                      const dc_sampler_forced* forced_or_null, dc_losses* out, const dc_loss_dump* dump_or_null);
+int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
+                      const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
+                      int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
+                      int32_t* arg_or_null);
 typedef struct dc_sample_opts {
   int32_t num_samples; float temperature; uint64_t seed;
 } dc_sample_opts;
