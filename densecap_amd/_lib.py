@@ -91,6 +91,11 @@ class DcLossDump(C.Structure):
     _fields_ = [("pos_input_idx", c_int32_p), ("pos_target_idx", c_int32_p), ("neg_input_idx", c_int32_p)]
 
 
+class DcLmGrads(C.Structure):
+    """dc_lm_grads: device buffers for the gradients of dc_op_lm_grad, in the layouts of dc_weights; codes may be null."""
+    _fields_ = [(n, C.c_void_p) for n in ("lm_enc_w", "lm_enc_b", "lm_emb", "lstm_w", "lstm_b", "lm_out_w", "lm_out_b", "codes")]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -207,6 +212,8 @@ _SIGS = {
                                     C.POINTER(DcSamplerForced)] + [C.c_void_p] * 6),
     "dc_forward_losses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump)]),
+    "dc_op_lm_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(DcLmGrads),
+                                C.POINTER(C.c_double), C.c_void_p]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -227,6 +234,15 @@ _BEAM_STD_HOOK_SIGS = {
     "dc_debug_beam_std_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DcBeamStdState),
                                          C.POINTER(DcBeamStdState), C.c_void_p, C.c_void_p]),
 }
+# the hooks of include/densecap_debug_grad.h (the language model's backward kernels; bound like the others)
+_GRAD_HOOK_SIGS = {
+    "dc_debug_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dc_debug_embed_segsum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dc_debug_softmax_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
+    "dc_debug_lstm_cell_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "dc_debug_lm_grad_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -241,7 +257,8 @@ def lib():
                 "libdensecap_hip.so not built at %s -- run `make -C densecap_amd/csrc` "
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
+                                  list(_GRAD_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

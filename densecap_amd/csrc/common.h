@@ -10,6 +10,7 @@
 #include "../../include/densecap_debug.h"
 #include "../../include/densecap_debug_sample.h"
 #include "../../include/densecap_debug_beam.h"
+#include "../../include/densecap_debug_grad.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -476,6 +477,30 @@ hipError_t launch_gather_rows(const float* src, const int32_t* idx, const int32_
                               float* out, hipStream_t s);
 hipError_t launch_gather_rows_i32(const int32_t* src, const int32_t* idx, const int32_t* count, int cap, int width,
                                   int32_t* out, hipStream_t s);
+
+// ---- language-model gradients (lm_grad.hip; docs/SEMANTICS.md, "Language-model gradients") ----
+// Weight gradient C(N,K) = sum_m A(m,N) * B(m,K) (rows of lda / ldb / ldc floats) on the fp32 MFMA, both operands read as they
+// lie in memory.  The rows are shared by wgrad_slices(M, N, K) workgroups per tile (a function of the sizes and the device
+// alone); with more than one, `ws` holds wgrad_ws_floats floats of partial tiles that a second launch adds in slice order.
+int wgrad_slices(int M, int N, int K);
+size_t wgrad_ws_floats(int M, int N, int K);
+hipError_t launch_wgrad(const float* A, int lda, const float* B, int ldb, int M, int N, int K, float* C, int ldc, float* ws,
+                        hipStream_t s);
+// out[c] = sum_m X[m][c] for c < N, a fixed tree of doubles
+hipError_t launch_colsum(const float* X, int ldx, int M, int N, float* out, hipStream_t s);
+// rows of logits (ld floats, V1 real columns) to rows of (softmax - onehot(tgt - 1)) * scale in place, columns past V1 zeroed;
+// lse_out (optional): the rows' log-sum-exp
+hipError_t launch_softmax_grad(float* x, int ld, int V1, const int32_t* tgt, float scale, double* lse_out, int rows, hipStream_t s);
+// LSTM cell backward on `rows` rows (see the kernel): dgates (rows, 4Hd) in gate order i, f, o, g and dc_prev (rows, Hd)
+hipError_t launch_lstm_cell_bwd(const float* gates_pre, const int32_t* tok, const float* xg, const float* c_prev, const float* c,
+                                const float* dh_a, const float* dh_b, const float* dc_in, float* dgates, float* dc_prev, int rows,
+                                int Hd, hipStream_t s);
+hipError_t launch_relu_mask(float* d, const float* y, size_t len, hipStream_t s);
+hipError_t launch_embed_rows(const float* emb, const int32_t* tok, int rows, int E, float* out, hipStream_t s);
+hipError_t launch_scatter_rows(const float* src, const int32_t* perm, int rows, int width, float* out, hipStream_t s);
+// demb[ids[t] - 1] = sum of dx[rows[i]] for i in [seg[t], seg[t + 1]), in that order, for t < ntok
+hipError_t launch_embed_segsum(const float* dx, int E, const int32_t* rows, const int32_t* seg, const int32_t* ids, int ntok,
+                               float* demb, hipStream_t s);
 
 // the fc7 rows the final NMS kept, of all images of a group, packed into one row block in pick order; *total = their number
 hipError_t launch_survivor_compact(const float* codes, const int32_t* picks, const int32_t* count, int count_stride, int nimg,

@@ -195,6 +195,13 @@ struct dc_ctx {
   float *out_w = nullptr, *out_b = nullptr, *anchors = nullptr;
   float* dec_w = nullptr;   // (V1pad + 4Hd, Hd): rows [0,V+1) = lm_out_w, zero rows up to V1pad (multiple of 64), then Wh^T
   int V1pad = 0;
+  // language-model gradients (lm_grad): the checkpoint-layout lstm_w (E+Hd, 4Hd) and lm_emb (V+2, E) as uploaded, and the two
+  // transposed copies the data gradients need, made on the first gradient call after a dc_load_weights: out_wT (Hd, V1pad; zero
+  // columns past V+1) and enc_wT (D, E).  lm_grad_ms: the event split of the last call (dc_debug_lm_grad_stage_ms).
+  float *lstm_w_ck = nullptr, *emb = nullptr, *out_wT = nullptr, *enc_wT = nullptr;
+  uint64_t grad_epoch = 0;
+  float lm_grad_ms[4] = {0, 0, 0, 0};
+  bool lm_grad_ran = false;
   // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
   // rounded up to fp16 (V1pad of them), the constant c of the bound.  Part of the weights, made with dec_w.
   uint16_t* scr_w = nullptr;
@@ -1051,6 +1058,209 @@ int lm_score_paired(dc_ctx* ctx, hipStream_t s, const float* codes, int n, int p
   return lm_rows_finish(ctx, s, w, body(), "lm_score_paired");
 }
 
+// Language-model gradients (docs/SEMANTICS.md, "Language-model gradients"): the forward of lm_score_paired with
+// every step's state kept, then the backward through it.  Rows are permuted longest caption first, as there.  The kept state
+// lives in SLOTS of rows, slot q at row off[q] of every buffer:
+//   slot 0 (n rows): the image cell -- X = enc, G = its full pre-activation, DG = its gate gradient
+//   slot 1 (n rows): h_0, c_0;  G = h_0.Wh (the START cell's pre-activation less xg[START]);  X = Emb[START]
+//   slot 1 + j (alive_j rows, j = 1 .. steps): h_j, c_j, the state projection j reads;  G = h_j.Wh;  X = Emb[w_j] -- the input
+//     of the cell that consumes h_j, whose gate gradient DG sits in the same slot (zero rows where the caption has ended)
+// so that X, H and DG are each ONE row-major matrix for the stacked weight gradients.  Launch list (lane 0's stream, eager):
+//   forward : gather codes; lm_start_state; the image cell once more into slots 0 / 1 (same descriptor, same bits); per step the
+//             GEMM of decode_step_desc + a copy of c into the next slot + lse_step_tail there
+//   backward: logits of all steps in one storing GEMM; softmax_grad rows; dH = dlogits.Wout (GEMM on out_wT);
+//             per step, last first: lstm_cell_bwd, then dh_prev = dgates.Wh^T (GEMM on the checkpoint lstm_w); the image cell
+//   stacked : dWout, dWx, dWh, dWenc (wgrad), the three bias column sums, dX = DG.Wx^T (GEMM), ReLU mask, dcodes (GEMM on enc_wT)
+//   rows    : embedding rows of the fed tokens for X (before `stacked`), the segment sum, the codes' rows back in caller order
+constexpr size_t kLmGradMaxScratch = (size_t)8 << 30;
+int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t* lab, int L, float weight, const dc_lm_grads& out,
+            double* loss, double* rowlik) {
+  const int Hd = ctx->Hd, E = ctx->E, D = ctx->D, V = ctx->V, V1 = V + 1, V1pad = ctx->V1pad;
+  const int nslots = V1pad / 32, ld = 2 * nslots + 1;
+  // the two transposed weights, once per loaded checkpoint
+  if (ctx->out_wT == nullptr || ctx->grad_epoch != ctx->weights_epoch) {
+    if (ctx->out_wT == nullptr) {
+      DCCHK(dev_alloc(ctx, (void**)&ctx->out_wT, (size_t)Hd * V1pad * 4));
+      DCCHK(dev_alloc(ctx, (void**)&ctx->enc_wT, (size_t)D * E * 4));
+    }
+    KCHK(launch_transpose2d(ctx->out_w, ctx->out_wT, V1pad, Hd, s));     // the rows of dec_w past V+1 are zero up to V1pad
+    KCHK(launch_transpose2d(ctx->enc_w, ctx->enc_wT, E, D, s));
+    ctx->grad_epoch = ctx->weights_epoch;
+  }
+  std::vector<int> len(n), order(n);
+  for (int r = 0; r < n; ++r) {
+    int l = 0;
+    while (l < L && lab[(size_t)r * L + l] != 0) ++l;
+    len[r] = l;
+    order[r] = r;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+  const int steps = len[order[0]] + 1;
+  // alive[j], j = 1 .. steps: rows projection j covers (caption length + 1 >= j); off[q]: first row of slot q
+  std::vector<int> alive(steps + 2, 0), off(steps + 3, 0);
+  for (int j = 1; j <= steps; ++j) {
+    int a = 0;
+    while (a < n && len[order[a]] + 1 >= j) ++a;
+    alive[j] = a;
+  }
+  off[0] = 0; off[1] = n; off[2] = 2 * n;
+  for (int j = 1; j <= steps; ++j) off[2 + j] = off[1 + j] + alive[j];
+  const int P = off[2 + steps], Mp = P - 2 * n;            // all rows; rows of the projections
+  // host tables: tgt (Mp) the projections' targets; fed (P) the token fed to the cell that consumes a slot's state (0: none);
+  // the permutation; the embedding gradient's sorted row list
+  std::vector<int32_t> tgt(Mp, 0), fed(P, 0);
+  for (int i = 0; i < n; ++i) fed[off[1] + i] = V1;         // START
+  for (int j = 1; j <= steps; ++j)
+    for (int i = 0; i < alive[j]; ++i) {
+      const int r = order[i];
+      tgt[off[1 + j] - 2 * n + i] = j <= len[r] ? lab[(size_t)r * L + j - 1] : V1;
+      fed[off[1 + j] + i] = j <= len[r] ? lab[(size_t)r * L + j - 1] : 0;
+    }
+  std::vector<int32_t> erow;
+  for (int r = n; r < P; ++r)
+    if (fed[r] > 0) erow.push_back(r);
+  std::stable_sort(erow.begin(), erow.end(), [&](int32_t a, int32_t b) { return fed[a] < fed[b]; });
+  std::vector<int32_t> eseg, eid;
+  for (size_t i = 0; i < erow.size(); ++i)
+    if (i == 0 || fed[erow[i]] != fed[erow[i - 1]]) { eseg.push_back((int32_t)i); eid.push_back(fed[erow[i]]); }
+  eseg.push_back((int32_t)erow.size());
+  const int ntok = (int)eid.size();
+  // ints on the device: [tgt (Mp) | fed (P) | order (n) | n | erow | eseg | eid]
+  std::vector<int32_t> ih;
+  ih.insert(ih.end(), tgt.begin(), tgt.end());
+  const size_t o_fed = ih.size();   ih.insert(ih.end(), fed.begin(), fed.end());
+  const size_t o_ord = ih.size();   for (int i = 0; i < n; ++i) ih.push_back(order[i]);
+  const size_t o_n = ih.size();     ih.push_back(n);
+  const size_t o_erow = ih.size();  ih.insert(ih.end(), erow.begin(), erow.end());
+  const size_t o_eseg = ih.size();  ih.insert(ih.end(), eseg.begin(), eseg.end());
+  const size_t o_eid = ih.size();   ih.insert(ih.end(), eid.begin(), eid.end());
+  // scratch
+  const size_t ws_floats = std::max(std::max(wgrad_ws_floats(Mp, V1, Hd), wgrad_ws_floats(P, E, 4 * Hd)),
+                                    std::max(wgrad_ws_floats(P - n, Hd, 4 * Hd), wgrad_ws_floats(n, E, D)));
+  float *gcodes, *Hb, *Cb, *Gb, *DGb, *Xb, *dXb, *part, *logits, *dHp, *dhc, *dcc, *dcodes, *ws;
+  double* acc;
+  int32_t* ints;
+  const std::vector<Carve> cv = {
+      {(void**)&gcodes, (size_t)n * D * 4},     {(void**)&Hb, (size_t)P * Hd * 4},       {(void**)&Cb, (size_t)P * Hd * 4},
+      {(void**)&Gb, (size_t)P * 4 * Hd * 4},    {(void**)&DGb, (size_t)P * 4 * Hd * 4},  {(void**)&Xb, (size_t)P * E * 4},
+      {(void**)&dXb, (size_t)P * E * 4},        {(void**)&part, (size_t)n * ld * 4},     {(void**)&logits, (size_t)Mp * V1pad * 4},
+      {(void**)&dHp, (size_t)Mp * Hd * 4},      {(void**)&dhc, (size_t)n * Hd * 4},      {(void**)&dcc, (size_t)n * Hd * 4},
+      {(void**)&dcodes, (size_t)n * D * 4},     {(void**)&ws, ws_floats * 4},            {(void**)&acc, (size_t)n * 8},
+      {(void**)&ints, ih.size() * 4},
+  };
+  const size_t bytes = carve(cv, nullptr);
+  if (bytes > kLmGradMaxScratch)
+    return ctx->fail(DC_E_UNSUPPORTED, "dc_op_lm_grad: n = %d rows of %d steps need %.2f GiB of kept state and scratch, more than the %d GiB "
+                     "a call may take; pass fewer rows per call", n, steps, (double)bytes / (double)((size_t)1 << 30),
+                     (int)(kLmGradMaxScratch >> 30));
+  Fp32Guard fp32(ctx->cfg);
+  const int plan = std::min(n, kScorePlanRows);
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, bytes));
+  carve(cv, base);
+  hipEvent_t ev[5] = {};
+  std::vector<double> acc_host(n);
+  auto slot = [&](float* b, int q, int width) { return b + (size_t)off[q] * width; };
+  auto body = [&]() -> int {
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    const int32_t *d_tgt = ints, *d_fed = ints + o_fed;
+    HIPCHK(hipMemcpyAsync(ints, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev[0], s));
+    // ---- forward ----
+    KCHK(launch_gather_rows(codes, ints + o_ord, ints + o_n, n, D, gcodes, s));
+    DCCHK(lm_start_state(ctx, s, gcodes, n, slot(Xb, 0, E), slot(Gb, 1, 4 * Hd), slot(Cb, 2, Hd), slot(Hb, 2, Hd), plan, nullptr, Ws()));
+    {                          // the image cell again, kept: its pre-activation, c_0 and h_0 (lm_start_state's first GEMM and tail)
+      GemmDesc g;
+      g.A = slot(Xb, 0, E); g.W = ctx->wxT; g.bias = ctx->lstm_b; g.C = slot(Gb, 0, 4 * Hd); g.M = n; g.N = 4 * Hd; g.K = E; g.ldc = 4 * Hd;
+      g.plan_M = plan;
+      DCCHK(run_gemm(ctx, g, s));
+      KCHK(launch_lstm_step_tail(nullptr, nullptr, 0, 0, 0, nullptr, slot(Gb, 0, 4 * Hd), slot(Cb, 1, Hd), slot(Hb, 1, Hd), n, nullptr, Hd, 1,
+                                 nullptr, 1, 0, s));
+    }
+    HIPCHK(hipMemsetAsync(acc, 0, (size_t)n * 8, s));
+    for (int j = 1; j <= steps; ++j) {
+      const bool last = j == steps;
+      GemmDesc v = decode_step_desc(ctx, slot(Hb, 1 + j, Hd), alive[j], plan, last, slot(Gb, 1 + j, 4 * Hd));
+      v.amax_val = part; v.amax_ld = ld; v.rowidx = d_tgt + (off[1 + j] - 2 * n);
+      DCCHK(run_gemm(ctx, v, s));
+      if (!last)               // the rows that go on take their step in the next slot: c is updated in place there
+        HIPCHK(hipMemcpyAsync(slot(Cb, 2 + j, Hd), slot(Cb, 1 + j, Hd), (size_t)alive[j + 1] * Hd * 4, hipMemcpyDeviceToDevice, s));
+      KCHK(launch_lse_step_tail(part, nslots, ld, v.rowidx, V1, ctx->xg, last ? nullptr : slot(Gb, 1 + j, 4 * Hd), slot(Cb, 2 + j, Hd),
+                                slot(Hb, 2 + j, Hd), acc, alive[j], Hd, s));
+    }
+    HIPCHK(hipMemcpyAsync(acc_host.data(), acc, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(ev[1], s));
+    // ---- backward: projections, then the steps ----
+    const float scale = (float)((double)weight / ((double)n * (double)(L + 2)));
+    {
+      GemmDesc g;              // the logits of every step, stored (the scorer's fused epilogue never writes them)
+      g.A = slot(Hb, 2, Hd); g.W = ctx->out_w; g.bias = ctx->out_b; g.C = logits; g.M = Mp; g.N = V1; g.K = Hd; g.ldc = V1pad;
+      DCCHK(run_gemm(ctx, g, s));
+      KCHK(launch_softmax_grad(logits, V1pad, V1, d_tgt, scale, nullptr, Mp, s));
+      g = GemmDesc();          // dH = dlogits.Wout
+      g.A = logits; g.W = ctx->out_wT; g.C = dHp; g.M = Mp; g.N = Hd; g.K = V1pad; g.ldc = Hd;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    HIPCHK(hipMemsetAsync(DGb, 0, (size_t)P * 4 * Hd * 4, s));
+    HIPCHK(hipMemsetAsync(dhc, 0, (size_t)n * Hd * 4, s));
+    HIPCHK(hipMemsetAsync(dcc, 0, (size_t)n * Hd * 4, s));
+    for (int j = steps; j >= 1; --j) {       // the cell that made h_j: kept in slot j, consumed h_{j-1}
+      KCHK(launch_lstm_cell_bwd(slot(Gb, j, 4 * Hd), d_fed + off[j], ctx->xg, slot(Cb, j, Hd), slot(Cb, 1 + j, Hd),
+                                dHp + (size_t)(off[1 + j] - 2 * n) * Hd, dhc, dcc, slot(DGb, j, 4 * Hd), dcc, alive[j], Hd, s));
+      GemmDesc g;              // dh_{j-1} = dgates.Wh^T: the checkpoint's Wh rows are (Hd, 4Hd), K contiguous
+      g.A = slot(DGb, j, 4 * Hd); g.W = ctx->lstm_w_ck + (size_t)E * 4 * Hd; g.C = dhc; g.M = alive[j]; g.N = Hd; g.K = 4 * Hd; g.ldc = Hd;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    KCHK(launch_lstm_cell_bwd(slot(Gb, 0, 4 * Hd), nullptr, nullptr, nullptr, slot(Cb, 1, Hd), nullptr, dhc, dcc, slot(DGb, 0, 4 * Hd), dcc, n,
+                              Hd, s));
+    HIPCHK(hipEventRecord(ev[2], s));
+    // ---- stacked gradients ----
+    KCHK(launch_embed_rows(ctx->emb, d_fed + n, P - n, E, slot(Xb, 1, E), s));
+    KCHK(launch_wgrad(logits, V1pad, slot(Hb, 2, Hd), Hd, Mp, V1, Hd, out.lm_out_w, Hd, ws, s));
+    KCHK(launch_colsum(logits, V1pad, Mp, V1, out.lm_out_b, s));
+    KCHK(launch_wgrad(Xb, E, DGb, 4 * Hd, P, E, 4 * Hd, out.lstm_w, 4 * Hd, ws, s));
+    KCHK(launch_wgrad(slot(Hb, 1, Hd), Hd, slot(DGb, 1, 4 * Hd), 4 * Hd, P - n, Hd, 4 * Hd, out.lstm_w + (size_t)E * 4 * Hd, 4 * Hd, ws, s));
+    KCHK(launch_colsum(DGb, 4 * Hd, P, 4 * Hd, out.lstm_b, s));
+    {
+      GemmDesc g;              // dX = DG.Wx^T for every cell: slot 0 is d(enc) before the ReLU, the rest feed the embedding rows
+      g.A = DGb; g.W = ctx->lstm_w_ck; g.C = dXb; g.M = P; g.N = E; g.K = 4 * Hd; g.ldc = E;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    KCHK(launch_relu_mask(dXb, Xb, (size_t)n * E, s));
+    KCHK(launch_wgrad(dXb, E, gcodes, D, n, E, D, out.lm_enc_w, D, ws, s));
+    KCHK(launch_colsum(dXb, E, n, E, out.lm_enc_b, s));
+    if (out.codes != nullptr) {
+      GemmDesc g;              // dcodes = d(enc).Wenc
+      g.A = dXb; g.W = ctx->enc_wT; g.C = dcodes; g.M = n; g.N = D; g.K = E; g.ldc = D;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    HIPCHK(hipEventRecord(ev[3], s));
+    // ---- rows ----
+    HIPCHK(hipMemsetAsync(out.lm_emb, 0, (size_t)(V + 2) * E * 4, s));
+    KCHK(launch_embed_segsum(dXb, E, ints + o_erow, ints + o_eseg, ints + o_eid, ntok, out.lm_emb, s));
+    if (out.codes != nullptr) KCHK(launch_scatter_rows(dcodes, ints + o_ord, n, D, out.codes, s));
+    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->lm_grad_ms[i], ev[i], ev[i + 1]);
+    ctx->lm_grad_ran = true;
+    double sum = 0.0;
+    for (int r = 0; r < n; ++r) sum += acc_host[r];           // (permuted order: longest caption first)
+    *loss = (double)weight * (-sum) / ((double)n * (double)(L + 2));
+    if (rowlik != nullptr)
+      for (int i = 0; i < n; ++i) rowlik[order[i]] = acc_host[i];
+    return DC_OK;
+  };
+  const int rc = body();
+  const hipError_t e = hipStreamSynchronize(s);
+  for (auto& evt : ev)
+    if (evt != nullptr) hipEventDestroy(evt);
+  hipFree(base);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_lm_grad: %s", hipGetErrorString(e));
+  return DC_OK;
+}
+
 // the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
 int check_sample_opts(dc_ctx* ctx, const dc_sample_opts* o, const char* who) {
   if (o == nullptr) return ctx->fail(DC_E_INVALID, "%s: null options", who);
@@ -1771,12 +1981,14 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
     DCCHK(upload(ctx, &lw, w->lstm_w, (size_t)(E + Hd) * 4 * Hd));
     DCCHK(dev_alloc(ctx, (void**)&ctx->wxT, (size_t)4 * Hd * E * 4));
     DCCHK(dev_alloc(ctx, (void**)&ctx->whT, (size_t)4 * Hd * Hd * 4));
+    ctx->lstm_w_ck = lw;
     KCHK(launch_transpose2d(lw, ctx->wxT, E, 4 * Hd, s));
     KCHK(launch_transpose2d(lw + (size_t)E * 4 * Hd, ctx->whT, Hd, 4 * Hd, s));
     // xg[v] = b + Emb[v].Wx for every token of the LookupTable (V+2 rows): the input half of the
     // gate pre-activation of every decode step becomes a row gather.
     float* emb = nullptr;
     DCCHK(upload(ctx, &emb, w->lm_emb, (size_t)(V + 2) * E));
+    ctx->emb = emb;
     DCCHK(dev_alloc(ctx, (void**)&ctx->xg, (size_t)(V + 2) * 4 * Hd * 4));
     DCCHK(linear(ctx, s, emb, ctx->wxT, ctx->lstm_b, ctx->xg, V + 2, 4 * Hd, E, 0));
     HIPCHK(hipStreamSynchronize(s));
@@ -3115,6 +3327,87 @@ int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on
   if (rc != DC_OK) return rc;
   if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
   return DC_OK;
+}
+
+int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels, int L, float weight, const dc_lm_grads* out,
+                  double* loss, double* rowlik_or_null) {
+  const char* who = "dc_op_lm_grad";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!codes || !labels || !out || !loss) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (!out->lm_enc_w || !out->lm_enc_b || !out->lm_emb || !out->lstm_w || !out->lstm_b || !out->lm_out_w || !out->lm_out_b)
+    return ctx->fail(DC_E_INVALID, "%s: null gradient buffer (only codes may be null)", who);
+  if (n < 1 || n > 1024) return ctx->fail(DC_E_INVALID, "%s: n must be in 1..1024 (got %d)", who, n);
+  if (L < 1 || L > 64) return ctx->fail(DC_E_INVALID, "%s: L must be in 1..64 (got %d)", who, L);
+  if (!std::isfinite(weight)) return ctx->fail(DC_E_INVALID, "%s: weight must be finite", who);
+  DCCHK(check_queries(ctx, labels, n, L, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  return lm_grad(ctx, s, codes, n, labels, L, weight, *out, loss, rowlik_or_null);
+}
+
+// ---- test hooks of the backward kernels (densecap_debug_grad.h) -----------------------------------------------------------------
+int dc_debug_wgrad(dc_ctx* ctx, const float* A, const float* B, int M, int N, int K, float* C) {
+  OP_PROLOGUE();
+  if (!A || !B || !C || M < 1 || N < 1 || K < 1) return ctx->fail(DC_E_INVALID, "dc_debug_wgrad: bad argument");
+  float* ws = nullptr;
+  const size_t wf = wgrad_ws_floats(M, N, K);
+  if (wf > 0) HIPCHK(hipMalloc((void**)&ws, wf * 4));
+  const hipError_t e = launch_wgrad(A, N, B, K, M, N, K, C, K, ws, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (ws != nullptr) hipFree(ws);
+  KCHK(e);
+  KCHK(e2);
+  return DC_OK;
+}
+int dc_debug_embed_segsum(dc_ctx* ctx, const float* dx, const int32_t* tok_host, int count, int E, int rows_out, float* demb) {
+  OP_PROLOGUE();
+  if (!dx || !tok_host || !demb || count < 1 || E < 1 || rows_out < 1) return ctx->fail(DC_E_INVALID, "dc_debug_embed_segsum: bad argument");
+  for (int i = 0; i < count; ++i)
+    if (tok_host[i] < 1 || tok_host[i] > rows_out) return ctx->fail(DC_E_INVALID, "dc_debug_embed_segsum: token %d outside 1..%d", (int)tok_host[i], rows_out);
+  std::vector<int32_t> rows(count), seg, ids;
+  for (int i = 0; i < count; ++i) rows[i] = i;
+  std::stable_sort(rows.begin(), rows.end(), [&](int32_t a, int32_t b) { return tok_host[a] < tok_host[b]; });
+  for (int i = 0; i < count; ++i)
+    if (i == 0 || tok_host[rows[i]] != tok_host[rows[i - 1]]) { seg.push_back(i); ids.push_back(tok_host[rows[i]]); }
+  seg.push_back(count);
+  std::vector<int32_t> ih(rows);
+  ih.insert(ih.end(), seg.begin(), seg.end());
+  ih.insert(ih.end(), ids.begin(), ids.end());
+  int32_t* d = nullptr;
+  HIPCHK(hipMalloc((void**)&d, ih.size() * 4));
+  hipError_t e = hipMemcpyAsync(d, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(demb, 0, (size_t)rows_out * E * 4, s);
+  if (e == hipSuccess) e = launch_embed_segsum(dx, E, d, d + count, d + count + seg.size(), (int)ids.size(), demb, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(d);
+  KCHK(e);
+  KCHK(e2);
+  return DC_OK;
+}
+int dc_debug_softmax_grad(dc_ctx* ctx, float* x, int rows, int V1, int ld, const int32_t* tgt, float scale, double* lse_out_or_null) {
+  OP_PROLOGUE();
+  if (!x || !tgt || rows < 1 || V1 < 1 || ld < V1) return ctx->fail(DC_E_INVALID, "dc_debug_softmax_grad: bad argument");
+  KCHK(launch_softmax_grad(x, ld, V1, tgt, scale, lse_out_or_null, rows, s));
+  OP_EPILOGUE();
+}
+int dc_debug_lstm_cell_bwd(dc_ctx* ctx, const float* gates_pre, const float* c_prev, const float* c, const float* dh,
+                           const float* dc, int rows, int Hd, float* dgates, float* dc_prev) {
+  OP_PROLOGUE();
+  if (!gates_pre || !c_prev || !c || !dh || !dc || !dgates || !dc_prev || rows < 1 || Hd < 1)
+    return ctx->fail(DC_E_INVALID, "dc_debug_lstm_cell_bwd: bad argument");
+  KCHK(launch_lstm_cell_bwd(gates_pre, nullptr, nullptr, c_prev, c, dh, nullptr, dc, dgates, dc_prev, rows, Hd, s));
+  OP_EPILOGUE();
+}
+int dc_debug_lm_grad_stage_ms(dc_ctx* ctx, float* ms) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ms) return ctx->fail(DC_E_INVALID, "dc_debug_lm_grad_stage_ms: null pointer");
+  if (!ctx->lm_grad_ran) return ctx->fail(DC_E_STATE, "dc_debug_lm_grad_stage_ms: no dc_op_lm_grad call has completed");
+  memcpy(ms, ctx->lm_grad_ms, 16);
+  return 4;
 }
 
 // ---- the truncated sampler's test hook (densecap_debug_sample.h) ----------------------------------------------------------------

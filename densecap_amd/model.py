@@ -172,6 +172,7 @@ class DenseCapModel:
         self.fc_dim = w.fc_dim
         check(self.ctx.h, self.lib.dc_load_weights(self.ctx.h, C.byref(w)), "dc_load_weights")
         self.ctx.seq_length = self.seq_length          # ops.lm_sample_n sizes its outputs by it
+        self.ctx.lm_dims = dict(E=int(w.enc_size), Hd=int(w.rnn_size), D=int(w.fc_dim), V=self.vocab_size)   # ops.lm_grad: its buffers
         self._keep = []
         self._push_test_args()
 
@@ -573,6 +574,28 @@ class DenseCapModel:
         (setTestArgs) play no part."""
         from . import ops
         return ops.forward_losses(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
+
+    def lm_gradients(self, codes, labels, weight=1.0):
+        """The captioning loss of n (fc7 code, caption) pairs and its gradients with respect to the seven language-model tensors
+        (checkpoint layouts) and the codes (dc_op_lm_grad; docs/SEMANTICS.md, "Language-model gradients"): a dict of numpy
+        arrays plus `loss` and `rowlik`.  labels (n, L) word ids padded with zeros.  The loaded weights do not change."""
+        from . import ops
+        return ops.lm_grad(self.ctx, codes, labels, weight)
+
+    def caption_gradients(self, img, boxes, labels):
+        """lm_gradients for the caller's boxes on an image: the fc7 codes of the boxes (xcycwh) through the caller-supplied-boxes
+        path without a final NMS, so that row i is box i, then lm_gradients(codes, labels)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        saved = self.opt["final_nms_thresh"]
+        self.opt["final_nms_thresh"] = 0.0
+        try:
+            (_b, feats, src), = self.extractFeatures_boxes([img], [boxes])
+        finally:
+            self.opt["final_nms_thresh"] = saved
+            self._push_test_args()
+        if len(feats) != len(labels) or not np.array_equal(src, np.arange(len(labels))):
+            raise ValueError("caption_gradients: %d boxes came back for %d label rows" % (len(feats), len(labels)))
+        return self.lm_gradients(feats, labels)
 
     def _encode_queries(self, captions, max_len=None):
         """strings (encode_captions, max_len words wide or as wide as the longest) or ready (Q, Tq) id rows -> (Q, Tq) int32"""

@@ -458,6 +458,93 @@ def lm_score(ctx, codes, queries):
     return o.numpy()
 
 
+LM_GRAD_KEYS = ("lm_enc_w", "lm_enc_b", "lm_emb", "lstm_w", "lstm_b", "lm_out_w", "lm_out_b", "codes")
+
+
+def lm_grad(ctx, codes, labels, weight=1.0, want_codes=True):
+    """The captioning loss of n (code, caption) pairs and its gradients (dc_op_lm_grad; docs/SEMANTICS.md, "Language-model
+    gradients") with the ctx's loaded language model.  codes (n, fc_dim); labels (n, L) int, words in [1, V] then zeros.
+    Returns a dict: the seven language-model tensors' gradients in checkpoint layouts and `codes` (n, fc_dim) as numpy arrays,
+    `loss` (float) and `rowlik` (n,) float64, every row's caption log-likelihood."""
+    dims = getattr(ctx, "lm_dims", None)
+    if dims is None:
+        raise _lib.DenseCapError("ops.lm_grad: the ctx carries no model dimensions (build a DenseCapModel on it first)")
+    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
+    x = _f32(codes)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if x.ndim != 2 or x.shape[1] != D:
+        raise ValueError("codes must be (n, %d), got %r" % (D, x.shape))
+    if lab.ndim != 2 or lab.shape[0] != x.shape[0]:
+        raise ValueError("labels must be (n, L) with one row per code, got %r for %d codes" % (lab.shape, x.shape[0]))
+    n, L = lab.shape
+    shapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
+              "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (n, D)}
+    xd = ctx.to_device(x)
+    bufs = {k: ctx.empty(shapes[k]) for k in LM_GRAD_KEYS if want_codes or k != "codes"}
+    g = _lib.DcLmGrads(**{k: b.ptr for k, b in bufs.items()})
+    loss = C.c_double(0.0)
+    rowlik = np.zeros((max(n, 1),), np.float64)
+    check(ctx.h, ctx.lib.dc_op_lm_grad(ctx.h, xd.ptr, n, lab.ctypes.data, L, float(weight), C.byref(g), C.byref(loss),
+                                       rowlik.ctypes.data), "dc_op_lm_grad")
+    out = {k: b.numpy() for k, b in bufs.items()}
+    out["loss"] = float(loss.value)
+    out["rowlik"] = rowlik[:n]
+    return out
+
+
+def lm_grad_stage_ms(ctx):
+    """The library's own event split of the last lm_grad call, in ms: forward, loop back through the steps, stacked
+    gradients, embedding and codes rows."""
+    ms = np.zeros(4, np.float32)
+    check(ctx.h, ctx.lib.dc_debug_lm_grad_stage_ms(ctx.h, ms.ctypes.data_as(_lib.c_float_p)), "dc_debug_lm_grad_stage_ms")
+    return dict(zip(("forward", "bptt", "stacked", "rows"), (float(v) for v in ms)))
+
+
+def wgrad(ctx, A, B):
+    """The weight-gradient kernel alone (dc_debug_wgrad): A (M, N), B (M, K) -> A^T B (N, K)."""
+    A = _f32(A); B = _f32(B)
+    (M, N), K = A.shape, B.shape[1]
+    ad = ctx.to_device(A); bd = ctx.to_device(B)
+    o = ctx.empty((N, K))
+    check(ctx.h, ctx.lib.dc_debug_wgrad(ctx.h, ad.ptr, bd.ptr, M, N, K, o.ptr), "dc_debug_wgrad")
+    return o.numpy()
+
+
+def embed_segsum(ctx, dx, tok, rows_out):
+    """The embedding segment sum alone (dc_debug_embed_segsum): dx (count, E), tok (count,) 1-based -> (rows_out, E)."""
+    dx = _f32(dx)
+    tok = np.ascontiguousarray(tok, dtype=np.int32)
+    d = ctx.to_device(dx)
+    o = ctx.empty((rows_out, dx.shape[1]))
+    check(ctx.h, ctx.lib.dc_debug_embed_segsum(ctx.h, d.ptr, tok.ctypes.data, len(tok), dx.shape[1], int(rows_out), o.ptr),
+          "dc_debug_embed_segsum")
+    return o.numpy()
+
+
+def softmax_grad(ctx, logits, tgt, scale, V1=None):
+    """The softmax cross-entropy gradient rows alone (dc_debug_softmax_grad): logits (rows, ld) with V1 <= ld real columns, tgt
+    (rows,) 1-based -> ((rows, ld) gradient rows, (rows,) float64 log-sum-exp)."""
+    x = _f32(logits)
+    rows, ld = x.shape
+    V1 = ld if V1 is None else int(V1)
+    xd = ctx.to_device(x); td = ctx.to_device(np.ascontiguousarray(tgt, dtype=np.int32))
+    lse = ctx.empty((rows,), np.float64)
+    check(ctx.h, ctx.lib.dc_debug_softmax_grad(ctx.h, xd.ptr, rows, V1, ld, td.ptr, float(scale), lse.ptr), "dc_debug_softmax_grad")
+    return xd.numpy(), lse.numpy()
+
+
+def lstm_cell_bwd(ctx, gates_pre, c_prev, c, dh, dc):
+    """The LSTM cell backward alone (dc_debug_lstm_cell_bwd): gates_pre (rows, 4Hd) in gate order i,f,o,g; the rest (rows, Hd)
+    -> (dgates (rows, 4Hd), dc_prev (rows, Hd))."""
+    g = _f32(gates_pre)
+    rows, Hd = g.shape[0], g.shape[1] // 4
+    d = [ctx.to_device(_f32(a)) for a in (g, c_prev, c, dh, dc)]
+    dg = ctx.empty((rows, 4 * Hd)); dcp = ctx.empty((rows, Hd))
+    check(ctx.h, ctx.lib.dc_debug_lstm_cell_bwd(ctx.h, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, rows, Hd, dg.ptr, dcp.ptr),
+          "dc_debug_lstm_cell_bwd")
+    return dg.numpy(), dcp.numpy()
+
+
 def check_sample_args(num_samples, temperature, seed, top_k=0, top_p=1.0, want_sample_logprob=False, vocab_size=None):
     """The rules of dc_sample_opts and dc_sample_trunc (docs/SEMANTICS.md, "Sampling captions"), checked before the library is
     called.  Returns the filled DcSampleOpts (the DcSampleTrunc beside it: sample_trunc_arg).  vocab_size (V): top_k's upper

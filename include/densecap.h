@@ -530,6 +530,21 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens);
 /* The scoring of dc_score_captions on given fc7 codes (n, fc_dim): loglik (n, Q), entry r*Q + q.  Device pointers
  * throughout (codes, queries, loglik); synchronous.  Same rules for the queries. */
 int dc_op_lm_score(dc_ctx* ctx, const float* codes, int n, const int32_t* queries, int Q, int Tq, float* loglik);
+/* Language-model gradients (docs/SEMANTICS.md, "Language-model gradients"): the captioning loss of n (code, caption) pairs and its
+ * gradient with respect to the seven language-model tensors and the codes.  codes: DEVICE (n, fc_dim); labels: HOST (n, L) int32,
+ * each row words in [1, V] followed by zeros (an all-zero row is an empty caption); loss = weight * (-sum_r rowlik_r) / (n (L+2)),
+ * rowlik_r the number dc_op_lm_score gives for the pair (code r, caption r).  out: DEVICE buffers in the layouts of dc_weights --
+ * lm_enc_w (E, fc_dim), lm_enc_b (E), lm_emb (V+2, E), lstm_w (E+Hd, 4Hd) gate order i,f,o,g, lstm_b (4Hd), lm_out_w (V+1, Hd),
+ * lm_out_b (V+1) -- and codes (n, fc_dim), which may be NULL; all are overwritten.  loss: HOST, one double; rowlik_or_null: HOST
+ * (n) doubles.  fp32 whatever dc_set_math_mode says, eager on lane 0, no float atomics (two identical calls give identical
+ * bits); the settings and the loaded weights are left as they were.  Synchronous.  Refused with DC_E_INVALID before anything
+ * is enqueued: n outside 1..1024, L outside 1..64, a label outside [0, V], a word after a zero, a non-finite weight; with
+ * DC_E_UNSUPPORTED: a call whose kept state would exceed 8 GiB of scratch. */
+typedef struct dc_lm_grads {
+  float* lm_enc_w; float* lm_enc_b; float* lm_emb; float* lstm_w; float* lstm_b; float* lm_out_w; float* lm_out_b; float* codes;
+} dc_lm_grads;
+int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels, int L, float weight, const dc_lm_grads* out,
+                  double* loss, double* rowlik_or_null);
 /* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
  * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */

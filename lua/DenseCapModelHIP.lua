@@ -119,6 +119,7 @@ function Model.fromCheckpoint(ref, gpu)
   if rll.test_max_proposals ~= nil then ll.test_max_proposals = rll.test_max_proposals end
   self.opt = {final_nms_thresh = getopt(ref.opt, 'final_nms_thresh', 0.3)}
   self.vocab_size, self.seq_length, self.fc_dim = lm.vocab_size, lm.seq_length, fcs[2].weight:size(1)
+  self.enc_size, self.rnn_size = lm.input_encoding_size, lm.rnn_size
   self.num_anchors = make_anchors.anchors:size(2)
   self.idx_to_token = lm.idx_to_token
   -- keep the reference's field layout for callers that reach into it
@@ -294,6 +295,45 @@ function Model:forward_losses(data, opts)
     end_objectness_loss = out.end_objectness_loss, end_box_reg_loss = out.end_box_reg_loss,
     captioning_loss = out.captioning_loss, total_loss = out.total_loss,
   }
+end
+
+-- Language-model gradients (dc_op_lm_grad; docs/SEMANTICS.md, "Language-model gradients"): codes FloatTensor (n, fc_dim), labels
+-- IntTensor (n, L) word ids padded with zeros, weight (default 1).  Returns a table with the gradients of the seven
+-- language-model tensors in the checkpoint's layouts and of the codes (FloatTensors), loss and rowlik (DoubleTensor (n)).
+function Model:lm_gradients(codes, labels, weight)
+  local x, lab = codes:float():contiguous(), labels:int():contiguous()
+  assert(x:dim() == 2 and x:size(2) == self.fc_dim and lab:dim() == 2 and lab:size(1) == x:size(1), 'codes (n,fc_dim), labels (n,L)')
+  local n, L = lab:size(1), lab:size(2)
+  local E, Hd, D, V = self.enc_size, self.rnn_size, self.fc_dim, self.vocab_size
+  local names = {'lm_enc_w', 'lm_enc_b', 'lm_emb', 'lstm_w', 'lstm_b', 'lm_out_w', 'lm_out_b', 'codes'}
+  local shapes = {lm_enc_w = {E, D}, lm_enc_b = {E}, lm_emb = {V + 2, E}, lstm_w = {E + Hd, 4 * Hd}, lstm_b = {4 * Hd},
+                  lm_out_w = {V + 1, Hd}, lm_out_b = {V + 1}, codes = {n, D}}
+  local g, out, dev = ffi.new('dc_lm_grads'), {}, {}
+  local function release() for _, p in ipairs(dev) do C.dc_free(self.ctx, p) end end
+  local function alloc(bytes)
+    local pp = ffi.new('void*[1]')
+    local rc = C.dc_malloc(self.ctx, pp, bytes)
+    if rc ~= 0 then release(); hip.check(self.ctx, rc, 'dc_malloc') end
+    dev[#dev + 1] = pp[0]
+    return pp[0]
+  end
+  local xd = alloc(x:nElement() * 4)
+  for _, k in ipairs(names) do
+    out[k] = torch.FloatTensor(unpack(shapes[k]))
+    g[k] = ffi.cast('float*', alloc(out[k]:nElement() * 4))
+  end
+  local loss, rowlik = ffi.new('double[1]'), torch.DoubleTensor(n)
+  local rc = C.dc_memcpy_h2d(self.ctx, xd, torch.data(x), x:nElement() * 4)
+  if rc == 0 then
+    rc = C.dc_op_lm_grad(self.ctx, ffi.cast('const float*', xd), n, torch.data(lab), L, weight or 1.0, g, loss, torch.data(rowlik))
+  end
+  for _, k in ipairs(names) do
+    if rc == 0 then rc = C.dc_memcpy_d2h(self.ctx, torch.data(out[k]), g[k], out[k]:nElement() * 4) end
+  end
+  release()
+  hip.check(self.ctx, rc, 'dc_op_lm_grad')
+  out.loss, out.rowlik = loss[0], rowlik
+  return out
 end
 
 -- Rank the regions of one image by log p(query | region) (teacher-forced LanguageModel:updateOutput with a gt_sequence,

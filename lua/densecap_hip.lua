@@ -74,6 +74,15 @@ typedef struct dc_loss_dump { int32_t* pos_input_idx; int32_t* pos_target_idx; i
 int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                       const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts_or_null,
                       const dc_sampler_forced* forced_or_null, dc_losses* out, const dc_loss_dump* dump_or_null);
+int dc_malloc(dc_ctx* ctx, void** dev_ptr, size_t bytes);
+int dc_free(dc_ctx* ctx, void* dev_ptr);
+int dc_memcpy_h2d(dc_ctx* ctx, void* dev_dst, const void* host_src, size_t bytes);
+int dc_memcpy_d2h(dc_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);
+typedef struct dc_lm_grads {
+  float* lm_enc_w; float* lm_enc_b; float* lm_emb; float* lstm_w; float* lstm_b; float* lm_out_w; float* lm_out_b; float* codes;
+} dc_lm_grads;
+int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels, int L, float weight, const dc_lm_grads* out,
+                  double* loss, double* rowlik_or_null);
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
                       const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
                       int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
