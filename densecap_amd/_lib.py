@@ -96,6 +96,12 @@ class DcLmGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("lm_enc_w", "lm_enc_b", "lm_emb", "lstm_w", "lstm_b", "lm_out_w", "lm_out_b", "codes")]
 
 
+class DcRecogGrads(C.Structure):
+    """dc_recog_grads: device buffers for the gradients of dc_op_recog_grad, in checkpoint layouts; all required."""
+    _fields_ = [(n, C.c_void_p) for n in ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "obj_w", "obj_b", "boxreg_w", "boxreg_b", "feat",
+                                          "roi_boxes")]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -214,6 +220,15 @@ _SIGS = {
                                     C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump)]),
     "dc_op_lm_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(DcLmGrads),
                                 C.POINTER(C.c_double), C.c_void_p]),
+    "dc_op_roi_pool_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 +
+                            [C.c_void_p] * 3),
+    "dc_op_recog_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.POINTER(DcLossOpts), C.POINTER(DcRecogGrads), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), c_int32_p]),
+    "dc_loss_gradients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
+                                    C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads)]),
+    "dc_feature_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -243,6 +258,14 @@ _GRAD_HOOK_SIGS = {
                                          C.c_void_p, C.c_void_p]),
     "dc_debug_lm_grad_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
 }
+# the hooks of include/densecap_debug_recog.h (the recognition net's backward kernels; bound like the others)
+_RECOG_HOOK_SIGS = {
+    "dc_debug_roi_tap_index": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4),
+    "dc_debug_end_crit_grad": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "dc_debug_heads_bwd": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "dc_debug_permute_fc6_back": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dc_debug_recog_grad_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -258,7 +281,7 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
-                                  list(_GRAD_HOOK_SIGS.items())):
+                                  list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -11,6 +11,7 @@
 #include "../../include/densecap_debug_sample.h"
 #include "../../include/densecap_debug_beam.h"
 #include "../../include/densecap_debug_grad.h"
+#include "../../include/densecap_debug_recog.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -530,6 +531,36 @@ hipError_t launch_bilinear_roi_pool_group(const float* feat_hwc, size_t feat_str
 hipError_t launch_bilinear_roi_pool(const float* feat_hwc, int h, int w, int C, const float* boxes, int B,
                                     const int32_t* B_dev, int img_h, int img_w, int HH, int WW, float* out,
                                     int out_layout, hipStream_t s);
+
+// ---- backward of bilinear RoI pooling (recog_grad.hip; docs/SEMANTICS.md, "Recognition-net gradients") ----
+// The tap list and the inverted index of B rows of HH x WW points on an h x w map (npix = h * w, T = B * HH * WW * 4 taps):
+// tap t = (row * HH * WW + point) * 4 + k lands on pixel tap_pix[t] (-1: outside the map) with weight tap_w[t]; pixel i's taps
+// are list[start[i] .. start[i + 1]) in ascending order.  count, cursor, chunk0, item_pix and part belong to the kernels.
+struct RoiGradWs {
+  int32_t *tap_pix, *list, *count, *start, *cursor, *chunk0, *item_pix;
+  float *tap_w, *part;
+};
+size_t roi_grad_ws_bytes(int B, int P, int npix, int C);
+RoiGradWs roi_grad_carve(void* base, int B, int P, int npix, int C);
+hipError_t launch_roi_tap_index(const float* boxes, int B, int h, int w, int img_h, int img_w, int HH, int WW, const RoiGradWs& ws,
+                                hipStream_t s);
+// dfeat (h, w, C) = the scatter sum of dout (B, HH, WW, C) over the index (every pixel is written; an untouched one is +0.0)
+hipError_t launch_roi_scatter_sum(const float* dout, int B, int h, int w, int C, int HH, int WW, const RoiGradWs& ws, float* dfeat,
+                                  hipStream_t s);
+// dboxes (B, 4): d/d(xc, yc, w, h) of sum(dout * pooled) with the floors held constant
+hipError_t launch_roi_box_grad(const float* feat_hwc, int h, int w, int C, const float* boxes, int B, int img_h, int img_w, int HH,
+                               int WW, const float* dout, float* dboxes, hipStream_t s);
+
+// the two end criteria's gradients in one launch (see end_crit_grad_kernel): dobj (n), dtrans and danchor (np, 4), *masked
+hipError_t launch_end_crit_grad(const float* obj, const float* trans, const float* anchors, const float* target, int n, int np,
+                                float w_obj, float w_box, float* dobj, float* dtrans, float* danchor, int32_t* masked, hipStream_t s);
+// the recognition heads' backward: dcodes (n, D), dw5 (5, D) and db5 (5) in the order obj, 4 boxreg; g (np, D) or null
+hipError_t launch_heads_bwd(const float* codes, const float* w5, const float* dobj, const float* dtrans, const float* g, int n, int np,
+                            int D, float* dcodes, float* dw5, float* db5, hipStream_t s);
+// (N, HW*C) with k' = p*C + c  ->  k = c*HW + p, the inverse of launch_permute_fc6; C % 64 == 0, HW <= 64, N <= 65535
+hipError_t launch_permute_fc6_back(const float* in, float* out, int N, int C, int HW, hipStream_t s);
+// out[r] = a[r] + (r < np ? b[r] : 0), n rows of four floats
+hipError_t launch_add_pos_rows4(const float* a, const float* b, int n, int np, float* out, hipStream_t s);
 
 // ---- image preprocessing (preprocess.hip; run_model.lua:67-74) -------------------------------------------------------
 void preprocess_scaled_size(int H0, int W0, int image_size, int* oh, int* ow);

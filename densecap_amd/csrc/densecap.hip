@@ -202,6 +202,14 @@ struct dc_ctx {
   uint64_t grad_epoch = 0;
   float lm_grad_ms[4] = {0, 0, 0, 0};
   bool lm_grad_ran = false;
+  // recognition-net gradients (recog_backward): fc7_wT (D, D) and fc6_wT (49*512, D), the transposed copies the data gradients
+  // need, made on the first call after a dc_load_weights; the RoI index's scratch (grow only); the event split of the last call
+  float *fc7_wT = nullptr, *fc6_wT = nullptr;
+  uint64_t recog_epoch = 0;
+  DevBuf roi_grad_ws, recog_ws, recog_aux_ws;   // (recog_ws: the backward's scratch; recog_aux_ws: the callers' few rows)
+  hipEvent_t recog_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  float recog_grad_ms[4] = {0, 0, 0, 0};
+  bool recog_grad_ran = false;
   // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
   // rounded up to fp16 (V1pad of them), the constant c of the bound.  Part of the weights, made with dec_w.
   uint16_t* scr_w = nullptr;
@@ -1774,6 +1782,10 @@ void dc_destroy(dc_ctx* ctx) {
   if (ctx->pre_scratch.p) hipFree(ctx->pre_scratch.p);
   if (ctx->pre_taps.p) hipFree(ctx->pre_taps.p);
   if (ctx->loss_ws.p) hipFree(ctx->loss_ws.p);
+  if (ctx->roi_grad_ws.p) hipFree(ctx->roi_grad_ws.p);
+  if (ctx->recog_ws.p) hipFree(ctx->recog_ws.p);
+  if (ctx->recog_aux_ws.p) hipFree(ctx->recog_aux_ws.p);
+  for (hipEvent_t e : ctx->recog_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
   delete ctx;
 }
@@ -3407,6 +3419,377 @@ int dc_debug_lm_grad_stage_ms(dc_ctx* ctx, float* ms) {
   if (!ms) return ctx->fail(DC_E_INVALID, "dc_debug_lm_grad_stage_ms: null pointer");
   if (!ctx->lm_grad_ran) return ctx->fail(DC_E_STATE, "dc_debug_lm_grad_stage_ms: no dc_op_lm_grad call has completed");
   memcpy(ms, ctx->lm_grad_ms, 16);
+  return 4;
+}
+
+// ---- recognition-net gradients (docs/SEMANTICS.md, "Recognition-net gradients") ------------------------------------
+int dc_feature_size(int H, int W, int* h, int* w) {
+  if (!h || !w || H < 1 || W < 1) return DC_E_INVALID;
+  int fh = H, fw = W;
+  for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
+    if (kVgg[i].pool_after) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+  *h = fh; *w = fw;
+  return DC_OK;
+}
+
+// The backward of bilinear RoI pooling on stream s (not synchronised): the tap index in the ctx's own scratch (grow only), the
+// scatter sum, the box gradient.  ev (optional): an event recorded between the scatter sum and the box gradient.
+// a context-owned scratch buffer that only grows (the stream is drained before a buffer in use is replaced)
+static int grow_ws(dc_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t s) {
+  if (b.p != nullptr && bytes <= b.bytes) return DC_OK;
+  if (b.p) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(b.p)); }
+  b = DevBuf();
+  HIPCHK(hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return DC_OK;
+}
+static int roi_pool_grad(dc_ctx* ctx, hipStream_t s, const float* feat, int h, int w, int C, const float* boxes, int B, int img_h,
+                         int img_w, int HH, int WW, const float* dout, float* dfeat, float* dboxes, hipEvent_t ev = nullptr) {
+  const size_t bytes = roi_grad_ws_bytes(B, HH * WW, h * w, C);
+  DCCHK(grow_ws(ctx, ctx->roi_grad_ws, bytes, s));
+  const RoiGradWs ws = roi_grad_carve(ctx->roi_grad_ws.p, B, HH * WW, h * w, C);
+  KCHK(launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s));
+  KCHK(launch_roi_scatter_sum(dout, B, h, w, C, HH, WW, ws, dfeat, s));
+  if (ev != nullptr) HIPCHK(hipEventRecord(ev, s));
+  if (dboxes != nullptr) KCHK(launch_roi_box_grad(feat, h, w, C, boxes, B, img_h, img_w, HH, WW, dout, dboxes, s));
+  return DC_OK;
+}
+static int check_roi_grad_shape(dc_ctx* ctx, int h, int w, int C, int B, int HH, int WW, const char* who) {
+  if (h < 1 || w < 1 || C < 4 || C % 4 || B < 1 || HH < 2 || WW < 2) return ctx->fail(DC_E_INVALID, "%s: bad shape", who);
+  if (HH * WW > 256) return ctx->fail(DC_E_UNSUPPORTED, "%s: HH * WW = %d points, more than the 256 a row may have", who, HH * WW);
+  if ((long long)h * w > (1 << 16) || (long long)B * HH * WW * 4 > (1 << 30))      // (the offsets are scanned by ONE workgroup)
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a map of %d x %d pixels (at most 65536: the trunk's output for the largest image) or %d rows "
+                     "are more than the index takes", who, h, w, B);
+  return DC_OK;
+}
+int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B, int img_h, int img_w,
+                        int HH, int WW, const float* dout, float* dfeat, float* dboxes_or_null) {
+  OP_PROLOGUE();
+  const char* who = "dc_op_roi_pool_grad";
+  if (!feat_hwc || !boxes || !dout || !dfeat) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_roi_grad_shape(ctx, h, w, C, B, HH, WW, who));
+  DCCHK(roi_pool_grad(ctx, s, feat_hwc, h, w, C, boxes, B, img_h, img_w, HH, WW, dout, dfeat, dboxes_or_null));
+  OP_EPILOGUE();
+}
+
+// What the backward reads of the forward: the lane's kept activations of the n sampled rows (or the caller's own).
+struct RecogKept {
+  const float *feat; int h, w;
+  const float *roi_boxes, *roi_feats, *fc6_out, *codes, *obj, *final_trans;
+  const float *target, *g;                   // (np, 4) target boxes; (np, D) gradient of the positive codes or null
+  int n, np, img_h, img_w;
+  float w_obj, w_box;
+};
+constexpr int kRecogK6 = 49 * 512;
+constexpr size_t kRecogGradMaxScratch = (size_t)8 << 30;
+// bytes a call takes: the two transposed weights (kept by the ctx) and the call's scratch
+static std::vector<Carve> recog_carve(dc_ctx* ctx, int n, float** p[12], int32_t** masked) {
+  const size_t D = (size_t)ctx->D, N = (size_t)n;
+  const size_t ws_floats = std::max(wgrad_ws_floats(n, ctx->D, ctx->D), wgrad_ws_floats(n, ctx->D, kRecogK6));
+  return {
+      {(void**)p[0], N * 4},           {(void**)p[1], N * 16},          {(void**)p[2], N * 16},      {(void**)p[3], N * D * 4},
+      {(void**)p[4], N * D * 4},       {(void**)p[5], N * kRecogK6 * 4}, {(void**)p[6], D * kRecogK6 * 4}, {(void**)p[7], 5 * D * 4},
+      {(void**)p[8], 256},             {(void**)p[9], N * 16},          {(void**)p[10], ws_floats * 4}, {(void**)p[11], 2 * 1024 * 4},
+      {(void**)masked, 256},
+  };
+}
+static int check_recog_scratch(dc_ctx* ctx, int n, int h, int w, const char* who) {
+  float* d[12]; float** p[12]; int32_t* m;
+  for (int i = 0; i < 12; ++i) p[i] = &d[i];
+  const size_t D = (size_t)ctx->D;
+  const size_t bytes = carve(recog_carve(ctx, n, p, &m), nullptr) + (D * D + D * kRecogK6) * 4 + roi_grad_ws_bytes(n, 49, h * w, 512);
+  if (bytes > kRecogGradMaxScratch)
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: n = %d rows at fc_dim = %d need %.2f GiB of scratch, more than the %d GiB a call may take", who,
+                     n, ctx->D, (double)bytes / (double)((size_t)1 << 30), (int)(kRecogGradMaxScratch >> 30));
+  return DC_OK;
+}
+static int check_recog_out(dc_ctx* ctx, const dc_recog_grads* o, const char* who) {
+  if (!o || !o->fc6_w || !o->fc6_b || !o->fc7_w || !o->fc7_b || !o->obj_w || !o->obj_b || !o->boxreg_w || !o->boxreg_b || !o->feat ||
+      !o->roi_boxes)
+    return ctx->fail(DC_E_INVALID, "%s: null recognition gradient buffer", who);
+  return DC_OK;
+}
+
+// Launch list (lane 0's stream, eager; the caller holds LossCfgGuard):
+//   end_crit_grad; heads_bwd; five small copies into the head outputs
+//   relu_mask (fc7); wgrad + colsum (fc7); GEMM on fc7_wT; relu_mask (fc6); wgrad + permute_fc6_back + colsum (fc6)
+//   GEMM on fc6_wT: dpool (n, 7, 7, 512)
+//   memset + roi_taps + roi_index_scan + roi_place + roi_sort_lists; roi_scatter_sum + roi_chunk_reduce
+//   roi_box_grad; add_pos_rows4
+static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const dc_recog_grads& out, int32_t* masked_end) {
+  const int D = ctx->D, n = in.n, np = in.np;
+  if (ctx->fc7_wT == nullptr || ctx->recog_epoch != ctx->weights_epoch) {
+    if (ctx->fc7_wT == nullptr) {
+      DCCHK(dev_alloc(ctx, (void**)&ctx->fc7_wT, (size_t)D * D * 4));
+      DCCHK(dev_alloc(ctx, (void**)&ctx->fc6_wT, (size_t)D * kRecogK6 * 4));
+    }
+    KCHK(launch_transpose2d(ctx->fc7_w, ctx->fc7_wT, D, D, s));
+    KCHK(launch_transpose2d(ctx->fc6_w, ctx->fc6_wT, D, kRecogK6, s));       // (the ctx's fc6_w is point-major: so is dpool)
+    ctx->recog_epoch = ctx->weights_epoch;
+  }
+  float *dobj, *dtrans, *danchor, *dcodes, *dx7, *dpool, *dw6, *dw5, *db5, *dbox, *ws, *spare;
+  int32_t* masked;
+  float** p[12] = {&dobj, &dtrans, &danchor, &dcodes, &dx7, &dpool, &dw6, &dw5, &db5, &dbox, &ws, &spare};
+  const std::vector<Carve> cv = recog_carve(ctx, n, p, &masked);
+  DCCHK(grow_ws(ctx, ctx->recog_ws, carve(cv, nullptr), s));       // kept by the context: 0.45 GB at the real model
+  carve(cv, ctx->recog_ws.p);
+  hipEvent_t* ev = ctx->recog_ev;
+  auto body = [&]() -> int {
+    for (int i = 0; i < 5; ++i)
+      if (ev[i] == nullptr) HIPCHK(hipEventCreate(&ev[i]));
+    HIPCHK(hipEventRecord(ev[0], s));
+    KCHK(launch_end_crit_grad(in.obj, in.final_trans, in.roi_boxes, in.target, n, np, in.w_obj, in.w_box, dobj, dtrans, danchor, masked, s));
+    KCHK(launch_heads_bwd(in.codes, ctx->head5_w, dobj, dtrans, in.g, n, np, D, dcodes, dw5, db5, s));
+    HIPCHK(hipMemcpyAsync(out.obj_w, dw5, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.boxreg_w, dw5 + D, (size_t)4 * D * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.obj_b, db5, 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.boxreg_b, db5 + 1, 16, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(masked_end, masked, 4, hipMemcpyDeviceToHost, s));
+    KCHK(launch_relu_mask(dcodes, in.codes, (size_t)n * D, s));
+    KCHK(launch_wgrad(dcodes, D, in.fc6_out, D, n, D, D, out.fc7_w, D, ws, s));
+    KCHK(launch_colsum(dcodes, D, n, D, out.fc7_b, s));
+    {
+      GemmDesc g;              // d(fc6 output) = d(fc7 pre-activation).W7
+      g.A = dcodes; g.W = ctx->fc7_wT; g.C = dx7; g.M = n; g.N = D; g.K = D; g.ldc = D;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    KCHK(launch_relu_mask(dx7, in.fc6_out, (size_t)n * D, s));
+    KCHK(launch_wgrad(dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, dw6, kRecogK6, ws, s));
+    KCHK(launch_permute_fc6_back(dw6, out.fc6_w, D, 512, 49, s));
+    KCHK(launch_colsum(dx7, D, n, D, out.fc6_b, s));
+    HIPCHK(hipEventRecord(ev[1], s));
+    {
+      GemmDesc g;              // dpool = d(fc6 pre-activation).W6, point-major
+      g.A = dx7; g.W = ctx->fc6_wT; g.C = dpool; g.M = n; g.N = kRecogK6; g.K = D; g.ldc = kRecogK6;
+      DCCHK(run_gemm(ctx, g, s));
+    }
+    HIPCHK(hipEventRecord(ev[2], s));
+    DCCHK(roi_pool_grad(ctx, s, in.feat, in.h, in.w, 512, in.roi_boxes, n, in.img_h, in.img_w, 7, 7, dpool, out.feat, dbox, ev[3]));
+    KCHK(launch_add_pos_rows4(dbox, danchor, n, np, out.roi_boxes, s));
+    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->recog_grad_ms[i], ev[i], ev[i + 1]);
+    ctx->recog_grad_ran = true;
+    return DC_OK;
+  };
+  const int rc = body();
+  const hipError_t e = rc != DC_OK ? hipStreamSynchronize(s) : hipSuccess;      // (a complete body has synchronised)
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "recognition backward: %s", hipGetErrorString(e));
+  return DC_OK;
+}
+
+int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const float* roi_boxes, int n, int num_pos,
+                     const float* target_boxes, const float* dcodes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null,
+                     const dc_recog_grads* out, double* end_objectness_loss, double* end_box_reg_loss, int32_t* masked_end) {
+  const char* who = "dc_op_recog_grad";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!feat_hwc || !roi_boxes || !end_objectness_loss || !end_box_reg_loss || !masked_end) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_recog_out(ctx, out, who));
+  const dc_loss_opts o = opts_or_null ? *opts_or_null : kLossDefaults;
+  DCCHK(check_sampler_opts(ctx, &o, who));
+  if (n < 1 || n > 1024) return ctx->fail(DC_E_INVALID, "%s: n must be in 1..1024 (got %d)", who, n);
+  if (num_pos < 0 || num_pos > n) return ctx->fail(DC_E_INVALID, "%s: num_pos must be in 0..n = %d (got %d)", who, n, num_pos);
+  if (n > o.batch_size) return ctx->fail(DC_E_INVALID, "%s: n = %d rows, more than batch_size = %d", who, n, (int)o.batch_size);
+  if (num_pos > 0 && !target_boxes) return ctx->fail(DC_E_INVALID, "%s: positive rows need target boxes", who);
+  if (img_h < 32 || img_w < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
+  DCCHK(check_image_size(ctx, img_h, img_w, who));
+  DCCHK(check_roi_grad_shape(ctx, h, w, 512, n, 7, 7, who));
+  DCCHK(check_recog_scratch(ctx, n, h, w, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  Lane& L = lane0(ctx);
+  DCCHK(lane_prepare(ctx, L, img_h, img_w, o.batch_size, 1));
+  hipStream_t s = L.stream;
+  const int D = ctx->D, np = num_pos;
+  // ---- the forward half, through dc_forward_losses' own calls ----
+  HIPCHK(hipMemcpyAsync(L.roi_boxes, roi_boxes, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
+  KCHK(launch_bilinear_roi_pool(feat_hwc, h, w, 512, L.roi_boxes, n, nullptr, img_h, img_w, 7, 7, L.roi_feats, 1, s));
+  DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, kRecogK6, 1, lane_ws(L), o.batch_size));
+  DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), o.batch_size));
+  KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
+  // the two end terms by loss_terms itself: its other three terms run on stand-ins (one zero score row, a unit anchor)
+  int32_t* idx = nullptr; double* terms = nullptr; int32_t* masked = nullptr; float* zeros = nullptr; double* rowlik = nullptr;
+  const std::vector<Carve> cv = {{(void**)&idx, 2 * 1024 * 4}, {(void**)&terms, 6 * 8}, {(void**)&masked, 2 * 4}, {(void**)&zeros, 64},
+                                 {(void**)&rowlik, 1024 * 8}};
+  DCCHK(grow_ws(ctx, ctx->recog_aux_ws, carve(cv, nullptr), s));
+  carve(cv, ctx->recog_aux_ws.p);
+  double terms_h[6] = {0};
+  // The contract with loss_terms_kernel this leans on: every term reads only its own inputs; the end objectness term reads
+  // obj[0, n) and num_pos, the end box term roi_boxes / final_trans / gt[pos_target_idx[r]] for r < num_pos; out[2], out[3] and
+  // out_masked[1] depend on nothing else.  The mid terms and the captioning term get inputs on which they stay finite (two-class
+  // scores of zero, the anchor (0, 0, 1, 1) with w, h > 0, zero row sums), and their weights are 0.
+  auto fwd = [&]() -> int {
+    std::vector<int32_t> ih(2 * 1024, 0);
+    for (int r = 0; r < 1024; ++r) ih[1024 + r] = r;                   // [0, 1024): zeros; [1024, 2048): 0, 1, 2 ..
+    const float unit[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f};   // a score row / transform of zeros, the anchor (0, 0, 1, 1)
+    HIPCHK(hipMemcpyAsync(idx, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(zeros, unit, sizeof unit, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(rowlik, 0, 1024 * 8, s));
+    LossTermArgs t{};
+    t.scores = zeros; t.anchors = zeros + 4; t.trans = zeros; t.gt = target_boxes; t.roi_boxes = L.roi_boxes; t.final_trans = L.final_trans;
+    t.obj = L.obj; t.pos_input_idx = idx; t.pos_target_idx = idx + 1024; t.neg_input_idx = idx; t.rowlik = rowlik;
+    t.num_pos = np; t.num_neg = n - np; t.L = 1;
+    t.w_mid_box = 0.f; t.w_mid_obj = 0.f; t.w_end_box = o.end_box_reg_weight; t.w_end_obj = o.end_objectness_weight; t.w_cap = 0.f;
+    t.out = terms; t.out_masked = masked;
+    KCHK(launch_loss_terms(t, s));
+    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DC_OK;
+  };
+  int rc = fwd();
+  if (rc != DC_OK) (void)hipStreamSynchronize(s);
+  L.have_times = false;
+  if (rc != DC_OK) { prof_collect(ctx); return rc; }
+  *end_objectness_loss = terms_h[2];
+  *end_box_reg_loss = terms_h[3];
+  RecogKept k{};
+  k.feat = feat_hwc; k.h = h; k.w = w; k.roi_boxes = L.roi_boxes; k.roi_feats = L.roi_feats; k.fc6_out = L.fc6_out; k.codes = L.codes;
+  k.obj = L.obj; k.final_trans = L.final_trans; k.target = target_boxes; k.g = dcodes_or_null; k.n = n; k.np = np;
+  k.img_h = img_h; k.img_w = img_w; k.w_obj = o.end_objectness_weight; k.w_box = o.end_box_reg_weight;
+  return recog_backward(ctx, s, k, *out, masked_end);
+}
+
+int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int Lw, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg) {
+  const char* who = "dc_loss_gradients";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_recog_out(ctx, rg, who));
+  if (!lg || !lg->lm_enc_w || !lg->lm_enc_b || !lg->lm_emb || !lg->lstm_w || !lg->lstm_b || !lg->lm_out_w || !lg->lm_out_b)
+    return ctx->fail(DC_E_INVALID, "%s: null language-model gradient buffer (only codes may be null)", who);
+  if (Lw > 64) return ctx->fail(DC_E_INVALID, "%s: L must be in 1..64 (got %d)", who, Lw);
+  const dc_loss_opts o = opts ? *opts : kLossDefaults;
+  int fh = 0, fw = 0;
+  if (H >= 32 && W >= 32 && o.batch_size >= 2 && o.batch_size <= 1024) {
+    (void)dc_feature_size(H, W, &fh, &fw);
+    DCCHK(check_recog_scratch(ctx, o.batch_size, fh, fw, who));
+  }
+  if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
+    return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
+  std::vector<int32_t> lists(3 * 1024);
+  const dc_loss_dump own = {lists.data(), lists.data() + 1024, lists.data() + 2048};
+  DCCHK(dc_forward_losses(ctx, img_chw, H, W, img_on_device, gt_boxes, gt_labels, G, Lw, opts, forced, out, &own));
+  const int np = out->num_pos, n = np + out->num_neg, D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
+  if (dump) {
+    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
+    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
+    std::copy(lists.begin() + 2048, lists.begin() + 2048 + out->num_neg, dump->neg_input_idx);
+  }
+  LossCfgGuard guard(ctx->cfg);
+  Lane& L = lane0(ctx);                       // dc_forward_losses left the sampled rows' activations in lane 0
+  hipStream_t s = L.stream;
+  // ---- the language model on the positive rows ----
+  float* gcodes = nullptr;
+  float* tgt_dev = nullptr;
+  const std::vector<Carve> cv = {{(void**)&gcodes, (size_t)std::max(np, 1) * D * 4}, {(void**)&tgt_dev, (size_t)std::max(np, 1) * 16}};
+  DCCHK(grow_ws(ctx, ctx->recog_aux_ws, carve(cv, nullptr), s));
+  carve(cv, ctx->recog_aux_ws.p);
+  auto body = [&]() -> int {
+    if (np > 0) {
+      std::vector<int32_t> lab((size_t)np * Lw);
+      std::vector<float> tgt((size_t)np * 4);
+      for (int r = 0; r < np; ++r) {
+        const int j = lists[1024 + r];
+        std::copy(gt_labels + (size_t)j * Lw, gt_labels + (size_t)(j + 1) * Lw, lab.begin() + (size_t)r * Lw);
+        std::copy(gt_boxes + (size_t)j * 4, gt_boxes + (size_t)(j + 1) * 4, tgt.begin() + (size_t)r * 4);
+      }
+      HIPCHK(hipMemcpyAsync(tgt_dev, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, s));     // (lm_grad synchronises before tgt dies)
+      dc_lm_grads lgo = *lg;
+      lgo.codes = gcodes;
+      double cap = 0.0;
+      DCCHK(lm_grad(ctx, s, L.codes, np, lab.data(), Lw, o.captioning_weight, lgo, &cap, nullptr));
+      if (lg->codes != nullptr) HIPCHK(hipMemcpyAsync(lg->codes, gcodes, (size_t)np * D * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      HIPCHK(hipMemsetAsync(lg->lm_enc_w, 0, (size_t)E * D * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lm_enc_b, 0, (size_t)E * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lm_emb, 0, (size_t)(V + 2) * E * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lstm_w, 0, (size_t)(E + Hd) * 4 * Hd * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lstm_b, 0, (size_t)4 * Hd * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lm_out_w, 0, (size_t)(V + 1) * Hd * 4, s));
+      HIPCHK(hipMemsetAsync(lg->lm_out_b, 0, (size_t)(V + 1) * 4, s));
+    }
+    if (n == 0) {
+      HIPCHK(hipMemsetAsync(rg->fc6_w, 0, (size_t)D * kRecogK6 * 4, s));
+      HIPCHK(hipMemsetAsync(rg->fc6_b, 0, (size_t)D * 4, s));
+      HIPCHK(hipMemsetAsync(rg->fc7_w, 0, (size_t)D * D * 4, s));
+      HIPCHK(hipMemsetAsync(rg->fc7_b, 0, (size_t)D * 4, s));
+      HIPCHK(hipMemsetAsync(rg->obj_w, 0, (size_t)D * 4, s));
+      HIPCHK(hipMemsetAsync(rg->obj_b, 0, 4, s));
+      HIPCHK(hipMemsetAsync(rg->boxreg_w, 0, (size_t)4 * D * 4, s));
+      HIPCHK(hipMemsetAsync(rg->boxreg_b, 0, 16, s));
+      HIPCHK(hipMemsetAsync(rg->feat, 0, (size_t)L.fh * L.fw * 512 * 4, s));
+      HIPCHK(hipStreamSynchronize(s));
+      return DC_OK;
+    }
+    RecogKept k{};
+    k.feat = L.feat; k.h = L.fh; k.w = L.fw; k.roi_boxes = L.roi_boxes; k.roi_feats = L.roi_feats; k.fc6_out = L.fc6_out; k.codes = L.codes;
+    k.obj = L.obj; k.final_trans = L.final_trans; k.target = tgt_dev; k.g = np > 0 ? gcodes : nullptr; k.n = n; k.np = np;
+    k.img_h = H; k.img_w = W; k.w_obj = o.end_objectness_weight; k.w_box = o.end_box_reg_weight;
+    int32_t masked_end = 0;
+    return recog_backward(ctx, s, k, *rg, &masked_end);
+  };
+  const int rc = body();
+  if (rc != DC_OK) (void)hipStreamSynchronize(s);
+  return rc;
+}
+
+// ---- test hooks of the recognition backward (densecap_debug_recog.h) -------------------------------------------------------------
+int dc_debug_roi_tap_index(dc_ctx* ctx, const float* boxes, int B, int h, int w, int img_h, int img_w, int HH, int WW,
+                           int32_t* tap_pix, float* tap_w, int32_t* start, int32_t* list) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_roi_tap_index";
+  if (!boxes || !tap_pix || !tap_w || !start || !list) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_roi_grad_shape(ctx, h, w, 4, B, HH, WW, who));
+  const int npix = h * w;
+  const size_t T = (size_t)B * HH * WW * 4;
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, roi_grad_ws_bytes(B, HH * WW, npix, 4)));
+  const RoiGradWs ws = roi_grad_carve(base, B, HH * WW, npix, 4);
+  hipError_t e = launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tap_pix, ws.tap_pix, T * 4, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tap_w, ws.tap_w, T * 4, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(start, ws.start, ((size_t)npix + 1) * 4, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(list, ws.list, T * 4, hipMemcpyDeviceToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(base);
+  KCHK(e);
+  KCHK(e2);
+  return DC_OK;
+}
+int dc_debug_end_crit_grad(dc_ctx* ctx, const float* obj, const float* trans, const float* anchors, const float* target, int n,
+                           int num_pos, float w_obj, float w_box, float* dobj, float* dtrans, float* danchor, int32_t* masked) {
+  OP_PROLOGUE();
+  if (!obj || !trans || !anchors || !dobj || !dtrans || !danchor || !masked || n < 1 || n > 1024 || num_pos < 0 || num_pos > n ||
+      (num_pos > 0 && !target))
+    return ctx->fail(DC_E_INVALID, "dc_debug_end_crit_grad: bad argument");
+  KCHK(launch_end_crit_grad(obj, trans, anchors, target, n, num_pos, w_obj, w_box, dobj, dtrans, danchor, masked, s));
+  OP_EPILOGUE();
+}
+int dc_debug_heads_bwd(dc_ctx* ctx, const float* codes, const float* w5, const float* dobj, const float* dtrans,
+                       const float* g_or_null, int n, int num_pos, int D, float* dcodes, float* dw5, float* db5) {
+  OP_PROLOGUE();
+  if (!codes || !w5 || !dobj || !dtrans || !dcodes || !dw5 || !db5 || n < 1 || num_pos < 0 || num_pos > n || D < 1)
+    return ctx->fail(DC_E_INVALID, "dc_debug_heads_bwd: bad argument");
+  KCHK(launch_heads_bwd(codes, w5, dobj, dtrans, g_or_null, n, num_pos, D, dcodes, dw5, db5, s));
+  OP_EPILOGUE();
+}
+int dc_debug_permute_fc6_back(dc_ctx* ctx, const float* in, float* out, int N, int C, int HW) {
+  OP_PROLOGUE();
+  if (!in || !out) return ctx->fail(DC_E_INVALID, "dc_debug_permute_fc6_back: null pointer");
+  KCHK(launch_permute_fc6_back(in, out, N, C, HW, s));
+  OP_EPILOGUE();
+}
+int dc_debug_recog_grad_stage_ms(dc_ctx* ctx, float* ms) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ms) return ctx->fail(DC_E_INVALID, "dc_debug_recog_grad_stage_ms: null pointer");
+  if (!ctx->recog_grad_ran) return ctx->fail(DC_E_STATE, "dc_debug_recog_grad_stage_ms: no recognition backward has completed");
+  memcpy(ms, ctx->recog_grad_ms, 16);
   return 4;
 }
 

@@ -15,6 +15,8 @@
 // every fp32 op rounds once, in source order (integer decisions depend on it)
 #pragma clang fp contract(off)
 
+#include "roi_sample.h"
+
 namespace {
 
 // One workgroup per box: phase 1 computes the HH*WW sampling positions once (BoxToAffine + grid + floor +
@@ -75,24 +77,8 @@ __global__ __launch_bounds__(256) void bilinear_roi_pool_kernel(const float* __r
     if (live && threadIdx.x < npts) {
       const int i = threadIdx.x / WW, j = threadIdx.x - i * WW;
       const f32x4 bx = pick != nullptr ? s_box : *reinterpret_cast<const f32x4*>(boxes + (size_t)b * 4);
-      // BoxToAffine.lua:88-91
-      const float th23 = __fdiv_rn(__fadd_rn(__fmul_rn(bx[0], 2.f), -1.f - img_w), img_w - 1.f);
-      const float th13 = __fdiv_rn(__fadd_rn(__fmul_rn(bx[1], 2.f), -1.f - img_h), img_h - 1.f);
-      const float th22 = __fdiv_rn(bx[2], img_w);
-      const float th11 = __fdiv_rn(bx[3], img_h);
-      // AffineGridGeneratorBHWD base grid: -1 + 2*i/(HH-1), computed in double then rounded
-      const float yb = (float)(-1.0 + ((double)i / (double)(HH - 1)) * 2.0);
-      const float xb = (float)(-1.0 + ((double)j / (double)(WW - 1)) * 2.0);
-      const float gy = __fadd_rn(__fadd_rn(__fmul_rn(yb, th11), __fmul_rn(xb, 0.f)), th13);
-      const float gx = __fadd_rn(__fadd_rn(__fmul_rn(yb, 0.f), __fmul_rn(xb, th22)), th23);
-      // BilinearSamplerBHWD_updateOutput
-      const float xcoord = __fdiv_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)(w - 1)), 2.f);
-      const float ycoord = __fdiv_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)(h - 1)), 2.f);
-      const float xfl = floorf(xcoord), yfl = floorf(ycoord);
-      // clamp before the int cast (far-away boxes): anything outside [-1, dim] is invalid either way
-      const int x0 = (int)fminf(fmaxf(xfl, -2.f), (float)w + 1.f), y0 = (int)fminf(fmaxf(yfl, -2.f), (float)h + 1.f);
-      const float wx = __fsub_rn(1.f, __fsub_rn(xcoord, xfl));
-      const float wy = __fsub_rn(1.f, __fsub_rn(ycoord, yfl));
+      const RoiPoint pt = roi_point(bx, img_h, img_w, HH, WW, i, j, h, w);      // (roi_sample.h: shared with the backward)
+      const int x0 = pt.x0, y0 = pt.y0;
       const bool xin0 = x0 >= 0 && x0 <= w - 1, xin1 = x0 + 1 >= 0 && x0 + 1 <= w - 1;
       const bool yin0 = y0 >= 0 && y0 <= h - 1, yin1 = y0 + 1 >= 0 && y0 + 1 <= h - 1;
       const int p = threadIdx.x;
@@ -100,10 +86,9 @@ __global__ __launch_bounds__(256) void bilinear_roi_pool_kernel(const float* __r
       s_off[p][1] = (xin1 && yin0) ? (y0 * w + x0 + 1) * C : -1;
       s_off[p][2] = (xin0 && yin1) ? ((y0 + 1) * w + x0) * C : -1;
       s_off[p][3] = (xin1 && yin1) ? ((y0 + 1) * w + x0 + 1) * C : -1;
-      s_w[p][0] = __fmul_rn(wx, wy);
-      s_w[p][1] = __fmul_rn(__fsub_rn(1.f, wx), wy);
-      s_w[p][2] = __fmul_rn(wx, __fsub_rn(1.f, wy));
-      s_w[p][3] = __fmul_rn(__fsub_rn(1.f, wx), __fsub_rn(1.f, wy));
+      float wt[4];
+      roi_tap_weights(pt.wx, pt.wy, wt);
+      s_w[p][0] = wt[0]; s_w[p][1] = wt[1]; s_w[p][2] = wt[2]; s_w[p][3] = wt[3];
     }
     __syncthreads();
     const int items = npts * C4;

@@ -575,6 +575,17 @@ class DenseCapModel:
         from . import ops
         return ops.forward_losses(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
 
+    def loss_gradients(self, img, gt_boxes, gt_labels, **opts):
+        """forward_losses (same arguments, the same numbers) and the gradient of end_objectness + end_box_reg + captioning with
+        respect to every parameter downstream of the RPN (dc_loss_gradients; docs/SEMANTICS.md, "Recognition-net gradients"):
+        the six losses and the counts, the eight recognition tensors (fc6_w, fc6_b, fc7_w, fc7_b, obj_w, obj_b, boxreg_w,
+        boxreg_b) and the seven language-model tensors in checkpoint layouts, `feat` (512, h, w) -- RoI pooling's share of the
+        feature map's gradient, the reference's layout --, `roi_boxes` (num_pos + num_neg, 4) and `codes` (num_pos, fc_dim), the
+        language model's gradient of the positive codes.  The mid criteria and the sampler / RPN / CNN backward are not part of
+        it; the loaded weights do not change."""
+        from . import ops
+        return ops.loss_gradients(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
+
     def lm_gradients(self, codes, labels, weight=1.0):
         """The captioning loss of n (fc7 code, caption) pairs and its gradients with respect to the seven language-model tensors
         (checkpoint layouts) and the codes (dc_op_lm_grad; docs/SEMANTICS.md, "Language-model gradients"): a dict of numpy

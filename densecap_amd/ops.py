@@ -500,6 +500,186 @@ def lm_grad_stage_ms(ctx):
     return dict(zip(("forward", "bptt", "stacked", "rows"), (float(v) for v in ms)))
 
 
+# ---- recognition-net gradients (docs/SEMANTICS.md, "Recognition-net gradients") ---------------------------------------------------
+RECOG_GRAD_KEYS = ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "obj_w", "obj_b", "boxreg_w", "boxreg_b", "feat", "roi_boxes")
+
+
+def feature_size(ctx, H, W):
+    """(h, w) of the trunk's output map for an H x W image (dc_feature_size)."""
+    h, w = C.c_int(0), C.c_int(0)
+    check(ctx.h, ctx.lib.dc_feature_size(int(H), int(W), C.byref(h), C.byref(w)), "dc_feature_size")
+    return h.value, w.value
+
+
+def roi_pool_grad(ctx, feat_chw, boxes, img_h, img_w, dout, HH=7, WW=7, want_boxes=True):
+    """nn.BilinearRoiPooling backward (dc_op_roi_pool_grad): feat (C,h,w), boxes (B,4) xcycwh, dout (B,C,HH,WW) in the reference's
+    layout -> (dfeat (C,h,w), dboxes (B,4) or None)."""
+    f = _f32(feat_chw); b = _f32(boxes).reshape(-1, 4); d = _f32(dout)
+    C_, h, w = f.shape
+    B = b.shape[0]
+    if d.shape != (B, C_, HH, WW):
+        raise ValueError("dout must be (B, C, HH, WW) = %r, got %r" % ((B, C_, HH, WW), d.shape))
+    fd = ctx.to_device(np.ascontiguousarray(f.transpose(1, 2, 0))); bd = ctx.to_device(b)
+    dd = ctx.to_device(np.ascontiguousarray(d.transpose(0, 2, 3, 1)))
+    df = ctx.empty((h, w, C_)); db = ctx.empty((B, 4)) if want_boxes else None
+    check(ctx.h, ctx.lib.dc_op_roi_pool_grad(ctx.h, fd.ptr, h, w, C_, bd.ptr, B, int(img_h), int(img_w), HH, WW, dd.ptr, df.ptr,
+                                             db.ptr if want_boxes else None), "dc_op_roi_pool_grad")
+    return np.ascontiguousarray(df.numpy().transpose(2, 0, 1)), (db.numpy() if want_boxes else None)
+
+
+def roi_tap_index(ctx, boxes, h, w, img_h, img_w, HH=7, WW=7):
+    """The tap list and the inverted index alone (dc_debug_roi_tap_index): (tap_pix (T,), tap_w (T,), start (h*w+1,), list
+    (start[-1],)) for T = B*HH*WW*4 taps, tap id = (row*HH*WW + point)*4 + k."""
+    b = _f32(boxes).reshape(-1, 4)
+    B = b.shape[0]
+    T = B * HH * WW * 4
+    bd = ctx.to_device(b)
+    tp = ctx.empty((T,), np.int32); tw = ctx.empty((T,)); st = ctx.empty((h * w + 1,), np.int32); li = ctx.empty((T,), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_roi_tap_index(ctx.h, bd.ptr, B, int(h), int(w), int(img_h), int(img_w), HH, WW, tp.ptr, tw.ptr,
+                                                st.ptr, li.ptr), "dc_debug_roi_tap_index")
+    start = st.numpy()
+    return tp.numpy(), tw.numpy(), start, li.numpy()[:start[-1]]
+
+
+def end_crit_grad(ctx, obj, trans, anchors, target, num_pos, w_obj=0.1, w_box=0.1):
+    """The two end criteria's gradients alone (dc_debug_end_crit_grad): obj (n,), trans (n,4), anchors (n,4), target (num_pos,4)
+    -> (dobj (n,), dtrans (num_pos,4), danchor (num_pos,4), masked)."""
+    obj = _f32(obj).reshape(-1)
+    n, np_ = len(obj), int(num_pos)
+    d = [ctx.to_device(_f32(a)) for a in (obj, np.reshape(trans, (n, 4)), np.reshape(anchors, (n, 4)))]
+    td = ctx.to_device(_f32(target).reshape(-1, 4)) if np_ > 0 else None
+    do = ctx.empty((n,)); dt = ctx.empty((max(np_, 1), 4)); da = ctx.empty((max(np_, 1), 4)); m = ctx.empty((1,), np.int32)
+    check(ctx.h, ctx.lib.dc_debug_end_crit_grad(ctx.h, d[0].ptr, d[1].ptr, d[2].ptr, td.ptr if td is not None else None, n, np_,
+                                                float(w_obj), float(w_box), do.ptr, dt.ptr, da.ptr, m.ptr), "dc_debug_end_crit_grad")
+    return do.numpy(), dt.numpy()[:np_], da.numpy()[:np_], int(m.numpy()[0])
+
+
+def heads_bwd(ctx, codes, w5, dobj, dtrans, g=None):
+    """The recognition heads' backward alone (dc_debug_heads_bwd): codes (n,D), w5 (5,D), dobj (n,), dtrans (num_pos,4), g
+    (num_pos,D) or None -> (dcodes (n,D), dw5 (5,D), db5 (5,))."""
+    x = _f32(codes)
+    n, D = x.shape
+    dt = _f32(dtrans).reshape(-1, 4)
+    np_ = len(dt)
+    xd = ctx.to_device(x); wd = ctx.to_device(_f32(w5).reshape(5, D)); od = ctx.to_device(_f32(dobj).reshape(n))
+    td = ctx.to_device(dt if np_ else np.zeros((1, 4), np.float32))
+    gd = ctx.to_device(_f32(g).reshape(np_, D)) if g is not None and np_ else None
+    dc = ctx.empty((n, D)); dw = ctx.empty((5, D)); db = ctx.empty((5,))
+    check(ctx.h, ctx.lib.dc_debug_heads_bwd(ctx.h, xd.ptr, wd.ptr, od.ptr, td.ptr, gd.ptr if gd is not None else None, n, np_, D,
+                                            dc.ptr, dw.ptr, db.ptr), "dc_debug_heads_bwd")
+    return dc.numpy(), dw.numpy(), db.numpy()
+
+
+def permute_fc6_back(ctx, x, C_, HW):
+    """(N, HW*C) with k' = p*C + c -> (N, C*HW) with k = c*HW + p (dc_debug_permute_fc6_back)."""
+    x = _f32(x)
+    N = x.shape[0]
+    xd = ctx.to_device(x); o = ctx.empty((N, C_ * HW))
+    check(ctx.h, ctx.lib.dc_debug_permute_fc6_back(ctx.h, xd.ptr, o.ptr, N, int(C_), int(HW)), "dc_debug_permute_fc6_back")
+    return o.numpy()
+
+
+def recog_grad_stage_ms(ctx):
+    """The library's own event split of the last recognition backward, in ms."""
+    ms = np.zeros(4, np.float32)
+    check(ctx.h, ctx.lib.dc_debug_recog_grad_stage_ms(ctx.h, ms.ctypes.data_as(_lib.c_float_p)), "dc_debug_recog_grad_stage_ms")
+    return dict(zip(("heads_fc", "dpool", "roi_scatter", "roi_boxes"), (float(v) for v in ms)))
+
+
+def _recog_bufs(ctx, D, h, w, rows):
+    shapes = {"fc6_w": (D, 512 * 49), "fc6_b": (D,), "fc7_w": (D, D), "fc7_b": (D,), "obj_w": (1, D), "obj_b": (1,),
+              "boxreg_w": (4, D), "boxreg_b": (4,), "feat": (h, w, 512), "roi_boxes": (max(rows, 1), 4)}
+    return {k: ctx.empty(shapes[k]) for k in RECOG_GRAD_KEYS}
+
+
+def _recog_out(bufs, n):
+    out = {k: b.numpy() for k, b in bufs.items()}
+    out["feat"] = np.ascontiguousarray(out["feat"].transpose(2, 0, 1))           # (512, h, w), the reference's layout
+    out["roi_boxes"] = out["roi_boxes"][:n]
+    return out
+
+
+def recog_grad(ctx, feat_chw, roi_boxes, num_pos, target_boxes, img_h, img_w, dcodes=None, **opts):
+    """The recognition net's gradients on given rows (dc_op_recog_grad; docs/SEMANTICS.md, "Recognition-net gradients") with the
+    ctx's loaded weights.  feat (512,h,w); roi_boxes (n,4), positives first; target_boxes (num_pos,4); dcodes (num_pos,fc_dim) or
+    None.  Returns a dict: the eight parameter gradients in checkpoint layouts, feat (512,h,w), roi_boxes (n,4),
+    end_objectness_loss, end_box_reg_loss (float) and masked_end."""
+    dims = getattr(ctx, "lm_dims", None)
+    if dims is None:
+        raise _lib.DenseCapError("ops.recog_grad: the ctx carries no model dimensions (build a DenseCapModel on it first)")
+    D = dims["D"]
+    f = _f32(feat_chw); b = _f32(roi_boxes).reshape(-1, 4)
+    n, np_ = len(b), int(num_pos)
+    if f.ndim != 3 or f.shape[0] != 512:
+        raise ValueError("feat must be (512, h, w), got %r" % (f.shape,))
+    h, w = f.shape[1:]
+    o = loss_opts(**opts)
+    fd = ctx.to_device(np.ascontiguousarray(f.transpose(1, 2, 0))); bd = ctx.to_device(b)
+    td = ctx.to_device(_f32(target_boxes).reshape(np_, 4)) if np_ > 0 else None
+    gd = ctx.to_device(_f32(dcodes).reshape(np_, D)) if dcodes is not None and np_ > 0 else None
+    bufs = _recog_bufs(ctx, D, h, w, n)
+    g = _lib.DcRecogGrads(**{k: v.ptr for k, v in bufs.items()})
+    lo, lb, m = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    check(ctx.h, ctx.lib.dc_op_recog_grad(ctx.h, fd.ptr, h, w, bd.ptr, n, np_, td.ptr if td is not None else None,
+                                          gd.ptr if gd is not None else None, int(img_h), int(img_w), C.byref(o), C.byref(g),
+                                          C.byref(lo), C.byref(lb), C.byref(m)), "dc_op_recog_grad")
+    out = _recog_out(bufs, n)
+    out.update(end_objectness_loss=float(lo.value), end_box_reg_loss=float(lb.value), masked_end=int(m.value))
+    return out
+
+
+def loss_gradients(ctx, img, gt_boxes, gt_labels, forced_pos=None, forced_neg=None, dump=False, on_device=False, **opts):
+    """dc_loss_gradients: the losses of forward_losses (same arguments, same numbers) and the gradient of end_objectness +
+    end_box_reg + captioning with respect to every parameter downstream of the RPN.  Returns forward_losses' dict plus the eight
+    recognition and seven language-model parameter gradients in checkpoint layouts, `codes` (num_pos, fc_dim) -- the language
+    model's gradient of the positive codes --, `feat` (512,h,w) -- RoI pooling's share of the feature map's gradient -- and
+    `roi_boxes` (num_pos + num_neg, 4)."""
+    dims = getattr(ctx, "lm_dims", None)
+    if dims is None:
+        raise _lib.DenseCapError("ops.loss_gradients: the ctx carries no model dimensions (build a DenseCapModel on it first)")
+    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
+    g = _f32(gt_boxes).reshape(-1, 4)
+    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
+    if lab.ndim != 2 or len(lab) != len(g):
+        raise ValueError("loss_gradients: gt_labels must be (G, L) with one row per ground-truth box")
+    o = loss_opts(**opts)
+    f, keep = _forced_lists(forced_pos, forced_neg)
+    out = _lib.DcLosses()
+    d = None
+    if dump:
+        lists = [np.zeros(max(int(o.batch_size), 1), np.int32) for _ in range(3)]
+        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
+    if on_device:
+        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
+    else:
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
+    h, w = feature_size(ctx, H, W)
+    cap = max(int(o.batch_size), 1)
+    rbufs = _recog_bufs(ctx, D, h, w, cap)
+    lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
+               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)}
+    lbufs = {k: ctx.empty(lshapes[k]) for k in LM_GRAD_KEYS}
+    rg = _lib.DcRecogGrads(**{k: v.ptr for k, v in rbufs.items()})
+    lg = _lib.DcLmGrads(**{k: v.ptr for k, v in lbufs.items()})
+    check(ctx.h, ctx.lib.dc_loss_gradients(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
+                                           len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
+                                           C.byref(out), C.byref(d) if d is not None else None, C.byref(rg), C.byref(lg)),
+          "dc_loss_gradients")
+    res = {k: float(getattr(out, k)) for k in LOSS_KEYS}
+    res.update({k: int(getattr(out, k)) for k in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
+    if dump:
+        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
+                   neg_input_idx=lists[2][:out.num_neg].copy())
+    n = out.num_pos + out.num_neg
+    if n == 0:
+        rbufs["roi_boxes"] = ctx.to_device(np.zeros((1, 4), np.float32))
+    res.update(_recog_out(rbufs, n))
+    res.update({k: b.numpy() for k, b in lbufs.items()})
+    res["codes"] = res["codes"][:out.num_pos] if out.num_pos > 0 else np.zeros((0, D), np.float32)
+    return res
+
+
 def wgrad(ctx, A, B):
     """The weight-gradient kernel alone (dc_debug_wgrad): A (M, N), B (M, K) -> A^T B (N, K)."""
     A = _f32(A); B = _f32(B)

@@ -545,6 +545,45 @@ typedef struct dc_lm_grads {
 } dc_lm_grads;
 int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels, int L, float weight, const dc_lm_grads* out,
                   double* loss, double* rowlik_or_null);
+/* nn.BilinearRoiPooling backward (docs/SEMANTICS.md, "Recognition-net gradients"): feat (h, w, C) HWC, boxes (B, 4) xcycwh image
+ * px and dout (B, HH, WW, C) -> dfeat (h, w, C), the scatter of weight * dout over the four taps of every point (out-of-map taps
+ * give nothing; every pixel is written, an untouched one is +0.0), and dboxes_or_null (B, 4), the derivatives of sum(dout *
+ * pooled) with the floors held constant.  Positions and weights are the forward's bits.  No float atomics: every sum has a fixed
+ * order and two identical calls give identical bits.  C % 4 == 0, B >= 1, HH, WW >= 2: DC_E_INVALID otherwise; HH * WW > 256,
+ * or h * w > 65536 pixels (the list offsets are scanned by one workgroup; 65536 is the trunk's output for the largest image the
+ * forward admits): DC_E_UNSUPPORTED.  The index's scratch is kept by the ctx and only grows.  Device pointers; synchronous. */
+int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B, int img_h, int img_w,
+                        int HH, int WW, const float* dout, float* dfeat, float* dboxes_or_null);
+/* Recognition-net gradients (docs/SEMANTICS.md, "Recognition-net gradients"): the gradient of end_objectness + end_box_reg (+ a
+ * caller's gradient of the positive codes) through the two recognition heads, fc7, fc6 and RoI pooling.  feat (h, w, 512) HWC,
+ * roi_boxes (n, 4) the sampled rows, positives first; target_boxes (num_pos, 4); dcodes_or_null (num_pos, fc_dim): all DEVICE.
+ * out: DEVICE buffers, all overwritten -- fc6_w (fc_dim, 512*49) in the checkpoint's (c, i, j) input order, fc6_b, fc7_w
+ * (fc_dim, fc_dim), fc7_b, obj_w (fc_dim), obj_b (1), boxreg_w (4, fc_dim), boxreg_b (4), feat (h, w, 512) -- RoI pooling's share
+ * of the feature map's gradient -- and roi_boxes (n, 4).  opts_or_null: batch_size (the rows the forward GEMMs are planned on) and
+ * the two end weights are read.  The losses (HOST doubles) and masked_end (HOST) are what dc_forward_losses reports for these rows.
+ * fp32 whatever dc_set_math_mode says, eager on lane 0, no float atomics; settings and weights are left as they were.
+ * Synchronous.  h and w are taken on trust: they are NOT checked against dc_feature_size(img_h, img_w), and only the caller's own
+ * feat buffers are indexed by them (the lane's buffers are sized from img_h, img_w and batch_size).  DC_E_INVALID before any
+ * launch: n outside 1..1024, num_pos outside 0..n, n > batch_size, a null output, positive rows without target boxes, an image
+ * side below 32 px, bad sampler options; DC_E_UNSUPPORTED: h * w > 65536, or scratch above 8 GiB.  The scratch (0.45 GB at the
+ * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the two mid criteria, the sampler / RPN / CNN backward, any optimiser. */
+typedef struct dc_recog_grads {
+  float* fc6_w; float* fc6_b; float* fc7_w; float* fc7_b; float* obj_w; float* obj_b; float* boxreg_w; float* boxreg_b; float* feat; float* roi_boxes;
+} dc_recog_grads;
+int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const float* roi_boxes, int n, int num_pos,
+                     const float* target_boxes, const float* dcodes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null,
+                     const dc_recog_grads* out, double* end_objectness_loss, double* end_box_reg_loss, int32_t* masked_end);
+/* dc_forward_losses (same arguments, the same dc_losses bit for bit), then the gradient of end_objectness + end_box_reg +
+ * captioning with respect to every parameter downstream of the RPN: dc_op_lm_grad on the positive rows' codes and the labels of
+ * their ground-truth boxes with weight = captioning_weight (lg: its seven tensors, all required; lg->codes may be NULL), then
+ * dc_op_recog_grad's backward with those code gradients (rg: all ten required; feat is (h, w, 512) for dc_feature_size(H, W),
+ * roi_boxes (num_pos + num_neg, 4) -- batch_size rows of room).  With no sampled row (num_pos + num_neg == 0) or no positive the
+ * corresponding gradients are zero.  Synchronous. */
+int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg);
+/* The size of the trunk's output map for an H x W image (four ceil-mode 2x2 pools). */
+int dc_feature_size(int H, int W, int* h, int* w);
 /* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
  * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */

@@ -83,6 +83,18 @@ typedef struct dc_lm_grads {
 } dc_lm_grads;
 int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels, int L, float weight, const dc_lm_grads* out,
                   double* loss, double* rowlik_or_null);
+int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C, const float* boxes, int B, int img_h, int img_w,
+                        int HH, int WW, const float* dout, float* dfeat, float* dboxes_or_null);
+typedef struct dc_recog_grads {
+  float* fc6_w; float* fc6_b; float* fc7_w; float* fc7_b; float* obj_w; float* obj_b; float* boxreg_w; float* boxreg_b; float* feat; float* roi_boxes;
+} dc_recog_grads;
+int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const float* roi_boxes, int n, int num_pos,
+                     const float* target_boxes, const float* dcodes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null,
+                     const dc_recog_grads* out, double* end_objectness_loss, double* end_box_reg_loss, int32_t* masked_end);
+int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg);
+int dc_feature_size(int H, int W, int* h, int* w);
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
                       const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
                       int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
