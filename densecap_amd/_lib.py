@@ -266,6 +266,14 @@ _RECOG_HOOK_SIGS = {
     "dc_debug_permute_fc6_back": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dc_debug_recog_grad_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
 }
+# the hooks of include/densecap_debug_bwd.h (the backward kernels on the operand forms production uses; bound like the others)
+_BWD_HOOK_SIGS = {
+    "dc_debug_wgrad_ld": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_int]),
+    "dc_debug_colsum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dc_debug_lstm_cell_bwd_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                  [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -281,7 +289,8 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
-                                  list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items())):
+                                  list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
+                                  list(_BWD_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -12,6 +12,7 @@
 #include "../../include/densecap_debug_beam.h"
 #include "../../include/densecap_debug_grad.h"
 #include "../../include/densecap_debug_recog.h"
+#include "../../include/densecap_debug_bwd.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -3422,6 +3422,45 @@ int dc_debug_lm_grad_stage_ms(dc_ctx* ctx, float* ms) {
   return 4;
 }
 
+// ---- the same kernels on the operand forms the backward passes use (densecap_debug_bwd.h) -----------------------------------------
+int dc_debug_wgrad_ld(dc_ctx* ctx, const float* A, int lda, const float* B, int ldb, int M, int N, int K, float* C, int ldc) {
+  OP_PROLOGUE();
+  if (!A || !B || !C || M < 1 || N < 1 || K < 1 || lda < N || ldb < K || ldc < K)
+    return ctx->fail(DC_E_INVALID, "dc_debug_wgrad_ld: bad argument");
+  float* ws = nullptr;
+  const size_t wf = wgrad_ws_floats(M, N, K);
+  if (wf > 0) HIPCHK(hipMalloc((void**)&ws, wf * 4));
+  const hipError_t e = launch_wgrad(A, lda, B, ldb, M, N, K, C, ldc, ws, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (ws != nullptr) hipFree(ws);
+  KCHK(e);
+  KCHK(e2);
+  return DC_OK;
+}
+int dc_debug_colsum(dc_ctx* ctx, const float* X, int ldx, int M, int N, float* out) {
+  OP_PROLOGUE();
+  if (!X || !out || M < 1 || N < 1 || ldx < N) return ctx->fail(DC_E_INVALID, "dc_debug_colsum: bad argument");
+  KCHK(launch_colsum(X, ldx, M, N, out, s));
+  OP_EPILOGUE();
+}
+int dc_debug_lstm_cell_bwd_ex(dc_ctx* ctx, const float* gates_pre, const int32_t* tok, const float* xg, int xg_rows,
+                              const float* c_prev, const float* c, const float* dh_a, const float* dh_b, const float* dc_in,
+                              int rows, int Hd, float* dgates, float* dc_prev) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_lstm_cell_bwd_ex";
+  if (!gates_pre || !c || (!dh_a && !dh_b) || !dgates || !dc_prev || rows < 1 || Hd < 1 || (tok != nullptr) != (xg != nullptr) ||
+      (xg != nullptr && xg_rows < 1))
+    return ctx->fail(DC_E_INVALID, "%s: bad argument", who);
+  if (tok != nullptr) {                          // the kernel trusts its tokens: the caller's are checked here
+    std::vector<int32_t> th(rows);
+    HIPCHK(hipMemcpy(th.data(), tok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < rows; ++r)
+      if (th[r] < 0 || th[r] > xg_rows) return ctx->fail(DC_E_INVALID, "%s: row %d: token %d outside 0..%d", who, r, (int)th[r], xg_rows);
+  }
+  KCHK(launch_lstm_cell_bwd(gates_pre, tok, xg, c_prev, c, dh_a, dh_b, dc_in, dgates, dc_prev, rows, Hd, s));
+  OP_EPILOGUE();
+}
+
 // ---- recognition-net gradients (docs/SEMANTICS.md, "Recognition-net gradients") ------------------------------------
 int dc_feature_size(int H, int W, int* h, int* w) {
   if (!h || !w || H < 1 || W < 1) return DC_E_INVALID;

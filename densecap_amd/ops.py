@@ -725,6 +725,51 @@ def lstm_cell_bwd(ctx, gates_pre, c_prev, c, dh, dc):
     return dg.numpy(), dcp.numpy()
 
 
+def wgrad_ld(ctx, A, B, N, K, C0):
+    """The weight-gradient kernel with leading dimensions (dc_debug_wgrad_ld): A (M, lda) and B (M, ldb) of which the first N and
+    K columns count, C0 (N, ldc) the output buffer's contents before the call -> the buffer after it (columns [K, ldc) untouched)."""
+    A = _f32(A); B = _f32(B); C0 = _f32(C0)
+    M = A.shape[0]
+    if B.shape[0] != M or C0.shape[0] != N or A.shape[1] < N or B.shape[1] < K or C0.shape[1] < K:
+        raise ValueError("wgrad_ld: shapes %r, %r, %r do not hold N = %d, K = %d" % (A.shape, B.shape, C0.shape, N, K))
+    ad = ctx.to_device(A); bd = ctx.to_device(B); cd = ctx.to_device(C0)
+    check(ctx.h, ctx.lib.dc_debug_wgrad_ld(ctx.h, ad.ptr, A.shape[1], bd.ptr, B.shape[1], M, int(N), int(K), cd.ptr, C0.shape[1]),
+          "dc_debug_wgrad_ld")
+    return cd.numpy()
+
+
+def colsum(ctx, X, N):
+    """The bias gradients' column sums alone (dc_debug_colsum): X (M, ldx) of which the first N columns count -> (N,)."""
+    X = _f32(X)
+    M, ldx = X.shape
+    if ldx < N:
+        raise ValueError("colsum: X has %d columns, N = %d" % (ldx, N))
+    xd = ctx.to_device(X)
+    o = ctx.empty((int(N),))
+    check(ctx.h, ctx.lib.dc_debug_colsum(ctx.h, xd.ptr, ldx, M, int(N), o.ptr), "dc_debug_colsum")
+    return o.numpy()
+
+
+def lstm_cell_bwd_ex(ctx, gates_pre, c, tok=None, xg=None, c_prev=None, dh_a=None, dh_b=None, dc_in=None, alias=False):
+    """The LSTM cell backward with every operand of its launcher (dc_debug_lstm_cell_bwd_ex): gates_pre (rows, 4Hd); c (rows, Hd);
+    tok (rows,) with xg (xg_rows, 4Hd), c_prev, dh_a, dh_b, dc_in (rows, Hd) or None.  alias=True writes dc_prev into dc_in's own
+    buffer.  -> (dgates (rows, 4Hd), dc_prev (rows, Hd))."""
+    g = _f32(gates_pre)
+    rows, Hd = g.shape[0], g.shape[1] // 4
+    dev = lambda a: None if a is None else ctx.to_device(_f32(a))
+    ptr = lambda d: None if d is None else d.ptr
+    gd, cd, xgd, cpd, had, hbd, dcd = (dev(a) for a in (g, c, xg, c_prev, dh_a, dh_b, dc_in))
+    td = None if tok is None else ctx.to_device(np.ascontiguousarray(tok, dtype=np.int32))
+    if alias and dcd is None:
+        raise ValueError("lstm_cell_bwd_ex: alias=True needs dc_in")
+    dg = ctx.empty((rows, 4 * Hd))
+    dcp = dcd if alias else ctx.empty((rows, Hd))
+    check(ctx.h, ctx.lib.dc_debug_lstm_cell_bwd_ex(ctx.h, gd.ptr, ptr(td), ptr(xgd), 0 if xg is None else len(xg), ptr(cpd), cd.ptr,
+                                                   ptr(had), ptr(hbd), ptr(dcd), rows, Hd, dg.ptr, dcp.ptr),
+          "dc_debug_lstm_cell_bwd_ex")
+    return dg.numpy(), dcp.numpy()
+
+
 def check_sample_args(num_samples, temperature, seed, top_k=0, top_p=1.0, want_sample_logprob=False, vocab_size=None):
     """The rules of dc_sample_opts and dc_sample_trunc (docs/SEMANTICS.md, "Sampling captions"), checked before the library is
     called.  Returns the filled DcSampleOpts (the DcSampleTrunc beside it: sample_trunc_arg).  vocab_size (V): top_k's upper

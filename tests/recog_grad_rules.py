@@ -70,15 +70,18 @@ def roi_pool(feat, boxes, img_h, img_w, HH=7, WW=7, variant=None, coords="float3
     return out.permute(1, 0, 2, 3)
 
 
-def roi_pool_grad(feat, boxes, img_h, img_w, dout, HH=7, WW=7, variant=None, coords="float32"):
-    """(dfeat (C, h, w), dboxes (B, 4)) float64 of sum(dout * pooled) for numpy inputs; dout (B, C, HH, WW)."""
+def roi_pool_grad(feat, boxes, img_h, img_w, dout, HH=7, WW=7, variant=None, coords="float32", dtype=None):
+    """(dfeat (C, h, w), dboxes (B, 4)) float64 of sum(dout * pooled) for numpy inputs; dout (B, C, HH, WW).  dtype: the type the
+    rules are evaluated in (float64; torch.float32 gives the error any fp32 evaluation carries)."""
     import torch
+    dtype = dtype or torch.float64
     with torch.enable_grad():
-        f = torch.tensor(np.asarray(feat, F32).astype(np.float64), requires_grad=True)
-        b = torch.tensor(np.asarray(boxes, F32).reshape(-1, 4).astype(np.float64), requires_grad=True)
-        s = (roi_pool(f, b, img_h, img_w, HH, WW, variant, coords) * torch.tensor(np.asarray(dout, F32).astype(np.float64))).sum()
+        f = torch.tensor(np.asarray(feat, F32).astype(np.float64), dtype=dtype, requires_grad=True)
+        b = torch.tensor(np.asarray(boxes, F32).reshape(-1, 4).astype(np.float64), dtype=dtype, requires_grad=True)
+        d = torch.tensor(np.asarray(dout, F32).astype(np.float64), dtype=dtype)
+        s = (roi_pool(f, b, img_h, img_w, HH, WW, variant, coords) * d).sum()
         df, db = torch.autograd.grad(s, [f, b])
-    return df.numpy(), db.numpy()
+    return df.double().numpy(), db.double().numpy()
 
 
 def _torch_params(W, dtype, requires_grad=True):

@@ -1,10 +1,12 @@
 """dc_op_lm_grad (docs/SEMANTICS.md, "Language-model gradients") against the float64 autograd restatement
 (tests/lm_grad_rules.py), through ops.lm_grad and the model's public methods.
 
-Largest observed max|dev - ref64| / max|ref64| per tensor over the five cases (MI355X; the bar is 1e-4): see DESIGN.md §16."""
+Largest observed max|dev - ref64| / max|ref64| per tensor and case (MI355X; the bar is 1e-4), and the worst per-row ratio of the
+2-D tensors beside the bar it was held to (tests/grad_bars.py): see DESIGN.md §16."""
 import numpy as np
 import pytest
 
+from tests import grad_bars as GB
 from tests import lm_grad_rules as G
 
 pytestmark = pytest.mark.gpu
@@ -13,13 +15,44 @@ REL = 1e-4                     # tests/parity.py's continuous-stage bar
 # (weights, n, L): the sets of tests/test_gpu_dims.py, and the default dimensions with a 200-word vocabulary
 CASES = {"minimal_1x1": ("minimal", 1, 1), "minimal_3x1": ("minimal", 3, 1), "odd32_5x3": ("odd32", 5, 3),
          "e_lt_h_70x9": ("e_lt_h", 70, 9), "default_7x15": ("default", 7, 15)}
-_models, _runs = {}, {}
+# The vocabularies and sizes of the product and of the op's limits.  "ckpt_vocab" is the checkpoint's V = 10,497 (V + 1 = 82 * 128
+# + 2: the last tile of the lm_out_w gradient has two live columns, lda = V1pad = 10,560 > N, dH = dlogits . Wout is a split-K
+# shape of 330 K tiles) at fc_dim = 256; big_vocab (V = 20,000) and e_gt_h (E > Hd) are tests/test_gpu_dims.py's sets; n = 1024
+# and L = 64 are the largest the op admits (L is bounded by the op, not by the model's seq_length).  A fourth entry fixes the
+# labels: "empty" (every caption empty: one projection step) or "full" (every caption full width).
+NEW_CASES = {"ckpt_vocab_3x2": ("ckpt_vocab", 3, 2), "ckpt_vocab_70x9": ("ckpt_vocab", 70, 9), "big_vocab_5x4": ("big_vocab", 5, 4),
+             "e_gt_h_5x5": ("e_gt_h", 5, 5), "minimal_1024x1": ("minimal", 1024, 1), "minimal_3x64": ("minimal", 3, 64),
+             "odd32_4x3_empty": ("odd32", 4, 3, "empty"), "odd32_4x3_full": ("odd32", 4, 3, "full")}
+CASES.update(NEW_CASES)
+_models, _runs, _wcache = {}, {}, {}
 
 
 def _weights(name):
     from densecap_amd.weights import make_synthetic_weights
     from tests.test_gpu_dims import set_weights
-    return make_synthetic_weights(seed=21, vocab_size=200, seq_length=15) if name == "default" else set_weights(name)
+    if name not in _wcache:
+        if name == "default":
+            _wcache[name] = make_synthetic_weights(seed=21, vocab_size=200, seq_length=15)
+        elif name == "ckpt_vocab":
+            _wcache[name] = make_synthetic_weights(seed=21, vocab_size=10497, seq_length=15, fc_dim=256)
+        else:
+            _wcache[name] = set_weights(name)
+    return _wcache[name]
+
+
+def case_inputs(case):
+    """(W, codes, labels) of a case: from the weights' shapes alone, so that the CPU tests can form them too."""
+    name, n, L = CASES[case][:3]
+    W = _weights(name)
+    D, V = int(W["lm_enc_w"].shape[1]), int(W["lm_out_w"].shape[0]) - 1
+    rng = np.random.default_rng(100 + n * 64 + L)
+    codes, lab = G.draw_codes(n, D, rng), G.draw_labels(n, L, V, rng)
+    mode = CASES[case][3] if len(CASES[case]) > 3 else None
+    if mode == "empty":
+        lab[:] = 0
+    elif mode == "full":
+        lab = np.where(lab == 0, rng.integers(1, V + 1, lab.shape), lab).astype(np.int32)
+    return W, codes, lab
 
 
 def _model(name):
@@ -34,10 +67,9 @@ def _model(name):
 def _run(case):
     """(model, W, codes, labels, device result, float64 reference) of a case, computed once."""
     if case not in _runs:
-        name, n, L = CASES[case]
-        m, W = _model(name)
-        rng = np.random.default_rng(100 + n * 64 + L)
-        codes, lab = G.draw_codes(n, m.fc_dim, rng), G.draw_labels(n, L, m.vocab_size, rng)
+        m, W = _model(CASES[case][0])
+        _, codes, lab = case_inputs(case)
+        assert codes.shape[1] == m.fc_dim and lab.max(initial=0) <= m.vocab_size
         _runs[case] = (m, W, codes, lab, m.lm_gradients(codes, lab), G.lm_grad(W, codes, lab))
     return _runs[case]
 
@@ -47,7 +79,7 @@ def _close_models():
     yield
     for m, _ in _models.values():
         m.ctx.close()
-    _models.clear(); _runs.clear()
+    _models.clear(); _runs.clear(); _wcache.clear()
 
 
 def _bits(a):
@@ -73,10 +105,24 @@ def test_gradients_match_the_float64_restatement(case):
 
 
 @pytest.mark.parametrize("case", list(CASES))
-def test_rowlik_is_lm_scores_number_bit_for_bit(case):
-    from densecap_amd import ops
+def test_every_row_matches_the_float64_restatement_at_the_float32_evaluations_bar(case):
+    """The five 2-D tensors row by row (tests/grad_bars.py): every row within 8 x the float32 evaluation's worst per-row ratio of
+    ITS OWN largest entry, and the rows whose reference is exactly zero all +0.0 bits."""
+    import torch
     m, W, codes, lab, dev, ref = _run(case)
-    want = np.diag(ops.lm_score(m.ctx, codes, lab)).astype(np.float32)
+    GB.assert_rows("lm_grad " + case, GB.LM_ROW_TENSORS, dev, ref, G.lm_grad(W, codes, lab, dtype=torch.float32))
+
+
+def _paired_scores(ctx, codes, lab, block=128):
+    """lm_score of code i against caption i, in blocks (a row's number does not depend on the rows scored beside it)."""
+    from densecap_amd import ops
+    return np.concatenate([np.diag(ops.lm_score(ctx, codes[i:i + block], lab[i:i + block])) for i in range(0, len(codes), block)])
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_rowlik_is_lm_scores_number_bit_for_bit(case):
+    m, W, codes, lab, dev, ref = _run(case)
+    want = _paired_scores(m.ctx, codes, lab).astype(np.float32)
     assert np.array_equal(_bits(dev["rowlik"].astype(np.float32)), _bits(want))
     assert dev["loss"] == pytest.approx(-dev["rowlik"].sum() / (lab.shape[0] * (lab.shape[1] + 2)), rel=1e-14)
 
@@ -85,7 +131,7 @@ def test_rowlik_is_lm_scores_number_bit_for_bit(case):
 def test_never_fed_embedding_rows_are_zero_and_two_calls_agree_bitwise(case):
     m, W, codes, lab, dev, ref = _run(case)
     fed = G.fed_rows(lab, m.vocab_size)
-    rest = np.array([r for r in range(m.vocab_size + 2) if r not in fed])
+    rest = np.array(sorted(set(range(m.vocab_size + 2)) - set(fed)))
     assert m.vocab_size + 1 in rest and not _bits(dev["lm_emb"][rest]).any()       # +0.0, the NULL row included
     assert all(dev["lm_emb"][r].any() for r in fed)
     assert _same(dev, m.lm_gradients(codes, lab))

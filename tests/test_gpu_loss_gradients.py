@@ -5,6 +5,7 @@ dc_forward_losses' bits, its language-model gradients dc_op_lm_grad's bits, its 
 import numpy as np
 import pytest
 
+from tests import grad_bars as GB
 from tests import lm_grad_rules as G
 from tests import loss_rules as LR
 from tests import recog_grad_rules as R
@@ -93,6 +94,19 @@ def test_recognition_gradients_match_the_rules_on_the_sampled_rows(run):
         assert res[k].shape == ref[k].shape and ratios[k] <= REL, (k, ratios[k])
     for k in ("end_objectness_loss", "end_box_reg_loss"):
         assert abs(res[k] - ref[k]) <= 1e-6 * abs(ref[k]), k
+
+
+def test_every_row_matches_the_rules_at_the_float32_evaluations_bar(run):
+    """The 2-D tensors of both backward passes row by row (tests/grad_bars.py), on the rows the sampler drew: the recognition
+    net's against R.recog_grad with the device's own codes gradient, the language model's against G.lm_grad on the kept codes.
+    Every row within 8 x the float32 evaluation's worst per-row ratio of its own largest entry; zero reference rows +0.0."""
+    import torch
+    m, W, img, gt, lab, res, kept = run
+    np_ = res["num_pos"]
+    args = (W, kept["feat"], kept["roi_boxes"], np_, gt[res["pos_target_idx"]], res["codes"], H, WD)
+    GB.assert_rows("loss_gradients recog", GB.RECOG_ROW_TENSORS, res, R.recog_grad(*args), R.recog_grad(*args, dtype=torch.float32))
+    largs = (W, kept["codes"][:np_], lab[res["pos_target_idx"]])
+    GB.assert_rows("loss_gradients lm", GB.LM_ROW_TENSORS, res, G.lm_grad(*largs), G.lm_grad(*largs, dtype=torch.float32))
 
 
 def test_two_calls_give_identical_bits(run):

@@ -1,12 +1,14 @@
 """dc_op_recog_grad (docs/SEMANTICS.md, "Recognition-net gradients") and its kernels alone (the hooks of
 include/densecap_debug_recog.h) against the float64 autograd restatement of tests/recog_grad_rules.py.
 
-Largest observed max|dev - ref64| / max|ref64| per tensor and case (MI355X; the bar is 1e-4): see DESIGN.md §17."""
+Largest observed max|dev - ref64| / max|ref64| per tensor and case (MI355X; the bar is 1e-4), and the worst per-row ratio of the
+2-D tensors beside the bar it was held to (tests/grad_bars.py): see DESIGN.md §17."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import grad_bars as GB
 from tests import recog_grad_rules as R
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +139,17 @@ def test_gradients_match_the_float64_restatement(case):
     for k in ("end_objectness_loss", "end_box_reg_loss"):
         assert abs(dev[k] - ref[k]) <= 1e-6 * abs(ref[k]), (k, dev[k], ref[k])
     assert dev["masked_end"] == ref["masked_end"] == len(CASES[case][3])
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_every_row_matches_the_float64_restatement_at_the_float32_evaluations_bar(case):
+    """fc6_w, fc7_w and boxreg_w row by row, feat pixel by pixel over its 512 channels, roi_boxes box by box
+    (tests/grad_bars.py): every row within 8 x the float32 evaluation's worst per-row ratio of ITS OWN largest entry, and the
+    rows whose reference is exactly zero (ReLU-dead rows, untouched pixels) all +0.0 bits."""
+    import torch
+    m, W, (feat, boxes, targets, g), dev, ref = _run(case)
+    ref32 = R.recog_grad(W, feat, boxes, CASES[case][2], targets, g, IMG[0], IMG[1], dtype=torch.float32)
+    GB.assert_rows("recog_grad " + case, GB.RECOG_ROW_TENSORS, dev, ref, ref32)
 
 
 def test_no_positive_row_means_no_box_terms():
