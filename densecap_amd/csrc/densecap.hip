@@ -19,6 +19,7 @@
 #include <memory>
 
 #include "common.h"
+#include "scratch.h"
 
 namespace {
 
@@ -34,7 +35,7 @@ enum Stage { ST_TRUNK = 0, ST_RPN, ST_NMS1, ST_ROIPOOL, ST_FC, ST_HEADS, ST_LSTM
 const char* kStageNames[ST_COUNT] = {"vgg16_trunk", "rpn_conv_heads_decode", "rpn_nms",   "bilinear_roi_pool",
                                      "fc6_fc7",     "recog_heads",           "lstm_decode", "final_nms_gather"};
 
-struct DevBuf {
+struct DevBuf {          // (a lane's arena: lane_prepare and lane_release own it)
   void* p = nullptr;
   size_t bytes = 0;
 };
@@ -173,6 +174,7 @@ struct dc_ctx {
   int max_lanes = 3;
   int group = 0;             // images per lane group (dc_set_group): 0 = default (1), 1 .. kGemmMaxGroup
   int arena_allocs = 0;      // lane workspace (re)allocations so far (dc_debug_fetch "arena_allocs")
+  ScratchStats scratch;      // what the Scratch blocks of the calls and the KeptBufs below count (dc_debug_fetch "scratch")
   double host_enqueue_ms = 0;  // host ms per image spent enqueueing in the last forward call (run_images)
   int64_t beam_chunk_floats = (int64_t)1 << 28;   // cap of the beam search's full-logits buffer (dc_debug_set)
   int64_t score_rows_cap = 0;      // rows (region x query) one chunk of dc_score_captions / dc_op_lm_score may hold (dc_debug_set); 0 = ~512 MiB of scratch
@@ -206,7 +208,7 @@ struct dc_ctx {
   // need, made on the first call after a dc_load_weights; the RoI index's scratch (grow only); the event split of the last call
   float *fc7_wT = nullptr, *fc6_wT = nullptr;
   uint64_t recog_epoch = 0;
-  DevBuf roi_grad_ws, recog_ws, recog_aux_ws;   // (recog_ws: the backward's scratch; recog_aux_ws: the callers' few rows)
+  KeptBuf roi_grad_ws{scratch}, recog_ws{scratch}, recog_aux_ws{scratch};   // (recog_ws: the backward's scratch; recog_aux_ws: the callers' few rows)
   hipEvent_t recog_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float recog_grad_ms[4] = {0, 0, 0, 0};
   bool recog_grad_ran = false;
@@ -227,12 +229,12 @@ struct dc_ctx {
   // split-bf16 mode: weight matrices that can take it, and their bf16 planes (made when the mode is first switched on)
   struct PlaneEnt { const float* W; size_t rows; int K; uint16_t* planes; };
   std::vector<PlaneEnt> planes;
-  DevBuf pre_src, pre_scratch;      // dc_preprocess_u8: uploaded bytes, width-pass plane (grow only)
-  DevBuf pre_taps;                  // ... and the tap tables of the sizes in pre_key, kept while the sizes repeat (webcam frames)
+  KeptBuf pre_src{scratch}, pre_scratch{scratch};      // dc_preprocess_u8: uploaded bytes, width-pass plane (grow only)
+  KeptBuf pre_taps{scratch};        // ... and the tap tables of the sizes in pre_key, kept while the sizes repeat (webcam frames)
   std::vector<char> pre_taps_host;  // (the host copy outlives its asynchronous upload)
   int pre_key[4] = {0, 0, 0, 0};    // H0, W0, oh, ow the tables were made for
   // dc_forward_losses: its scratch (grow only) and what the last call left there for dc_debug_fetch "loss_*"
-  DevBuf loss_ws;
+  KeptBuf loss_ws{scratch};
   struct LossKeep {
     const float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr;
     const double* rowlik = nullptr;
@@ -412,6 +414,25 @@ void prof_collect(dc_ctx* ctx) {
   ctx->prof_pending.clear();
 }
 
+int fail_on_fault(dc_ctx* ctx, uint32_t fault, const char* who);
+// the fault word after a synchronised per-op call
+int check_fault_word(dc_ctx* ctx, const char* who) {
+  if (ctx->fault_dev == nullptr) return DC_OK;
+  uint32_t f = 0;
+  if (hipMemcpy(&f, ctx->fault_dev, 4, hipMemcpyDeviceToHost) != hipSuccess) return ctx->fail(DC_E_HIP, "%s: fault word read failed", who);
+  return f == 0 ? DC_OK : fail_on_fault(ctx, f, who);
+}
+// How a synchronous call that enqueued on `s` ends, with rc the status of what it enqueued: drain, collect the MFMA profile,
+// then report -- rc first, the drain's error next and (fault: the calls that check it) the fault word last.  A Scratch the
+// caller holds is still alive here: what the call copies out of it goes between this and its return.
+int call_finish(dc_ctx* ctx, hipStream_t s, int rc, const char* who, bool fault = false) {
+  const hipError_t e = hipStreamSynchronize(s);
+  prof_collect(ctx);
+  if (rc != DC_OK) return rc;
+  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return fault ? check_fault_word(ctx, who) : DC_OK;
+}
+
 // `planes` (optional): the caller's own bf16 planes of W for the split-bf16 mode (per-op entry points; the model's weights
 // are looked up in ctx->planes)
 int linear(dc_ctx* ctx, hipStream_t s, const float* A, const float* W, const float* bias, float* C, int M, int N,
@@ -444,7 +465,6 @@ int conv3x3_pool(dc_ctx* ctx, hipStream_t s, const float* in, const float* w, co
   return run_gemm(ctx, d, s, ws);
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 // num_proposals = -1 (LocalizationLayer.lua:322-324: uncapped RPN NMS): capacity = every anchor of this image size
 int effective_proposals(const dc_ctx* ctx, int H, int W);
 constexpr size_t kSplitkWsFloats = (size_t)6400 * 128 * 128;  // 400 MiB per lane: split-K partial outputs (up to 8 x an eight-image group's 8 x 384 x 4096 fc6 rows), tail plans, stream-K slots
@@ -489,18 +509,6 @@ void lane_release(Lane& L) {
   for (auto& ev : L.ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {L.ev_fork, L.ev_join, L.ev_fork2, L.ev_join2}) if (ev) (void)hipEventDestroy(ev);
   for (hipStream_t st : {L.aux, L.aux2, L.stream}) if (st) (void)hipStreamDestroy(st);
-}
-
-// Pieces of one allocation: `carve(cv, base)` points each *p at its own 256-byte aligned piece of `base` and returns the
-// bytes all of them take (base = null: only the bytes).
-struct Carve { void** p; size_t bytes; };
-size_t carve(const std::vector<Carve>& cv, void* base) {
-  size_t total = 0;
-  for (const Carve& c : cv) {
-    if (base != nullptr) *c.p = static_cast<char*>(base) + total;
-    total += al(c.bytes);
-  }
-  return total;
 }
 
 // floats per row of the buffer that holds, by route, a row's full logits, its arg-max partials or its fp16 screen scores
@@ -891,8 +899,9 @@ struct LmRows {
   float *enc = nullptr, *g0 = nullptr, *h0 = nullptr, *c0 = nullptr;          // per region: encoder output, gates, START state
   float *h = nullptr, *c = nullptr, *gates = nullptr, *part = nullptr;        // per row: state, gates, the step GEMM's partials
   double* acc = nullptr;                // per row: the sum of its log-probability terms
-  void* base = nullptr;
   std::vector<double> acc_host;         // acc of the chunk just run (lm_chunk_end)
+  Scratch block;                        // what the pointers above are carved from (lm_rows_alloc)
+  LmRows(dc_ctx* ctx, hipStream_t s) : block(ctx->scratch, s) {}
 };
 // The chunk: as many whole items as `rows_cap` rows hold (the caller's dc_debug_set knob; 0 = ~512 MiB of scratch at row_bytes a
 // row), at least one.  The per-region GEMMs are planned on min(n, kScorePlanRows) rows: every plan then stays on the
@@ -906,7 +915,7 @@ void lm_rows_plan(LmRows& w, int n, int items, int64_t rows_cap, size_t row_byte
   w.plan = std::min(n, kScorePlanRows);
   w.rmax = (size_t)w.chunk * n;
 }
-// One allocation for the shared pieces (ld: floats of partials per row) and the caller's `extra` ones; lm_rows_finish frees it.
+// One allocation for the shared pieces (ld: floats of partials per row) and the caller's `extra` ones; it dies with w.
 int lm_rows_alloc(dc_ctx* ctx, LmRows& w, int ld, const std::vector<Carve>& extra) {
   const size_t n = w.n, E = ctx->E, Hd = ctx->Hd;
   std::vector<Carve> cv = {
@@ -915,8 +924,7 @@ int lm_rows_alloc(dc_ctx* ctx, LmRows& w, int ld, const std::vector<Carve>& extr
       {(void**)&w.gates, w.rmax * 4 * Hd * 4}, {(void**)&w.part, w.rmax * ld * 4},    {(void**)&w.acc, w.rmax * 8},
   };
   cv.insert(cv.end(), extra.begin(), extra.end());
-  HIPCHK(hipMalloc(&w.base, carve(cv, nullptr)));
-  carve(cv, w.base);
+  HIPCHK(w.block.alloc(cv));
   return DC_OK;
 }
 // A chunk of ni items begins: the rows' integers go up (`ints` to `ints_dev`), acc -- and `flags`, one byte per row, where the
@@ -935,15 +943,6 @@ int lm_chunk_end(dc_ctx* ctx, hipStream_t s, LmRows& w, int ni) {
   w.acc_host.resize((size_t)ni * w.n);
   HIPCHK(hipMemcpyAsync(w.acc_host.data(), w.acc, w.acc_host.size() * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  return DC_OK;
-}
-// Every exit path of the two ends here with rc, the status of what was enqueued: drain, free, report.
-int lm_rows_finish(dc_ctx* ctx, hipStream_t s, LmRows& w, int rc, const char* who) {
-  const hipError_t e = hipStreamSynchronize(s);
-  hipFree(w.base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
   return DC_OK;
 }
 
@@ -973,7 +972,7 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
   const int steps_max = len[order[0]] + 1;
   Fp32Guard fp32(ctx->cfg);
-  LmRows w;
+  LmRows w(ctx, s);
   lm_rows_plan(w, n, Q, ctx->score_rows_cap, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps_max * 4);
   int32_t* tgt = nullptr;       // the rows' targets, step by step
   DCCHK(lm_rows_alloc(ctx, w, ld, {{(void**)&tgt, w.rmax * steps_max * 4}}));
@@ -1008,7 +1007,7 @@ int lm_score(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_
     }
     return DC_OK;
   };
-  return lm_rows_finish(ctx, s, w, body(), "lm_score");
+  return call_finish(ctx, s, body(), "lm_score");
 }
 
 // Paired teacher-forced scoring (dc_forward_losses): n rows, row r scored against ITS OWN label row lab[r*L .. r*L+L) (words, then
@@ -1029,7 +1028,7 @@ int lm_score_paired(dc_ctx* ctx, hipStream_t s, const float* codes, int n, int p
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
   const int steps = len[order[0]] + 1;
   Fp32Guard fp32(ctx->cfg);
-  LmRows w;
+  LmRows w(ctx, s);
   lm_rows_plan(w, n, 1, 0, (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)steps * 4);
   w.plan = std::min(plan, kScorePlanRows);
   int32_t* ints = nullptr;      // the rows' targets step by step, then the permutation and the row count
@@ -1063,7 +1062,7 @@ int lm_score_paired(dc_ctx* ctx, hipStream_t s, const float* codes, int n, int p
     for (int i = 0; i < n; ++i) out[order[i]] = w.acc_host[i];
     return DC_OK;
   };
-  return lm_rows_finish(ctx, s, w, body(), "lm_score_paired");
+  return call_finish(ctx, s, body(), "lm_score_paired");
 }
 
 // Language-model gradients (docs/SEMANTICS.md, "Language-model gradients"): the forward of lm_score_paired with
@@ -1163,9 +1162,8 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
                      (int)(kLmGradMaxScratch >> 30));
   Fp32Guard fp32(ctx->cfg);
   const int plan = std::min(n, kScorePlanRows);
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, bytes));
-  carve(cv, base);
+  Scratch base(ctx->scratch, s);
+  HIPCHK(base.alloc(cv));
   hipEvent_t ev[5] = {};
   std::vector<double> acc_host(n);
   auto slot = [&](float* b, int q, int width) { return b + (size_t)off[q] * width; };
@@ -1258,15 +1256,10 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
       for (int i = 0; i < n; ++i) rowlik[order[i]] = acc_host[i];
     return DC_OK;
   };
-  const int rc = body();
-  const hipError_t e = hipStreamSynchronize(s);
+  const int rc = call_finish(ctx, s, body(), "dc_op_lm_grad");
   for (auto& evt : ev)
     if (evt != nullptr) hipEventDestroy(evt);
-  hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_lm_grad: %s", hipGetErrorString(e));
-  return DC_OK;
+  return rc;
 }
 
 // the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
@@ -1329,7 +1322,7 @@ int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int
   const bool by_rows = trunc != nullptr || sample_logprob != nullptr;
   const int nslots = ctx->V1pad / 32, ld = by_rows ? V1 : 5 * nslots;
   Fp32Guard fp32(ctx->cfg);
-  LmRows w;
+  LmRows w(ctx, s);
   lm_rows_plan(w, n, S, ctx->sample_rows_cap,
                (size_t)Hd * 6 * 4 + (size_t)ld * 4 + 8 + (size_t)T * 4 + 8 + 1 + (by_rows ? 8 : 0));
   if (w.rmax > (size_t)INT32_MAX / (size_t)std::max(ld, 4 * Hd))
@@ -1396,7 +1389,7 @@ int lm_sample_n(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int
     }
     return DC_OK;
   };
-  return lm_rows_finish(ctx, s, w, body(), "lm_sample_n");
+  return call_finish(ctx, s, body(), "lm_sample_n");
 }
 
 // the validity rules of docs/SEMANTICS.md for a (Q, Tq) block of queries in host memory
@@ -1778,16 +1771,9 @@ void dc_destroy(dc_ctx* ctx) {
   hipDeviceSynchronize();
   for (auto& lp : ctx->lanes) lane_release(*lp);
   for (void* p : ctx->owned) hipFree(p);
-  if (ctx->pre_src.p) hipFree(ctx->pre_src.p);
-  if (ctx->pre_scratch.p) hipFree(ctx->pre_scratch.p);
-  if (ctx->pre_taps.p) hipFree(ctx->pre_taps.p);
-  if (ctx->loss_ws.p) hipFree(ctx->loss_ws.p);
-  if (ctx->roi_grad_ws.p) hipFree(ctx->roi_grad_ws.p);
-  if (ctx->recog_ws.p) hipFree(ctx->recog_ws.p);
-  if (ctx->recog_aux_ws.p) hipFree(ctx->recog_aux_ws.p);
   for (hipEvent_t e : ctx->recog_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
-  delete ctx;
+  delete ctx;                 // (the kept buffers free themselves here)
 }
 
 const char* dc_last_error(const dc_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
@@ -1903,6 +1889,14 @@ static float screen_bound_c(int K) {
   return nextafterf((float)c, INFINITY);
 }
 
+// n floats of a checkpoint weight in `stage`, on the device for the one launch that repacks them into the ctx's own layout
+static int stage_weight(dc_ctx* ctx, Scratch& stage, const float* host, size_t n, float** dev) {
+  HIPCHK(stage.alloc(n * 4));
+  *dev = static_cast<float*>(stage.get());
+  HIPCHK(hipMemcpy(*dev, host, n * 4, hipMemcpyHostToDevice));
+  return DC_OK;
+}
+
 int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   if (!ctx || !w) return DC_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1925,30 +1919,29 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   hipStream_t s;
   DCCHK(lane0_stream(ctx, &s));
   const int k = ctx->k, R = ctx->R, V = ctx->V, E = ctx->E, Hd = ctx->Hd, D = ctx->D;
-  float* tmp = nullptr;
   // VGG convs: conv1_1 stays OIHW (direct kernel); the rest are repacked to (Cout, 9*Cin)
   DCCHK(upload(ctx, &ctx->conv_w[0], w->conv_w[0], (size_t)64 * 27));
   DCCHK(upload(ctx, &ctx->conv_b[0], w->conv_b[0], 64));
   for (int i = 1; i < DC_NUM_VGG_CONVS; ++i) {
     const size_t n = (size_t)kVgg[i].cout * kVgg[i].cin * 9;
     if (!w->conv_w[i] || !w->conv_b[i]) return ctx->fail(DC_E_INVALID, "null conv weight %d", i);
-    HIPCHK(hipMalloc(&tmp, n * 4));
-    HIPCHK(hipMemcpy(tmp, w->conv_w[i], n * 4, hipMemcpyHostToDevice));
+    Scratch stage(ctx->scratch, s);
+    float* tmp = nullptr;
+    DCCHK(stage_weight(ctx, stage, w->conv_w[i], n, &tmp));
     DCCHK(dev_alloc(ctx, (void**)&ctx->conv_w[i], n * 4));
     KCHK(launch_pack_conv3x3(tmp, ctx->conv_w[i], kVgg[i].cout, kVgg[i].cin, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(tmp));
     DCCHK(upload(ctx, &ctx->conv_b[i], w->conv_b[i], kVgg[i].cout));
   }
   {  // RPN conv
     const size_t n = (size_t)R * 512 * 9;
     if (!w->rpn_conv_w) return ctx->fail(DC_E_INVALID, "null rpn_conv_w");
-    HIPCHK(hipMalloc(&tmp, n * 4));
-    HIPCHK(hipMemcpy(tmp, w->rpn_conv_w, n * 4, hipMemcpyHostToDevice));
+    Scratch stage(ctx->scratch, s);
+    float* tmp = nullptr;
+    DCCHK(stage_weight(ctx, stage, w->rpn_conv_w, n, &tmp));
     DCCHK(dev_alloc(ctx, (void**)&ctx->rpn_w, n * 4));
     KCHK(launch_pack_conv3x3(tmp, ctx->rpn_w, R, 512, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(tmp));
     DCCHK(upload(ctx, &ctx->rpn_b, w->rpn_conv_b, R));
   }
   {  // fused 1x1 heads: rows [0,4k) box, [4k,6k) score
@@ -1965,12 +1958,12 @@ int dc_load_weights(dc_ctx* ctx, const dc_weights* w) {
   {  // fc6: permute K from (c,i,j) to (i,j,c) to match the channels-last RoI features
     const size_t n = (size_t)D * 512 * 49;
     if (!w->fc6_w) return ctx->fail(DC_E_INVALID, "null fc6_w");
-    HIPCHK(hipMalloc(&tmp, n * 4));
-    HIPCHK(hipMemcpy(tmp, w->fc6_w, n * 4, hipMemcpyHostToDevice));
+    Scratch stage(ctx->scratch, s);
+    float* tmp = nullptr;
+    DCCHK(stage_weight(ctx, stage, w->fc6_w, n, &tmp));
     DCCHK(dev_alloc(ctx, (void**)&ctx->fc6_w, n * 4));
     KCHK(launch_permute_fc6(tmp, ctx->fc6_w, D, 512, 49, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(tmp));
     DCCHK(upload(ctx, &ctx->fc6_b, w->fc6_b, D));
   }
   DCCHK(upload(ctx, &ctx->fc7_w, w->fc7_w, (size_t)D * D));
@@ -2279,34 +2272,27 @@ int dc_preprocess_u8(dc_ctx* ctx, const uint8_t* rgb_hwc, int H0, int W0, int on
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s;
   DCCHK(lane0_stream(ctx, &s));
-  auto grow = [&](DevBuf& b, size_t bytes) -> int {
-    if (b.bytes >= bytes) return DC_OK;
-    if (b.p) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(b.p)); b = DevBuf(); }
-    HIPCHK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return DC_OK;
-  };
   const uint8_t* src = rgb_hwc;
   if (!on_device) {
     const size_t nb = (size_t)H0 * W0 * 3;
-    DCCHK(grow(ctx->pre_src, nb));
-    HIPCHK(hipMemcpyAsync(ctx->pre_src.p, rgb_hwc, nb, hipMemcpyHostToDevice, s));
-    src = static_cast<const uint8_t*>(ctx->pre_src.p);
+    HIPCHK(ctx->pre_src.grow(nb, s));
+    HIPCHK(hipMemcpyAsync(ctx->pre_src.get(), rgb_hwc, nb, hipMemcpyHostToDevice, s));
+    src = static_cast<const uint8_t*>(ctx->pre_src.get());
   }
-  DCCHK(grow(ctx->pre_scratch, preprocess_scratch_bytes(H0, W0, oh, ow)));
+  HIPCHK(ctx->pre_scratch.grow(preprocess_scratch_bytes(H0, W0, oh, ow), s));
   const int key[4] = {H0, W0, oh, ow};
-  if (ctx->pre_taps.p == nullptr || memcmp(key, ctx->pre_key, sizeof key) != 0) {
+  if (ctx->pre_taps.get() == nullptr || memcmp(key, ctx->pre_key, sizeof key) != 0) {
     // new sizes: rebuild the tables (round-5 advisor finding: they were rebuilt, uploaded from pageable memory and waited
     // for on every frame).  The host copy is replaced only after the stream has drained its previous upload.
     HIPCHK(hipStreamSynchronize(s));
     ctx->pre_taps_host.resize(preprocess_taps_bytes(oh, ow));
     preprocess_make_taps(H0, W0, oh, ow, ctx->pre_taps_host.data());
-    DCCHK(grow(ctx->pre_taps, ctx->pre_taps_host.size()));
-    HIPCHK(hipMemcpyAsync(ctx->pre_taps.p, ctx->pre_taps_host.data(), ctx->pre_taps_host.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx->pre_taps.grow(ctx->pre_taps_host.size(), s));
+    HIPCHK(hipMemcpyAsync(ctx->pre_taps.get(), ctx->pre_taps_host.data(), ctx->pre_taps_host.size(), hipMemcpyHostToDevice, s));
     memcpy(ctx->pre_key, key, sizeof key);
   }
   const float mean_bgr[3] = {103.939f, 116.779f, 123.68f};          // run_model.lua:73
-  KCHK(launch_preprocess_u8(src, H0, W0, oh, ow, mean_bgr, ctx->pre_scratch.p, ctx->pre_taps.p, out_chw_dev, scaled_rgb_dev, s));
+  KCHK(launch_preprocess_u8(src, H0, W0, oh, ow, mean_bgr, ctx->pre_scratch.get(), ctx->pre_taps.get(), out_chw_dev, scaled_rgb_dev, s));
   HIPCHK(hipStreamSynchronize(s));
   return DC_OK;
 }
@@ -2345,21 +2331,18 @@ static int64_t sample_noise_debug(dc_ctx* ctx, int what, uint64_t seed, const in
       (what == 0 && (int64_t)first + count > ((int64_t)1 << 23)))
     return ctx->fail(DC_E_INVALID, "dc_debug_fetch: sample noise: at most 2^23 values, indices below 2^23");
   if (count == 0) return 0;
-  void* dev = nullptr;
-  HIPCHK(hipMalloc(&dev, (size_t)count * (what == 1 ? 20 : 4)));
-  hipError_t e = hipSuccess;
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc((size_t)count * (what == 1 ? 20 : 4)));
+  void* dev = block.get();
   if (what == 0) {
-    e = launch_sample_noise_gumbel(first, (size_t)count, static_cast<float*>(dev), s);
+    KCHK(launch_sample_noise_gumbel(first, (size_t)count, static_cast<float*>(dev), s));
   } else {
     int32_t* kd = reinterpret_cast<int32_t*>(static_cast<char*>(dev) + (size_t)count * 4);
-    e = hipMemcpyAsync(kd, srtv, (size_t)count * 16, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_sample_noise_bits(seed, kd, (size_t)count, static_cast<uint32_t*>(dev), s);
+    HIPCHK(hipMemcpyAsync(kd, srtv, (size_t)count * 16, hipMemcpyHostToDevice, s));
+    KCHK(launch_sample_noise_bits(seed, kd, (size_t)count, static_cast<uint32_t*>(dev), s));
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(host_out, dev, (size_t)count * 4, hipMemcpyDeviceToHost, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  hipFree(dev);
-  if (e != hipSuccess || e2 != hipSuccess)
-    return ctx->fail(DC_E_HIP, "dc_debug_fetch: sample noise: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  HIPCHK(hipMemcpyAsync(host_out, dev, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+  DCCHK(call_finish(ctx, s, DC_OK, "dc_debug_fetch: sample noise"));
   return count;
 }
 
@@ -2385,6 +2368,12 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     static_cast<int32_t*>(host_buf)[0] = ctx->lm_parts;
     static_cast<int32_t*>(host_buf)[1] = (int32_t)ctx->lm_screened;
     return 2;
+  }
+  if (strcmp(name, "scratch") == 0) {
+    if (capacity_bytes < 24) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    const int64_t v[3] = {ctx->scratch.live, ctx->scratch.kept_bytes, ctx->scratch.kept_allocs};
+    memcpy(host_buf, v, sizeof v);
+    return 3;
   }
   if (strncmp(name, "lm_op_", 6) == 0) {            // what the last dc_op_lm_sample kept (dc_debug_set "lm_op_keep")
     const struct { const char* n; const std::vector<char>* v; int esize; } kept[] = {
@@ -2603,24 +2592,11 @@ int dc_synchronize(dc_ctx* ctx) {
 }
 
 
-// the fault word after a synchronised per-op call
-static int check_fault_word(dc_ctx* ctx, const char* who) {
-  if (ctx->fault_dev == nullptr) return DC_OK;
-  uint32_t f = 0;
-  if (hipMemcpy(&f, ctx->fault_dev, 4, hipMemcpyDeviceToHost) != hipSuccess) return ctx->fail(DC_E_HIP, "%s: fault word read failed", who);
-  return f == 0 ? DC_OK : fail_on_fault(ctx, f, who);
-}
-
-// split-bf16 mode on a per-op call: the caller's weight matrix gets temporary planes (the model's own are made once)
-static int op_planes(dc_ctx* ctx, hipStream_t s, const float* W, int N, int K, uint16_t** out) {
-  *out = nullptr;
+// split-bf16 mode on a per-op call: the caller's weight matrix gets temporary planes in `pl` (the model's own are made once)
+static int op_planes(dc_ctx* ctx, hipStream_t s, const float* W, int N, int K, Scratch& pl) {
   if (ctx->cfg.math_mode != DC_MATH_SPLIT_BF16 || !ctx->cfg.bf3_presplit || K % 32) return DC_OK;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(out), (size_t)3 * N * K * 2));
-  if (hipError_t e = launch_split_planes(W, *out, (size_t)N, K, s); e != hipSuccess) {
-    (void)hipFree(*out);                     // (round-5 advisor finding: the planes leaked when the launch failed)
-    *out = nullptr;
-    return ctx->fail(DC_E_HIP, "launch_split_planes: %s", hipGetErrorString(e));
-  }
+  HIPCHK(pl.alloc((size_t)3 * N * K * 2));
+  KCHK(launch_split_planes(W, static_cast<uint16_t*>(pl.get()), (size_t)N, K, s));
   return DC_OK;
 }
 
@@ -2645,21 +2621,13 @@ int dc_op_pack_conv3x3_weights(dc_ctx* ctx, const float* w, float* out, int Cout
   OP_PROLOGUE(); KCHK(launch_pack_conv3x3(w, out, Cout, Cin, s)); OP_EPILOGUE();
 }
 // A per-op contraction with the weight `w` (N x K): `run(ws, planes)` on the split-K scratch and (split-bf16 mode) temporary
-// planes of `w`, then synchronise, free both and read the fault word.  `who` names the entry point in the messages.
+// planes of `w`, then synchronise and read the fault word.  `who` names the entry point in the messages.
 static int op_gemm(dc_ctx* ctx, hipStream_t s, const float* w, int N, int K, const char* who,
                    const std::function<int(const Ws&, const uint16_t*)>& run) {
-  float* ws = nullptr;
-  HIPCHK(hipMalloc((void**)&ws, kSplitkWsFloats * 4));
-  uint16_t* pl = nullptr;
-  if (int rc0 = op_planes(ctx, s, w, N, K, &pl); rc0 != DC_OK) { (void)hipFree(ws); return rc0; }
-  int rc = run(Ws{ws, kSplitkWsFloats}, pl);
-  hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(ws);
-  if (pl) (void)hipFree(pl);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "%s sync: %s", who, hipGetErrorString(e2));
-  return check_fault_word(ctx, who);
+  Scratch ws(ctx->scratch, s), pl(ctx->scratch, s);
+  HIPCHK(ws.alloc(kSplitkWsFloats * 4));
+  DCCHK(op_planes(ctx, s, w, N, K, pl));
+  return call_finish(ctx, s, run(Ws{static_cast<float*>(ws.get()), kSplitkWsFloats}, static_cast<const uint16_t*>(pl.get())), who, true);
 }
 
 int dc_op_conv3x3(dc_ctx* ctx, const float* in, const float* w, const float* b, float* out, int n_img, int H, int W,
@@ -2728,18 +2696,13 @@ int dc_op_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_
   OP_PROLOGUE();
   if (n < 0) return ctx->fail(DC_E_INVALID, "dc_op_nms: n must be >= 0");
   if (n == 0) { HIPCHK(hipMemsetAsync(count, 0, 4, s)); OP_EPILOGUE(); }
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, nms_workspace_bytes(n)));
+  Scratch base(ctx->scratch, s);
+  HIPCHK(base.alloc(nms_workspace_bytes(n)));
   NmsWorkspace ws;
-  nms_workspace_bind(ws, base, n);
+  nms_workspace_bind(ws, base.get(), n);
   ensure_fault_word(ctx);
-  hipError_t e = launch_nms(ws, boxes, scores, valid, n, nullptr, thresh, max_boxes, picks, count, ctx->cfg.nms_band, s,
-                            ctx->fault_dev);
-  hipError_t e2 = hipStreamSynchronize(s);
-  hipFree(base);
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "nms launch: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms sync: %s", hipGetErrorString(e2));
-  return check_fault_word(ctx, "dc_op_nms");
+  KCHK(launch_nms(ws, boxes, scores, valid, n, nullptr, thresh, max_boxes, picks, count, ctx->cfg.nms_band, s, ctx->fault_dev));
+  return call_finish(ctx, s, DC_OK, "dc_op_nms", true);
 }
 constexpr int kNmsMultiMax = 4096;       // rows and picks of the multi-order NMS (boxes.hip: one 64-bit word of the removed set per lane)
 int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n, int Q, float thresh,
@@ -2752,15 +2715,10 @@ int dc_op_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const 
     return ctx->fail(DC_E_INVALID, "dc_op_nms_multi: max_picks must be in 1..%d (got %d)", kNmsMultiMax, max_picks);
   if (n > kNmsMultiMax)
     return ctx->fail(DC_E_UNSUPPORTED, "dc_op_nms_multi: %d boxes exceed the %d the per-query scan holds", n, kNmsMultiMax);
-  void* ws = nullptr;
-  HIPCHK(hipMalloc(&ws, nms_multi_workspace_bytes(n)));
-  const hipError_t e = launch_nms_multi(ws, boxes, scores, valid_or_null, n, nullptr, Q, thresh, max_picks, picks, counts, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  hipFree(ws);
-  prof_collect(ctx);
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "nms_multi launch: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "nms_multi sync: %s", hipGetErrorString(e2));
-  return DC_OK;
+  Scratch ws(ctx->scratch, s);
+  HIPCHK(ws.alloc(nms_multi_workspace_bytes(n)));
+  KCHK(launch_nms_multi(ws.get(), boxes, scores, valid_or_null, n, nullptr, Q, thresh, max_picks, picks, counts, s));
+  return call_finish(ctx, s, DC_OK, "dc_op_nms_multi");
 }
 constexpr int kEvalMaxDet = 4096, kEvalMaxGt = 512;   // per image (eval_match.hip: the sort keys and the M x M bit mask live in LDS)
 // The ABI carries the merge threshold as a float, the reference compares doubles against the literal 0.7: the double with the
@@ -2836,31 +2794,29 @@ int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, i
   if (np < 0 || np > opts->batch_size || nn < 0 || nn > opts->batch_size)
     return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: a forced list holds 0..batch_size entries (got %d, %d)", np, nn);
   const size_t ws_bytes = box_sampler_ws_bytes(A, G), forced_bytes = (size_t)2048 * 4;
-  char* ws = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&ws), ws_bytes + forced_bytes));
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc(ws_bytes + forced_bytes));
+  char* ws = static_cast<char*>(block.get());
   int32_t* fdev = reinterpret_cast<int32_t*>(ws + ws_bytes);
   BoxSamplerArgs a{};
   a.boxes = boxes; a.gt = gt; a.A = A; a.G = G;
   a.x_max = (float)img_w; a.y_max = (float)img_h; a.bounds = opts->remove_outbounds;
   a.high = opts->high_thresh; a.low = opts->low_thresh; a.batch = opts->batch_size;
   a.seed_lo = (uint32_t)(opts->seed & 0xffffffffull); a.seed_hi = (uint32_t)(opts->seed >> 32);
-  hipError_t e = hipSuccess;
   if (forced && forced->pos_sample_idx) {
-    if (np > 0) e = hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)np * 4, hipMemcpyHostToDevice, s);
+    if (np > 0) HIPCHK(hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)np * 4, hipMemcpyHostToDevice, s));
     a.forced_pos = fdev; a.n_forced_pos = np;
   }
-  if (e == hipSuccess && forced && forced->neg_sample_idx) {
-    if (nn > 0) e = hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)nn * 4, hipMemcpyHostToDevice, s);
+  if (forced && forced->neg_sample_idx) {
+    if (nn > 0) HIPCHK(hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)nn * 4, hipMemcpyHostToDevice, s));
     a.forced_neg = fdev + 1024; a.n_forced_neg = nn;
   }
   a.pos_input_idx = pos_input_idx; a.pos_target_idx = pos_target_idx; a.neg_input_idx = neg_input_idx; a.counts = counts;
   a.max_iou_user = max_iou; a.arg_user = arg; a.ws = ws;
-  if (e == hipSuccess) e = launch_box_sampler(a, s);
+  KCHK(launch_box_sampler(a, s));
   int32_t c[8] = {0};
-  if (e == hipSuccess) e = hipMemcpyAsync(c, counts, sizeof c, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(ws);
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_op_box_sampler: %s", hipGetErrorString(e));
+  HIPCHK(hipMemcpyAsync(c, counts, sizeof c, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   if (c[5] || c[6])
     return ctx->fail(DC_E_INVALID, "dc_op_box_sampler: %d forced positive and %d forced negative ranks lie outside the candidate lists (%d, %d)",
                      c[5], c[6], c[2], c[3]);
@@ -2885,13 +2841,13 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
       {(void**)&b.c, rows * Hd * 4},   {(void**)&b.amax, rows * lm_amax_floats(ctx) * 4},
       {(void**)&b.hb, rows * ctx->scr_Kp * 2}, {(void**)&b.hnorm, rows * 4}, {(void**)&b.cand, rows * ctx->T * 4}, {(void**)&b.best, rows * 4},
   };
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-  carve(cv, base);
-  int rc = ctx->cfg.beam_size > 0 ? beam_search(ctx, lane0(ctx), s, {ctx->cfg.beam_size, false}, codes, n, {tokens})
-                                  : lm_sample(ctx, s, b, lane_ws(lane0(ctx)), codes, n, 0, nullptr, tokens);
-  hipError_t e2 = hipStreamSynchronize(s);
-  if (ctx->lm_op_keep && rc == DC_OK && e2 == hipSuccess && ctx->cfg.beam_size == 0) {
+  Scratch base(ctx->scratch, s);
+  HIPCHK(base.alloc(cv));
+  DCCHK(call_finish(ctx, s,
+                    ctx->cfg.beam_size > 0 ? beam_search(ctx, lane0(ctx), s, {ctx->cfg.beam_size, false}, codes, n, {tokens})
+                                           : lm_sample(ctx, s, b, lane_ws(lane0(ctx)), codes, n, 0, nullptr, tokens),
+                    "dc_op_lm_sample"));
+  if (ctx->lm_op_keep && ctx->cfg.beam_size == 0) {
     const bool scr = ctx->lm_screened & 1;      // lm_sample: one part
     const struct { std::vector<char>* v; const void* p; size_t bytes; } keep[] = {
         {&ctx->lm_op_h, b.h, rows * Hd * 4}, {&ctx->lm_op_c, b.c, rows * Hd * 4},
@@ -2899,13 +2855,9 @@ int dc_op_lm_sample(dc_ctx* ctx, const float* codes, int n, int32_t* tokens) {
         {&ctx->lm_op_best, b.best, scr ? rows * 4 : 0}};
     for (const auto& k : keep) {
       k.v->resize(k.bytes);
-      if (k.bytes && e2 == hipSuccess) e2 = hipMemcpy(k.v->data(), k.p, k.bytes, hipMemcpyDeviceToHost);
+      if (k.bytes) HIPCHK(hipMemcpy(k.v->data(), k.p, k.bytes, hipMemcpyDeviceToHost));
     }
   }
-  hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "lm_sample sync: %s", hipGetErrorString(e2));
   return DC_OK;
 }
 
@@ -3005,12 +2957,11 @@ int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int im
   const std::vector<Carve> cv = {{(void**)&sc_d, ll.size() * 4}, {(void**)&valid_d, (size_t)L.P},
                                  {(void**)&mask_d, nms_multi_workspace_bytes(L.P)}, {(void**)&picks_d, (size_t)Q * M * 4},
                                  {(void**)&counts_d, (size_t)Q * 4}};
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-  carve(cv, base);
+  hipStream_t s = L.stream;
   std::vector<int32_t> pk((size_t)Q * M);
+  Scratch base(ctx->scratch, s);                 // (made after pk: the stream is drained before pk dies)
+  HIPCHK(base.alloc(cv));
   auto body = [&]() -> int {
-    hipStream_t s = L.stream;
     HIPCHK(hipMemcpyAsync(sc_d, ll.data(), ll.size() * 4, hipMemcpyHostToDevice, s));
     if (masked) HIPCHK(hipMemcpyAsync(valid_d, vh.data(), vh.size(), hipMemcpyHostToDevice, s));
     KCHK(launch_nms_multi(mask_d, L.final_xyxy, sc_d, masked ? valid_d : nullptr, L.P, L.count1, Q, opts->nms_thresh, M, picks_d,
@@ -3019,12 +2970,7 @@ int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int im
     HIPCHK(hipMemcpyAsync(count, counts_d, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
     return DC_OK;
   };
-  const int rc = body();
-  const hipError_t e = hipStreamSynchronize(L.stream);
-  hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  DCCHK(call_finish(ctx, s, body(), who));
   for (int q = 0; q < Q; ++q)
     for (int j = 0; j < count[q]; ++j) {
       const int r = j < M ? pk[(size_t)q * M + j] : -1;
@@ -3100,15 +3046,9 @@ int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
       {(void**)&neg_idx, 1024 * 4},       {(void**)&counts, 8 * 4},           {(void**)&sel, 1024 * 4},
       {(void**)&rowlik, 1024 * 8},        {(void**)&terms, 6 * 8},            {(void**)&masked, 2 * 4},
   };
-  const size_t total = carve(cv, nullptr);
   ctx->loss_keep = dc_ctx::LossKeep();
-  if (ctx->loss_ws.p == nullptr || total > ctx->loss_ws.bytes) {
-    if (ctx->loss_ws.p) HIPCHK(hipFree(ctx->loss_ws.p));
-    ctx->loss_ws = DevBuf();
-    HIPCHK(hipMalloc(&ctx->loss_ws.p, total));
-    ctx->loss_ws.bytes = total;
-  }
-  carve(cv, ctx->loss_ws.p);
+  HIPCHK(ctx->loss_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->loss_ws.get());
   int32_t c8[8] = {0};
   std::vector<int32_t> lists(3 * 1024);
   std::vector<double> rl;
@@ -3306,12 +3246,7 @@ int dc_op_lm_beam_n(dc_ctx* ctx, const float* codes, int n, const dc_beam_opts* 
   if (!codes || !captions || !logprob) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
   if (n <= 0) return ctx->fail(DC_E_INVALID, "%s: n must be > 0", who);
   DCCHK(check_beam_opts(ctx, opts, who));
-  const int rc = lm_beam_std(ctx, lane0(ctx), s, codes, n, *opts, captions, logprob);
-  const hipError_t e = hipStreamSynchronize(s);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s sync: %s", who, hipGetErrorString(e));
-  return DC_OK;
+  return call_finish(ctx, s, lm_beam_std(ctx, lane0(ctx), s, codes, n, *opts, captions, logprob), who);
 }
 int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const dc_beam_opts* opts, dc_result* out,
                      int32_t* captions, float* logprob) {
@@ -3327,17 +3262,11 @@ int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on
   const size_t N = (size_t)opts->n_best, T = (size_t)ctx->T;
   int32_t* cap_d = nullptr; float* lp_d = nullptr;
   const std::vector<Carve> cv = {{(void**)&cap_d, (size_t)K * N * T * 4}, {(void**)&lp_d, (size_t)K * N * 4}};
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-  carve(cv, base);
-  const int rc = lm_beam_std(ctx, L, L.stream, L.out_feats, K, *opts, cap_d, lp_d);
-  hipError_t e = hipStreamSynchronize(L.stream);
-  if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(captions, cap_d, (size_t)K * N * T * 4, hipMemcpyDeviceToHost);
-  if (rc == DC_OK && e == hipSuccess) e = hipMemcpy(logprob, lp_d, (size_t)K * N * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(base);
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  Scratch base(ctx->scratch, L.stream);
+  HIPCHK(base.alloc(cv));
+  DCCHK(call_finish(ctx, L.stream, lm_beam_std(ctx, L, L.stream, L.out_feats, K, *opts, cap_d, lp_d), who));
+  HIPCHK(hipMemcpy(captions, cap_d, (size_t)K * N * T * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(logprob, lp_d, (size_t)K * N * 4, hipMemcpyDeviceToHost));
   return DC_OK;
 }
 
@@ -3365,15 +3294,11 @@ int dc_op_lm_grad(dc_ctx* ctx, const float* codes, int n, const int32_t* labels,
 int dc_debug_wgrad(dc_ctx* ctx, const float* A, const float* B, int M, int N, int K, float* C) {
   OP_PROLOGUE();
   if (!A || !B || !C || M < 1 || N < 1 || K < 1) return ctx->fail(DC_E_INVALID, "dc_debug_wgrad: bad argument");
-  float* ws = nullptr;
+  Scratch ws(ctx->scratch, s);
   const size_t wf = wgrad_ws_floats(M, N, K);
-  if (wf > 0) HIPCHK(hipMalloc((void**)&ws, wf * 4));
-  const hipError_t e = launch_wgrad(A, N, B, K, M, N, K, C, K, ws, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  if (ws != nullptr) hipFree(ws);
-  KCHK(e);
-  KCHK(e2);
-  return DC_OK;
+  if (wf > 0) HIPCHK(ws.alloc(wf * 4));
+  KCHK(launch_wgrad(A, N, B, K, M, N, K, C, K, static_cast<float*>(ws.get()), s));
+  OP_EPILOGUE();
 }
 int dc_debug_embed_segsum(dc_ctx* ctx, const float* dx, const int32_t* tok_host, int count, int E, int rows_out, float* demb) {
   OP_PROLOGUE();
@@ -3389,16 +3314,13 @@ int dc_debug_embed_segsum(dc_ctx* ctx, const float* dx, const int32_t* tok_host,
   std::vector<int32_t> ih(rows);
   ih.insert(ih.end(), seg.begin(), seg.end());
   ih.insert(ih.end(), ids.begin(), ids.end());
-  int32_t* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, ih.size() * 4));
-  hipError_t e = hipMemcpyAsync(d, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(demb, 0, (size_t)rows_out * E * 4, s);
-  if (e == hipSuccess) e = launch_embed_segsum(dx, E, d, d + count, d + count + seg.size(), (int)ids.size(), demb, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  hipFree(d);
-  KCHK(e);
-  KCHK(e2);
-  return DC_OK;
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc(ih.size() * 4));
+  int32_t* d = static_cast<int32_t*>(block.get());
+  HIPCHK(hipMemcpyAsync(d, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(demb, 0, (size_t)rows_out * E * 4, s));
+  KCHK(launch_embed_segsum(dx, E, d, d + count, d + count + seg.size(), (int)ids.size(), demb, s));
+  OP_EPILOGUE();
 }
 int dc_debug_softmax_grad(dc_ctx* ctx, float* x, int rows, int V1, int ld, const int32_t* tgt, float scale, double* lse_out_or_null) {
   OP_PROLOGUE();
@@ -3427,15 +3349,11 @@ int dc_debug_wgrad_ld(dc_ctx* ctx, const float* A, int lda, const float* B, int 
   OP_PROLOGUE();
   if (!A || !B || !C || M < 1 || N < 1 || K < 1 || lda < N || ldb < K || ldc < K)
     return ctx->fail(DC_E_INVALID, "dc_debug_wgrad_ld: bad argument");
-  float* ws = nullptr;
+  Scratch ws(ctx->scratch, s);
   const size_t wf = wgrad_ws_floats(M, N, K);
-  if (wf > 0) HIPCHK(hipMalloc((void**)&ws, wf * 4));
-  const hipError_t e = launch_wgrad(A, lda, B, ldb, M, N, K, C, ldc, ws, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  if (ws != nullptr) hipFree(ws);
-  KCHK(e);
-  KCHK(e2);
-  return DC_OK;
+  if (wf > 0) HIPCHK(ws.alloc(wf * 4));
+  KCHK(launch_wgrad(A, lda, B, ldb, M, N, K, C, ldc, static_cast<float*>(ws.get()), s));
+  OP_EPILOGUE();
 }
 int dc_debug_colsum(dc_ctx* ctx, const float* X, int ldx, int M, int N, float* out) {
   OP_PROLOGUE();
@@ -3473,20 +3391,11 @@ int dc_feature_size(int H, int W, int* h, int* w) {
 
 // The backward of bilinear RoI pooling on stream s (not synchronised): the tap index in the ctx's own scratch (grow only), the
 // scatter sum, the box gradient.  ev (optional): an event recorded between the scatter sum and the box gradient.
-// a context-owned scratch buffer that only grows (the stream is drained before a buffer in use is replaced)
-static int grow_ws(dc_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t s) {
-  if (b.p != nullptr && bytes <= b.bytes) return DC_OK;
-  if (b.p) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(b.p)); }
-  b = DevBuf();
-  HIPCHK(hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return DC_OK;
-}
 static int roi_pool_grad(dc_ctx* ctx, hipStream_t s, const float* feat, int h, int w, int C, const float* boxes, int B, int img_h,
                          int img_w, int HH, int WW, const float* dout, float* dfeat, float* dboxes, hipEvent_t ev = nullptr) {
   const size_t bytes = roi_grad_ws_bytes(B, HH * WW, h * w, C);
-  DCCHK(grow_ws(ctx, ctx->roi_grad_ws, bytes, s));
-  const RoiGradWs ws = roi_grad_carve(ctx->roi_grad_ws.p, B, HH * WW, h * w, C);
+  HIPCHK(ctx->roi_grad_ws.grow(bytes, s));
+  const RoiGradWs ws = roi_grad_carve(ctx->roi_grad_ws.get(), B, HH * WW, h * w, C);
   KCHK(launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s));
   KCHK(launch_roi_scatter_sum(dout, B, h, w, C, HH, WW, ws, dfeat, s));
   if (ev != nullptr) HIPCHK(hipEventRecord(ev, s));
@@ -3521,22 +3430,28 @@ struct RecogKept {
 };
 constexpr int kRecogK6 = 49 * 512;
 constexpr size_t kRecogGradMaxScratch = (size_t)8 << 30;
-// bytes a call takes: the two transposed weights (kept by the ctx) and the call's scratch
-static std::vector<Carve> recog_carve(dc_ctx* ctx, int n, float** p[12], int32_t** masked) {
+// The scratch of one recog_backward call on n rows, and its carve list (in ctx->recog_ws)
+struct RecogScratch {
+  float *dobj = nullptr, *dtrans = nullptr, *danchor = nullptr, *dcodes = nullptr, *dx7 = nullptr, *dpool = nullptr, *dw6 = nullptr;
+  float *dw5 = nullptr, *db5 = nullptr, *dbox = nullptr, *ws = nullptr, *spare = nullptr;
+  int32_t* masked = nullptr;
+};
+static std::vector<Carve> recog_carve(const dc_ctx* ctx, int n, RecogScratch& r) {
   const size_t D = (size_t)ctx->D, N = (size_t)n;
   const size_t ws_floats = std::max(wgrad_ws_floats(n, ctx->D, ctx->D), wgrad_ws_floats(n, ctx->D, kRecogK6));
   return {
-      {(void**)p[0], N * 4},           {(void**)p[1], N * 16},          {(void**)p[2], N * 16},      {(void**)p[3], N * D * 4},
-      {(void**)p[4], N * D * 4},       {(void**)p[5], N * kRecogK6 * 4}, {(void**)p[6], D * kRecogK6 * 4}, {(void**)p[7], 5 * D * 4},
-      {(void**)p[8], 256},             {(void**)p[9], N * 16},          {(void**)p[10], ws_floats * 4}, {(void**)p[11], 2 * 1024 * 4},
-      {(void**)masked, 256},
+      {(void**)&r.dobj, N * 4},        {(void**)&r.dtrans, N * 16},          {(void**)&r.danchor, N * 16},
+      {(void**)&r.dcodes, N * D * 4},  {(void**)&r.dx7, N * D * 4},          {(void**)&r.dpool, N * kRecogK6 * 4},
+      {(void**)&r.dw6, D * kRecogK6 * 4}, {(void**)&r.dw5, 5 * D * 4},       {(void**)&r.db5, 256},
+      {(void**)&r.dbox, N * 16},       {(void**)&r.ws, ws_floats * 4},       {(void**)&r.spare, 2 * 1024 * 4},
+      {(void**)&r.masked, 256},
   };
 }
+// bytes a call takes: the two transposed weights (kept by the ctx) and the call's scratch
 static int check_recog_scratch(dc_ctx* ctx, int n, int h, int w, const char* who) {
-  float* d[12]; float** p[12]; int32_t* m;
-  for (int i = 0; i < 12; ++i) p[i] = &d[i];
+  RecogScratch r;
   const size_t D = (size_t)ctx->D;
-  const size_t bytes = carve(recog_carve(ctx, n, p, &m), nullptr) + (D * D + D * kRecogK6) * 4 + roi_grad_ws_bytes(n, 49, h * w, 512);
+  const size_t bytes = carve(recog_carve(ctx, n, r), nullptr) + (D * D + D * kRecogK6) * 4 + roi_grad_ws_bytes(n, 49, h * w, 512);
   if (bytes > kRecogGradMaxScratch)
     return ctx->fail(DC_E_UNSUPPORTED, "%s: n = %d rows at fc_dim = %d need %.2f GiB of scratch, more than the %d GiB a call may take", who,
                      n, ctx->D, (double)bytes / (double)((size_t)1 << 30), (int)(kRecogGradMaxScratch >> 30));
@@ -3566,57 +3481,50 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
     KCHK(launch_transpose2d(ctx->fc6_w, ctx->fc6_wT, D, kRecogK6, s));       // (the ctx's fc6_w is point-major: so is dpool)
     ctx->recog_epoch = ctx->weights_epoch;
   }
-  float *dobj, *dtrans, *danchor, *dcodes, *dx7, *dpool, *dw6, *dw5, *db5, *dbox, *ws, *spare;
-  int32_t* masked;
-  float** p[12] = {&dobj, &dtrans, &danchor, &dcodes, &dx7, &dpool, &dw6, &dw5, &db5, &dbox, &ws, &spare};
-  const std::vector<Carve> cv = recog_carve(ctx, n, p, &masked);
-  DCCHK(grow_ws(ctx, ctx->recog_ws, carve(cv, nullptr), s));       // kept by the context: 0.45 GB at the real model
-  carve(cv, ctx->recog_ws.p);
+  RecogScratch r;
+  const std::vector<Carve> cv = recog_carve(ctx, n, r);
+  HIPCHK(ctx->recog_ws.grow(carve(cv, nullptr), s));               // kept by the context: 0.45 GB at the real model
+  carve(cv, ctx->recog_ws.get());
   hipEvent_t* ev = ctx->recog_ev;
   auto body = [&]() -> int {
     for (int i = 0; i < 5; ++i)
       if (ev[i] == nullptr) HIPCHK(hipEventCreate(&ev[i]));
     HIPCHK(hipEventRecord(ev[0], s));
-    KCHK(launch_end_crit_grad(in.obj, in.final_trans, in.roi_boxes, in.target, n, np, in.w_obj, in.w_box, dobj, dtrans, danchor, masked, s));
-    KCHK(launch_heads_bwd(in.codes, ctx->head5_w, dobj, dtrans, in.g, n, np, D, dcodes, dw5, db5, s));
-    HIPCHK(hipMemcpyAsync(out.obj_w, dw5, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(out.boxreg_w, dw5 + D, (size_t)4 * D * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(out.obj_b, db5, 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(out.boxreg_b, db5 + 1, 16, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(masked_end, masked, 4, hipMemcpyDeviceToHost, s));
-    KCHK(launch_relu_mask(dcodes, in.codes, (size_t)n * D, s));
-    KCHK(launch_wgrad(dcodes, D, in.fc6_out, D, n, D, D, out.fc7_w, D, ws, s));
-    KCHK(launch_colsum(dcodes, D, n, D, out.fc7_b, s));
+    KCHK(launch_end_crit_grad(in.obj, in.final_trans, in.roi_boxes, in.target, n, np, in.w_obj, in.w_box, r.dobj, r.dtrans, r.danchor, r.masked, s));
+    KCHK(launch_heads_bwd(in.codes, ctx->head5_w, r.dobj, r.dtrans, in.g, n, np, D, r.dcodes, r.dw5, r.db5, s));
+    HIPCHK(hipMemcpyAsync(out.obj_w, r.dw5, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.boxreg_w, r.dw5 + D, (size_t)4 * D * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.obj_b, r.db5, 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.boxreg_b, r.db5 + 1, 16, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(masked_end, r.masked, 4, hipMemcpyDeviceToHost, s));
+    KCHK(launch_relu_mask(r.dcodes, in.codes, (size_t)n * D, s));
+    KCHK(launch_wgrad(r.dcodes, D, in.fc6_out, D, n, D, D, out.fc7_w, D, r.ws, s));
+    KCHK(launch_colsum(r.dcodes, D, n, D, out.fc7_b, s));
     {
       GemmDesc g;              // d(fc6 output) = d(fc7 pre-activation).W7
-      g.A = dcodes; g.W = ctx->fc7_wT; g.C = dx7; g.M = n; g.N = D; g.K = D; g.ldc = D;
+      g.A = r.dcodes; g.W = ctx->fc7_wT; g.C = r.dx7; g.M = n; g.N = D; g.K = D; g.ldc = D;
       DCCHK(run_gemm(ctx, g, s));
     }
-    KCHK(launch_relu_mask(dx7, in.fc6_out, (size_t)n * D, s));
-    KCHK(launch_wgrad(dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, dw6, kRecogK6, ws, s));
-    KCHK(launch_permute_fc6_back(dw6, out.fc6_w, D, 512, 49, s));
-    KCHK(launch_colsum(dx7, D, n, D, out.fc6_b, s));
+    KCHK(launch_relu_mask(r.dx7, in.fc6_out, (size_t)n * D, s));
+    KCHK(launch_wgrad(r.dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, r.dw6, kRecogK6, r.ws, s));
+    KCHK(launch_permute_fc6_back(r.dw6, out.fc6_w, D, 512, 49, s));
+    KCHK(launch_colsum(r.dx7, D, n, D, out.fc6_b, s));
     HIPCHK(hipEventRecord(ev[1], s));
     {
       GemmDesc g;              // dpool = d(fc6 pre-activation).W6, point-major
-      g.A = dx7; g.W = ctx->fc6_wT; g.C = dpool; g.M = n; g.N = kRecogK6; g.K = D; g.ldc = kRecogK6;
+      g.A = r.dx7; g.W = ctx->fc6_wT; g.C = r.dpool; g.M = n; g.N = kRecogK6; g.K = D; g.ldc = kRecogK6;
       DCCHK(run_gemm(ctx, g, s));
     }
     HIPCHK(hipEventRecord(ev[2], s));
-    DCCHK(roi_pool_grad(ctx, s, in.feat, in.h, in.w, 512, in.roi_boxes, n, in.img_h, in.img_w, 7, 7, dpool, out.feat, dbox, ev[3]));
-    KCHK(launch_add_pos_rows4(dbox, danchor, n, np, out.roi_boxes, s));
+    DCCHK(roi_pool_grad(ctx, s, in.feat, in.h, in.w, 512, in.roi_boxes, n, in.img_h, in.img_w, 7, 7, r.dpool, out.feat, r.dbox, ev[3]));
+    KCHK(launch_add_pos_rows4(r.dbox, r.danchor, n, np, out.roi_boxes, s));
     HIPCHK(hipEventRecord(ev[4], s));
     HIPCHK(hipStreamSynchronize(s));
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->recog_grad_ms[i], ev[i], ev[i + 1]);
     ctx->recog_grad_ran = true;
     return DC_OK;
   };
-  const int rc = body();
-  const hipError_t e = rc != DC_OK ? hipStreamSynchronize(s) : hipSuccess;      // (a complete body has synchronised)
-  prof_collect(ctx);
-  if (rc != DC_OK) return rc;
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "recognition backward: %s", hipGetErrorString(e));
-  return DC_OK;
+  return call_finish(ctx, s, body(), "recognition backward");
 }
 
 int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const float* roi_boxes, int n, int num_pos,
@@ -3654,8 +3562,8 @@ int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const flo
   int32_t* idx = nullptr; double* terms = nullptr; int32_t* masked = nullptr; float* zeros = nullptr; double* rowlik = nullptr;
   const std::vector<Carve> cv = {{(void**)&idx, 2 * 1024 * 4}, {(void**)&terms, 6 * 8}, {(void**)&masked, 2 * 4}, {(void**)&zeros, 64},
                                  {(void**)&rowlik, 1024 * 8}};
-  DCCHK(grow_ws(ctx, ctx->recog_aux_ws, carve(cv, nullptr), s));
-  carve(cv, ctx->recog_aux_ws.p);
+  HIPCHK(ctx->recog_aux_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->recog_aux_ws.get());
   double terms_h[6] = {0};
   // The contract with loss_terms_kernel this leans on: every term reads only its own inputs; the end objectness term reads
   // obj[0, n) and num_pos, the end box term roi_boxes / final_trans / gt[pos_target_idx[r]] for r < num_pos; out[2], out[3] and
@@ -3727,8 +3635,8 @@ int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   float* gcodes = nullptr;
   float* tgt_dev = nullptr;
   const std::vector<Carve> cv = {{(void**)&gcodes, (size_t)std::max(np, 1) * D * 4}, {(void**)&tgt_dev, (size_t)std::max(np, 1) * 16}};
-  DCCHK(grow_ws(ctx, ctx->recog_aux_ws, carve(cv, nullptr), s));
-  carve(cv, ctx->recog_aux_ws.p);
+  HIPCHK(ctx->recog_aux_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->recog_aux_ws.get());
   auto body = [&]() -> int {
     if (np > 0) {
       std::vector<int32_t> lab((size_t)np * Lw);
@@ -3787,19 +3695,15 @@ int dc_debug_roi_tap_index(dc_ctx* ctx, const float* boxes, int B, int h, int w,
   DCCHK(check_roi_grad_shape(ctx, h, w, 4, B, HH, WW, who));
   const int npix = h * w;
   const size_t T = (size_t)B * HH * WW * 4;
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, roi_grad_ws_bytes(B, HH * WW, npix, 4)));
-  const RoiGradWs ws = roi_grad_carve(base, B, HH * WW, npix, 4);
-  hipError_t e = launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(tap_pix, ws.tap_pix, T * 4, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(tap_w, ws.tap_w, T * 4, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(start, ws.start, ((size_t)npix + 1) * 4, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(list, ws.list, T * 4, hipMemcpyDeviceToDevice, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  hipFree(base);
-  KCHK(e);
-  KCHK(e2);
-  return DC_OK;
+  Scratch base(ctx->scratch, s);
+  HIPCHK(base.alloc(roi_grad_ws_bytes(B, HH * WW, npix, 4)));
+  const RoiGradWs ws = roi_grad_carve(base.get(), B, HH * WW, npix, 4);
+  KCHK(launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s));
+  HIPCHK(hipMemcpyAsync(tap_pix, ws.tap_pix, T * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(tap_w, ws.tap_w, T * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(start, ws.start, ((size_t)npix + 1) * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(list, ws.list, T * 4, hipMemcpyDeviceToDevice, s));
+  OP_EPILOGUE();
 }
 int dc_debug_end_crit_grad(dc_ctx* ctx, const float* obj, const float* trans, const float* anchors, const float* target, int n,
                            int num_pos, float w_obj, float w_box, float* dobj, float* dtrans, float* danchor, int32_t* masked) {
@@ -3985,17 +3889,12 @@ int dc_debug_beam_std_finish(dc_ctx* ctx, const float* beam_lp, const int32_t* b
       n_best > beam || !(length_alpha >= 0.f && length_alpha <= 2.f))
     return ctx->fail(DC_E_INVALID, "dc_debug_beam_std_finish: bad argument");
   const std::vector<float> pen = beam_std_pen(T, length_alpha);
-  float* pen_d = nullptr;
-  HIPCHK(hipMalloc((void**)&pen_d, pen.size() * 4));
-  hipError_t e = hipMemcpy(pen_d, pen.data(), pen.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = launch_beam_std_finish(beam_lp, beams, len, pen_d, length_alpha != 0.f, nprop, beam, T, n_best, captions, logprob, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(pen_d);
-  prof_collect(ctx);
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_beam_std_finish: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_beam_std_finish sync: %s", hipGetErrorString(e2));
-  return DC_OK;
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc(pen.size() * 4));
+  float* pen_d = static_cast<float*>(block.get());
+  HIPCHK(hipMemcpy(pen_d, pen.data(), pen.size() * 4, hipMemcpyHostToDevice));
+  KCHK(launch_beam_std_finish(beam_lp, beams, len, pen_d, length_alpha != 0.f, nprop, beam, T, n_best, captions, logprob, s));
+  OP_EPILOGUE();
 }
 // the standard hooks take their width as an argument, validated like a call's options, and run in fp32 like the search
 static int beam_std_hook_opts(dc_ctx* ctx, int beam, const char* who) {
@@ -4054,15 +3953,14 @@ int dc_debug_rescore_tail(dc_ctx* ctx, const void* scores, const float* h, const
   const size_t Hd = ctx->Hd, rows = n;
   float *hs = nullptr, *cs = nullptr, *ns = nullptr;
   const std::vector<Carve> cv = {{(void**)&hs, rows * Hd * 4}, {(void**)&cs, rows * Hd * 4}, {(void**)&ns, rows * 4}};
-  void* base = nullptr;
+  Scratch base(ctx->scratch, s);
   int live = n;
   if (step) {
     if (n_dev_or_null) {
       HIPCHK(hipMemcpy(&live, n_dev_or_null, 4, hipMemcpyDeviceToHost));
       live = std::max(0, std::min(n, live));
     }
-    HIPCHK(hipMalloc(&base, carve(cv, nullptr)));
-    carve(cv, base);
+    HIPCHK(base.alloc(cv));
   }
   RescoreTail a{};
   a.scores = static_cast<const _Float16*>(scores); a.ld = ctx->V1pad; a.wnorm = reinterpret_cast<const _Float16*>(ctx->scr_wnorm);
@@ -4071,22 +3969,14 @@ int dc_debug_rescore_tail(dc_ctx* ctx, const void* scores, const float* h, const
   a.hnorm = step ? ns : const_cast<float*>(hnorm);
   a.n = n; a.n_dev = n_dev_or_null; a.Hd = ctx->Hd; a.seq = tok_out; a.T = 1; a.t = 0; a.hb = hb_out; a.Kp = ctx->scr_Kp;
   a.cand = cand_out; a.bestv = best_out;
-  hipError_t e = hipSuccess;
   const struct { void* scratch; const void* in; void* out; size_t row; } st[] = {
       {hs, h, h_out, Hd * 4}, {cs, c, c_out, Hd * 4}, {ns, hnorm, hnorm_out, 4}};
   if (step)
-    for (const auto& p : st)
-      if (e == hipSuccess) e = hipMemcpyAsync(p.scratch, p.in, rows * p.row, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = launch_lstm_rescore_tail(a, s);
+    for (const auto& p : st) HIPCHK(hipMemcpyAsync(p.scratch, p.in, rows * p.row, hipMemcpyDeviceToDevice, s));
+  KCHK(launch_lstm_rescore_tail(a, s));
   if (step && live > 0)
-    for (const auto& p : st)
-      if (e == hipSuccess) e = hipMemcpyAsync(p.out, p.scratch, (size_t)live * p.row, hipMemcpyDeviceToDevice, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  if (base) hipFree(base);
-  prof_collect(ctx);
-  if (e != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_rescore_tail: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return ctx->fail(DC_E_HIP, "dc_debug_rescore_tail sync: %s", hipGetErrorString(e2));
-  return DC_OK;
+    for (const auto& p : st) HIPCHK(hipMemcpyAsync(p.out, p.scratch, (size_t)live * p.row, hipMemcpyDeviceToDevice, s));
+  OP_EPILOGUE();
 }
 
 }  // extern "C"

@@ -31,6 +31,9 @@ int dc_mfma_profile(dc_ctx* ctx, int reset, int64_t* launches, double* total_ms,
  * "fault_word" (int32: the ctx's sticky device fault word, which the NMS band scan and stream-K report through and every
  * packed result carries -- 0 after a clean forward, -1 if it does not exist), or
  * "arena_allocs" (int32: how many times a lane workspace has been (re)allocated -- it only grows), or
+ * "scratch" (3 x int64, no forward needed: the call-scoped device blocks alive now -- 0 between calls, whatever way the last
+ * call ended; the bytes held by the context's seven grow-only buffers, those of dc_preprocess_u8, dc_forward_losses and the
+ * gradient passes; how many times one of those buffers has been (re)allocated -- unchanged by a call whose shapes fit), or
  * "host_enqueue_us" (int32: host microseconds per image spent enqueueing in the last dc_forward_batch).
  * "decode_screen_cand" (int32, group x P x T: the screened greedy decode's candidate count of every (row, step) of lane 0's
  * last group -- -1 = a non-finite score or bound, above 64 = the row scanned every column exactly; rows the route did not
