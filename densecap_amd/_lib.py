@@ -102,6 +102,11 @@ class DcRecogGrads(C.Structure):
                                           "roi_boxes")]
 
 
+class DcRpnGrads(C.Structure):
+    """dc_rpn_grads: device buffers for the RPN's gradients, in checkpoint layouts, and a feature-map gradient; all required."""
+    _fields_ = [(n, C.c_void_p) for n in ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "feat")]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -229,6 +234,13 @@ _SIGS = {
                                     C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
                                     C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads)]),
     "dc_feature_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dc_op_conv3x3_grad": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "dc_op_rpn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(DcLossOpts), C.c_float,
+                                 C.POINTER(DcRpnGrads), C.POINTER(C.c_double), C.POINTER(C.c_double), c_int32_p]),
+    "dc_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
+                                      C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads), C.c_float, C.POINTER(DcRpnGrads)]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -274,6 +286,14 @@ _BWD_HOOK_SIGS = {
     "dc_debug_lstm_cell_bwd_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
                                   [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
+# the hooks of include/densecap_debug_rpn.h (the RPN backward's kernels; bound like the others)
+_RPN_HOOK_SIGS = {
+    "dc_debug_conv3x3_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "dc_debug_rpn_dheads": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "dc_debug_rpn_heads_bwd": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "dc_debug_rpn_grad_kept": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_float_p]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -290,7 +310,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
-                                  list(_BWD_HOOK_SIGS.items())):
+                                  list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

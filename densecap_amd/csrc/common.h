@@ -13,6 +13,7 @@
 #include "../../include/densecap_debug_grad.h"
 #include "../../include/densecap_debug_recog.h"
 #include "../../include/densecap_debug_bwd.h"
+#include "../../include/densecap_debug_rpn.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -562,6 +563,36 @@ hipError_t launch_heads_bwd(const float* codes, const float* w5, const float* do
 hipError_t launch_permute_fc6_back(const float* in, float* out, int N, int C, int HW, hipStream_t s);
 // out[r] = a[r] + (r < np ? b[r] : 0), n rows of four floats
 hipError_t launch_add_pos_rows4(const float* a, const float* b, int n, int np, float* out, hipStream_t s);
+
+// ---- backward of a 3x3 / stride 1 / pad 1 convolution (rpn_grad.hip; docs/SEMANTICS.md, "Convolution gradients") ----
+// dw (Cout, Cin, 3, 3) = sum over the pixels of dy (h, w, Cout) times the nine shifted copies of x (h, w, Cin), zero outside the
+// map, on the fp32 MFMA; no im2col buffer.  The pixels are shared by S slices per tile (1..64; conv3x3_wgrad_slices is the
+// production choice, a function of the sizes and the device alone); `ws` holds conv3x3_wgrad_ws_floats(S, ..) floats of partial
+// tiles, added in slice order.  Cin % 32 == 0, h * w <= 65536.
+int conv3x3_wgrad_slices(int P, int Cout, int Cin);
+size_t conv3x3_wgrad_ws_floats(int S, int Cout, int Cin);
+hipError_t launch_conv3x3_wgrad(const float* x, const float* dy, int h, int w, int Cin, int Cout, int S, float* dw, float* ws,
+                                hipStream_t s);
+// wf (Cin, Cout, 3, 3) with wf[c][o][tap] = w[o][c][8 - tap]: dx = conv3x3(dy, wf).  w: OIHW, or (packed) launch_pack_conv3x3's form
+hipError_t launch_conv3x3_flip(const float* w, int Cout, int Cin, int packed, float* wf, hipStream_t s);
+
+// ---- RPN gradients (rpn_grad.hip; docs/SEMANTICS.md, "RPN gradients") ----
+// The gradient at the RPN's head outputs, dheads (h * w, 6k) in the layout of the heads: the two mid criteria on the sampled rows,
+// ApplyBoxTransform:backward of droi (n, 4) or null, scattered by the sampler's copy rule (the last sampled row that names an
+// input row wins), plus decay * trans on every box element.  trans, anchors, boxes (A, 4) and scores (A, 2) are the training
+// forward's rows, A = k * h * w; win_all / win_pos: A int32 each of scratch.  n = num_pos + num_neg <= 1024; the lists are trusted.
+struct RpnDheadsArgs {
+  const float *trans, *scores, *anchors, *boxes, *gt, *droi;
+  const int32_t *pos_input_idx, *pos_target_idx, *neg_input_idx;
+  int num_pos, num_neg, h, w, k;
+  float w_mid_obj, w_mid_box, decay;
+  int32_t *win_all, *win_pos;
+  float* dheads;
+};
+hipError_t launch_rpn_dheads(const RpnDheadsArgs& a, hipStream_t s);
+// dhidden (P, R) = (hidden > 0) * (dheads (P, K6) . W (K6, R)), fp32 in ascending K6 order; K6 <= 12288
+hipError_t launch_rpn_heads_bwd(const float* dheads, const float* W, const float* hidden, int P, int K6, int R, float* dhidden,
+                                hipStream_t s);
 
 // ---- image preprocessing (preprocess.hip; run_model.lua:67-74) -------------------------------------------------------
 void preprocess_scaled_size(int H0, int W0, int image_size, int* oh, int* ow);

@@ -212,6 +212,15 @@ struct dc_ctx {
   hipEvent_t recog_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float recog_grad_ms[4] = {0, 0, 0, 0};
   bool recog_grad_ran = false;
+  // RPN gradients (rpn_backward): the RPN convolution's flipped, transposed weights, OIHW and in the engine's packed form (512,
+  // 9R), made on first need and again when weights_epoch moves; the backward's scratch and the op's forward rows (grow only);
+  // what the last backward left there for the hooks: its event split and the RPN's share of the feature map's gradient
+  KeptBuf rpn_wf{scratch}, rpn_ws{scratch}, rpn_aux_ws{scratch};
+  uint64_t rpn_epoch = 0;
+  hipEvent_t rpn_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  float rpn_grad_ms[4] = {0, 0, 0, 0};
+  const float* rpn_dfeat = nullptr;
+  int rpn_dfeat_pixels = 0;
   // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
   // rounded up to fp16 (V1pad of them), the constant c of the bound.  Part of the weights, made with dec_w.
   uint16_t* scr_w = nullptr;
@@ -1772,6 +1781,7 @@ void dc_destroy(dc_ctx* ctx) {
   for (auto& lp : ctx->lanes) lane_release(*lp);
   for (void* p : ctx->owned) hipFree(p);
   for (hipEvent_t e : ctx->recog_ev) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : ctx->rpn_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
   delete ctx;                 // (the kept buffers free themselves here)
 }
@@ -3976,6 +3986,371 @@ int dc_debug_rescore_tail(dc_ctx* ctx, const void* scores, const float* h, const
   KCHK(launch_lstm_rescore_tail(a, s));
   if (step && live > 0)
     for (const auto& p : st) HIPCHK(hipMemcpyAsync(p.out, p.scratch, (size_t)live * p.row, hipMemcpyDeviceToDevice, s));
+  OP_EPILOGUE();
+}
+
+// ---- convolution gradients (docs/SEMANTICS.md, "Convolution gradients") --------------------------------------------
+// Can the engine run dx = conv3x3(dy, flipped weights)?  Its conv descriptor's own rule (operands within the 32-bit buffer
+// offsets, at most 2048 input channels), which mfma_gemm_can_pool states for a conv of these sizes.
+static bool conv3x3_dx_fits(int h, int wd, int Cin, int Cout) {
+  GemmDesc d;
+  d.conv = 1; d.M = h * wd; d.H = h; d.Wd = wd; d.Cin = Cout; d.K = 9 * Cout; d.N = Cin; d.ldc = Cin;
+  return mfma_gemm_can_pool(d);
+}
+static int check_conv3x3_grad_shape(dc_ctx* ctx, int h, int wd, int Cin, int Cout, bool dx, const char* who) {
+  if (h < 1 || wd < 1 || Cin < 1 || Cout < 1 || Cin % 32 || Cout % 32)
+    return ctx->fail(DC_E_INVALID, "%s: need Cin %% 32 == 0, Cout %% 32 == 0 and positive sizes", who);
+  if ((long long)h * wd > (1 << 16))
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a map of %d x %d pixels, more than the 65536 the kernels take", who, h, wd);
+  if (dx && !conv3x3_dx_fits(h, wd, Cin, Cout))
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a gradient of %d x %d x %d exceeds the engine's 32-bit operand offsets", who, h, wd, Cout);
+  return DC_OK;
+}
+// What one call carves from its block: the weight gradient's partial tiles, the flipped weights in OIHW and packed, the engine's
+// split-K scratch (the last three only where dx is wanted)
+struct ConvGradScratch { float *part = nullptr, *wf = nullptr, *wfp = nullptr, *splitk = nullptr; };
+static std::vector<Carve> conv3x3_grad_carve(int Cin, int Cout, int S, bool dw, bool dx, ConvGradScratch& r) {
+  const size_t wn = (size_t)Cout * Cin * 9 * 4;
+  return {{(void**)&r.part, dw ? conv3x3_wgrad_ws_floats(S, Cout, Cin) * 4 : 0},
+          {(void**)&r.wf, dx ? wn : 0}, {(void**)&r.wfp, dx ? wn : 0}, {(void**)&r.splitk, dx ? kSplitkWsFloats * 4 : 0}};
+}
+// Launch list (stream s, eager, not synchronised; the caller holds LossCfgGuard):
+//   conv3x3_wgrad + conv3x3_wgrad_finish (dw); colsum (db); conv3x3_flip + pack_conv3x3 + the engine's conv (dx)
+static int conv3x3_grad(dc_ctx* ctx, hipStream_t s, const float* x, const float* w, const float* dy, int h, int wd, int Cin, int Cout,
+                        int S, float* dw, float* db, float* dx, const ConvGradScratch& r) {
+  if (dw != nullptr) KCHK(launch_conv3x3_wgrad(x, dy, h, wd, Cin, Cout, S, dw, r.part, s));
+  if (db != nullptr) KCHK(launch_colsum(dy, Cout, h * wd, Cout, db, s));
+  if (dx != nullptr) {
+    KCHK(launch_conv3x3_flip(w, Cout, Cin, 0, r.wf, s));
+    KCHK(launch_pack_conv3x3(r.wf, r.wfp, Cin, Cout, s));
+    DCCHK(conv3x3(ctx, s, dy, r.wfp, nullptr, dx, 1, h, wd, Cout, Cin, 0, Ws{r.splitk, kSplitkWsFloats}));
+  }
+  return DC_OK;
+}
+int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float* dy, int h, int w_px, int Cin, int Cout, float* dw,
+                       float* db, float* dx) {
+  OP_PROLOGUE();
+  const char* who = "dc_op_conv3x3_grad";
+  if (!dy || (dw && !x) || (dx && !w)) return ctx->fail(DC_E_INVALID, "%s: null input", who);
+  if (!dw && !db && !dx) return ctx->fail(DC_E_INVALID, "%s: no output asked for", who);
+  DCCHK(check_conv3x3_grad_shape(ctx, h, w_px, Cin, Cout, dx != nullptr, who));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  const int S = conv3x3_wgrad_slices(h * w_px, Cout, Cin);
+  ConvGradScratch r;
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc(conv3x3_grad_carve(Cin, Cout, S, dw != nullptr, dx != nullptr, r)));
+  return call_finish(ctx, s, conv3x3_grad(ctx, s, x, w, dy, h, w_px, Cin, Cout, S, dw, db, dx, r), who, dx != nullptr);
+}
+
+// ---- RPN gradients (docs/SEMANTICS.md, "RPN gradients") -------------------------------------------------------------
+// What the backward reads of the forward: the feature map, the RPN's hidden map after its in-place ReLU, the rows rpn_decode and
+// rpn_score_rows made of the heads (A = k * h * w each), the sampler's lists and the ground truth on the device, and the
+// gradient of the sampled boxes (n, 4) or null.
+struct RpnKept {
+  const float* feat; int h, w;
+  const float *hidden, *trans, *scores, *anchors, *boxes, *gt, *droi;
+  const int32_t *pos_idx, *pos_tgt, *neg_idx;
+  int np, nn;
+  float w_mid_obj, w_mid_box, decay;
+};
+struct RpnScratch {
+  int32_t *win_all = nullptr, *win_pos = nullptr;
+  float *dheads = nullptr, *dhidden = nullptr, *dw6 = nullptr, *db6 = nullptr, *ws = nullptr, *part = nullptr, *dfeat = nullptr;
+};
+static std::vector<Carve> rpn_carve(const dc_ctx* ctx, int h, int w, int S, RpnScratch& r) {
+  const size_t hw = (size_t)h * w, K6 = (size_t)6 * ctx->k, R = (size_t)ctx->R, A = hw * ctx->k;
+  return {{(void**)&r.win_all, A * 4},         {(void**)&r.win_pos, A * 4},      {(void**)&r.dheads, hw * K6 * 4},
+          {(void**)&r.dhidden, hw * R * 4},    {(void**)&r.dw6, K6 * R * 4},     {(void**)&r.db6, K6 * 4},
+          {(void**)&r.ws, wgrad_ws_floats((int)hw, (int)K6, (int)R) * 4},
+          {(void**)&r.part, conv3x3_wgrad_ws_floats(S, (int)R, 512) * 4},        {(void**)&r.dfeat, hw * 512 * 4}};
+}
+static int check_rpn_out(dc_ctx* ctx, const dc_rpn_grads* o, const char* who) {
+  if (!o || !o->rpn_conv_w || !o->rpn_conv_b || !o->rpn_box_w || !o->rpn_box_b || !o->rpn_score_w || !o->rpn_score_b || !o->feat)
+    return ctx->fail(DC_E_INVALID, "%s: null RPN gradient buffer", who);
+  return DC_OK;
+}
+static int check_rpn_grad_shape(dc_ctx* ctx, int h, int w, float decay, const char* who) {
+  if (!(decay >= 0.f) || !std::isfinite(decay)) return ctx->fail(DC_E_INVALID, "%s: box_reg_decay must be finite and >= 0", who);
+  if (h < 1 || w < 1) return ctx->fail(DC_E_INVALID, "%s: bad map size", who);
+  if ((long long)h * w > (1 << 16))
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: a map of %d x %d pixels, more than the 65536 the kernels take", who, h, w);
+  if (ctx->R % 32 || !conv3x3_dx_fits(h, w, 512, ctx->R) || (size_t)6 * ctx->k * 4 > 48 * 1024)
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: rpn_hidden = %d, num_anchors = %d: the hidden map's gradient does not fit the engine's conv "
+                     "descriptor (a multiple of 32 channels, 32-bit operand offsets) or a head row the row kernel's LDS", who, ctx->R, ctx->k);
+  return DC_OK;
+}
+// Launch list (lane 0's stream, eager; the caller holds LossCfgGuard; ws: the lane's split-K scratch):
+//   [conv3x3_flip + pack_conv3x3 after a dc_load_weights]
+//   2 x memset + rpn_winner + rpn_dheads
+//   wgrad + colsum on dheads, four copies into the head outputs; rpn_heads_bwd
+//   conv3x3_wgrad + conv3x3_wgrad_finish; colsum
+//   the engine's conv on the flipped weights: the RPN's share of the feature map's gradient, kept in ctx->rpn_ws
+// feat_add == null: out.feat = that share; else out.feat = feat_add + the share, one fp32 add per element.
+static int rpn_backward(dc_ctx* ctx, hipStream_t s, const RpnKept& in, const dc_rpn_grads& out, const float* feat_add, const Ws& ws) {
+  const int k = ctx->k, R = ctx->R, h = in.h, w = in.w, hw = h * w, K6 = 6 * k;
+  const size_t wn = (size_t)R * 512 * 9;
+  if (ctx->rpn_wf.get() == nullptr || ctx->rpn_wf.bytes() < 2 * wn * 4 || ctx->rpn_epoch != ctx->weights_epoch) {
+    HIPCHK(ctx->rpn_wf.grow(2 * wn * 4, s));
+    float* wf = static_cast<float*>(ctx->rpn_wf.get());
+    KCHK(launch_conv3x3_flip(ctx->rpn_w, R, 512, 1, wf + wn, s));           // (the ctx keeps rpn_w packed)
+    KCHK(launch_pack_conv3x3(wf + wn, wf, 512, R, s));
+    ctx->rpn_epoch = ctx->weights_epoch;
+  }
+  const int S = conv3x3_wgrad_slices(hw, R, 512);
+  RpnScratch r;
+  const std::vector<Carve> cv = rpn_carve(ctx, h, w, S, r);
+  HIPCHK(ctx->rpn_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->rpn_ws.get());
+  ctx->rpn_dfeat = nullptr;
+  hipEvent_t* ev = ctx->rpn_ev;
+  auto body = [&]() -> int {
+    for (int i = 0; i < 5; ++i)
+      if (ev[i] == nullptr) HIPCHK(hipEventCreate(&ev[i]));
+    HIPCHK(hipEventRecord(ev[0], s));
+    RpnDheadsArgs a{};
+    a.trans = in.trans; a.scores = in.scores; a.anchors = in.anchors; a.boxes = in.boxes; a.gt = in.gt; a.droi = in.droi;
+    a.pos_input_idx = in.pos_idx; a.pos_target_idx = in.pos_tgt; a.neg_input_idx = in.neg_idx;
+    a.num_pos = in.np; a.num_neg = in.nn; a.h = h; a.w = w; a.k = k;
+    a.w_mid_obj = in.w_mid_obj; a.w_mid_box = in.w_mid_box; a.decay = in.decay;
+    a.win_all = r.win_all; a.win_pos = r.win_pos; a.dheads = r.dheads;
+    KCHK(launch_rpn_dheads(a, s));
+    HIPCHK(hipEventRecord(ev[1], s));
+    KCHK(launch_wgrad(r.dheads, K6, in.hidden, R, hw, K6, R, r.dw6, R, r.ws, s));
+    KCHK(launch_colsum(r.dheads, K6, hw, K6, r.db6, s));
+    HIPCHK(hipMemcpyAsync(out.rpn_box_w, r.dw6, (size_t)4 * k * R * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.rpn_score_w, r.dw6 + (size_t)4 * k * R, (size_t)2 * k * R * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.rpn_box_b, r.db6, (size_t)4 * k * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.rpn_score_b, r.db6 + 4 * k, (size_t)2 * k * 4, hipMemcpyDeviceToDevice, s));
+    KCHK(launch_rpn_heads_bwd(r.dheads, ctx->heads_w, in.hidden, hw, K6, R, r.dhidden, s));
+    HIPCHK(hipEventRecord(ev[2], s));
+    KCHK(launch_conv3x3_wgrad(in.feat, r.dhidden, h, w, 512, R, S, out.rpn_conv_w, r.part, s));
+    KCHK(launch_colsum(r.dhidden, R, hw, R, out.rpn_conv_b, s));
+    HIPCHK(hipEventRecord(ev[3], s));
+    DCCHK(conv3x3(ctx, s, r.dhidden, static_cast<const float*>(ctx->rpn_wf.get()), nullptr, r.dfeat, 1, h, w, R, 512, 0, ws));
+    if (feat_add != nullptr) KCHK(launch_add_pos_rows4(feat_add, r.dfeat, hw * 128, hw * 128, out.feat, s));
+    else HIPCHK(hipMemcpyAsync(out.feat, r.dfeat, (size_t)hw * 512 * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->rpn_grad_ms[i], ev[i], ev[i + 1]);
+    ctx->rpn_dfeat = r.dfeat; ctx->rpn_dfeat_pixels = hw;
+    return DC_OK;
+  };
+  return call_finish(ctx, s, body(), "RPN backward", true);
+}
+
+int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32_t* pos_input_idx, const int32_t* pos_target_idx,
+                   int num_pos, const int32_t* neg_input_idx, int num_neg, const float* gt_boxes, int G,
+                   const float* droi_boxes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null, float box_reg_decay,
+                   const dc_rpn_grads* out, double* mid_objectness_loss, double* mid_box_reg_loss, int32_t* masked_mid) {
+  const char* who = "dc_op_rpn_grad";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!feat_hwc || !gt_boxes || !mid_objectness_loss || !mid_box_reg_loss || !masked_mid) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  DCCHK(check_rpn_out(ctx, out, who));
+  const dc_loss_opts o = opts_or_null ? *opts_or_null : kLossDefaults;
+  DCCHK(check_sampler_opts(ctx, &o, who));
+  const int np = num_pos, nn = num_neg;
+  if (np < 0 || nn < 0 || (long long)np + nn > 1024) return ctx->fail(DC_E_INVALID, "%s: num_pos + num_neg must be in 0..1024 (got %d + %d)", who, np, nn);
+  if ((np > 0 && (!pos_input_idx || !pos_target_idx)) || (nn > 0 && !neg_input_idx)) return ctx->fail(DC_E_INVALID, "%s: null list", who);
+  if (G < 1 || G > 512) return ctx->fail(DC_E_INVALID, "%s: G must be in 1..512 (got %d)", who, G);
+  if (img_h < 32 || img_w < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
+  DCCHK(check_image_size(ctx, img_h, img_w, who));
+  DCCHK(check_rpn_grad_shape(ctx, h, w, box_reg_decay, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  const int k = ctx->k, R = ctx->R, hw = h * w, A = k * hw;
+  // the caller's lists and boxes are checked on the host: the kernels trust them
+  std::vector<int32_t> lists(3 * 1024, 0);
+  std::vector<float> gth((size_t)G * 4);
+  if (np > 0) {
+    HIPCHK(hipMemcpy(lists.data(), pos_input_idx, (size_t)np * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lists.data() + 1024, pos_target_idx, (size_t)np * 4, hipMemcpyDeviceToHost));
+  }
+  if (nn > 0) HIPCHK(hipMemcpy(lists.data() + 2048, neg_input_idx, (size_t)nn * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(gth.data(), gt_boxes, gth.size() * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < np; ++r)
+    if (lists[r] < 0 || lists[r] >= A || lists[1024 + r] < 0 || lists[1024 + r] >= G)
+      return ctx->fail(DC_E_INVALID, "%s: positive row %d names input %d of %d, ground-truth box %d of %d", who, r, lists[r], A, lists[1024 + r], G);
+  for (int r = 0; r < nn; ++r)
+    if (lists[2048 + r] < 0 || lists[2048 + r] >= A) return ctx->fail(DC_E_INVALID, "%s: negative row %d names input %d of %d", who, r, lists[2048 + r], A);
+  for (int j = 0; j < G; ++j) {
+    const float* b = gth.data() + (size_t)j * 4;
+    if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3])) || !(b[2] > 0.f) || !(b[3] > 0.f))
+      return ctx->fail(DC_E_INVALID, "%s: ground-truth box %d is not finite with w > 0 and h > 0", who, j);
+  }
+  LossCfgGuard guard(ctx->cfg);
+  Lane& L = lane0(ctx);
+  DCCHK(lane_prepare(ctx, L, img_h, img_w, o.batch_size, 1));
+  hipStream_t s = L.stream;
+  // ---- the forward half, through dc_forward_losses' own calls, on rows of this call's own ----
+  float *hidden = nullptr, *heads = nullptr, *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr, *gt_dev = nullptr;
+  float *stand = nullptr;
+  int32_t *idx = nullptr, *masked = nullptr;
+  double *terms = nullptr, *rowlik = nullptr;
+  const std::vector<Carve> cv = {
+      {(void**)&hidden, (size_t)hw * R * 4}, {(void**)&heads, (size_t)hw * 6 * k * 4}, {(void**)&boxes, (size_t)A * 16},
+      {(void**)&anchors, (size_t)A * 16},    {(void**)&trans, (size_t)A * 16},         {(void**)&scores, (size_t)A * 8},
+      {(void**)&gt_dev, (size_t)G * 16},     {(void**)&stand, 3 * 1024 * 16},          {(void**)&idx, 3 * 1024 * 4},
+      {(void**)&masked, 2 * 4},              {(void**)&terms, 6 * 8},                  {(void**)&rowlik, 1024 * 8}};
+  HIPCHK(ctx->rpn_aux_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->rpn_aux_ws.get());
+  double terms_h[6] = {0};
+  int32_t masked_h[2] = {0, 0};
+  // The contract with loss_terms_kernel this leans on (as dc_op_recog_grad does for the other two terms): every term reads only
+  // its own inputs.  The two end terms and the captioning term get inputs on which they stay finite -- recognition logits and
+  // final transforms of zero, the RoI box (0, 0, 1, 1), zero row sums -- and their weights are 0.
+  std::vector<float> st((size_t)3 * 1024 * 4, 0.f);         // [0, 1024) rows: RoI boxes; [1024, 2048): final transforms; then logits
+  for (int r = 0; r < 1024; ++r) { st[(size_t)r * 4 + 2] = 1.f; st[(size_t)r * 4 + 3] = 1.f; }
+  auto fwd = [&]() -> int {
+    ensure_fault_word(ctx);
+    DCCHK(conv3x3(ctx, s, feat_hwc, ctx->rpn_w, ctx->rpn_b, hidden, 1, h, w, 512, R, 1, lane_ws(L)));
+    DCCHK(linear(ctx, s, hidden, ctx->heads_w, ctx->heads_b, heads, hw, 6 * k, R, 0, Ws(), hw));
+    KCHK(launch_rpn_decode(heads, 1, h, w, k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], img_h, img_w, boxes, anchors,
+                           trans, nullptr, nullptr, nullptr, 0, s));
+    KCHK(launch_rpn_score_rows(heads, h, w, k, scores, s));
+    HIPCHK(hipMemcpyAsync(idx, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(gt_dev, gth.data(), gth.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(stand, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(rowlik, 0, 1024 * 8, s));
+    LossTermArgs t{};
+    t.scores = scores; t.anchors = anchors; t.trans = trans; t.gt = gt_dev; t.roi_boxes = stand; t.final_trans = stand + 1024 * 4;
+    t.obj = stand + 2048 * 4; t.pos_input_idx = idx; t.pos_target_idx = idx + 1024; t.neg_input_idx = idx + 2048; t.rowlik = rowlik;
+    t.num_pos = np; t.num_neg = nn; t.L = 1;
+    t.w_mid_box = o.mid_box_reg_weight; t.w_mid_obj = o.mid_objectness_weight; t.w_end_box = 0.f; t.w_end_obj = 0.f; t.w_cap = 0.f;
+    t.out = terms; t.out_masked = masked;
+    KCHK(launch_loss_terms(t, s));
+    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(masked_h, masked, sizeof masked_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DC_OK;
+  };
+  const int rc = fwd();
+  if (rc != DC_OK) (void)hipStreamSynchronize(s);
+  L.have_times = false;
+  if (rc != DC_OK) { prof_collect(ctx); return rc; }
+  *mid_objectness_loss = terms_h[0];
+  *mid_box_reg_loss = terms_h[1];
+  *masked_mid = masked_h[0];
+  RpnKept kp{};
+  kp.feat = feat_hwc; kp.h = h; kp.w = w; kp.hidden = hidden; kp.trans = trans; kp.scores = scores; kp.anchors = anchors; kp.boxes = boxes;
+  kp.gt = gt_dev; kp.droi = np + nn > 0 ? droi_boxes_or_null : nullptr; kp.pos_idx = idx; kp.pos_tgt = idx + 1024; kp.neg_idx = idx + 2048;
+  kp.np = np; kp.nn = nn; kp.w_mid_obj = o.mid_objectness_weight; kp.w_mid_box = o.mid_box_reg_weight; kp.decay = box_reg_decay;
+  return rpn_backward(ctx, s, kp, *out, nullptr, lane_ws(L));
+}
+
+// What dc_forward_backward reads of what dc_loss_gradients left, none of which anything between the RPN's forward and here
+// writes: lane 0's feat and rpn_hidden (the trunk and the RPN write them; RoI pooling, fc6 / fc7, the language model and the two
+// backward passes read feat or own buffers), the rows loss_keep points at in ctx->loss_ws (boxes, anchors, trans, scores:
+// written by rpn_decode / rpn_score_rows only), and rg->roi_boxes.  The lists and the ground truth go up again from the host.
+int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                        const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                        dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
+                        const dc_rpn_grads* pg) {
+  const char* who = "dc_forward_backward";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  DCCHK(check_rpn_out(ctx, pg, who));
+  int fh = 1, fw = 1;
+  if (H >= 1 && W >= 1) (void)dc_feature_size(H, W, &fh, &fw);
+  DCCHK(check_rpn_grad_shape(ctx, fh, fw, box_reg_decay, who));
+  if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
+    return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
+  std::vector<int32_t> lists(3 * 1024, 0);
+  const dc_loss_dump own = {lists.data(), lists.data() + 1024, lists.data() + 2048};
+  DCCHK(dc_loss_gradients(ctx, img_chw, H, W, img_on_device, gt_boxes, gt_labels, G, L, opts, forced, out, &own, rg, lg));
+  const int np = out->num_pos, nn = out->num_neg;
+  if (dump) {
+    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
+    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
+    std::copy(lists.begin() + 2048, lists.begin() + 2048 + nn, dump->neg_input_idx);
+  }
+  const dc_loss_opts o = opts ? *opts : kLossDefaults;
+  const dc_ctx::LossKeep& keep = ctx->loss_keep;
+  Lane& Ln = lane0(ctx);
+  if (keep.boxes == nullptr || keep.A != ctx->k * Ln.fh * Ln.fw) return ctx->fail(DC_E_STATE, "%s: the forward left no RPN rows", who);
+  LossCfgGuard guard(ctx->cfg);
+  hipStream_t s = Ln.stream;
+  float* gt_dev = nullptr;
+  int32_t* idx = nullptr;
+  const std::vector<Carve> cv = {{(void**)&gt_dev, (size_t)G * 16}, {(void**)&idx, 3 * 1024 * 4}};
+  HIPCHK(ctx->rpn_aux_ws.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->rpn_aux_ws.get());
+  HIPCHK(hipMemcpyAsync(idx, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(gt_dev, gt_boxes, (size_t)G * 16, hipMemcpyHostToDevice, s));
+  RpnKept kp{};
+  kp.feat = Ln.feat; kp.h = Ln.fh; kp.w = Ln.fw; kp.hidden = Ln.rpn_hidden; kp.trans = keep.trans; kp.scores = keep.scores;
+  kp.anchors = keep.anchors; kp.boxes = keep.boxes; kp.gt = gt_dev; kp.droi = np + nn > 0 ? rg->roi_boxes : nullptr;
+  kp.pos_idx = idx; kp.pos_tgt = idx + 1024; kp.neg_idx = idx + 2048; kp.np = np; kp.nn = nn;
+  kp.w_mid_obj = o.mid_objectness_weight; kp.w_mid_box = o.mid_box_reg_weight; kp.decay = box_reg_decay;
+  const int rc = rpn_backward(ctx, s, kp, *pg, rg->feat, lane_ws(Ln));
+  if (rc != DC_OK) (void)hipStreamSynchronize(s);             // (the lists' upload reads this frame)
+  return rc;
+}
+
+// ---- test hooks of the RPN backward (densecap_debug_rpn.h) ----------------------------------------------------------------------------
+int dc_debug_rpn_dheads(dc_ctx* ctx, const float* trans, const float* scores, const float* anchors, const float* boxes, int h, int w_px,
+                        int k, const int32_t* pos_input_idx, const int32_t* pos_target_idx, int num_pos, const int32_t* neg_input_idx,
+                        int num_neg, const float* gt, int G, const float* droi_or_null, float w_mid_obj, float w_mid_box, float decay,
+                        float* dheads) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_rpn_dheads";
+  if (!trans || !scores || !anchors || !boxes || !gt || !dheads || h < 1 || w_px < 1 || k < 1 || G < 1 || num_pos < 0 || num_neg < 0 ||
+      (long long)num_pos + num_neg > 1024 || (long long)h * w_px > (1 << 16) || k > 4096 || (num_pos > 0 && (!pos_input_idx || !pos_target_idx)) ||
+      (num_neg > 0 && !neg_input_idx))
+    return ctx->fail(DC_E_INVALID, "%s: bad argument", who);
+  const int A = k * h * w_px;
+  std::vector<int32_t> li(3 * 1024, 0);                       // the kernels trust their lists: the caller's are checked here
+  if (num_pos > 0) {
+    HIPCHK(hipMemcpy(li.data(), pos_input_idx, (size_t)num_pos * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(li.data() + 1024, pos_target_idx, (size_t)num_pos * 4, hipMemcpyDeviceToHost));
+  }
+  if (num_neg > 0) HIPCHK(hipMemcpy(li.data() + 2048, neg_input_idx, (size_t)num_neg * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < num_pos; ++r)
+    if (li[r] < 0 || li[r] >= A || li[1024 + r] < 0 || li[1024 + r] >= G) return ctx->fail(DC_E_INVALID, "%s: positive row %d out of range", who, r);
+  for (int r = 0; r < num_neg; ++r)
+    if (li[2048 + r] < 0 || li[2048 + r] >= A) return ctx->fail(DC_E_INVALID, "%s: negative row %d out of range", who, r);
+  RpnDheadsArgs a{};
+  Scratch block(ctx->scratch, s);
+  HIPCHK(block.alloc(std::vector<Carve>{{(void**)&a.win_all, (size_t)A * 4}, {(void**)&a.win_pos, (size_t)A * 4}}));
+  a.trans = trans; a.scores = scores; a.anchors = anchors; a.boxes = boxes; a.gt = gt; a.droi = droi_or_null;
+  a.pos_input_idx = pos_input_idx; a.pos_target_idx = pos_target_idx; a.neg_input_idx = neg_input_idx;
+  a.num_pos = num_pos; a.num_neg = num_neg; a.h = h; a.w = w_px; a.k = k;
+  a.w_mid_obj = w_mid_obj; a.w_mid_box = w_mid_box; a.decay = decay; a.dheads = dheads;
+  KCHK(launch_rpn_dheads(a, s));
+  OP_EPILOGUE();
+}
+int dc_debug_rpn_heads_bwd(dc_ctx* ctx, const float* dheads, const float* heads_w, const float* hidden, int P, int K6, int R,
+                           float* dhidden) {
+  OP_PROLOGUE();
+  if (!dheads || !heads_w || !hidden || !dhidden || P < 1 || K6 < 1 || R < 1 || K6 > 12288)
+    return ctx->fail(DC_E_INVALID, "dc_debug_rpn_heads_bwd: bad argument");
+  KCHK(launch_rpn_heads_bwd(dheads, heads_w, hidden, P, K6, R, dhidden, s));
+  OP_EPILOGUE();
+}
+int dc_debug_rpn_grad_kept(dc_ctx* ctx, float* feat_rpn, int pixels, float* ms) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_rpn_grad_kept";
+  if (!ms) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (ctx->rpn_dfeat == nullptr) return ctx->fail(DC_E_STATE, "%s: no RPN backward has completed", who);
+  if (feat_rpn != nullptr) {
+    if (pixels != ctx->rpn_dfeat_pixels) return ctx->fail(DC_E_INVALID, "%s: the kept map has %d pixels (got %d)", who, ctx->rpn_dfeat_pixels, pixels);
+    HIPCHK(hipMemcpyAsync(feat_rpn, ctx->rpn_dfeat, (size_t)pixels * 512 * 4, hipMemcpyDeviceToDevice, s));
+  }
+  memcpy(ms, ctx->rpn_grad_ms, 16);
+  OP_EPILOGUE();
+}
+
+// ---- test hook of the convolution backward (densecap_debug_rpn.h) ------------------------------------------------------------------
+int dc_debug_conv3x3_wgrad(dc_ctx* ctx, const float* x, const float* dy, int h, int w_px, int Cin, int Cout, int slices, float* dw) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_conv3x3_wgrad";
+  if (!x || !dy || !dw || slices < 0 || slices > 64) return ctx->fail(DC_E_INVALID, "%s: bad argument", who);
+  DCCHK(check_conv3x3_grad_shape(ctx, h, w_px, Cin, Cout, false, who));
+  const int S = slices > 0 ? slices : conv3x3_wgrad_slices(h * w_px, Cout, Cin);
+  Scratch ws(ctx->scratch, s);
+  HIPCHK(ws.alloc(conv3x3_wgrad_ws_floats(S, Cout, Cin) * 4));
+  KCHK(launch_conv3x3_wgrad(x, dy, h, w_px, Cin, Cout, S, dw, static_cast<float*>(ws.get()), s));
   OP_EPILOGUE();
 }
 

@@ -172,7 +172,8 @@ class DenseCapModel:
         self.fc_dim = w.fc_dim
         check(self.ctx.h, self.lib.dc_load_weights(self.ctx.h, C.byref(w)), "dc_load_weights")
         self.ctx.seq_length = self.seq_length          # ops.lm_sample_n sizes its outputs by it
-        self.ctx.lm_dims = dict(E=int(w.enc_size), Hd=int(w.rnn_size), D=int(w.fc_dim), V=self.vocab_size)   # ops.lm_grad: its buffers
+        self.ctx.lm_dims = dict(E=int(w.enc_size), Hd=int(w.rnn_size), D=int(w.fc_dim), V=self.vocab_size, k=int(w.num_anchors),
+                                R=int(w.rpn_hidden))   # ops.lm_grad, ops.recog_grad, ops.rpn_grad: their buffers
         self._keep = []
         self._push_test_args()
 
@@ -581,10 +582,21 @@ class DenseCapModel:
         the six losses and the counts, the eight recognition tensors (fc6_w, fc6_b, fc7_w, fc7_b, obj_w, obj_b, boxreg_w,
         boxreg_b) and the seven language-model tensors in checkpoint layouts, `feat` (512, h, w) -- RoI pooling's share of the
         feature map's gradient, the reference's layout --, `roi_boxes` (num_pos + num_neg, 4) and `codes` (num_pos, fc_dim), the
-        language model's gradient of the positive codes.  The mid criteria and the sampler / RPN / CNN backward are not part of
-        it; the loaded weights do not change."""
+        language model's gradient of the positive codes.  The CNN backward and an optimiser are not built; the loaded weights do not
+        change."""
         from . import ops
         return ops.loss_gradients(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
+
+    def forward_backward(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, **opts):
+        """DenseCapModel:forward_backward (DenseCapModel.lua:401-474) with the reference's default -finetune_cnn_after -1
+        (dc_forward_backward; docs/SEMANTICS.md, "RPN gradients"): loss_gradients' dict (same arguments, the same numbers) plus
+        the gradients of the RPN's six tensors (rpn_conv_w, rpn_conv_b, rpn_box_w, rpn_box_b, rpn_score_w, rpn_score_b) in
+        checkpoint layouts -- the two mid criteria and box_reg_decay (train_opts.lua:42) through the sampler's backward, the
+        heads and the RPN's convolution.  `feat` (512, h, w) is now the complete grad_cnn_features, `feat_roi` and `feat_rpn`
+        its two shares.  Together: the gradient of all five criteria with respect to all 21 tensors outside the CNN.  The CNN
+        backward and an optimiser are not built; the loaded weights do not change."""
+        from . import ops
+        return ops.forward_backward(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, **opts)
 
     def lm_gradients(self, codes, labels, weight=1.0):
         """The captioning loss of n (fc7 code, caption) pairs and its gradients with respect to the seven language-model tensors

@@ -750,6 +750,190 @@ def colsum(ctx, X, N):
     return o.numpy()
 
 
+# ---- convolution gradients (docs/SEMANTICS.md, "Convolution gradients") ------------------------------------------------------------
+def conv3x3_grad(ctx, x_chw, w_oihw, dy_chw, want=("dw", "db", "dx")):
+    """The backward of nn.SpatialConvolution(Cin,Cout,3,3,1,1,1,1) on one map (dc_op_conv3x3_grad): x (Cin,h,w) the layer's input,
+    w (Cout,Cin,3,3), dy (Cout,h,w) the gradient at its output -> a dict of the outputs named in `want`: dw (Cout,Cin,3,3), db
+    (Cout,), dx (Cin,h,w).  x may be None when dw is not wanted, w when dx is not."""
+    dy = _f32(dy_chw)
+    Cout, h, w = dy.shape
+    Cin = _f32(x_chw).shape[0] if x_chw is not None else _f32(w_oihw).shape[1]
+    xd = ctx.to_device(np.ascontiguousarray(_f32(x_chw).transpose(1, 2, 0))) if x_chw is not None else None
+    wd = ctx.to_device(_f32(w_oihw)) if w_oihw is not None else None
+    dd = ctx.to_device(np.ascontiguousarray(dy.transpose(1, 2, 0)))
+    shapes = {"dw": (Cout, Cin, 3, 3), "db": (Cout,), "dx": (h, w, Cin)}
+    bufs = {k: ctx.empty(shapes[k]) for k in ("dw", "db", "dx") if k in want}
+    ptr = lambda d: None if d is None else d.ptr
+    check(ctx.h, ctx.lib.dc_op_conv3x3_grad(ctx.h, ptr(xd), ptr(wd), dd.ptr, h, w, Cin, Cout, ptr(bufs.get("dw")), ptr(bufs.get("db")),
+                                            ptr(bufs.get("dx"))), "dc_op_conv3x3_grad")
+    out = {k: b.numpy() for k, b in bufs.items()}
+    if "dx" in out:
+        out["dx"] = np.ascontiguousarray(out["dx"].transpose(2, 0, 1))
+    return out
+
+
+def conv3x3_wgrad(ctx, x_chw, dy_chw, slices=0):
+    """The convolution's weight-gradient kernel alone (dc_debug_conv3x3_wgrad): x (Cin,h,w), dy (Cout,h,w) -> dw (Cout,Cin,3,3)
+    with the pixels shared by `slices` slices per tile (0: the production choice)."""
+    x = _f32(x_chw); dy = _f32(dy_chw)
+    (Cin, h, w), Cout = x.shape, dy.shape[0]
+    xd = ctx.to_device(np.ascontiguousarray(x.transpose(1, 2, 0))); dd = ctx.to_device(np.ascontiguousarray(dy.transpose(1, 2, 0)))
+    o = ctx.empty((Cout, Cin, 3, 3))
+    check(ctx.h, ctx.lib.dc_debug_conv3x3_wgrad(ctx.h, xd.ptr, dd.ptr, h, w, Cin, Cout, int(slices), o.ptr), "dc_debug_conv3x3_wgrad")
+    return o.numpy()
+
+
+# ---- RPN gradients (docs/SEMANTICS.md, "RPN gradients") -----------------------------------------------------------------------------
+RPN_GRAD_KEYS = ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "feat")
+BOX_REG_DECAY = 5e-5               # train_opts.lua:42
+
+
+def _rpn_bufs(ctx, k, R, h, w):
+    shapes = {"rpn_conv_w": (R, 512, 3, 3), "rpn_conv_b": (R,), "rpn_box_w": (4 * k, R, 1, 1), "rpn_box_b": (4 * k,),
+              "rpn_score_w": (2 * k, R, 1, 1), "rpn_score_b": (2 * k,), "feat": (h, w, 512)}
+    return {n: ctx.empty(shapes[n]) for n in RPN_GRAD_KEYS}
+
+
+def _rpn_dims(ctx, who):
+    dims = getattr(ctx, "lm_dims", None)
+    if dims is None or "k" not in dims:
+        raise _lib.DenseCapError("ops.%s: the ctx carries no model dimensions (build a DenseCapModel on it first)" % who)
+    return dims["k"], dims["R"]
+
+
+def rpn_grad_kept(ctx, pixels=None):
+    """What the last RPN backward left (dc_debug_rpn_grad_kept): (feat_rpn (512, h*w) or None, the library's event split in ms)."""
+    ms = np.zeros(4, np.float32)
+    f = ctx.empty((pixels, 512)) if pixels else None
+    check(ctx.h, ctx.lib.dc_debug_rpn_grad_kept(ctx.h, f.ptr if f is not None else None, int(pixels or 0),
+                                                ms.ctypes.data_as(_lib.c_float_p)), "dc_debug_rpn_grad_kept")
+    return (f.numpy() if f is not None else None), dict(zip(("dheads", "heads", "conv_wgrad", "conv_dgrad"), (float(v) for v in ms)))
+
+
+def rpn_grad(ctx, feat_chw, pos_input_idx, pos_target_idx, neg_input_idx, gt_boxes, img_h, img_w, droi_boxes=None,
+             box_reg_decay=BOX_REG_DECAY, **opts):
+    """The RPN's gradients on given lists (dc_op_rpn_grad; docs/SEMANTICS.md, "RPN gradients") with the ctx's loaded weights.
+    feat (512,h,w); the three lists as forward_losses dumps them; gt_boxes (G,4); droi_boxes (num_pos + num_neg, 4) or None.
+    Returns a dict: the six RPN tensors' gradients in checkpoint layouts, feat (512,h,w) -- the RPN's share --,
+    mid_objectness_loss, mid_box_reg_loss (float) and masked_mid."""
+    k, R = _rpn_dims(ctx, "rpn_grad")
+    f = _f32(feat_chw)
+    if f.ndim != 3 or f.shape[0] != 512:
+        raise ValueError("feat must be (512, h, w), got %r" % (f.shape,))
+    h, w = f.shape[1:]
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    pi, pt, ni = i32(pos_input_idx), i32(pos_target_idx), i32(neg_input_idx)
+    if len(pi) != len(pt):
+        raise ValueError("rpn_grad: pos_input_idx and pos_target_idx differ in length")
+    g = _f32(gt_boxes).reshape(-1, 4)
+    n = len(pi) + len(ni)
+    o = loss_opts(**opts)
+    fd = ctx.to_device(np.ascontiguousarray(f.transpose(1, 2, 0))); gd = ctx.to_device(g)
+    dev = lambda a: ctx.to_device(a) if len(a) else None
+    pid, ptd, nid = dev(pi), dev(pt), dev(ni)
+    dd = ctx.to_device(_f32(droi_boxes).reshape(n, 4)) if droi_boxes is not None and n > 0 else None
+    ptr = lambda d: None if d is None else d.ptr
+    bufs = _rpn_bufs(ctx, k, R, h, w)
+    pg = _lib.DcRpnGrads(**{name: b.ptr for name, b in bufs.items()})
+    lo, lb, m = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    check(ctx.h, ctx.lib.dc_op_rpn_grad(ctx.h, fd.ptr, h, w, ptr(pid), ptr(ptd), len(pi), ptr(nid), len(ni), gd.ptr, len(g), ptr(dd),
+                                        int(img_h), int(img_w), C.byref(o), float(box_reg_decay), C.byref(pg), C.byref(lo),
+                                        C.byref(lb), C.byref(m)), "dc_op_rpn_grad")
+    out = {name: b.numpy() for name, b in bufs.items()}
+    out["feat"] = np.ascontiguousarray(out["feat"].transpose(2, 0, 1))
+    out.update(mid_objectness_loss=float(lo.value), mid_box_reg_loss=float(lb.value), masked_mid=int(m.value))
+    return out
+
+
+def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY, forced_pos=None, forced_neg=None, dump=False,
+                     on_device=False, **opts):
+    """dc_forward_backward: loss_gradients (same arguments, the same numbers) and the RPN's gradients.  Returns loss_gradients'
+    dict plus the six RPN tensors, `feat_rpn` and `feat_roi` (512,h,w) -- the RPN's and RoI pooling's shares of the feature map's
+    gradient -- with `feat` now their sum, the complete grad_cnn_features."""
+    dims = getattr(ctx, "lm_dims", None)
+    k, R = _rpn_dims(ctx, "forward_backward")
+    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
+    g = _f32(gt_boxes).reshape(-1, 4)
+    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
+    if lab.ndim != 2 or len(lab) != len(g):
+        raise ValueError("forward_backward: gt_labels must be (G, L) with one row per ground-truth box")
+    o = loss_opts(**opts)
+    f, keep = _forced_lists(forced_pos, forced_neg)
+    out = _lib.DcLosses()
+    d = None
+    if dump:
+        lists = [np.zeros(max(int(o.batch_size), 1), np.int32) for _ in range(3)]
+        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
+    if on_device:
+        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
+    else:
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
+    h, w = feature_size(ctx, H, W)
+    cap = max(int(o.batch_size), 1)
+    rbufs = _recog_bufs(ctx, D, h, w, cap)
+    lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
+               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)}
+    lbufs = {n: ctx.empty(lshapes[n]) for n in LM_GRAD_KEYS}
+    pbufs = _rpn_bufs(ctx, k, R, h, w)
+    rg = _lib.DcRecogGrads(**{n: v.ptr for n, v in rbufs.items()})
+    lg = _lib.DcLmGrads(**{n: v.ptr for n, v in lbufs.items()})
+    pg = _lib.DcRpnGrads(**{n: v.ptr for n, v in pbufs.items()})
+    check(ctx.h, ctx.lib.dc_forward_backward(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
+                                             len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
+                                             C.byref(out), C.byref(d) if d is not None else None, C.byref(rg), C.byref(lg),
+                                             float(box_reg_decay), C.byref(pg)), "dc_forward_backward")
+    res = {n: float(getattr(out, n)) for n in LOSS_KEYS}
+    res.update({n: int(getattr(out, n)) for n in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
+    if dump:
+        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
+                   neg_input_idx=lists[2][:out.num_neg].copy())
+    n = out.num_pos + out.num_neg
+    if n == 0:
+        rbufs["roi_boxes"] = ctx.to_device(np.zeros((1, 4), np.float32))
+    res.update(_recog_out(rbufs, n))
+    res.update({n_: b.numpy() for n_, b in lbufs.items()})
+    res["codes"] = res["codes"][:out.num_pos] if out.num_pos > 0 else np.zeros((0, D), np.float32)
+    res["feat_roi"] = res["feat"]
+    res.update({n_: b.numpy() for n_, b in pbufs.items() if n_ != "feat"})
+    res["feat"] = np.ascontiguousarray(pbufs["feat"].numpy().transpose(2, 0, 1))
+    share, _ms = rpn_grad_kept(ctx, h * w)
+    res["feat_rpn"] = np.ascontiguousarray(share.reshape(h, w, 512).transpose(2, 0, 1))
+    return res
+
+
+def rpn_dheads(ctx, trans, scores, anchors, boxes, h, w, k, pos_input_idx, pos_target_idx, neg_input_idx, gt, droi=None,
+               w_mid_obj=0.1, w_mid_box=0.05, decay=0.0):
+    """The gradient at the RPN's head outputs alone (dc_debug_rpn_dheads): the forward's rows (A,4) / (A,2), the lists, gt (G,4),
+    droi (n,4) or None -> dheads (h*w, 6k)."""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    pi, pt, ni = i32(pos_input_idx), i32(pos_target_idx), i32(neg_input_idx)
+    A = k * h * w
+    td, sd, ad, bd = (ctx.to_device(_f32(a).reshape(A, c)) for a, c in ((trans, 4), (scores, 2), (anchors, 4), (boxes, 4)))
+    gd = ctx.to_device(_f32(gt).reshape(-1, 4))
+    dev = lambda a: ctx.to_device(a) if len(a) else None
+    pid, ptd, nid = dev(pi), dev(pt), dev(ni)
+    n = len(pi) + len(ni)
+    dd = ctx.to_device(_f32(droi).reshape(n, 4)) if droi is not None and n > 0 else None
+    ptr = lambda d: None if d is None else d.ptr
+    o = ctx.empty((h * w, 6 * k))
+    check(ctx.h, ctx.lib.dc_debug_rpn_dheads(ctx.h, td.ptr, sd.ptr, ad.ptr, bd.ptr, int(h), int(w), int(k), ptr(pid), ptr(ptd), len(pi),
+                                             ptr(nid), len(ni), gd.ptr, len(_f32(gt).reshape(-1, 4)), ptr(dd), float(w_mid_obj),
+                                             float(w_mid_box), float(decay), o.ptr), "dc_debug_rpn_dheads")
+    return o.numpy()
+
+
+def rpn_heads_bwd(ctx, dheads, heads_w, hidden):
+    """The heads' data gradient with the ReLU mask alone (dc_debug_rpn_heads_bwd): dheads (P,K6), heads_w (K6,R), hidden (P,R)
+    -> dhidden (P,R)."""
+    d = _f32(dheads); W = _f32(heads_w); y = _f32(hidden)
+    (P, K6), R = d.shape, W.shape[1]
+    dd, wd, yd = ctx.to_device(d), ctx.to_device(W), ctx.to_device(y)
+    o = ctx.empty((P, R))
+    check(ctx.h, ctx.lib.dc_debug_rpn_heads_bwd(ctx.h, dd.ptr, wd.ptr, yd.ptr, P, K6, R, o.ptr), "dc_debug_rpn_heads_bwd")
+    return o.numpy()
+
+
 def lstm_cell_bwd_ex(ctx, gates_pre, c, tok=None, xg=None, c_prev=None, dh_a=None, dh_b=None, dc_in=None, alias=False):
     """The LSTM cell backward with every operand of its launcher (dc_debug_lstm_cell_bwd_ex): gates_pre (rows, 4Hd); c (rows, Hd);
     tok (rows,) with xg (xg_rows, 4Hd), c_prev, dh_a, dh_b, dc_in (rows, Hd) or None.  alias=True writes dc_prev into dc_in's own

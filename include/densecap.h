@@ -566,7 +566,8 @@ int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C,
  * feat buffers are indexed by them (the lane's buffers are sized from img_h, img_w and batch_size).  DC_E_INVALID before any
  * launch: n outside 1..1024, num_pos outside 0..n, n > batch_size, a null output, positive rows without target boxes, an image
  * side below 32 px, bad sampler options; DC_E_UNSUPPORTED: h * w > 65536, or scratch above 8 GiB.  The scratch (0.45 GB at the
- * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the two mid criteria, the sampler / RPN / CNN backward, any optimiser. */
+ * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the CNN backward,
+ * any optimiser. */
 typedef struct dc_recog_grads {
   float* fc6_w; float* fc6_b; float* fc7_w; float* fc7_b; float* obj_w; float* obj_b; float* boxreg_w; float* boxreg_b; float* feat; float* roi_boxes;
 } dc_recog_grads;
@@ -584,6 +585,51 @@ int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
                       dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg);
 /* The size of the trunk's output map for an H x W image (four ceil-mode 2x2 pools). */
 int dc_feature_size(int H, int W, int* h, int* w);
+/* The backward of a 3x3 / stride 1 / pad 1 convolution on an HWC map (docs/SEMANTICS.md, "Convolution gradients"), the brick of
+ * the RPN's and a CNN's backward: x (h, w, Cin) the layer's input, w (Cout, Cin, 3, 3) its weights in the checkpoint's OIHW order,
+ * dy (h, w, Cout) the gradient at the convolution's own output (a ReLU's mask is the caller's) -> dw (Cout, Cin, 3, 3),
+ * db (Cout) and dx (h, w, Cin).  Each output may be NULL to skip it; x may be NULL when dw is, w when dx is.  dw is the sum over
+ * the pixels of dy times the shifted x, zero outside the map, on the fp32 MFMA with no im2col buffer; dx is the convolution of dy
+ * with the flipped, transposed weights on the forward's engine.  fp32 whatever dc_set_math_mode says, no float atomics: every
+ * sum has a fixed order and two identical calls give identical bits.  DC_E_INVALID before any launch: Cin % 32, Cout % 32, a
+ * non-positive size, a missing input, no output at all; DC_E_UNSUPPORTED: h * w > 65536, or (dx only) a dy the engine's 32-bit
+ * operand offsets do not take (Cout > 2048).  Device pointers; synchronous. */
+int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float* dy, int h, int w_px, int Cin, int Cout, float* dw,
+                       float* db, float* dx);
+/* RPN gradients (docs/SEMANTICS.md, "RPN gradients"): DEVICE buffers for the gradients of the RPN's six tensors in checkpoint
+ * layouts -- rpn_conv_w (rpn_hidden, 512, 3, 3), rpn_conv_b, rpn_box_w (4k, rpn_hidden), rpn_box_b, rpn_score_w (2k, rpn_hidden),
+ * rpn_score_b -- and feat (h, w, 512), a gradient of the feature map.  All required, all overwritten. */
+typedef struct dc_rpn_grads {
+  float* rpn_conv_w; float* rpn_conv_b; float* rpn_box_w; float* rpn_box_b; float* rpn_score_w; float* rpn_score_b; float* feat;
+} dc_rpn_grads;
+/* The RPN half of the training step on caller-supplied data, as dc_op_recog_grad is the recognition half: the gradient of
+ * mid_objectness + mid_box_reg + 0.5 * box_reg_decay * |transforms|^2 + <droi_boxes, sampled boxes> through the sampler's
+ * backward, the two 1x1 heads and the RPN's 3x3 convolution.  feat_hwc (h, w, 512); pos_input_idx, pos_target_idx (num_pos) and
+ * neg_input_idx (num_neg): rows of the k * h * w RPN outputs and of gt_boxes (G, 4), as dc_forward_losses dumps them;
+ * droi_boxes_or_null (num_pos + num_neg, 4), positives first: all DEVICE.  The sampler's backward COPIES: where several sampled
+ * rows name one input row, the last one wins (negatives after positives).  The RPN's training forward runs through the same calls
+ * as dc_forward_losses; the two mid losses (HOST doubles) and masked_mid (HOST) are what that call reports for these rows.
+ * opts_or_null: batch_size and the two mid weights are read.  out->feat is the RPN's share of the feature map's gradient.
+ * fp32 whatever dc_set_math_mode says, eager on lane 0, no float atomics (two identical calls give identical bits); settings and
+ * weights are left as they were.  h and w are taken on trust, as dc_op_recog_grad takes them.  Synchronous.  DC_E_INVALID before
+ * any launch: an index outside [0, k h w) or [0, G), num_pos + num_neg > 1024, a negative or non-finite box_reg_decay, a null
+ * output, G outside 1..512, a ground-truth box that is not finite with w, h > 0, an image side below 32 px;
+ * DC_E_UNSUPPORTED: h * w > 65536, or an rpn_hidden the engine's conv descriptor does not take (not a multiple of 32, above 2048). */
+int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32_t* pos_input_idx, const int32_t* pos_target_idx,
+                   int num_pos, const int32_t* neg_input_idx, int num_neg, const float* gt_boxes, int G,
+                   const float* droi_boxes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null, float box_reg_decay,
+                   const dc_rpn_grads* out, double* mid_objectness_loss, double* mid_box_reg_loss, int32_t* masked_mid);
+/* DenseCapModel:forward_backward with the reference's default -finetune_cnn_after -1: dc_loss_gradients (same arguments; out, rg
+ * and lg are that call's bits), then dc_op_rpn_grad's backward on what that call left -- lane 0's feature map and RPN hidden map,
+ * the RPN rows, the sampler's lists and rg->roi_boxes as droi_boxes.  pg: the six RPN tensors and feat (h, w, 512), the TOTAL
+ * grad_cnn_features = rg->feat + the RPN's share, one fp32 add per element (LocalizationLayer.lua:550,581,601); rg->feat keeps RoI
+ * pooling's share.  box_reg_decay: train_opts.lua's -box_reg_decay (5e-5 there).  With no sampled row the RPN gradients are the
+ * decay term's alone.  Together the three structs hold the gradient of all five criteria and the decay with respect to all 21
+ * tensors outside the CNN.  Not here: the CNN's backward, any optimiser.  Synchronous. */
+int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                        const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                        dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
+                        const dc_rpn_grads* pg);
 /* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
  * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */

@@ -121,6 +121,7 @@ function Model.fromCheckpoint(ref, gpu)
   self.vocab_size, self.seq_length, self.fc_dim = lm.vocab_size, lm.seq_length, fcs[2].weight:size(1)
   self.enc_size, self.rnn_size = lm.input_encoding_size, lm.rnn_size
   self.num_anchors = make_anchors.anchors:size(2)
+  self.rpn_hidden = rconv.nOutputPlane
   self.idx_to_token = lm.idx_to_token
   -- keep the reference's field layout for callers that reach into it
   -- `model.nets.language_model.beam_size = n` (LanguageModel.lua:129-131) keeps working: the assignment reaches the library
@@ -301,8 +302,8 @@ end
 -- of the RPN (dc_loss_gradients; docs/SEMANTICS.md, "Recognition-net gradients").  data and opts as forward_losses.  Returns
 -- forward_backward's loss keys, num_pos and num_neg, and `grads`: FloatTensors in the checkpoint's layouts for fc6_w, fc6_b, fc7_w,
 -- fc7_b, obj_w, obj_b, boxreg_w, boxreg_b and the seven language-model tensors, feat (512, h, w) -- RoI pooling's share of
--- grad_cnn_features --, roi_boxes (num_pos + num_neg, 4) and codes (num_pos, fc_dim).  The mid criteria and the sampler / RPN / CNN
--- backward are not part of it.
+-- grad_cnn_features --, roi_boxes (num_pos + num_neg, 4) and codes (num_pos, fc_dim).  The CNN backward and an optimiser are not
+-- built.
 function Model:loss_gradients(data, opts)
   opts = opts or {}
   local input = data.image
@@ -362,6 +363,90 @@ function Model:loss_gradients(data, opts)
   hip.check(self.ctx, rc, 'dc_loss_gradients')
   local n = out.num_pos + out.num_neg
   grads.feat = grads.feat:permute(3, 1, 2):contiguous()                       -- (512, h, w), the reference's layout
+  grads.roi_boxes = n > 0 and grads.roi_boxes[{{1, n}}]:clone() or torch.FloatTensor()
+  grads.codes = out.num_pos > 0 and grads.codes[{{1, out.num_pos}}]:clone() or torch.FloatTensor()
+  return {
+    mid_objectness_loss = out.mid_objectness_loss, mid_box_reg_loss = out.mid_box_reg_loss,
+    end_objectness_loss = out.end_objectness_loss, end_box_reg_loss = out.end_box_reg_loss,
+    captioning_loss = out.captioning_loss, total_loss = out.total_loss,
+    num_pos = out.num_pos, num_neg = out.num_neg, grads = grads,
+  }
+end
+
+-- DenseCapModel:forward_backward (DenseCapModel.lua:401-474) with the reference's default -finetune_cnn_after -1
+-- (dc_forward_backward; docs/SEMANTICS.md, "RPN gradients").  data and opts as forward_losses, plus opts.box_reg_decay
+-- (train_opts.lua:42: 5e-5).  Returns the reference's loss keys, num_pos and num_neg, and `grads`: loss_gradients' tensors plus
+-- rpn_conv_w, rpn_conv_b, rpn_box_w, rpn_box_b, rpn_score_w, rpn_score_b in the checkpoint's layouts -- all 21 tensors outside the
+-- CNN --, feat (512, h, w), now the complete grad_cnn_features, and feat_roi, RoI pooling's share of it.  The CNN backward and an
+-- optimiser are not built; the loaded weights do not change.
+function Model:forward_backward(data, opts)
+  opts = opts or {}
+  local input = data.image
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local gb, gl = data.gt_boxes, data.gt_labels
+  if gb:dim() == 3 then gb = gb[1] end
+  if gl:dim() == 3 then gl = gl[1] end
+  gb, gl = gb:float():contiguous(), gl:int():contiguous()
+  assert(gb:dim() == 2 and gb:size(2) == 4 and gl:dim() == 2 and gl:size(1) == gb:size(1), 'gt_boxes (G,4), gt_labels (G,L)')
+  local function get(k, d) if opts[k] == nil then return d end return opts[k] end
+  local o = ffi.new('dc_loss_opts')
+  o.batch_size = get('sampler_batch_size', 256)
+  o.high_thresh, o.low_thresh = get('sampler_high_thresh', 0.7), get('sampler_low_thresh', 0.3)
+  o.remove_outbounds = get('train_remove_outbounds_boxes', 1)
+  o.mid_box_reg_weight, o.mid_objectness_weight = get('mid_box_reg_weight', 0.05), get('mid_objectness_weight', 0.1)
+  o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
+  o.captioning_weight = get('captioning_weight', 1.0)
+  o.seed = get('loss_seed', 0)
+  local decay = get('box_reg_decay', 5e-5)
+  local hw = ffi.new('int[2]')
+  hip.check(self.ctx, C.dc_feature_size(img:size(3), img:size(4), hw, hw + 1), 'dc_feature_size')
+  local h, w, cap = hw[0], hw[1], o.batch_size
+  local E, Hd, D, V = self.enc_size, self.rnn_size, self.fc_dim, self.vocab_size
+  local k, R = self.num_anchors, self.rpn_hidden
+  local rnames = {'fc6_w', 'fc6_b', 'fc7_w', 'fc7_b', 'obj_w', 'obj_b', 'boxreg_w', 'boxreg_b', 'feat', 'roi_boxes'}
+  local lnames = {'lm_enc_w', 'lm_enc_b', 'lm_emb', 'lstm_w', 'lstm_b', 'lm_out_w', 'lm_out_b', 'codes'}
+  local pnames = {'rpn_conv_w', 'rpn_conv_b', 'rpn_box_w', 'rpn_box_b', 'rpn_score_w', 'rpn_score_b', 'feat'}
+  local shapes = {fc6_w = {D, 512 * 49}, fc6_b = {D}, fc7_w = {D, D}, fc7_b = {D}, obj_w = {1, D}, obj_b = {1}, boxreg_w = {4, D},
+                  boxreg_b = {4}, feat = {h, w, 512}, roi_boxes = {cap, 4},
+                  lm_enc_w = {E, D}, lm_enc_b = {E}, lm_emb = {V + 2, E}, lstm_w = {E + Hd, 4 * Hd}, lstm_b = {4 * Hd},
+                  lm_out_w = {V + 1, Hd}, lm_out_b = {V + 1}, codes = {cap, D},
+                  rpn_conv_w = {R, 512, 3, 3}, rpn_conv_b = {R}, rpn_box_w = {4 * k, R, 1, 1}, rpn_box_b = {4 * k},
+                  rpn_score_w = {2 * k, R, 1, 1}, rpn_score_b = {2 * k}}
+  local rg, lg, pg = ffi.new('dc_recog_grads'), ffi.new('dc_lm_grads'), ffi.new('dc_rpn_grads')
+  local grads, dev = {}, {}
+  local function release() for _, p in ipairs(dev) do C.dc_free(self.ctx, p) end end
+  local function alloc(bytes)
+    local pp = ffi.new('void*[1]')
+    local rc = C.dc_malloc(self.ctx, pp, bytes)
+    if rc ~= 0 then release(); hip.check(self.ctx, rc, 'dc_malloc') end
+    dev[#dev + 1] = pp[0]
+    return pp[0]
+  end
+  local host = {}                                   -- {struct, field, tensor}: what comes back
+  local function bind(struct, names, rename)
+    for _, name in ipairs(names) do
+      local t = torch.FloatTensor(unpack(shapes[name]))
+      struct[name] = ffi.cast('float*', alloc(t:nElement() * 4))
+      local key = rename and rename[name] or name
+      grads[key] = t
+      host[#host + 1] = {struct, name, t}
+    end
+  end
+  bind(rg, rnames, {feat = 'feat_roi'})
+  bind(lg, lnames)
+  bind(pg, pnames)
+  local out = ffi.new('dc_losses')
+  local rc = C.dc_forward_backward(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl), gb:size(1),
+                                   gl:size(2), o, nil, out, nil, rg, lg, decay, pg)
+  for _, e in ipairs(host) do
+    if rc == 0 then rc = C.dc_memcpy_d2h(self.ctx, torch.data(e[3]), e[1][e[2]], e[3]:nElement() * 4) end
+  end
+  release()
+  hip.check(self.ctx, rc, 'dc_forward_backward')
+  local n = out.num_pos + out.num_neg
+  grads.feat = grads.feat:permute(3, 1, 2):contiguous()                       -- (512, h, w), the reference's layout
+  grads.feat_roi = grads.feat_roi:permute(3, 1, 2):contiguous()
   grads.roi_boxes = n > 0 and grads.roi_boxes[{{1, n}}]:clone() or torch.FloatTensor()
   grads.codes = out.num_pos > 0 and grads.codes[{{1, out.num_pos}}]:clone() or torch.FloatTensor()
   return {

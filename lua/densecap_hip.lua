@@ -95,6 +95,19 @@ int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
                       const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                       dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg);
 int dc_feature_size(int H, int W, int* h, int* w);
+int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float* dy, int h, int w_px, int Cin, int Cout, float* dw,
+                       float* db, float* dx);
+typedef struct dc_rpn_grads {
+  float* rpn_conv_w; float* rpn_conv_b; float* rpn_box_w; float* rpn_box_b; float* rpn_score_w; float* rpn_score_b; float* feat;
+} dc_rpn_grads;
+int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32_t* pos_input_idx, const int32_t* pos_target_idx,
+                   int num_pos, const int32_t* neg_input_idx, int num_neg, const float* gt_boxes, int G,
+                   const float* droi_boxes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null, float box_reg_decay,
+                   const dc_rpn_grads* out, double* mid_objectness_loss, double* mid_box_reg_loss, int32_t* masked_mid);
+int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                        const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                        dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
+                        const dc_rpn_grads* pg);
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
                       const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
                       int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
