@@ -465,7 +465,8 @@ hipError_t launch_rpn_score_rows(const float* heads, int h, int w, int k, float*
 // scores (A,2), anchors / trans (A,4) of the RPN; the sampler's lists; gt (G,4); roi_boxes / final_trans (n,4) and obj (n) of the
 // n = num_pos + num_neg <= 1024 sampled rows, positives first; rowlik (num_pos) the rows' caption log-likelihoods; L the label
 // width.  out: six doubles (mid objectness, mid box, end objectness, end box, captioning, total); out_masked: rows masked in the
-// two box terms.
+// two box terms.  A term is computed only if its input is non-null -- mid objectness: scores; mid box: anchors; end objectness:
+// obj; end box: roi_boxes; captioning: rowlik -- and is 0.0, with no masked row, otherwise; it reads its own inputs only.
 struct LossTermArgs {
   const float *scores, *anchors, *trans, *gt, *roi_boxes, *final_trans, *obj;
   const int32_t *pos_input_idx, *pos_target_idx, *neg_input_idx;

@@ -164,6 +164,22 @@ struct Lane {
 
 struct ProfEvt { hipEvent_t a, b; double flops; };
 
+// The record of one training forward: train_forward fills it; the backward stages, the entry points' results and dc_debug_fetch
+// "loss_*" read it.  The device rows live in ctx->loss_ws; feat, rpn_hidden and the n = np + nn sampled rows' activations in lane
+// 0.  valid: cleared when a forward stage starts, set when it has completed.
+struct TrainFwd {
+  bool valid = false;
+  float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr, *gt = nullptr;   // (A,4) x 3, (A,2), (G,4)
+  int32_t *pos_idx = nullptr, *pos_tgt = nullptr, *neg_idx = nullptr;                               // the sampler's lists
+  double* rowlik = nullptr;                                                                         // (np)
+  std::vector<int32_t> lists = std::vector<int32_t>(3 * 1024);      // host copies: pos_idx at 0, pos_tgt at 1024, neg_idx at 2048
+  int32_t counts[8] = {0}, masked[2] = {0, 0};                      // the sampler's eight counts; loss_terms' two and its
+  double terms[6] = {0};                                            // six doubles
+  int A = 0, G = 0, np = 0, nn = 0, h = 0, w = 0, H = 0, W = 0;
+  dc_loss_opts opts{};                                              // resolved (the defaults for a null pointer)
+  float stage_ms[5] = {0, 0, 0, 0, 0};
+};
+
 }  // namespace
 
 struct dc_ctx {
@@ -242,14 +258,10 @@ struct dc_ctx {
   KeptBuf pre_taps{scratch};        // ... and the tap tables of the sizes in pre_key, kept while the sizes repeat (webcam frames)
   std::vector<char> pre_taps_host;  // (the host copy outlives its asynchronous upload)
   int pre_key[4] = {0, 0, 0, 0};    // H0, W0, oh, ow the tables were made for
-  // dc_forward_losses: its scratch (grow only) and what the last call left there for dc_debug_fetch "loss_*"
+  // the training forward: its scratch (grow only) and the record of the last one
   KeptBuf loss_ws{scratch};
-  struct LossKeep {
-    const float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr;
-    const double* rowlik = nullptr;
-    int A = 0, n = 0, num_pos = 0;
-    float stage_ms[5] = {0, 0, 0, 0, 0};
-  } loss_keep;
+  TrainFwd train;
+  int32_t* row_ramp = nullptr;           // 0, 1 .. 1023 on the device, made on first need (dc_op_recog_grad's pos_target_idx)
   // MFMA profile
   bool prof = false;
   std::vector<ProfEvt> prof_pending;
@@ -2401,9 +2413,10 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
   if (ctx->lanes.empty() || !ctx->lanes[0]->arena.p) return ctx->fail(DC_E_STATE, "no forward has run yet");
   Lane& L = *ctx->lanes[0];
   const int P = L.P;
-  if (strncmp(name, "loss_", 5) == 0) {             // what the last dc_forward_losses left (include/densecap.h, at that function)
-    const dc_ctx::LossKeep& k = ctx->loss_keep;
-    if (k.boxes == nullptr) return ctx->fail(DC_E_STATE, "dc_debug_fetch: %s: no dc_forward_losses call has got that far", name);
+  if (strncmp(name, "loss_", 5) == 0) {             // the record of the last training forward (include/densecap.h, at dc_forward_losses)
+    const TrainFwd& k = ctx->train;
+    const int64_t kn = k.np + k.nn;
+    if (!k.valid) return ctx->fail(DC_E_STATE, "dc_debug_fetch: %s: no dc_forward_losses call has got that far", name);
     if (strcmp(name, "loss_stage_ms") == 0) {
       if (capacity_bytes < 20) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
       memcpy(host_buf, k.stage_ms, 20);
@@ -2412,9 +2425,9 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     const struct { const char* n; const void* p; int64_t elems; int esize; } kept[] = {
         {"loss_rpn_boxes", k.boxes, (int64_t)k.A * 4, 4},     {"loss_rpn_anchors", k.anchors, (int64_t)k.A * 4, 4},
         {"loss_rpn_trans", k.trans, (int64_t)k.A * 4, 4},     {"loss_rpn_scores", k.scores, (int64_t)k.A * 2, 4},
-        {"loss_obj", L.obj, (int64_t)k.n, 4},                 {"loss_final_trans", L.final_trans, (int64_t)k.n * 4, 4},
-        {"loss_roi_boxes", L.roi_boxes, (int64_t)k.n * 4, 4}, {"loss_codes", L.codes, (int64_t)k.n * ctx->D, 4},
-        {"loss_rowlik", k.rowlik, (int64_t)k.num_pos, 8}};
+        {"loss_obj", L.obj, kn, 4},                           {"loss_final_trans", L.final_trans, kn * 4, 4},
+        {"loss_roi_boxes", L.roi_boxes, kn * 4, 4},           {"loss_codes", L.codes, kn * ctx->D, 4},
+        {"loss_rowlik", k.rowlik, (int64_t)k.np, 8}};
     for (const auto& e : kept) {
       if (strcmp(name, e.n) != 0) continue;
       const int64_t bytes = e.elems * e.esize;
@@ -2790,6 +2803,24 @@ static int check_sampler_opts(dc_ctx* ctx, const dc_loss_opts* o, const char* wh
     return ctx->fail(DC_E_INVALID, "%s: remove_outbounds must be 0 or 1 (got %d)", who, o->remove_outbounds);
   return DC_OK;
 }
+// The sampler on s with a call's settings and forced lists (checked by the caller); a: its rows, outputs and scratch; fdev: 2048
+// ints of device scratch for the forced lists
+static int enqueue_box_sampler(dc_ctx* ctx, hipStream_t s, BoxSamplerArgs a, int img_h, int img_w, const dc_loss_opts& o,
+                               const dc_sampler_forced* forced, int32_t* fdev) {
+  a.x_max = (float)img_w; a.y_max = (float)img_h; a.bounds = o.remove_outbounds;
+  a.high = o.high_thresh; a.low = o.low_thresh; a.batch = o.batch_size;
+  a.seed_lo = (uint32_t)(o.seed & 0xffffffffull); a.seed_hi = (uint32_t)(o.seed >> 32);
+  if (forced && forced->pos_sample_idx) {
+    if (forced->num_pos > 0) HIPCHK(hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)forced->num_pos * 4, hipMemcpyHostToDevice, s));
+    a.forced_pos = fdev; a.n_forced_pos = forced->num_pos;
+  }
+  if (forced && forced->neg_sample_idx) {
+    if (forced->num_neg > 0) HIPCHK(hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)forced->num_neg * 4, hipMemcpyHostToDevice, s));
+    a.forced_neg = fdev + 1024; a.n_forced_neg = forced->num_neg;
+  }
+  KCHK(launch_box_sampler(a, s));
+  return DC_OK;
+}
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w, const dc_loss_opts* opts,
                       const dc_sampler_forced* forced, int32_t* pos_input_idx, int32_t* pos_target_idx, int32_t* neg_input_idx,
                       int32_t* counts, float* max_iou, int32_t* arg) {
@@ -2807,23 +2838,11 @@ int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, i
   Scratch block(ctx->scratch, s);
   HIPCHK(block.alloc(ws_bytes + forced_bytes));
   char* ws = static_cast<char*>(block.get());
-  int32_t* fdev = reinterpret_cast<int32_t*>(ws + ws_bytes);
   BoxSamplerArgs a{};
   a.boxes = boxes; a.gt = gt; a.A = A; a.G = G;
-  a.x_max = (float)img_w; a.y_max = (float)img_h; a.bounds = opts->remove_outbounds;
-  a.high = opts->high_thresh; a.low = opts->low_thresh; a.batch = opts->batch_size;
-  a.seed_lo = (uint32_t)(opts->seed & 0xffffffffull); a.seed_hi = (uint32_t)(opts->seed >> 32);
-  if (forced && forced->pos_sample_idx) {
-    if (np > 0) HIPCHK(hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    a.forced_pos = fdev; a.n_forced_pos = np;
-  }
-  if (forced && forced->neg_sample_idx) {
-    if (nn > 0) HIPCHK(hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)nn * 4, hipMemcpyHostToDevice, s));
-    a.forced_neg = fdev + 1024; a.n_forced_neg = nn;
-  }
   a.pos_input_idx = pos_input_idx; a.pos_target_idx = pos_target_idx; a.neg_input_idx = neg_input_idx; a.counts = counts;
   a.max_iou_user = max_iou; a.arg_user = arg; a.ws = ws;
-  KCHK(launch_box_sampler(a, s));
+  DCCHK(enqueue_box_sampler(ctx, s, a, img_h, img_w, *opts, forced, reinterpret_cast<int32_t*>(ws + ws_bytes)));
   int32_t c[8] = {0};
   HIPCHK(hipMemcpyAsync(c, counts, sizeof c, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -3005,124 +3024,168 @@ struct LossCfgGuard {
 };
 static const dc_loss_opts kLossDefaults = {256, 0.7f, 0.3f, 1, 0.05f, 0.1f, 0.1f, 0.1f, 1.0f, 0};
 
-// The training forward of one image and its five criteria: LocalizationLayer:_forward_train (LocalizationLayer.lua:383-527) and
-// DenseCapModel:forward_backward's forward half (DenseCapModel.lua:401-459).  Launch list (lane 0's stream, eager):
-//   image copy; the trunk (enqueue_trunk); RPN conv; heads; rpn_decode with clip = 0 (boxes, anchors, trans); rpn_score_rows
-//   memset + box_sampler_match + box_sampler_draw; the counts and lists come back (the host sizes the rest by them)
-//   bilinear RoI pooling of the n = num_pos + num_neg sampled boxes (gathered by the kernel); fc6; fc7; recog_heads
-//   lm_score_paired on the num_pos positive rows (its own scratch; the row sums come back and go up again: num_pos doubles)
-//   loss_terms (one workgroup); six doubles and two counts come back
-int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
-                      const int32_t* gt_labels, int G, int Lw, const dc_loss_opts* opts, const dc_sampler_forced* forced,
-                      dc_losses* out, const dc_loss_dump* dump) {
-  const char* who = "dc_forward_losses";
-  if (!ctx) return DC_E_INVALID;
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
-  if (!img_chw || !gt_boxes || !gt_labels || !out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
-  if (H < 32 || W < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
-  DCCHK(check_image_size(ctx, H, W, who));
-  if (G < 1 || G > 512) return ctx->fail(DC_E_UNSUPPORTED, "%s: G must be in 1..512 (got %d)", who, G);
-  DCCHK(check_queries(ctx, gt_labels, G, Lw, who));
+namespace {
+// ---- the training path: dc_forward_losses, dc_loss_gradients and dc_forward_backward (at the end of the RPN gradients' section)
+// are one, two and three of the stages train_forward, train_recog_lm_backward and train_rpn_backward, in that order, on one
+// TrainFwd record; dc_op_recog_grad and dc_op_rpn_grad run the same pieces on a caller's rows.
+struct TrainCall {             // the arguments the three entry points share, as the entry point got them (o: resolved)
+  const char* who; const float* img; int H, W, on_device; const float* gt_boxes; const int32_t* gt_labels; int G, Lw;
+  dc_loss_opts o; const dc_sampler_forced* forced; dc_losses* out; const dc_loss_dump* dump;
+};
+void feature_size(int H, int W, int* h, int* w) {
+  for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
+    if (kVgg[i].pool_after) { H = (H + 1) / 2; W = (W + 1) / 2; }
+  *h = H; *w = W;
+}
+int check_gt_boxes(dc_ctx* ctx, const char* who, const float* host_boxes, int G) {
   for (int j = 0; j < G; ++j) {
-    const float* b = gt_boxes + (size_t)j * 4;
+    const float* b = host_boxes + (size_t)j * 4;
     if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3])) || !(b[2] > 0.f) || !(b[3] > 0.f))
       return ctx->fail(DC_E_INVALID, "%s: ground-truth box %d (%g, %g, %g, %g) is not finite with w > 0 and h > 0", who, j, (double)b[0],
                        (double)b[1], (double)b[2], (double)b[3]);
   }
-  const dc_loss_opts o = opts ? *opts : kLossDefaults;
-  DCCHK(check_sampler_opts(ctx, &o, who));
-  const int batch = o.batch_size;
-  const int fnp = forced && forced->pos_sample_idx ? forced->num_pos : 0, fnn = forced && forced->neg_sample_idx ? forced->num_neg : 0;
-  if (fnp < 0 || fnp > batch || fnn < 0 || fnn > batch || fnp + fnn > batch)
-    return ctx->fail(DC_E_INVALID, "%s: forced lists hold 0..batch_size entries, batch_size in all (got %d, %d)", who, fnp, fnn);
+  return DC_OK;
+}
+// lists (host): pos_input_idx at 0, pos_target_idx at 1024, neg_input_idx at 2048; the kernels trust them.  code: DC_E_HIP for
+// the sampler's own output, DC_E_INVALID for a caller's lists.
+int check_sampled_lists(dc_ctx* ctx, const char* who, int code, const int32_t* lists, int np, int nn, int A, int G) {
+  for (int r = 0; r < np + nn; ++r) {
+    const int i = r < np ? lists[r] : lists[2048 + r - np], j = r < np ? lists[1024 + r] : 0;
+    if (i < 0 || i >= A || j < 0 || j >= G)
+      return ctx->fail(code, "%s: sampled row %d names input %d of %d, ground-truth box %d of %d", who, r, i, A, j, G);
+  }
+  return DC_OK;
+}
+int check_dump(dc_ctx* ctx, const char* who, const dc_loss_dump* dump) {
   if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
     return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
-  HIPCHK(hipSetDevice(ctx->device));
-  drain_lanes(ctx);
-  LossCfgGuard guard(ctx->cfg);
-  Lane& L = lane0(ctx);
-  DCCHK(lane_prepare(ctx, L, H, W, batch, 1));
+  return DC_OK;
+}
+int check_forward_args(dc_ctx* ctx, const TrainCall& c) {
+  const char* who = c.who;
+  if (!c.img || !c.gt_boxes || !c.gt_labels || !c.out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (c.H < 32 || c.W < 32) return ctx->fail(DC_E_INVALID, "%s: image side below 32 px", who);
+  DCCHK(check_image_size(ctx, c.H, c.W, who));
+  if (c.G < 1 || c.G > 512) return ctx->fail(DC_E_UNSUPPORTED, "%s: G must be in 1..512 (got %d)", who, c.G);
+  DCCHK(check_queries(ctx, c.gt_labels, c.G, c.Lw, who));
+  DCCHK(check_gt_boxes(ctx, who, c.gt_boxes, c.G));
+  DCCHK(check_sampler_opts(ctx, &c.o, who));
+  const int batch = c.o.batch_size;
+  const int fnp = c.forced && c.forced->pos_sample_idx ? c.forced->num_pos : 0, fnn = c.forced && c.forced->neg_sample_idx ? c.forced->num_neg : 0;
+  if (fnp < 0 || fnp > batch || fnn < 0 || fnn > batch || fnp + fnn > batch)
+    return ctx->fail(DC_E_INVALID, "%s: forced lists hold 0..batch_size entries, batch_size in all (got %d, %d)", who, fnp, fnn);
+  return check_dump(ctx, who, c.dump);
+}
+// memset on s of every {pointer, bytes} entry (the gradients of a call with no sampled or no positive row)
+int zero_fill(dc_ctx* ctx, hipStream_t s, std::initializer_list<std::pair<void*, size_t>> tab) {
+  for (const auto& e : tab)
+    if (e.second > 0) HIPCHK(hipMemsetAsync(e.first, 0, e.second, s));
+  return DC_OK;
+}
+// The RPN's training forward (LocalizationLayer.lua:405-412) from a feature map into the given buffers: all A = k * h * w rows,
+// not clipped, raw scores.  Launch list: RPN conv; heads; rpn_decode with clip = 0 (boxes, anchors, trans); rpn_score_rows.
+int rpn_train_forward(dc_ctx* ctx, Lane& L, const float* feat, int h, int w, int img_h, int img_w, float* hidden, float* heads,
+                      float* boxes, float* anchors, float* trans, float* scores) {
   hipStream_t s = L.stream;
-  const int A = L.A, k = ctx->k, D = ctx->D;
-  // ---- scratch: what the lane does not hold (kept for dc_debug_fetch "loss_*" until the next call) ----
-  float *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr, *gt_dev = nullptr;
+  const int k = ctx->k;
+  DCCHK(conv3x3(ctx, s, feat, ctx->rpn_w, ctx->rpn_b, hidden, 1, h, w, 512, ctx->R, 1, lane_ws(L)));
+  DCCHK(linear(ctx, s, hidden, ctx->heads_w, ctx->heads_b, heads, h * w, 6 * k, ctx->R, 0, Ws(), h * w));
+  KCHK(launch_rpn_decode(heads, 1, h, w, k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], img_h, img_w, boxes, anchors,
+                         trans, nullptr, nullptr, nullptr, 0, s));
+  KCHK(launch_rpn_score_rows(heads, h, w, k, scores, s));
+  return DC_OK;
+}
+// fc6, fc7 and the recognition heads on the n pooled rows of L.roi_feats (their boxes in L.roi_boxes), planned for `batch` rows
+int recog_rows_forward(dc_ctx* ctx, Lane& L, int n, int batch) {
+  hipStream_t s = L.stream;
+  const int D = ctx->D;
+  DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, 49 * 512, 1, lane_ws(L), batch));
+  DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), batch));
+  KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
+  return DC_OK;
+}
+// loss_terms on a record's rows and lists and the sampled rows' recognition outputs; what is null has its term skipped
+// (LossTermArgs).  Its six doubles and two counts go through terms / masked (device) into the record.
+int enqueue_loss_terms(dc_ctx* ctx, hipStream_t s, TrainFwd& f, const float* roi_boxes, const float* final_trans, const float* obj, int Lw,
+                       double* terms, int32_t* masked) {
+  const dc_loss_opts& o = f.opts;
+  LossTermArgs t{};
+  t.scores = f.scores; t.anchors = f.anchors; t.trans = f.trans; t.gt = f.gt; t.roi_boxes = roi_boxes; t.final_trans = final_trans;
+  t.obj = obj; t.pos_input_idx = f.pos_idx; t.pos_target_idx = f.pos_tgt; t.neg_input_idx = f.neg_idx; t.rowlik = f.rowlik;
+  t.num_pos = f.np; t.num_neg = f.nn; t.L = Lw;
+  t.w_mid_box = o.mid_box_reg_weight; t.w_mid_obj = o.mid_objectness_weight; t.w_end_box = o.end_box_reg_weight;
+  t.w_end_obj = o.end_objectness_weight; t.w_cap = o.captioning_weight;
+  t.out = terms; t.out_masked = masked;
+  KCHK(launch_loss_terms(t, s));
+  HIPCHK(hipMemcpyAsync(f.terms, terms, sizeof f.terms, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(f.masked, masked, sizeof f.masked, hipMemcpyDeviceToHost, s));
+  return DC_OK;
+}
+
+// The training forward of one image and its five criteria: LocalizationLayer:_forward_train (LocalizationLayer.lua:383-527) and
+// DenseCapModel:forward_backward's forward half (DenseCapModel.lua:401-459).  The caller has checked c, holds LossCfgGuard and
+// has prepared lane 0 for (H, W, batch_size).  Launch list (lane 0's stream, eager):
+//   image copy; the trunk (enqueue_trunk); rpn_train_forward
+//   memset + box_sampler_match + box_sampler_draw; the counts and lists come back (the host sizes the rest by them)
+//   bilinear RoI pooling of the n = num_pos + num_neg sampled boxes (gathered by the kernel); recog_rows_forward
+//   lm_score_paired on the num_pos positive rows (its own scratch; the row sums come back and go up again: num_pos doubles)
+//   loss_terms (one workgroup); six doubles and two counts come back
+int train_forward(dc_ctx* ctx, const TrainCall& c, Lane& L, TrainFwd& f) {
+  const char* who = c.who;
+  const dc_loss_opts& o = c.o;
+  const int H = c.H, W = c.W, G = c.G, Lw = c.Lw, batch = o.batch_size, A = L.A;
+  hipStream_t s = L.stream;
+  f.valid = false;
+  // ---- scratch: what the lane does not hold (kept for the later stages and dc_debug_fetch "loss_*" until the next call) ----
   void* samp_ws = nullptr;
-  int32_t *fdev = nullptr, *pos_idx = nullptr, *pos_tgt = nullptr, *neg_idx = nullptr, *counts = nullptr, *sel = nullptr, *masked = nullptr;
-  double *rowlik = nullptr, *terms = nullptr;
+  int32_t *fdev = nullptr, *counts = nullptr, *sel = nullptr, *masked = nullptr;
+  double* terms = nullptr;
   const std::vector<Carve> cv = {
-      {(void**)&boxes, (size_t)A * 16},   {(void**)&anchors, (size_t)A * 16}, {(void**)&trans, (size_t)A * 16},
-      {(void**)&scores, (size_t)A * 8},   {(void**)&gt_dev, (size_t)G * 16},  {(void**)&samp_ws, box_sampler_ws_bytes(A, G)},
-      {(void**)&fdev, 2048 * 4},          {(void**)&pos_idx, 1024 * 4},       {(void**)&pos_tgt, 1024 * 4},
-      {(void**)&neg_idx, 1024 * 4},       {(void**)&counts, 8 * 4},           {(void**)&sel, 1024 * 4},
-      {(void**)&rowlik, 1024 * 8},        {(void**)&terms, 6 * 8},            {(void**)&masked, 2 * 4},
+      {(void**)&f.boxes, (size_t)A * 16},  {(void**)&f.anchors, (size_t)A * 16}, {(void**)&f.trans, (size_t)A * 16},
+      {(void**)&f.scores, (size_t)A * 8},  {(void**)&f.gt, (size_t)G * 16},      {(void**)&samp_ws, box_sampler_ws_bytes(A, G)},
+      {(void**)&fdev, 2048 * 4},           {(void**)&f.pos_idx, 1024 * 4},       {(void**)&f.pos_tgt, 1024 * 4},
+      {(void**)&f.neg_idx, 1024 * 4},      {(void**)&counts, 8 * 4},             {(void**)&sel, 1024 * 4},
+      {(void**)&f.rowlik, 1024 * 8},       {(void**)&terms, 6 * 8},              {(void**)&masked, 2 * 4},
   };
-  ctx->loss_keep = dc_ctx::LossKeep();
   HIPCHK(ctx->loss_ws.grow(carve(cv, nullptr), s));
   carve(cv, ctx->loss_ws.get());
-  int32_t c8[8] = {0};
-  std::vector<int32_t> lists(3 * 1024);
+  f.A = A; f.G = G; f.H = H; f.W = W; f.opts = o;
+  int32_t* const lists = f.lists.data();
   std::vector<double> rl;
-  double terms_h[6] = {0};
-  int32_t masked_h[2] = {0, 0};
-  int np = 0, nn = 0;
   auto body = [&]() -> int {
     HIPCHK(hipEventRecord(L.ev[0], s));
-    HIPCHK(hipMemcpyAsync(L.img, img_chw, (size_t)3 * H * W * 4, img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    int h = 0, w = 0;
-    DCCHK(enqueue_trunk(ctx, L, 1, &h, &w));
+    HIPCHK(hipMemcpyAsync(L.img, c.img, (size_t)3 * H * W * 4, c.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    DCCHK(enqueue_trunk(ctx, L, 1, &f.h, &f.w));
+    const int h = f.h, w = f.w;
     ensure_fault_word(ctx);
-    // ---- RPN in training form (LocalizationLayer.lua:405-412): all A rows, not clipped, raw scores ----
-    DCCHK(conv3x3(ctx, s, L.feat, ctx->rpn_w, ctx->rpn_b, L.rpn_hidden, 1, h, w, 512, ctx->R, 1, lane_ws(L)));
-    DCCHK(linear(ctx, s, L.rpn_hidden, ctx->heads_w, ctx->heads_b, L.heads, h * w, 6 * k, ctx->R, 0, Ws(), h * w));
-    KCHK(launch_rpn_decode(L.heads, 1, h, w, k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], H, W, boxes, anchors, trans,
-                           nullptr, nullptr, nullptr, 0, s));
-    KCHK(launch_rpn_score_rows(L.heads, h, w, k, scores, s));
+    DCCHK(rpn_train_forward(ctx, L, L.feat, h, w, H, W, L.rpn_hidden, L.heads, f.boxes, f.anchors, f.trans, f.scores));
     HIPCHK(hipEventRecord(L.ev[1], s));
     // ---- the sampler ----
-    HIPCHK(hipMemcpyAsync(gt_dev, gt_boxes, (size_t)G * 16, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.gt, c.gt_boxes, (size_t)G * 16, hipMemcpyHostToDevice, s));
     BoxSamplerArgs a{};
-    a.boxes = boxes; a.gt = gt_dev; a.A = A; a.G = G;
-    a.x_max = (float)W; a.y_max = (float)H; a.bounds = o.remove_outbounds;
-    a.high = o.high_thresh; a.low = o.low_thresh; a.batch = batch;
-    a.seed_lo = (uint32_t)(o.seed & 0xffffffffull); a.seed_hi = (uint32_t)(o.seed >> 32);
-    if (forced && forced->pos_sample_idx) {
-      if (fnp > 0) HIPCHK(hipMemcpyAsync(fdev, forced->pos_sample_idx, (size_t)fnp * 4, hipMemcpyHostToDevice, s));
-      a.forced_pos = fdev; a.n_forced_pos = fnp;
-    }
-    if (forced && forced->neg_sample_idx) {
-      if (fnn > 0) HIPCHK(hipMemcpyAsync(fdev + 1024, forced->neg_sample_idx, (size_t)fnn * 4, hipMemcpyHostToDevice, s));
-      a.forced_neg = fdev + 1024; a.n_forced_neg = fnn;
-    }
-    a.pos_input_idx = pos_idx; a.pos_target_idx = pos_tgt; a.neg_input_idx = neg_idx; a.counts = counts; a.ws = samp_ws;
-    KCHK(launch_box_sampler(a, s));
-    HIPCHK(hipMemcpyAsync(c8, counts, sizeof c8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(lists.data(), pos_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(lists.data() + 1024, pos_tgt, 1024 * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(lists.data() + 2048, neg_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
+    a.boxes = f.boxes; a.gt = f.gt; a.A = A; a.G = G;
+    a.pos_input_idx = f.pos_idx; a.pos_target_idx = f.pos_tgt; a.neg_input_idx = f.neg_idx; a.counts = counts; a.ws = samp_ws;
+    DCCHK(enqueue_box_sampler(ctx, s, a, H, W, o, c.forced, fdev));
+    HIPCHK(hipMemcpyAsync(f.counts, counts, sizeof f.counts, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists, f.pos_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists + 1024, f.pos_tgt, 1024 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(lists + 2048, f.neg_idx, 1024 * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(L.ev[2], s));
     HIPCHK(hipStreamSynchronize(s));
-    np = c8[0]; nn = c8[1];
-    if (c8[5] || c8[6])
+    const int np = f.np = f.counts[0], nn = f.nn = f.counts[1];
+    if (f.counts[5] || f.counts[6])
       return ctx->fail(DC_E_INVALID, "%s: %d forced positive and %d forced negative ranks lie outside the candidate lists (%d, %d)", who,
-                       c8[5], c8[6], c8[2], c8[3]);
+                       f.counts[5], f.counts[6], f.counts[2], f.counts[3]);
     const int n = np + nn;
     if (np < 0 || nn < 0 || n > batch)
       return ctx->fail(DC_E_INVALID, "%s: the forced lists give %d + %d sampled rows, more than batch_size = %d", who, np, nn, batch);
-    for (int r = 0; r < np; ++r)
-      if (lists[r] < 0 || lists[r] >= A || lists[1024 + r] < 0 || lists[1024 + r] >= G)
-        return ctx->fail(DC_E_HIP, "%s: sampler row %d names input %d, ground-truth box %d", who, r, lists[r], lists[1024 + r]);
-    for (int r = 0; r < nn; ++r)
-      if (lists[2048 + r] < 0 || lists[2048 + r] >= A) return ctx->fail(DC_E_HIP, "%s: sampler negative %d names input %d", who, r, lists[2048 + r]);
-    ctx->loss_keep.boxes = boxes; ctx->loss_keep.anchors = anchors; ctx->loss_keep.trans = trans; ctx->loss_keep.scores = scores;
-    ctx->loss_keep.rowlik = rowlik; ctx->loss_keep.A = A; ctx->loss_keep.n = n; ctx->loss_keep.num_pos = np;
+    DCCHK(check_sampled_lists(ctx, who, DC_E_HIP, lists, np, nn, A, G));
     if (n > 0) {
       // ---- RoI pooling, fc6 / fc7, recognition heads on the sampled rows, positives first (LocalizationLayer.lua:443-452) ----
-      HIPCHK(hipMemcpyAsync(sel, pos_idx, (size_t)np * 4, hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemcpyAsync(sel + np, neg_idx, (size_t)nn * 4, hipMemcpyDeviceToDevice, s));
-      KCHK(launch_bilinear_roi_pool_group(L.feat, 0, 1, h, w, 512, L.roi_boxes, n, nullptr, 0, sel, boxes, 0, H, W, 7, 7, L.roi_feats, 1, s));
-      DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, 49 * 512, 1, lane_ws(L), batch));
-      DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), batch));
-      KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
+      HIPCHK(hipMemcpyAsync(sel, f.pos_idx, (size_t)np * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(sel + np, f.neg_idx, (size_t)nn * 4, hipMemcpyDeviceToDevice, s));
+      KCHK(launch_bilinear_roi_pool_group(L.feat, 0, 1, h, w, 512, L.roi_boxes, n, nullptr, 0, sel, f.boxes, 0, H, W, 7, 7, L.roi_feats, 1, s));
+      DCCHK(recog_rows_forward(ctx, L, n, batch));
     }
     HIPCHK(hipEventRecord(L.ev[3], s));
     // ---- captioning: every positive row against the labels of its ground-truth box ----
@@ -3130,22 +3193,12 @@ int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
     if (np > 0) {
       std::vector<int32_t> lab((size_t)np * Lw);
       for (int r = 0; r < np; ++r)
-        std::copy(gt_labels + (size_t)lists[1024 + r] * Lw, gt_labels + (size_t)(lists[1024 + r] + 1) * Lw, lab.begin() + (size_t)r * Lw);
+        std::copy(c.gt_labels + (size_t)lists[1024 + r] * Lw, c.gt_labels + (size_t)(lists[1024 + r] + 1) * Lw, lab.begin() + (size_t)r * Lw);
       DCCHK(lm_score_paired(ctx, s, L.codes, np, batch, lab.data(), Lw, rl.data()));
-      HIPCHK(hipMemcpyAsync(rowlik, rl.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(f.rowlik, rl.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipEventRecord(L.ev[4], s));
-    // ---- the five criteria ----
-    LossTermArgs t{};
-    t.scores = scores; t.anchors = anchors; t.trans = trans; t.gt = gt_dev; t.roi_boxes = L.roi_boxes; t.final_trans = L.final_trans;
-    t.obj = L.obj; t.pos_input_idx = pos_idx; t.pos_target_idx = pos_tgt; t.neg_input_idx = neg_idx; t.rowlik = rowlik;
-    t.num_pos = np; t.num_neg = nn; t.L = Lw;
-    t.w_mid_box = o.mid_box_reg_weight; t.w_mid_obj = o.mid_objectness_weight; t.w_end_box = o.end_box_reg_weight;
-    t.w_end_obj = o.end_objectness_weight; t.w_cap = o.captioning_weight;
-    t.out = terms; t.out_masked = masked;
-    KCHK(launch_loss_terms(t, s));
-    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(masked_h, masked, sizeof masked_h, hipMemcpyDeviceToHost, s));
+    DCCHK(enqueue_loss_terms(ctx, s, f, L.roi_boxes, L.final_trans, L.obj, Lw, terms, masked));         // the five criteria
     HIPCHK(hipEventRecord(L.ev[5], s));
     HIPCHK(hipStreamSynchronize(s));
     return DC_OK;
@@ -3153,20 +3206,25 @@ int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
   const int rc = body();
   if (rc != DC_OK) { drain_lanes(ctx); prof_collect(ctx); return rc; }
   prof_collect(ctx);
-  for (int i = 0; i < 5; ++i) (void)hipEventElapsedTime(&ctx->loss_keep.stage_ms[i], L.ev[i], L.ev[i + 1]);
+  for (int i = 0; i < 5; ++i) (void)hipEventElapsedTime(&f.stage_ms[i], L.ev[i], L.ev[i + 1]);
   L.have_times = false;                       // the lane's stage events no longer time a dc_forward_test
   DCCHK(check_fault_word(ctx, who));
-  out->mid_objectness_loss = terms_h[0]; out->mid_box_reg_loss = terms_h[1]; out->end_objectness_loss = terms_h[2];
-  out->end_box_reg_loss = terms_h[3]; out->captioning_loss = terms_h[4]; out->total_loss = terms_h[5];
-  out->num_pos = np; out->num_neg = nn; out->total_pos = c8[2]; out->total_neg = c8[3];
-  out->masked_mid = masked_h[0]; out->masked_end = masked_h[1]; out->flags = c8[4];
-  if (dump) {
-    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
-    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
-    std::copy(lists.begin() + 2048, lists.begin() + 2048 + nn, dump->neg_input_idx);
-  }
+  f.valid = true;
   return DC_OK;
 }
+// dc_losses and the caller's dump from the record
+void fill_losses(const TrainFwd& f, dc_losses* out, const dc_loss_dump* dump) {
+  out->mid_objectness_loss = f.terms[0]; out->mid_box_reg_loss = f.terms[1]; out->end_objectness_loss = f.terms[2];
+  out->end_box_reg_loss = f.terms[3]; out->captioning_loss = f.terms[4]; out->total_loss = f.terms[5];
+  out->num_pos = f.np; out->num_neg = f.nn; out->total_pos = f.counts[2]; out->total_neg = f.counts[3];
+  out->masked_mid = f.masked[0]; out->masked_end = f.masked[1]; out->flags = f.counts[4];
+  if (dump) {
+    std::copy(f.lists.begin(), f.lists.begin() + f.np, dump->pos_input_idx);
+    std::copy(f.lists.begin() + 1024, f.lists.begin() + 1024 + f.np, dump->pos_target_idx);
+    std::copy(f.lists.begin() + 2048, f.lists.begin() + 2048 + f.nn, dump->neg_input_idx);
+  }
+}
+}  // namespace
 
 static int op_lm_sample_n(dc_ctx* ctx, const float* codes, int n, const int32_t* row_ids, const dc_sample_opts* opts,
                           const dc_sample_trunc* trunc, int32_t* samples, float* logprob, float* sample_logprob, const char* who) {
@@ -3392,10 +3450,7 @@ int dc_debug_lstm_cell_bwd_ex(dc_ctx* ctx, const float* gates_pre, const int32_t
 // ---- recognition-net gradients (docs/SEMANTICS.md, "Recognition-net gradients") ------------------------------------
 int dc_feature_size(int H, int W, int* h, int* w) {
   if (!h || !w || H < 1 || W < 1) return DC_E_INVALID;
-  int fh = H, fw = W;
-  for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
-    if (kVgg[i].pool_after) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
-  *h = fh; *w = fw;
+  feature_size(H, W, h, w);
   return DC_OK;
 }
 
@@ -3536,6 +3591,12 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
   };
   return call_finish(ctx, s, body(), "recognition backward");
 }
+// RecogKept of the n rows recog_rows_forward left in lane 0, on the feature map `feat`
+static RecogKept recog_kept(const Lane& L, const float* feat, int h, int w, int n, int np, const float* target, const float* g, int img_h,
+                            int img_w, const dc_loss_opts& o) {
+  return {feat, h, w, L.roi_boxes, L.roi_feats, L.fc6_out, L.codes, L.obj, L.final_trans, target, g, n, np, img_h, img_w,
+          o.end_objectness_weight, o.end_box_reg_weight};
+}
 
 int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const float* roi_boxes, int n, int num_pos,
                      const float* target_boxes, const float* dcodes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null,
@@ -3561,140 +3622,98 @@ int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const flo
   Lane& L = lane0(ctx);
   DCCHK(lane_prepare(ctx, L, img_h, img_w, o.batch_size, 1));
   hipStream_t s = L.stream;
-  const int D = ctx->D, np = num_pos;
-  // ---- the forward half, through dc_forward_losses' own calls ----
-  HIPCHK(hipMemcpyAsync(L.roi_boxes, roi_boxes, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
-  KCHK(launch_bilinear_roi_pool(feat_hwc, h, w, 512, L.roi_boxes, n, nullptr, img_h, img_w, 7, 7, L.roi_feats, 1, s));
-  DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, kRecogK6, 1, lane_ws(L), o.batch_size));
-  DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), o.batch_size));
-  KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
-  // the two end terms by loss_terms itself: its other three terms run on stand-ins (one zero score row, a unit anchor)
-  int32_t* idx = nullptr; double* terms = nullptr; int32_t* masked = nullptr; float* zeros = nullptr; double* rowlik = nullptr;
-  const std::vector<Carve> cv = {{(void**)&idx, 2 * 1024 * 4}, {(void**)&terms, 6 * 8}, {(void**)&masked, 2 * 4}, {(void**)&zeros, 64},
-                                 {(void**)&rowlik, 1024 * 8}};
+  const int np = num_pos;
+  if (ctx->row_ramp == nullptr) {            // the targets come gathered: row r's is target_boxes[r]
+    std::vector<int32_t> ramp(1024);
+    for (int r = 0; r < 1024; ++r) ramp[r] = r;
+    DCCHK(dev_alloc(ctx, (void**)&ctx->row_ramp, ramp.size() * 4));
+    HIPCHK(hipMemcpy(ctx->row_ramp, ramp.data(), ramp.size() * 4, hipMemcpyHostToDevice));
+  }
+  double* terms = nullptr;
+  int32_t* masked = nullptr;
+  const std::vector<Carve> cv = {{(void**)&terms, 6 * 8}, {(void**)&masked, 2 * 4}};
   HIPCHK(ctx->recog_aux_ws.grow(carve(cv, nullptr), s));
   carve(cv, ctx->recog_aux_ws.get());
-  double terms_h[6] = {0};
-  // The contract with loss_terms_kernel this leans on: every term reads only its own inputs; the end objectness term reads
-  // obj[0, n) and num_pos, the end box term roi_boxes / final_trans / gt[pos_target_idx[r]] for r < num_pos; out[2], out[3] and
-  // out_masked[1] depend on nothing else.  The mid terms and the captioning term get inputs on which they stay finite (two-class
-  // scores of zero, the anchor (0, 0, 1, 1) with w, h > 0, zero row sums), and their weights are 0.
+  TrainFwd f;                                // the rows' targets as a record's ground truth; no RPN rows, no row sums
+  f.gt = const_cast<float*>(target_boxes); f.pos_tgt = ctx->row_ramp; f.np = np; f.nn = n - np; f.opts = o;
+  // ---- the forward half: the training forward's own pieces on the caller's boxes; loss_terms with its two end terms only ----
   auto fwd = [&]() -> int {
-    std::vector<int32_t> ih(2 * 1024, 0);
-    for (int r = 0; r < 1024; ++r) ih[1024 + r] = r;                   // [0, 1024): zeros; [1024, 2048): 0, 1, 2 ..
-    const float unit[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f};   // a score row / transform of zeros, the anchor (0, 0, 1, 1)
-    HIPCHK(hipMemcpyAsync(idx, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(zeros, unit, sizeof unit, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(rowlik, 0, 1024 * 8, s));
-    LossTermArgs t{};
-    t.scores = zeros; t.anchors = zeros + 4; t.trans = zeros; t.gt = target_boxes; t.roi_boxes = L.roi_boxes; t.final_trans = L.final_trans;
-    t.obj = L.obj; t.pos_input_idx = idx; t.pos_target_idx = idx + 1024; t.neg_input_idx = idx; t.rowlik = rowlik;
-    t.num_pos = np; t.num_neg = n - np; t.L = 1;
-    t.w_mid_box = 0.f; t.w_mid_obj = 0.f; t.w_end_box = o.end_box_reg_weight; t.w_end_obj = o.end_objectness_weight; t.w_cap = 0.f;
-    t.out = terms; t.out_masked = masked;
-    KCHK(launch_loss_terms(t, s));
-    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(L.roi_boxes, roi_boxes, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
+    KCHK(launch_bilinear_roi_pool(feat_hwc, h, w, 512, L.roi_boxes, n, nullptr, img_h, img_w, 7, 7, L.roi_feats, 1, s));
+    DCCHK(recog_rows_forward(ctx, L, n, o.batch_size));
+    DCCHK(enqueue_loss_terms(ctx, s, f, L.roi_boxes, L.final_trans, L.obj, 1, terms, masked));
     HIPCHK(hipStreamSynchronize(s));
     return DC_OK;
   };
-  int rc = fwd();
-  if (rc != DC_OK) (void)hipStreamSynchronize(s);
+  const int rc = fwd();
   L.have_times = false;
-  if (rc != DC_OK) { prof_collect(ctx); return rc; }
-  *end_objectness_loss = terms_h[2];
-  *end_box_reg_loss = terms_h[3];
-  RecogKept k{};
-  k.feat = feat_hwc; k.h = h; k.w = w; k.roi_boxes = L.roi_boxes; k.roi_feats = L.roi_feats; k.fc6_out = L.fc6_out; k.codes = L.codes;
-  k.obj = L.obj; k.final_trans = L.final_trans; k.target = target_boxes; k.g = dcodes_or_null; k.n = n; k.np = np;
-  k.img_h = img_h; k.img_w = img_w; k.w_obj = o.end_objectness_weight; k.w_box = o.end_box_reg_weight;
-  return recog_backward(ctx, s, k, *out, masked_end);
+  if (rc != DC_OK) { (void)hipStreamSynchronize(s); prof_collect(ctx); return rc; }
+  *end_objectness_loss = f.terms[2];
+  *end_box_reg_loss = f.terms[3];
+  return recog_backward(ctx, s, recog_kept(L, feat_hwc, h, w, n, np, target_boxes, dcodes_or_null, img_h, img_w, o), *out, masked_end);
 }
 
-int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
-                      const int32_t* gt_labels, int G, int Lw, const dc_loss_opts* opts, const dc_sampler_forced* forced,
-                      dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg) {
-  const char* who = "dc_loss_gradients";
-  if (!ctx) return DC_E_INVALID;
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
-  if (!out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+namespace {
+int check_recog_lm_args(dc_ctx* ctx, const TrainCall& c, const dc_recog_grads* rg, const dc_lm_grads* lg) {
+  const char* who = c.who;
+  if (!c.out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
   DCCHK(check_recog_out(ctx, rg, who));
   if (!lg || !lg->lm_enc_w || !lg->lm_enc_b || !lg->lm_emb || !lg->lstm_w || !lg->lstm_b || !lg->lm_out_w || !lg->lm_out_b)
     return ctx->fail(DC_E_INVALID, "%s: null language-model gradient buffer (only codes may be null)", who);
-  if (Lw > 64) return ctx->fail(DC_E_INVALID, "%s: L must be in 1..64 (got %d)", who, Lw);
-  const dc_loss_opts o = opts ? *opts : kLossDefaults;
-  int fh = 0, fw = 0;
-  if (H >= 32 && W >= 32 && o.batch_size >= 2 && o.batch_size <= 1024) {
-    (void)dc_feature_size(H, W, &fh, &fw);
-    DCCHK(check_recog_scratch(ctx, o.batch_size, fh, fw, who));
+  if (c.Lw > 64) return ctx->fail(DC_E_INVALID, "%s: L must be in 1..64 (got %d)", who, c.Lw);
+  if (c.H >= 32 && c.W >= 32 && c.o.batch_size >= 2 && c.o.batch_size <= 1024) {
+    int fh = 0, fw = 0;
+    feature_size(c.H, c.W, &fh, &fw);
+    DCCHK(check_recog_scratch(ctx, c.o.batch_size, fh, fw, who));
   }
-  if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
-    return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
-  std::vector<int32_t> lists(3 * 1024);
-  const dc_loss_dump own = {lists.data(), lists.data() + 1024, lists.data() + 2048};
-  DCCHK(dc_forward_losses(ctx, img_chw, H, W, img_on_device, gt_boxes, gt_labels, G, Lw, opts, forced, out, &own));
-  const int np = out->num_pos, n = np + out->num_neg, D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
-  if (dump) {
-    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
-    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
-    std::copy(lists.begin() + 2048, lists.begin() + 2048 + out->num_neg, dump->neg_input_idx);
-  }
-  LossCfgGuard guard(ctx->cfg);
-  Lane& L = lane0(ctx);                       // dc_forward_losses left the sampled rows' activations in lane 0
+  return check_dump(ctx, who, c.dump);
+}
+// The backward of the captioning loss and of the two end criteria on the record's sampled rows (their activations in lane 0):
+// lm_grad on the np positive rows, its gradient of their codes added in recog_backward on all n.  No positive row: the
+// language model's gradients are zero; no sampled row: the recognition net's too.
+int train_recog_lm_backward(dc_ctx* ctx, const TrainCall& c, Lane& L, const TrainFwd& f, const dc_recog_grads& rg, const dc_lm_grads& lg) {
+  const int np = f.np, n = np + f.nn, Lw = c.Lw;
+  const size_t D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
   hipStream_t s = L.stream;
-  // ---- the language model on the positive rows ----
-  float* gcodes = nullptr;
-  float* tgt_dev = nullptr;
+  float *gcodes = nullptr, *tgt_dev = nullptr;
   const std::vector<Carve> cv = {{(void**)&gcodes, (size_t)std::max(np, 1) * D * 4}, {(void**)&tgt_dev, (size_t)std::max(np, 1) * 16}};
   HIPCHK(ctx->recog_aux_ws.grow(carve(cv, nullptr), s));
   carve(cv, ctx->recog_aux_ws.get());
   auto body = [&]() -> int {
     if (np > 0) {
       std::vector<int32_t> lab((size_t)np * Lw);
-      std::vector<float> tgt((size_t)np * 4);
+      std::vector<float> tgt((size_t)np * 4);                 // (end_crit_grad takes the positives' targets gathered)
       for (int r = 0; r < np; ++r) {
-        const int j = lists[1024 + r];
-        std::copy(gt_labels + (size_t)j * Lw, gt_labels + (size_t)(j + 1) * Lw, lab.begin() + (size_t)r * Lw);
-        std::copy(gt_boxes + (size_t)j * 4, gt_boxes + (size_t)(j + 1) * 4, tgt.begin() + (size_t)r * 4);
+        const int j = f.lists[1024 + r];
+        std::copy(c.gt_labels + (size_t)j * Lw, c.gt_labels + (size_t)(j + 1) * Lw, lab.begin() + (size_t)r * Lw);
+        std::copy(c.gt_boxes + (size_t)j * 4, c.gt_boxes + (size_t)(j + 1) * 4, tgt.begin() + (size_t)r * 4);
       }
       HIPCHK(hipMemcpyAsync(tgt_dev, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, s));     // (lm_grad synchronises before tgt dies)
-      dc_lm_grads lgo = *lg;
+      dc_lm_grads lgo = lg;
       lgo.codes = gcodes;
       double cap = 0.0;
-      DCCHK(lm_grad(ctx, s, L.codes, np, lab.data(), Lw, o.captioning_weight, lgo, &cap, nullptr));
-      if (lg->codes != nullptr) HIPCHK(hipMemcpyAsync(lg->codes, gcodes, (size_t)np * D * 4, hipMemcpyDeviceToDevice, s));
+      // (lm_grad runs its own teacher-forced forward after train_forward's lm_score_paired; its loss value is not used)
+      DCCHK(lm_grad(ctx, s, L.codes, np, lab.data(), Lw, f.opts.captioning_weight, lgo, &cap, nullptr));
+      if (lg.codes != nullptr) HIPCHK(hipMemcpyAsync(lg.codes, gcodes, (size_t)np * D * 4, hipMemcpyDeviceToDevice, s));
     } else {
-      HIPCHK(hipMemsetAsync(lg->lm_enc_w, 0, (size_t)E * D * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lm_enc_b, 0, (size_t)E * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lm_emb, 0, (size_t)(V + 2) * E * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lstm_w, 0, (size_t)(E + Hd) * 4 * Hd * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lstm_b, 0, (size_t)4 * Hd * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lm_out_w, 0, (size_t)(V + 1) * Hd * 4, s));
-      HIPCHK(hipMemsetAsync(lg->lm_out_b, 0, (size_t)(V + 1) * 4, s));
+      DCCHK(zero_fill(ctx, s, {{lg.lm_enc_w, E * D * 4}, {lg.lm_enc_b, E * 4}, {lg.lm_emb, (V + 2) * E * 4}, {lg.lstm_w, (E + Hd) * 4 * Hd * 4},
+                               {lg.lstm_b, 4 * Hd * 4}, {lg.lm_out_w, (V + 1) * Hd * 4}, {lg.lm_out_b, (V + 1) * 4}}));
     }
     if (n == 0) {
-      HIPCHK(hipMemsetAsync(rg->fc6_w, 0, (size_t)D * kRecogK6 * 4, s));
-      HIPCHK(hipMemsetAsync(rg->fc6_b, 0, (size_t)D * 4, s));
-      HIPCHK(hipMemsetAsync(rg->fc7_w, 0, (size_t)D * D * 4, s));
-      HIPCHK(hipMemsetAsync(rg->fc7_b, 0, (size_t)D * 4, s));
-      HIPCHK(hipMemsetAsync(rg->obj_w, 0, (size_t)D * 4, s));
-      HIPCHK(hipMemsetAsync(rg->obj_b, 0, 4, s));
-      HIPCHK(hipMemsetAsync(rg->boxreg_w, 0, (size_t)4 * D * 4, s));
-      HIPCHK(hipMemsetAsync(rg->boxreg_b, 0, 16, s));
-      HIPCHK(hipMemsetAsync(rg->feat, 0, (size_t)L.fh * L.fw * 512 * 4, s));
+      DCCHK(zero_fill(ctx, s, {{rg.fc6_w, D * kRecogK6 * 4}, {rg.fc6_b, D * 4}, {rg.fc7_w, D * D * 4}, {rg.fc7_b, D * 4}, {rg.obj_w, D * 4},
+                               {rg.obj_b, 4}, {rg.boxreg_w, 4 * D * 4}, {rg.boxreg_b, 16}, {rg.feat, (size_t)f.h * f.w * 512 * 4}}));
       HIPCHK(hipStreamSynchronize(s));
       return DC_OK;
     }
-    RecogKept k{};
-    k.feat = L.feat; k.h = L.fh; k.w = L.fw; k.roi_boxes = L.roi_boxes; k.roi_feats = L.roi_feats; k.fc6_out = L.fc6_out; k.codes = L.codes;
-    k.obj = L.obj; k.final_trans = L.final_trans; k.target = tgt_dev; k.g = np > 0 ? gcodes : nullptr; k.n = n; k.np = np;
-    k.img_h = H; k.img_w = W; k.w_obj = o.end_objectness_weight; k.w_box = o.end_box_reg_weight;
     int32_t masked_end = 0;
-    return recog_backward(ctx, s, k, *rg, &masked_end);
+    return recog_backward(ctx, s, recog_kept(L, L.feat, f.h, f.w, n, np, tgt_dev, np > 0 ? gcodes : nullptr, f.H, f.W, f.opts), rg, &masked_end);
   };
   const int rc = body();
   if (rc != DC_OK) (void)hipStreamSynchronize(s);
   return rc;
 }
+}  // namespace
+
 
 // ---- test hooks of the recognition backward (densecap_debug_recog.h) -------------------------------------------------------------
 int dc_debug_roi_tap_index(dc_ctx* ctx, const float* boxes, int B, int h, int w, int img_h, int img_w, int HH, int WW,
@@ -4138,6 +4157,11 @@ static int rpn_backward(dc_ctx* ctx, hipStream_t s, const RpnKept& in, const dc_
   };
   return call_finish(ctx, s, body(), "RPN backward", true);
 }
+// RpnKept of a record's rows and lists on the feature map `feat` and the hidden map made of it (droi: (np + nn, 4) or null)
+static RpnKept rpn_kept(const TrainFwd& f, const float* feat, const float* hidden, const float* droi, float decay) {
+  return {feat, f.h, f.w, hidden, f.trans, f.scores, f.anchors, f.boxes, f.gt, f.np + f.nn > 0 ? droi : nullptr, f.pos_idx, f.pos_tgt,
+          f.neg_idx, f.np, f.nn, f.opts.mid_objectness_weight, f.opts.mid_box_reg_weight, decay};
+}
 
 int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32_t* pos_input_idx, const int32_t* pos_target_idx,
                    int num_pos, const int32_t* neg_input_idx, int num_neg, const float* gt_boxes, int G,
@@ -4160,8 +4184,10 @@ int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32
   HIPCHK(hipSetDevice(ctx->device));
   drain_lanes(ctx);
   const int k = ctx->k, R = ctx->R, hw = h * w, A = k * hw;
+  TrainFwd f;                                // this call's own rows and lists, as a training forward would have recorded them
+  f.np = np; f.nn = nn; f.h = h; f.w = w; f.opts = o;
   // the caller's lists and boxes are checked on the host: the kernels trust them
-  std::vector<int32_t> lists(3 * 1024, 0);
+  std::vector<int32_t>& lists = f.lists;       // (host)
   std::vector<float> gth((size_t)G * 4);
   if (np > 0) {
     HIPCHK(hipMemcpy(lists.data(), pos_input_idx, (size_t)np * 4, hipMemcpyDeviceToHost));
@@ -4169,124 +4195,97 @@ int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32
   }
   if (nn > 0) HIPCHK(hipMemcpy(lists.data() + 2048, neg_input_idx, (size_t)nn * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(gth.data(), gt_boxes, gth.size() * 4, hipMemcpyDeviceToHost));
-  for (int r = 0; r < np; ++r)
-    if (lists[r] < 0 || lists[r] >= A || lists[1024 + r] < 0 || lists[1024 + r] >= G)
-      return ctx->fail(DC_E_INVALID, "%s: positive row %d names input %d of %d, ground-truth box %d of %d", who, r, lists[r], A, lists[1024 + r], G);
-  for (int r = 0; r < nn; ++r)
-    if (lists[2048 + r] < 0 || lists[2048 + r] >= A) return ctx->fail(DC_E_INVALID, "%s: negative row %d names input %d of %d", who, r, lists[2048 + r], A);
-  for (int j = 0; j < G; ++j) {
-    const float* b = gth.data() + (size_t)j * 4;
-    if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3])) || !(b[2] > 0.f) || !(b[3] > 0.f))
-      return ctx->fail(DC_E_INVALID, "%s: ground-truth box %d is not finite with w > 0 and h > 0", who, j);
-  }
+  DCCHK(check_sampled_lists(ctx, who, DC_E_INVALID, lists.data(), np, nn, A, G));
+  DCCHK(check_gt_boxes(ctx, who, gth.data(), G));
   LossCfgGuard guard(ctx->cfg);
   Lane& L = lane0(ctx);
   DCCHK(lane_prepare(ctx, L, img_h, img_w, o.batch_size, 1));
   hipStream_t s = L.stream;
-  // ---- the forward half, through dc_forward_losses' own calls, on rows of this call's own ----
-  float *hidden = nullptr, *heads = nullptr, *boxes = nullptr, *anchors = nullptr, *trans = nullptr, *scores = nullptr, *gt_dev = nullptr;
-  float *stand = nullptr;
+  // ---- the forward half: rpn_train_forward on rows of this call's own; loss_terms with its two mid terms only ----
+  float *hidden = nullptr, *heads = nullptr;
   int32_t *idx = nullptr, *masked = nullptr;
-  double *terms = nullptr, *rowlik = nullptr;
+  double* terms = nullptr;
   const std::vector<Carve> cv = {
-      {(void**)&hidden, (size_t)hw * R * 4}, {(void**)&heads, (size_t)hw * 6 * k * 4}, {(void**)&boxes, (size_t)A * 16},
-      {(void**)&anchors, (size_t)A * 16},    {(void**)&trans, (size_t)A * 16},         {(void**)&scores, (size_t)A * 8},
-      {(void**)&gt_dev, (size_t)G * 16},     {(void**)&stand, 3 * 1024 * 16},          {(void**)&idx, 3 * 1024 * 4},
-      {(void**)&masked, 2 * 4},              {(void**)&terms, 6 * 8},                  {(void**)&rowlik, 1024 * 8}};
+      {(void**)&hidden, (size_t)hw * R * 4}, {(void**)&heads, (size_t)hw * 6 * k * 4}, {(void**)&f.boxes, (size_t)A * 16},
+      {(void**)&f.anchors, (size_t)A * 16},  {(void**)&f.trans, (size_t)A * 16},       {(void**)&f.scores, (size_t)A * 8},
+      {(void**)&f.gt, (size_t)G * 16},       {(void**)&idx, 3 * 1024 * 4},             {(void**)&masked, 2 * 4},
+      {(void**)&terms, 6 * 8}};
   HIPCHK(ctx->rpn_aux_ws.grow(carve(cv, nullptr), s));
   carve(cv, ctx->rpn_aux_ws.get());
-  double terms_h[6] = {0};
-  int32_t masked_h[2] = {0, 0};
-  // The contract with loss_terms_kernel this leans on (as dc_op_recog_grad does for the other two terms): every term reads only
-  // its own inputs.  The two end terms and the captioning term get inputs on which they stay finite -- recognition logits and
-  // final transforms of zero, the RoI box (0, 0, 1, 1), zero row sums -- and their weights are 0.
-  std::vector<float> st((size_t)3 * 1024 * 4, 0.f);         // [0, 1024) rows: RoI boxes; [1024, 2048): final transforms; then logits
-  for (int r = 0; r < 1024; ++r) { st[(size_t)r * 4 + 2] = 1.f; st[(size_t)r * 4 + 3] = 1.f; }
+  f.pos_idx = idx; f.pos_tgt = idx + 1024; f.neg_idx = idx + 2048;
   auto fwd = [&]() -> int {
     ensure_fault_word(ctx);
-    DCCHK(conv3x3(ctx, s, feat_hwc, ctx->rpn_w, ctx->rpn_b, hidden, 1, h, w, 512, R, 1, lane_ws(L)));
-    DCCHK(linear(ctx, s, hidden, ctx->heads_w, ctx->heads_b, heads, hw, 6 * k, R, 0, Ws(), hw));
-    KCHK(launch_rpn_decode(heads, 1, h, w, k, ctx->anchors, ctx->fc[0], ctx->fc[1], ctx->fc[2], ctx->fc[3], img_h, img_w, boxes, anchors,
-                           trans, nullptr, nullptr, nullptr, 0, s));
-    KCHK(launch_rpn_score_rows(heads, h, w, k, scores, s));
+    DCCHK(rpn_train_forward(ctx, L, feat_hwc, h, w, img_h, img_w, hidden, heads, f.boxes, f.anchors, f.trans, f.scores));
     HIPCHK(hipMemcpyAsync(idx, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(gt_dev, gth.data(), gth.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(stand, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(rowlik, 0, 1024 * 8, s));
-    LossTermArgs t{};
-    t.scores = scores; t.anchors = anchors; t.trans = trans; t.gt = gt_dev; t.roi_boxes = stand; t.final_trans = stand + 1024 * 4;
-    t.obj = stand + 2048 * 4; t.pos_input_idx = idx; t.pos_target_idx = idx + 1024; t.neg_input_idx = idx + 2048; t.rowlik = rowlik;
-    t.num_pos = np; t.num_neg = nn; t.L = 1;
-    t.w_mid_box = o.mid_box_reg_weight; t.w_mid_obj = o.mid_objectness_weight; t.w_end_box = 0.f; t.w_end_obj = 0.f; t.w_cap = 0.f;
-    t.out = terms; t.out_masked = masked;
-    KCHK(launch_loss_terms(t, s));
-    HIPCHK(hipMemcpyAsync(terms_h, terms, sizeof terms_h, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(masked_h, masked, sizeof masked_h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(f.gt, gth.data(), gth.size() * 4, hipMemcpyHostToDevice, s));
+    DCCHK(enqueue_loss_terms(ctx, s, f, nullptr, nullptr, nullptr, 1, terms, masked));
     HIPCHK(hipStreamSynchronize(s));
     return DC_OK;
   };
   const int rc = fwd();
-  if (rc != DC_OK) (void)hipStreamSynchronize(s);
   L.have_times = false;
-  if (rc != DC_OK) { prof_collect(ctx); return rc; }
-  *mid_objectness_loss = terms_h[0];
-  *mid_box_reg_loss = terms_h[1];
-  *masked_mid = masked_h[0];
-  RpnKept kp{};
-  kp.feat = feat_hwc; kp.h = h; kp.w = w; kp.hidden = hidden; kp.trans = trans; kp.scores = scores; kp.anchors = anchors; kp.boxes = boxes;
-  kp.gt = gt_dev; kp.droi = np + nn > 0 ? droi_boxes_or_null : nullptr; kp.pos_idx = idx; kp.pos_tgt = idx + 1024; kp.neg_idx = idx + 2048;
-  kp.np = np; kp.nn = nn; kp.w_mid_obj = o.mid_objectness_weight; kp.w_mid_box = o.mid_box_reg_weight; kp.decay = box_reg_decay;
-  return rpn_backward(ctx, s, kp, *out, nullptr, lane_ws(L));
+  if (rc != DC_OK) { (void)hipStreamSynchronize(s); prof_collect(ctx); return rc; }
+  *mid_objectness_loss = f.terms[0];
+  *mid_box_reg_loss = f.terms[1];
+  *masked_mid = f.masked[0];
+  return rpn_backward(ctx, s, rpn_kept(f, feat_hwc, hidden, droi_boxes_or_null, box_reg_decay), *out, nullptr, lane_ws(L));
 }
 
-// What dc_forward_backward reads of what dc_loss_gradients left, none of which anything between the RPN's forward and here
-// writes: lane 0's feat and rpn_hidden (the trunk and the RPN write them; RoI pooling, fc6 / fc7, the language model and the two
-// backward passes read feat or own buffers), the rows loss_keep points at in ctx->loss_ws (boxes, anchors, trans, scores:
-// written by rpn_decode / rpn_score_rows only), and rg->roi_boxes.  The lists and the ground truth go up again from the host.
+namespace {
+int check_rpn_args(dc_ctx* ctx, const TrainCall& c, const dc_rpn_grads* pg, float box_reg_decay) {
+  DCCHK(check_rpn_out(ctx, pg, c.who));
+  int fh = 1, fw = 1;
+  if (c.H >= 1 && c.W >= 1) feature_size(c.H, c.W, &fh, &fw);
+  DCCHK(check_rpn_grad_shape(ctx, fh, fw, box_reg_decay, c.who));
+  return check_dump(ctx, c.who, c.dump);
+}
+// The RPN backward on the record's rows, lists and ground truth and lane 0's feat and rpn_hidden; pg.feat = feat_add + its share
+int train_rpn_backward(dc_ctx* ctx, Lane& L, const TrainFwd& f, float box_reg_decay, const float* droi, const float* feat_add,
+                       const dc_rpn_grads& pg) {
+  return rpn_backward(ctx, L.stream, rpn_kept(f, L.feat, L.rpn_hidden, droi, box_reg_decay), pg, feat_add, lane_ws(L));
+}
+// The three entry points: the first `stages` of the three stages.  Every argument is refused before anything is allocated or
+// launched, in the order the refusals have always come in (RPN, recognition / language model, forward; every family ends with
+// the dump's); one LossCfgGuard, one drain, one lane_prepare; the stages on ctx->train; dc_losses and the dump from it.
+int train_call(dc_ctx* ctx, const TrainCall& c, int stages, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
+               const dc_rpn_grads* pg) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", c.who);
+  if (stages > 2) DCCHK(check_rpn_args(ctx, c, pg, box_reg_decay));
+  if (stages > 1) DCCHK(check_recog_lm_args(ctx, c, rg, lg));
+  DCCHK(check_forward_args(ctx, c));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  Lane& L = lane0(ctx);
+  DCCHK(lane_prepare(ctx, L, c.H, c.W, c.o.batch_size, 1));
+  DCCHK(train_forward(ctx, c, L, ctx->train));
+  fill_losses(ctx->train, c.out, c.dump);
+  if (stages > 1) DCCHK(train_recog_lm_backward(ctx, c, L, ctx->train, *rg, *lg));
+  if (stages > 2) DCCHK(train_rpn_backward(ctx, L, ctx->train, box_reg_decay, rg->roi_boxes, rg->feat, *pg));
+  return DC_OK;
+}
+}  // namespace
+
+#define TRAIN_ARGS(name) {name, img_chw, H, W, img_on_device, gt_boxes, gt_labels, G, L, opts ? *opts : kLossDefaults, forced, out, dump}
+int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump) {
+  return train_call(ctx, TRAIN_ARGS("dc_forward_losses"), 1, nullptr, nullptr, 0.f, nullptr);
+}
+int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                      const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                      dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg) {
+  return train_call(ctx, TRAIN_ARGS("dc_loss_gradients"), 2, rg, lg, 0.f, nullptr);
+}
 int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                         const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg) {
-  const char* who = "dc_forward_backward";
-  if (!ctx) return DC_E_INVALID;
-  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
-  DCCHK(check_rpn_out(ctx, pg, who));
-  int fh = 1, fw = 1;
-  if (H >= 1 && W >= 1) (void)dc_feature_size(H, W, &fh, &fw);
-  DCCHK(check_rpn_grad_shape(ctx, fh, fw, box_reg_decay, who));
-  if (dump && (!dump->pos_input_idx || !dump->pos_target_idx || !dump->neg_input_idx))
-    return ctx->fail(DC_E_INVALID, "%s: a dump needs all three lists", who);
-  std::vector<int32_t> lists(3 * 1024, 0);
-  const dc_loss_dump own = {lists.data(), lists.data() + 1024, lists.data() + 2048};
-  DCCHK(dc_loss_gradients(ctx, img_chw, H, W, img_on_device, gt_boxes, gt_labels, G, L, opts, forced, out, &own, rg, lg));
-  const int np = out->num_pos, nn = out->num_neg;
-  if (dump) {
-    std::copy(lists.begin(), lists.begin() + np, dump->pos_input_idx);
-    std::copy(lists.begin() + 1024, lists.begin() + 1024 + np, dump->pos_target_idx);
-    std::copy(lists.begin() + 2048, lists.begin() + 2048 + nn, dump->neg_input_idx);
-  }
-  const dc_loss_opts o = opts ? *opts : kLossDefaults;
-  const dc_ctx::LossKeep& keep = ctx->loss_keep;
-  Lane& Ln = lane0(ctx);
-  if (keep.boxes == nullptr || keep.A != ctx->k * Ln.fh * Ln.fw) return ctx->fail(DC_E_STATE, "%s: the forward left no RPN rows", who);
-  LossCfgGuard guard(ctx->cfg);
-  hipStream_t s = Ln.stream;
-  float* gt_dev = nullptr;
-  int32_t* idx = nullptr;
-  const std::vector<Carve> cv = {{(void**)&gt_dev, (size_t)G * 16}, {(void**)&idx, 3 * 1024 * 4}};
-  HIPCHK(ctx->rpn_aux_ws.grow(carve(cv, nullptr), s));
-  carve(cv, ctx->rpn_aux_ws.get());
-  HIPCHK(hipMemcpyAsync(idx, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(gt_dev, gt_boxes, (size_t)G * 16, hipMemcpyHostToDevice, s));
-  RpnKept kp{};
-  kp.feat = Ln.feat; kp.h = Ln.fh; kp.w = Ln.fw; kp.hidden = Ln.rpn_hidden; kp.trans = keep.trans; kp.scores = keep.scores;
-  kp.anchors = keep.anchors; kp.boxes = keep.boxes; kp.gt = gt_dev; kp.droi = np + nn > 0 ? rg->roi_boxes : nullptr;
-  kp.pos_idx = idx; kp.pos_tgt = idx + 1024; kp.neg_idx = idx + 2048; kp.np = np; kp.nn = nn;
-  kp.w_mid_obj = o.mid_objectness_weight; kp.w_mid_box = o.mid_box_reg_weight; kp.decay = box_reg_decay;
-  const int rc = rpn_backward(ctx, s, kp, *pg, rg->feat, lane_ws(Ln));
-  if (rc != DC_OK) (void)hipStreamSynchronize(s);             // (the lists' upload reads this frame)
-  return rc;
+  return train_call(ctx, TRAIN_ARGS("dc_forward_backward"), 3, rg, lg, box_reg_decay, pg);
 }
+#undef TRAIN_ARGS
+
 
 // ---- test hooks of the RPN backward (densecap_debug_rpn.h) ----------------------------------------------------------------------------
 int dc_debug_rpn_dheads(dc_ctx* ctx, const float* trans, const float* scores, const float* anchors, const float* boxes, int h, int w_px,

@@ -325,62 +325,72 @@ __global__ __launch_bounds__(LT_THREADS) void loss_terms_kernel(LossTermArgs a) 
   if (tid < 2) s_masked[tid] = 0;
   __syncthreads();
   const int np = a.num_pos, nn = a.num_neg, n = np + nn;
-  double out[6];
+  double out[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};          // (a term whose input is null is skipped by every thread: 0.0, no masked row)
   // mid objectness: mean over the positives of -LogSoftMax(s)[0] + mean over the negatives of -LogSoftMax(s)[1]
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
-    double v = 0.0;
-    if (r < np) { const int i = a.pos_input_idx[r]; v = lt_nll2(a.scores[(size_t)i * 2], a.scores[(size_t)i * 2 + 1], 0); }
-    buf[r] = v;
+  if (a.scores != nullptr) {
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
+      double v = 0.0;
+      if (r < np) { const int i = a.pos_input_idx[r]; v = lt_nll2(a.scores[(size_t)i * 2], a.scores[(size_t)i * 2 + 1], 0); }
+      buf[r] = v;
+    }
+    const double mo_pos = lt_tree_sum(buf, tid);
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
+      double v = 0.0;
+      if (r < nn) { const int i = a.neg_input_idx[r]; v = lt_nll2(a.scores[(size_t)i * 2], a.scores[(size_t)i * 2 + 1], 1); }
+      buf[r] = v;
+    }
+    const double mo_neg = lt_tree_sum(buf, tid);
+    out[0] = (double)a.w_mid_obj * ((np > 0 ? mo_pos / (double)np : 0.0) + (nn > 0 ? mo_neg / (double)nn : 0.0));
   }
-  const double mo_pos = lt_tree_sum(buf, tid);
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
-    double v = 0.0;
-    if (r < nn) { const int i = a.neg_input_idx[r]; v = lt_nll2(a.scores[(size_t)i * 2], a.scores[(size_t)i * 2 + 1], 1); }
-    buf[r] = v;
-  }
-  const double mo_neg = lt_tree_sum(buf, tid);
-  out[0] = (double)a.w_mid_obj * ((np > 0 ? mo_pos / (double)np : 0.0) + (nn > 0 ? mo_neg / (double)nn : 0.0));
   // mid box regression: the RPN's transforms of the positive rows against their anchors' inverse transform
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
-    double v = 0.0;
-    if (r < np) {
-      const int i = a.pos_input_idx[r];
-      int m = 0;
-      v = lt_box_row(a.anchors + (size_t)i * 4, a.trans + (size_t)i * 4, a.gt + (size_t)a.pos_target_idx[r] * 4, &m);
-      if (m) atomicAdd(&s_masked[0], 1);
+  if (a.anchors != nullptr) {
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
+      double v = 0.0;
+      if (r < np) {
+        const int i = a.pos_input_idx[r];
+        int m = 0;
+        v = lt_box_row(a.anchors + (size_t)i * 4, a.trans + (size_t)i * 4, a.gt + (size_t)a.pos_target_idx[r] * 4, &m);
+        if (m) atomicAdd(&s_masked[0], 1);
+      }
+      buf[r] = v;
     }
-    buf[r] = v;
+    const double mb = lt_tree_sum(buf, tid);
+    out[1] = np > 0 ? (double)a.w_mid_box * (mb / (4.0 * (double)np)) : 0.0;
   }
-  const double mb = lt_tree_sum(buf, tid);
-  out[1] = np > 0 ? (double)a.w_mid_box * (mb / (4.0 * (double)np)) : 0.0;
   // end objectness: the binary logistic loss of every row's recognition logit, the first num_pos rows labelled 1
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
-    double v = 0.0;
-    if (r < n) {
-      const double x = (double)a.obj[r], off = x < 0.0 ? x : 0.0;
-      v = log(exp(off) + exp(off - x)) - off;
-      if (r >= np) v = v + x;
+  if (a.obj != nullptr) {
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
+      double v = 0.0;
+      if (r < n) {
+        const double x = (double)a.obj[r], off = x < 0.0 ? x : 0.0;
+        v = log(exp(off) + exp(off - x)) - off;
+        if (r >= np) v = v + x;
+      }
+      buf[r] = v;
     }
-    buf[r] = v;
+    const double eo = lt_tree_sum(buf, tid);
+    out[2] = n > 0 ? (double)a.w_end_obj * (eo / (double)n) : 0.0;
   }
-  const double eo = lt_tree_sum(buf, tid);
-  out[2] = n > 0 ? (double)a.w_end_obj * (eo / (double)n) : 0.0;
   // end box regression: the final transforms of the positive rows against their RoI boxes' inverse transform
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
-    double v = 0.0;
-    if (r < np) {
-      int m = 0;
-      v = lt_box_row(a.roi_boxes + (size_t)r * 4, a.final_trans + (size_t)r * 4, a.gt + (size_t)a.pos_target_idx[r] * 4, &m);
-      if (m) atomicAdd(&s_masked[1], 1);
+  if (a.roi_boxes != nullptr) {
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) {
+      double v = 0.0;
+      if (r < np) {
+        int m = 0;
+        v = lt_box_row(a.roi_boxes + (size_t)r * 4, a.final_trans + (size_t)r * 4, a.gt + (size_t)a.pos_target_idx[r] * 4, &m);
+        if (m) atomicAdd(&s_masked[1], 1);
+      }
+      buf[r] = v;
     }
-    buf[r] = v;
+    const double eb = lt_tree_sum(buf, tid);
+    out[3] = np > 0 ? (double)a.w_end_box * (eb / (4.0 * (double)np)) : 0.0;
   }
-  const double eb = lt_tree_sum(buf, tid);
-  out[3] = np > 0 ? (double)a.w_end_box * (eb / (4.0 * (double)np)) : 0.0;
   // captioning: -sum of the rows' log-likelihoods over num_pos * (L + 2) (batch and time average)
-  for (int r = tid; r < LT_ROWS; r += LT_THREADS) buf[r] = r < np ? -a.rowlik[r] : 0.0;
-  const double cap = lt_tree_sum(buf, tid);
-  out[4] = np > 0 ? (double)a.w_cap * (cap / ((double)np * (double)(a.L + 2))) : 0.0;
+  if (a.rowlik != nullptr) {
+    for (int r = tid; r < LT_ROWS; r += LT_THREADS) buf[r] = r < np ? -a.rowlik[r] : 0.0;
+    const double cap = lt_tree_sum(buf, tid);
+    out[4] = np > 0 ? (double)a.w_cap * (cap / ((double)np * (double)(a.L + 2))) : 0.0;
+  }
   out[5] = (((out[0] + out[1]) + out[2]) + out[3]) + out[4];
   if (tid == 0) {
     for (int d = 0; d < 6; ++d) a.out[d] = out[d];

@@ -382,36 +382,48 @@ def box_sampler(ctx, boxes, gt, img_h, img_w, forced_pos=None, forced_neg=None, 
     return out
 
 
+def _train_args(who, ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump, on_device, opts):
+    """What forward_losses, loss_gradients and forward_backward hand to the library alike: (their C arguments up to the dump,
+    the DcLosses the call fills, the dump's three lists or None, (H, W), batch_size, the objects the pointers point into)."""
+    g = _f32(gt_boxes).reshape(-1, 4)
+    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
+    if lab.ndim != 2 or len(lab) != len(g):
+        raise ValueError("%s: gt_labels must be (G, L) with one row per ground-truth box" % who)
+    o = loss_opts(**opts)
+    f, keep = _forced_lists(forced_pos, forced_neg)
+    out = _lib.DcLosses()
+    cap = max(int(o.batch_size), 1)
+    lists = [np.zeros(cap, np.int32) for _ in range(3)] if dump else None
+    d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists]) if dump else None
+    if not on_device:
+        img = np.ascontiguousarray(img, dtype=np.float32)
+    H, W = int(img.shape[1]), int(img.shape[2])
+    args = (ctx.h, img.ptr if on_device else img.ctypes.data, H, W, 1 if on_device else 0, g.ctypes.data, lab.ctypes.data, len(g),
+            lab.shape[1], C.byref(o), C.byref(f) if f is not None else None, C.byref(out), C.byref(d) if d is not None else None)
+    return args, out, lists, (H, W), cap, (img, g, lab, o, f, keep, d)
+
+
+def _train_result(out, lists):
+    """The losses, the counts and (with a dump) the three lists of a training call's result."""
+    res = {k: float(getattr(out, k)) for k in LOSS_KEYS}
+    res.update({k: int(getattr(out, k)) for k in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
+    if lists is not None:
+        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
+                   neg_input_idx=lists[2][:out.num_neg].copy())
+    return res
+
+
+
 def forward_losses(ctx, img, gt_boxes, gt_labels, forced_pos=None, forced_neg=None, dump=False, on_device=False, **opts):
     """The validation losses of one image (dc_forward_losses; docs/SEMANTICS.md, "Validation losses") on a ctx with weights
     loaded.  img: (3,H,W) float32 host array, or with on_device an ops.DeviceArray; gt_boxes (G,4) xcycwh in the resized frame;
     gt_labels (G,L) int32, words then zeros.  Returns a dict with the reference's six keys (float), the sampler's counts
     (num_pos, num_neg, total_pos, total_neg, masked_mid, masked_end, flags) and, with dump, its three index lists."""
-    g = _f32(gt_boxes).reshape(-1, 4)
-    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
-    if lab.ndim != 2 or len(lab) != len(g):
-        raise ValueError("forward_losses: gt_labels must be (G, L) with one row per ground-truth box")
-    o = loss_opts(**opts)
-    f, keep = _forced_lists(forced_pos, forced_neg)
-    out = _lib.DcLosses()
-    d = None
-    if dump:
-        lists = [np.zeros(int(o.batch_size), np.int32) for _ in range(3)]
-        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
-    if on_device:
-        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
-    else:
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
-    check(ctx.h, ctx.lib.dc_forward_losses(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
-                                           len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
-                                           C.byref(out), C.byref(d) if d is not None else None), "dc_forward_losses")
-    res = {k: float(getattr(out, k)) for k in LOSS_KEYS}
-    res.update({k: int(getattr(out, k)) for k in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
-    if dump:
-        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
-                   neg_input_idx=lists[2][:out.num_neg].copy())
-    return res
+    args, out, lists, _hw, _cap, _keep = _train_args("forward_losses", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
+                                                    on_device, opts)
+    check(ctx.h, ctx.lib.dc_forward_losses(*args), "dc_forward_losses")
+    return _train_result(out, lists)
+
 
 
 def check_localize_args(nms_thresh, max_regions, min_objectness):
@@ -628,6 +640,29 @@ def recog_grad(ctx, feat_chw, roi_boxes, num_pos, target_boxes, img_h, img_w, dc
     return out
 
 
+def _grad_bufs(ctx, dims, h, w, cap):
+    """Device buffers of the recognition and language-model gradients for up to cap rows, and the two structs over them."""
+    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
+    rbufs = _recog_bufs(ctx, D, h, w, cap)
+    lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
+               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)}
+    lbufs = {k: ctx.empty(lshapes[k]) for k in LM_GRAD_KEYS}
+    rg = _lib.DcRecogGrads(**{k: v.ptr for k, v in rbufs.items()})
+    return rbufs, lbufs, rg, _lib.DcLmGrads(**{k: v.ptr for k, v in lbufs.items()})
+
+
+def _grad_out(ctx, out, rbufs, lbufs, D):
+    """The host arrays of _grad_bufs after a call that sampled out.num_pos + out.num_neg rows."""
+    n = out.num_pos + out.num_neg
+    if n == 0:
+        rbufs["roi_boxes"] = ctx.to_device(np.zeros((1, 4), np.float32))
+    res = _recog_out(rbufs, n)
+    res.update({k: b.numpy() for k, b in lbufs.items()})
+    res["codes"] = res["codes"][:out.num_pos] if out.num_pos > 0 else np.zeros((0, D), np.float32)
+    return res
+
+
+
 def loss_gradients(ctx, img, gt_boxes, gt_labels, forced_pos=None, forced_neg=None, dump=False, on_device=False, **opts):
     """dc_loss_gradients: the losses of forward_losses (same arguments, same numbers) and the gradient of end_objectness +
     end_box_reg + captioning with respect to every parameter downstream of the RPN.  Returns forward_losses' dict plus the eight
@@ -637,47 +672,15 @@ def loss_gradients(ctx, img, gt_boxes, gt_labels, forced_pos=None, forced_neg=No
     dims = getattr(ctx, "lm_dims", None)
     if dims is None:
         raise _lib.DenseCapError("ops.loss_gradients: the ctx carries no model dimensions (build a DenseCapModel on it first)")
-    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
-    g = _f32(gt_boxes).reshape(-1, 4)
-    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
-    if lab.ndim != 2 or len(lab) != len(g):
-        raise ValueError("loss_gradients: gt_labels must be (G, L) with one row per ground-truth box")
-    o = loss_opts(**opts)
-    f, keep = _forced_lists(forced_pos, forced_neg)
-    out = _lib.DcLosses()
-    d = None
-    if dump:
-        lists = [np.zeros(max(int(o.batch_size), 1), np.int32) for _ in range(3)]
-        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
-    if on_device:
-        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
-    else:
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
+    args, out, lists, (H, W), cap, _keep = _train_args("loss_gradients", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
+                                                      on_device, opts)
     h, w = feature_size(ctx, H, W)
-    cap = max(int(o.batch_size), 1)
-    rbufs = _recog_bufs(ctx, D, h, w, cap)
-    lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
-               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)}
-    lbufs = {k: ctx.empty(lshapes[k]) for k in LM_GRAD_KEYS}
-    rg = _lib.DcRecogGrads(**{k: v.ptr for k, v in rbufs.items()})
-    lg = _lib.DcLmGrads(**{k: v.ptr for k, v in lbufs.items()})
-    check(ctx.h, ctx.lib.dc_loss_gradients(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
-                                           len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
-                                           C.byref(out), C.byref(d) if d is not None else None, C.byref(rg), C.byref(lg)),
-          "dc_loss_gradients")
-    res = {k: float(getattr(out, k)) for k in LOSS_KEYS}
-    res.update({k: int(getattr(out, k)) for k in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
-    if dump:
-        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
-                   neg_input_idx=lists[2][:out.num_neg].copy())
-    n = out.num_pos + out.num_neg
-    if n == 0:
-        rbufs["roi_boxes"] = ctx.to_device(np.zeros((1, 4), np.float32))
-    res.update(_recog_out(rbufs, n))
-    res.update({k: b.numpy() for k, b in lbufs.items()})
-    res["codes"] = res["codes"][:out.num_pos] if out.num_pos > 0 else np.zeros((0, D), np.float32)
+    rbufs, lbufs, rg, lg = _grad_bufs(ctx, dims, h, w, cap)
+    check(ctx.h, ctx.lib.dc_loss_gradients(*args, C.byref(rg), C.byref(lg)), "dc_loss_gradients")
+    res = _train_result(out, lists)
+    res.update(_grad_out(ctx, out, rbufs, lbufs, dims["D"]))
     return res
+
 
 
 def wgrad(ctx, A, B):
@@ -852,54 +855,23 @@ def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY,
     gradient -- with `feat` now their sum, the complete grad_cnn_features."""
     dims = getattr(ctx, "lm_dims", None)
     k, R = _rpn_dims(ctx, "forward_backward")
-    E, Hd, D, V = dims["E"], dims["Hd"], dims["D"], dims["V"]
-    g = _f32(gt_boxes).reshape(-1, 4)
-    lab = np.ascontiguousarray(gt_labels, dtype=np.int32)
-    if lab.ndim != 2 or len(lab) != len(g):
-        raise ValueError("forward_backward: gt_labels must be (G, L) with one row per ground-truth box")
-    o = loss_opts(**opts)
-    f, keep = _forced_lists(forced_pos, forced_neg)
-    out = _lib.DcLosses()
-    d = None
-    if dump:
-        lists = [np.zeros(max(int(o.batch_size), 1), np.int32) for _ in range(3)]
-        d = _lib.DcLossDump(*[a.ctypes.data_as(_lib.c_int32_p) for a in lists])
-    if on_device:
-        ptr, H, W = img.ptr, img.shape[1], img.shape[2]
-    else:
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        ptr, H, W = img.ctypes.data, img.shape[1], img.shape[2]
+    args, out, lists, (H, W), cap, _keep = _train_args("forward_backward", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
+                                                      on_device, opts)
     h, w = feature_size(ctx, H, W)
-    cap = max(int(o.batch_size), 1)
-    rbufs = _recog_bufs(ctx, D, h, w, cap)
-    lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
-               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)}
-    lbufs = {n: ctx.empty(lshapes[n]) for n in LM_GRAD_KEYS}
+    rbufs, lbufs, rg, lg = _grad_bufs(ctx, dims, h, w, cap)
     pbufs = _rpn_bufs(ctx, k, R, h, w)
-    rg = _lib.DcRecogGrads(**{n: v.ptr for n, v in rbufs.items()})
-    lg = _lib.DcLmGrads(**{n: v.ptr for n, v in lbufs.items()})
     pg = _lib.DcRpnGrads(**{n: v.ptr for n, v in pbufs.items()})
-    check(ctx.h, ctx.lib.dc_forward_backward(ctx.h, ptr, int(H), int(W), 1 if on_device else 0, g.ctypes.data, lab.ctypes.data,
-                                             len(g), lab.shape[1], C.byref(o), C.byref(f) if f is not None else None,
-                                             C.byref(out), C.byref(d) if d is not None else None, C.byref(rg), C.byref(lg),
-                                             float(box_reg_decay), C.byref(pg)), "dc_forward_backward")
-    res = {n: float(getattr(out, n)) for n in LOSS_KEYS}
-    res.update({n: int(getattr(out, n)) for n in ("num_pos", "num_neg", "total_pos", "total_neg", "masked_mid", "masked_end", "flags")})
-    if dump:
-        res.update(pos_input_idx=lists[0][:out.num_pos].copy(), pos_target_idx=lists[1][:out.num_pos].copy(),
-                   neg_input_idx=lists[2][:out.num_neg].copy())
-    n = out.num_pos + out.num_neg
-    if n == 0:
-        rbufs["roi_boxes"] = ctx.to_device(np.zeros((1, 4), np.float32))
-    res.update(_recog_out(rbufs, n))
-    res.update({n_: b.numpy() for n_, b in lbufs.items()})
-    res["codes"] = res["codes"][:out.num_pos] if out.num_pos > 0 else np.zeros((0, D), np.float32)
+    check(ctx.h, ctx.lib.dc_forward_backward(*args, C.byref(rg), C.byref(lg), float(box_reg_decay), C.byref(pg)),
+          "dc_forward_backward")
+    res = _train_result(out, lists)
+    res.update(_grad_out(ctx, out, rbufs, lbufs, dims["D"]))
     res["feat_roi"] = res["feat"]
-    res.update({n_: b.numpy() for n_, b in pbufs.items() if n_ != "feat"})
+    res.update({n: b.numpy() for n, b in pbufs.items() if n != "feat"})
     res["feat"] = np.ascontiguousarray(pbufs["feat"].numpy().transpose(2, 0, 1))
     share, _ms = rpn_grad_kept(ctx, h * w)
     res["feat_rpn"] = np.ascontiguousarray(share.reshape(h, w, 512).transpose(2, 0, 1))
     return res
+
 
 
 def rpn_dheads(ctx, trans, scores, anchors, boxes, h, w, k, pos_input_idx, pos_target_idx, neg_input_idx, gt, droi=None,

@@ -244,7 +244,8 @@ typedef struct dc_loss_dump { int32_t* pos_input_idx; int32_t* pos_target_idx; i
  * The result does not depend on num_proposals, lanes, groups, caption order or beam size, and the call leaves every setting
  * as it found it.  Anything outside the ranges above is refused (DC_E_INVALID; G > 512: DC_E_UNSUPPORTED) before anything is
  * enqueued; forced lists that give more than batch_size rows in all are DC_E_INVALID.
- * Stage-wise test hooks, read with dc_debug_fetch after a call: "loss_rpn_boxes", "loss_rpn_anchors", "loss_rpn_trans" (A,4),
+ * Stage-wise test hooks, read with dc_debug_fetch after a call that completed its forward (dc_loss_gradients and
+ * dc_forward_backward run the same one and leave the same): "loss_rpn_boxes", "loss_rpn_anchors", "loss_rpn_trans" (A,4),
  * "loss_rpn_scores" (A,2) float; "loss_obj" (n), "loss_final_trans" (n,4), "loss_roi_boxes" (n,4), "loss_codes" (n,fc_dim)
  * float of the n sampled rows; "loss_rowlik" (num_pos) double, every positive row's caption log-likelihood; "loss_stage_ms" 5 float: trunk + RPN, match + assign + draw,
  * RoI pool + fc, paired scoring, loss terms. */
@@ -579,7 +580,9 @@ int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const flo
  * their ground-truth boxes with weight = captioning_weight (lg: its seven tensors, all required; lg->codes may be NULL), then
  * dc_op_recog_grad's backward with those code gradients (rg: all ten required; feat is (h, w, 512) for dc_feature_size(H, W),
  * roi_boxes (num_pos + num_neg, 4) -- batch_size rows of room).  With no sampled row (num_pos + num_neg == 0) or no positive the
- * corresponding gradients are zero.  Synchronous. */
+ * corresponding gradients are zero.  Every argument, dc_forward_losses' included, is refused before anything is allocated or
+ * launched, with dc_forward_losses' codes and texts; the message begins with this function's name (dc_forward_backward: with
+ * its own), not with "dc_forward_losses:".  Synchronous. */
 int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                       const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                       dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg);
@@ -620,8 +623,8 @@ int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32
                    const float* droi_boxes_or_null, int img_h, int img_w, const dc_loss_opts* opts_or_null, float box_reg_decay,
                    const dc_rpn_grads* out, double* mid_objectness_loss, double* mid_box_reg_loss, int32_t* masked_mid);
 /* DenseCapModel:forward_backward with the reference's default -finetune_cnn_after -1: dc_loss_gradients (same arguments; out, rg
- * and lg are that call's bits), then dc_op_rpn_grad's backward on what that call left -- lane 0's feature map and RPN hidden map,
- * the RPN rows, the sampler's lists and rg->roi_boxes as droi_boxes.  pg: the six RPN tensors and feat (h, w, 512), the TOTAL
+ * and lg are that call's bits), then dc_op_rpn_grad's backward on what the forward left on the device -- lane 0's feature map
+ * and RPN hidden map, the RPN rows, the sampler's lists, the ground truth -- and rg->roi_boxes as droi_boxes.  pg: the six RPN tensors and feat (h, w, 512), the TOTAL
  * grad_cnn_features = rg->feat + the RPN's share, one fp32 add per element (LocalizationLayer.lua:550,581,601); rg->feat keeps RoI
  * pooling's share.  box_reg_decay: train_opts.lua's -box_reg_decay (5e-5 there).  With no sampled row the RPN gradients are the
  * decay term's alone.  Together the three structs hold the gradient of all five criteria and the decay with respect to all 21

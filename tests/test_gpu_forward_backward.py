@@ -118,6 +118,114 @@ def test_two_calls_give_identical_bits(run):
         assert np.array_equal(_bits(again[k]), _bits(res[k])), k
 
 
+def _assert_same_result(a, b):
+    """Every key of two result dicts: arrays by dtype, shape and bytes, scalars by value."""
+    assert set(a) == set(b)
+    for k, v in a.items():
+        if isinstance(v, np.ndarray):
+            assert v.dtype == b[k].dtype and v.shape == b[k].shape and v.tobytes() == b[k].tobytes(), k
+        else:
+            assert _bits(np.float64(v)) == _bits(np.float64(b[k])), k
+
+
+def test_the_forward_record_is_per_call(run):
+    """A training forward at another size (another map, another A) and a test forward in between leave nothing behind."""
+    from densecap_amd.weights import make_synthetic_image
+    m, W, img, gt, lab, res, feat = run
+    m.forward_losses(make_synthetic_image(64, 96, 2), np.array([[40, 30, 30, 24]], F32), np.ones((1, 1), np.int32), **OPTS)
+    m.forward_test(img)
+    _assert_same_result(m.forward_backward(img, gt, lab, box_reg_decay=DECAY, dump=True, **OPTS), res)
+
+
+def fetch_loss_names(m, num_pos, num_neg):
+    """Every "loss_*" array of dc_debug_fetch, and loss_stage_ms."""
+    A, n = m.num_anchors * MAP[0] * MAP[1], num_pos + num_neg
+    shapes = {"loss_rpn_boxes": (A, 4), "loss_rpn_anchors": (A, 4), "loss_rpn_trans": (A, 4), "loss_rpn_scores": (A, 2), "loss_obj": (n,),
+              "loss_final_trans": (n, 4), "loss_roi_boxes": (n, 4), "loss_codes": (n, m.fc_dim)}
+    out = {}
+    for k, s in shapes.items():
+        out[k], count = m.debug_fetch(k, s)
+        assert count == int(np.prod(s)), k
+    out["loss_rowlik"], count = m.debug_fetch("loss_rowlik", (num_pos,), np.float64)
+    assert count == num_pos
+    out["loss_stage_ms"], count = m.debug_fetch("loss_stage_ms", (5,))
+    assert count == 5
+    return out
+
+
+def test_the_fetch_names_hold_the_same_bits_after_every_entry_point(run):
+    m, W, img, gt, lab, res, feat = run
+    first = None
+    for call in (m.forward_losses, m.loss_gradients, m.forward_backward):
+        r = call(img, gt, lab, **OPTS)
+        got = fetch_loss_names(m, r["num_pos"], r["num_neg"])
+        ms = got.pop("loss_stage_ms")
+        assert ms.shape == (5,) and np.isfinite(ms).all() and (ms >= 0).all(), call.__name__
+        first = first or got
+        for k in got:
+            assert got[k].size > 0 and got[k].tobytes() == first[k].tobytes(), (call.__name__, k)
+
+
+def test_no_sampled_row_means_zero_gradients_and_forward_losses_numbers(run):
+    """Both forced lists empty, box_reg_decay = 0 (the decay term is decay * trans on every RPN row, sampled or not: it alone
+    would be left in the RPN's gradients)."""
+    m, W, img, gt, lab, res, feat = run
+    empty = dict(forced_pos=[], forced_neg=[])
+    a = m.forward_backward(img, gt, lab, box_reg_decay=0.0, dump=True, **empty, **OPTS)
+    fl = m.forward_losses(img, gt, lab, **empty, **OPTS)
+    assert a["num_pos"] == a["num_neg"] == 0
+    for k in RR.TENSORS + G.TENSORS + R.RPN_PARAMS + ("feat", "feat_roi", "feat_rpn"):
+        assert (a[k] == 0).all(), k
+    for k in LR.LOSS_KEYS:
+        assert _bits(np.float64(a[k])) == _bits(np.float64(fl[k])), k
+
+
+SENTINEL = np.float32(-7.5)
+# the refusals of dc_forward_backward's own arguments and of the calls it used to nest: what, the error code
+FB_REFUSALS = (("decay", -1), ("gt_w0", -1), ("G0", -5), ("G513", -5))
+
+
+def forward_backward_refusals(m, img, gt, lab):
+    """dc_forward_backward with one bad argument at a time on sentinel-filled outputs: ({what: code}, every output buffer still
+    holds the sentinel)."""
+    import ctypes as C
+    from densecap_amd import _lib, ops
+    ctx, k, Rh, D, E, Hd, V = m.ctx, m.num_anchors, m.ctx.lm_dims["R"], m.fc_dim, m.ctx.lm_dims["E"], m.ctx.lm_dims["Hd"], m.vocab_size
+    h, w = MAP
+    cap = OPTS["batch_size"]
+    shapes = [{"fc6_w": (D, 512 * 49), "fc6_b": (D,), "fc7_w": (D, D), "fc7_b": (D,), "obj_w": (1, D), "obj_b": (1,), "boxreg_w": (4, D),
+               "boxreg_b": (4,), "feat": (h, w, 512), "roi_boxes": (cap, 4)},
+              {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
+               "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (cap, D)},
+              {"rpn_conv_w": (Rh, 512, 3, 3), "rpn_conv_b": (Rh,), "rpn_box_w": (4 * k, Rh), "rpn_box_b": (4 * k,),
+               "rpn_score_w": (2 * k, Rh), "rpn_score_b": (2 * k,), "feat": (h, w, 512)}]
+    bufs = [{n: ctx.to_device(np.full(s, SENTINEL, F32)) for n, s in sh.items()} for sh in shapes]
+    rg, lg, pg = (T(**{n: b.ptr for n, b in bs.items()}) for T, bs in zip((_lib.DcRecogGrads, _lib.DcLmGrads, _lib.DcRpnGrads), bufs))
+    o = ops.loss_opts(**OPTS)
+    img = np.ascontiguousarray(img, F32)
+    lab513 = np.ones((513, lab.shape[1]), np.int32)
+    gt513 = np.tile(gt, (130, 1))[:513].copy()
+    bad_gt = gt.copy()
+    bad_gt[1, 2] = 0.0
+
+    def call(g=gt, labels=lab, G=len(gt), decay=DECAY):
+        out = _lib.DcLosses()
+        g, labels = np.ascontiguousarray(g, F32), np.ascontiguousarray(labels, np.int32)
+        return ctx.lib.dc_forward_backward(ctx.h, img.ctypes.data, H, WD, 0, g.ctypes.data, labels.ctypes.data, G, labels.shape[1],
+                                           C.byref(o), None, C.byref(out), None, C.byref(rg), C.byref(lg), float(decay), C.byref(pg))
+    codes = {"decay": call(decay=-1e-3), "gt_w0": call(g=bad_gt), "G0": call(G=0), "G513": call(g=gt513, labels=lab513, G=513)}
+    untouched = all(np.array_equal(_bits(b.numpy()), _bits(np.full(sh[n], SENTINEL, F32)))
+                    for sh, bs in zip(shapes, bufs) for n, b in bs.items())
+    return codes, untouched
+
+
+def test_refusals_of_the_outer_call_come_before_any_launch_and_leave_the_outputs_alone(run):
+    m, W, img, gt, lab, res, feat = run
+    codes, untouched = forward_backward_refusals(m, img, gt, lab)
+    assert codes == dict(FB_REFUSALS) and untouched
+    _assert_same_result(m.forward_backward(img, gt, lab, box_reg_decay=DECAY, dump=True, **OPTS), res)     # the context works on
+
+
 def test_a_gradient_step_lowers_the_float64_loss_as_first_order_predicts(run):
     """W' = W - eta g on the six RPN tensors, g the DEVICE's gradient, the lists held: the float64 restated loss mid_objectness +
     mid_box_reg + 0.5 decay |trans|^2 + <droi, boxes> drops by eta |g|^2 within 10 %.  eta is halved until the restatement itself,

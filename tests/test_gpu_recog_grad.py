@@ -175,23 +175,34 @@ def test_two_calls_give_identical_bits(case):
 
 
 def test_losses_are_forward_losses_numbers_for_the_same_rows():
-    """The forward half goes through dc_forward_losses' own calls: on its sampled rows (dump) the two end losses are its bits."""
+    """The forward half goes through dc_forward_losses' own calls, and loss_terms skips the terms an op gives no inputs for: on
+    dc_forward_losses' sampled rows (dump) and feature map the two end losses and their masked count are its bits, and so are
+    dc_op_rpn_grad's two mid losses and theirs.  In the second case every positive row is masked in both box terms: the ground-truth
+    boxes are 1e5 times as tall, as wide or both as any anchor, thresholds 0 / 0 (every input that overlaps anything is positive)."""
     from densecap_amd import ops
     from densecap_amd.weights import make_synthetic_image
     m, W = _model("minimal")
     img = make_synthetic_image(IMG[0], IMG[1], 3)
-    rng = np.random.default_rng(4)
-    gt = R.draw_boxes(rng, 3, IMG[0], IMG[1], MAP[0], MAP[1])
     lab = np.ones((3, 1), np.int32)
-    fl = m.forward_losses(img, gt, lab, dump=True, batch_size=16)
-    n = fl["num_pos"] + fl["num_neg"]
-    feat, boxes = np.zeros((MAP[0], MAP[1], 512), F32), np.zeros((n, 4), F32)
-    assert m.ctx.lib.dc_debug_fetch(m.ctx.h, b"feat_hwc", feat.ctypes.data, feat.nbytes) == feat.size
-    assert m.ctx.lib.dc_debug_fetch(m.ctx.h, b"loss_roi_boxes", boxes.ctypes.data, boxes.nbytes) == boxes.size
-    feat = feat.transpose(2, 0, 1)
-    rg = ops.recog_grad(m.ctx, feat, boxes[:n], fl["num_pos"], gt[fl["pos_target_idx"]], IMG[0], IMG[1], batch_size=16)
-    assert rg["end_objectness_loss"] == fl["end_objectness_loss"] and rg["end_box_reg_loss"] == fl["end_box_reg_loss"]
-    assert rg["masked_end"] == fl["masked_end"]
+    for masked in (False, True):
+        gt = R.draw_boxes(np.random.default_rng(4), 3, IMG[0], IMG[1], MAP[0], MAP[1])
+        opts = dict(batch_size=16)
+        if masked:
+            gt[:] = [[IMG[1] / 2, IMG[0] / 2, 40, 724e5], [IMG[1] / 2, IMG[0] / 2, 724e5, 40], [IMG[1] / 2, IMG[0] / 2, 724e5, 724e5]]
+            opts.update(high_thresh=0.0, low_thresh=0.0)
+        fl = m.forward_losses(img, gt, lab, dump=True, **opts)
+        n = fl["num_pos"] + fl["num_neg"]
+        feat, boxes = np.zeros((MAP[0], MAP[1], 512), F32), np.zeros((n, 4), F32)
+        assert m.ctx.lib.dc_debug_fetch(m.ctx.h, b"feat_hwc", feat.ctypes.data, feat.nbytes) == feat.size
+        assert m.ctx.lib.dc_debug_fetch(m.ctx.h, b"loss_roi_boxes", boxes.ctypes.data, boxes.nbytes) == boxes.size
+        feat = feat.transpose(2, 0, 1)
+        rg = ops.recog_grad(m.ctx, feat, boxes[:n], fl["num_pos"], gt[fl["pos_target_idx"]], IMG[0], IMG[1], **opts)
+        assert rg["end_objectness_loss"] == fl["end_objectness_loss"] and rg["end_box_reg_loss"] == fl["end_box_reg_loss"]
+        assert rg["masked_end"] == fl["masked_end"]
+        pg = ops.rpn_grad(m.ctx, feat, fl["pos_input_idx"], fl["pos_target_idx"], fl["neg_input_idx"], gt, IMG[0], IMG[1], **opts)
+        assert pg["mid_objectness_loss"] == fl["mid_objectness_loss"] and pg["mid_box_reg_loss"] == fl["mid_box_reg_loss"]
+        assert pg["masked_mid"] == fl["masked_mid"]
+        assert (fl["masked_mid"] >= 1 and fl["masked_end"] >= 1) == masked and fl["num_pos"] >= 1
 
 
 def test_refusals_come_before_any_launch():
