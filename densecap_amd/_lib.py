@@ -107,6 +107,11 @@ class DcRpnGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "feat")]
 
 
+class DcTrainOpts(C.Structure):
+    """dc_train_opts: Adam's settings and the L2 weight decay (train_opts.lua's defaults: 1e-5, 0.9, 0.999, 1e-8, 1e-6)."""
+    _fields_ = [(n, C.c_double) for n in ("learning_rate", "beta1", "beta2", "epsilon", "weight_decay")]
+
+
 class DcBeamStdState(C.Structure):
     """dc_beam_std_state (include/densecap_debug_beam.h): dc_beam_state plus len."""
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
@@ -241,6 +246,12 @@ _SIGS = {
     "dc_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
                                       C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads), C.c_float, C.POINTER(DcRpnGrads)]),
+    "dc_train_begin": (C.c_int, [C.c_void_p, C.POINTER(DcTrainOpts)]),
+    "dc_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump), C.c_float]),
+    "dc_train_end": (C.c_int, [C.c_void_p]),
+    "dc_get_weights": (C.c_int, [C.c_void_p, C.POINTER(DcWeights)]),
+    "dc_op_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(DcTrainOpts)]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -294,6 +305,13 @@ _RPN_HOOK_SIGS = {
     "dc_debug_rpn_heads_bwd": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "dc_debug_rpn_grad_kept": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_float_p]),
 }
+# the hooks of include/densecap_debug_optim.h (the optimiser's kernels; bound like the others)
+_OPTIM_HOOK_SIGS = {
+    "dc_debug_adam_multi": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_size_t), C.c_int, C.c_int,
+                                                                                   C.POINTER(DcTrainOpts), C.c_int]),
+    "dc_debug_screen_operands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dc_debug_unpack_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -310,7 +328,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
-                                  list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items())):
+                                  list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

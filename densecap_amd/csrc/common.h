@@ -14,6 +14,7 @@
 #include "../../include/densecap_debug_recog.h"
 #include "../../include/densecap_debug_bwd.h"
 #include "../../include/densecap_debug_rpn.h"
+#include "../../include/densecap_debug_optim.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -594,6 +595,27 @@ hipError_t launch_rpn_dheads(const RpnDheadsArgs& a, hipStream_t s);
 // dhidden (P, R) = (hidden > 0) * (dheads (P, K6) . W (K6, R)), fp32 in ascending K6 order; K6 <= 12288
 hipError_t launch_rpn_heads_bwd(const float* dheads, const float* W, const float* hidden, int P, int K6, int R, float* dhidden,
                                 hipStream_t s);
+
+// ---- the optimiser (optim.hip; docs/SEMANTICS.md, "Training step") ----
+// One segment of an Adam launch: p, m, v (n floats each) are updated in place from g; chunk0 = adam_chunks of the segments in
+// front of it.  The table on the device holds nseg + 1 entries: the last one carries the total in chunk0 and nothing else.
+struct AdamSeg {
+  float* p; const float* g; float* m; float* v;
+  size_t n;
+  unsigned long long chunk0;
+};
+// The step's scalars, each computed in double on the host and rounded to float once: b1 = beta1, c1 = 1 - beta1, b2 = beta2,
+// c2 = 1 - beta2, eps, wd = weight_decay, nstep = -(lr * sqrt(1 - beta2^t) / (1 - beta1^t))
+struct AdamScalars { float b1, c1, b2, c2, eps, wd, nstep; };
+unsigned long long adam_chunks(size_t n);
+// grid_or_0: 0 = the production grid (min(chunks, 2048) workgroups); > 0: that many (a test hook: the result does not depend on it)
+hipError_t launch_adam_multi(const AdamSeg* seg_dev, int nseg, unsigned long long chunks, const AdamScalars& k, int grid_or_0,
+                             hipStream_t s);
+// The decode screen's operands from W (V1, Hd) fp32: wb (V1pad, Kp) bf16 bits, zero padded; wn (V1pad) the rows' 2-norms rounded
+// up to fp16, zero past V1
+hipError_t launch_screen_operands(const float* W, int V1, int Hd, int V1pad, int Kp, uint16_t* wb, uint16_t* wn, hipStream_t s);
+// launch_pack_conv3x3's inverse: (Cout, 9 Cin) with k = tap * Cin + c -> OIHW
+hipError_t launch_unpack_conv3x3(const float* packed, float* oihw, int Cout, int Cin, hipStream_t s);
 
 // ---- image preprocessing (preprocess.hip; run_model.lua:67-74) -------------------------------------------------------
 void preprocess_scaled_size(int H0, int W0, int image_size, int* oh, int* ow);

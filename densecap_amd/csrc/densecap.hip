@@ -262,6 +262,20 @@ struct dc_ctx {
   KeptBuf loss_ws{scratch};
   TrainFwd train;
   int32_t* row_ramp = nullptr;           // 0, 1 .. 1023 on the device, made on first need (dc_op_recog_grad's pos_target_idx)
+  // the training step (dc_train_begin .. dc_train_end): the options and the step count; the gradient arena and the
+  // two moments (one carve list, three blocks: train_arena_carve); the OIHW master of the RPN convolution; the feat / roi_boxes
+  // outputs the stages insist on (grow only); the segment table on the device (optim_tab: dc_op_adam's and the hook's own);
+  // the event split of the last step (backward, Adam launch, refresh; dc_debug_fetch "train_step_ms")
+  bool training = false;
+  bool fc6_grad_engine = false;          // recog_backward leaves fc6's weight gradient in the engine's (i, j, c) order (dc_train_step)
+  dc_train_opts train_opts{};
+  int train_t = 0;
+  KeptBuf train_g{scratch}, train_m{scratch}, train_v{scratch}, train_master{scratch}, train_out{scratch}, train_tab{scratch};
+  KeptBuf optim_tab{scratch};
+  int train_nseg = 0;
+  unsigned long long train_chunks = 0;
+  hipEvent_t train_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float train_ms[3] = {0, 0, 0};
   // MFMA profile
   bool prof = false;
   std::vector<ProfEvt> prof_pending;
@@ -1794,6 +1808,7 @@ void dc_destroy(dc_ctx* ctx) {
   for (void* p : ctx->owned) hipFree(p);
   for (hipEvent_t e : ctx->recog_ev) if (e) hipEventDestroy(e);
   for (hipEvent_t e : ctx->rpn_ev) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : ctx->train_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
   delete ctx;                 // (the kept buffers free themselves here)
 }
@@ -2390,6 +2405,16 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     static_cast<int32_t*>(host_buf)[0] = ctx->lm_parts;
     static_cast<int32_t*>(host_buf)[1] = (int32_t)ctx->lm_screened;
     return 2;
+  }
+  if (strcmp(name, "train_step_ms") == 0) {          // the last dc_train_step: backward (the three stages), Adam launch, refresh
+    if (capacity_bytes < 12) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    memcpy(host_buf, ctx->train_ms, 12);
+    return 3;
+  }
+  if (strcmp(name, "train_t") == 0) {
+    if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    *static_cast<int32_t*>(host_buf) = ctx->training ? ctx->train_t : -1;
+    return 1;
   }
   if (strcmp(name, "scratch") == 0) {
     if (capacity_bytes < 24) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
@@ -3571,8 +3596,12 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
       DCCHK(run_gemm(ctx, g, s));
     }
     KCHK(launch_relu_mask(r.dx7, in.fc6_out, (size_t)n * D, s));
-    KCHK(launch_wgrad(r.dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, r.dw6, kRecogK6, r.ws, s));
-    KCHK(launch_permute_fc6_back(r.dw6, out.fc6_w, D, 512, 49, s));
+    if (ctx->fc6_grad_engine) {        // the training step updates fc6 where it lives: its gradient stays in the engine's order
+      KCHK(launch_wgrad(r.dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, out.fc6_w, kRecogK6, r.ws, s));
+    } else {
+      KCHK(launch_wgrad(r.dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, r.dw6, kRecogK6, r.ws, s));
+      KCHK(launch_permute_fc6_back(r.dw6, out.fc6_w, D, 512, 49, s));
+    }
     KCHK(launch_colsum(r.dx7, D, n, D, out.fc6_b, s));
     HIPCHK(hipEventRecord(ev[1], s));
     {
@@ -4283,6 +4312,314 @@ int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg) {
   return train_call(ctx, TRAIN_ARGS("dc_forward_backward"), 3, rg, lg, box_reg_decay, pg);
+}
+// ---- the training step (docs/SEMANTICS.md, "Training step") ----------------------------------------------------------
+namespace {
+// The trained tensors as the Adam launch sees them: 17 segments for the checkpoint's 21 tensors.  A segment's parameter is the
+// ctx's own engine buffer wherever that is the checkpoint layout, a concatenation of checkpoint layouts (the fused heads) or a
+// permutation of one tensor (fc6): Adam is elementwise.  The two exceptions: lstm_w lives in lstm_w_ck (the engine reads the
+// transposed halves made of it) and the RPN convolution in an OIHW master (the engine reads the packed form made of it).
+struct TrainArena {
+  float *rpn_conv_w = nullptr, *rpn_conv_b = nullptr, *heads_w = nullptr, *heads_b = nullptr, *fc6_w = nullptr, *fc6_b = nullptr;
+  float *fc7_w = nullptr, *fc7_b = nullptr, *head5_w = nullptr, *head5_b = nullptr, *enc_w = nullptr, *enc_b = nullptr, *emb = nullptr;
+  float *lstm_w = nullptr, *lstm_b = nullptr, *out_w = nullptr, *out_b = nullptr;
+};
+struct TrainSeg { float* TrainArena::*slot; float* p; size_t n; };
+void train_segments(const dc_ctx* ctx, std::vector<TrainSeg>& out) {
+  const size_t k = ctx->k, R = ctx->R, D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
+  out = {{&TrainArena::rpn_conv_w, static_cast<float*>(ctx->train_master.get()), R * 512 * 9},
+          {&TrainArena::rpn_conv_b, ctx->rpn_b, R},
+          {&TrainArena::heads_w, ctx->heads_w, 6 * k * R},         // rpn_box_w (4k, R), then rpn_score_w (2k, R)
+          {&TrainArena::heads_b, ctx->heads_b, 6 * k},
+          {&TrainArena::fc6_w, ctx->fc6_w, D * kRecogK6},          // the engine's (i, j, c) input order: gradient and moments too
+          {&TrainArena::fc6_b, ctx->fc6_b, D},
+          {&TrainArena::fc7_w, ctx->fc7_w, D * D},
+          {&TrainArena::fc7_b, ctx->fc7_b, D},
+          {&TrainArena::head5_w, ctx->head5_w, 5 * D},             // obj_w (D), then boxreg_w (4, D)
+          {&TrainArena::head5_b, ctx->head5_b, 5},
+          {&TrainArena::enc_w, ctx->enc_w, E * D},
+          {&TrainArena::enc_b, ctx->enc_b, E},
+          {&TrainArena::emb, ctx->emb, (V + 2) * E},
+          {&TrainArena::lstm_w, ctx->lstm_w_ck, (E + Hd) * 4 * Hd},
+          {&TrainArena::lstm_b, ctx->lstm_b, 4 * Hd},
+          {&TrainArena::out_w, ctx->dec_w, (V + 1) * Hd},          // the lm_out_w rows of dec_w
+          {&TrainArena::out_b, ctx->out_b, V + 1}};
+}
+// the arena's carve list (the gradients'; the two moments' blocks are carved by the same list): bytes with base == null
+size_t train_arena_carve(const std::vector<TrainSeg>& segs, TrainArena& a, void* base) {
+  std::vector<Carve> cv;
+  for (const TrainSeg& sg : segs) cv.push_back({(void**)&(a.*(sg.slot)), sg.n * 4});
+  return carve(cv, base);
+}
+int check_train_opts(dc_ctx* ctx, const dc_train_opts* o, const char* who) {
+  if (!o) return ctx->fail(DC_E_INVALID, "%s: null options", who);
+  if (!std::isfinite(o->learning_rate) || o->learning_rate < 0) return ctx->fail(DC_E_INVALID, "%s: learning_rate must be finite and >= 0", who);
+  if (!(o->beta1 >= 0 && o->beta1 < 1) || !(o->beta2 >= 0 && o->beta2 < 1)) return ctx->fail(DC_E_INVALID, "%s: beta1 and beta2 must lie in [0, 1)", who);
+  if (!std::isfinite(o->epsilon) || !(o->epsilon > 0)) return ctx->fail(DC_E_INVALID, "%s: epsilon must be finite and > 0", who);
+  if (!std::isfinite(o->weight_decay) || o->weight_decay < 0) return ctx->fail(DC_E_INVALID, "%s: weight_decay must be finite and >= 0", who);
+  return DC_OK;
+}
+// The scalars of step t >= 1: each computed in double and rounded to float once (optim_updates.lua:56-84 computes them in double too)
+AdamScalars adam_scalars(const dc_train_opts& o, int t) {
+  const double step = o.learning_rate * std::sqrt(1.0 - std::pow(o.beta2, (double)t)) / (1.0 - std::pow(o.beta1, (double)t));
+  return {(float)o.beta1, (float)(1.0 - o.beta1), (float)o.beta2, (float)(1.0 - o.beta2), (float)o.epsilon, (float)o.weight_decay,
+          -(float)step};
+}
+// A segment table on the device (tab grows to hold it): nseg entries and the closing one; *chunks = the launch's work items
+int upload_adam_table(dc_ctx* ctx, KeptBuf& tab, hipStream_t s, std::vector<AdamSeg>& segs, unsigned long long* chunks) {
+  unsigned long long c = 0;
+  for (AdamSeg& e : segs) { e.chunk0 = c; c += adam_chunks(e.n); }
+  segs.push_back({nullptr, nullptr, nullptr, nullptr, 0, c});
+  HIPCHK(tab.grow(segs.size() * sizeof(AdamSeg), s));
+  HIPCHK(hipMemcpy(tab.get(), segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice));
+  *chunks = c;
+  return DC_OK;
+}
+void train_release(dc_ctx* ctx) {
+  for (KeptBuf* b : {&ctx->train_g, &ctx->train_m, &ctx->train_v, &ctx->train_master, &ctx->train_out, &ctx->train_tab}) b->reset();
+  ctx->training = false;
+  ctx->train_t = 0;
+  ctx->train_nseg = 0;
+  ctx->train_chunks = 0;
+}
+// Every operand the library derives from a trained weight, remade on s from the updated parameters (the list: DESIGN.md §19).
+// Pointers do not move, so a captured forward stays valid and weights_epoch stays where it is; the gradient side's copies
+// (out_wT, enc_wT; fc7_wT, fc6_wT; the RPN's flipped weights) are remade by their owners before their next use.  xg comes from
+// the GEMM dc_load_weights runs, in fp32 whatever dc_set_math_mode says.
+int train_refresh(dc_ctx* ctx, hipStream_t s) {
+  const int R = ctx->R, V = ctx->V, E = ctx->E, Hd = ctx->Hd;
+  KCHK(launch_pack_conv3x3(static_cast<const float*>(ctx->train_master.get()), ctx->rpn_w, R, 512, s));
+  KCHK(launch_transpose2d(ctx->lstm_w_ck, ctx->wxT, E, 4 * Hd, s));
+  KCHK(launch_transpose2d(ctx->lstm_w_ck + (size_t)E * 4 * Hd, ctx->whT, Hd, 4 * Hd, s));
+  {
+    Fp32Guard fp32(ctx->cfg);        // xg as a ctx makes it that loads its weights before the math mode is switched
+    DCCHK(linear(ctx, s, ctx->emb, ctx->wxT, ctx->lstm_b, ctx->xg, V + 2, 4 * Hd, E, 0));
+  }
+  HIPCHK(hipMemcpyAsync(ctx->dec_w + (size_t)ctx->V1pad * Hd, ctx->whT, (size_t)4 * Hd * Hd * 4, hipMemcpyDeviceToDevice, s));
+  KCHK(launch_screen_operands(ctx->dec_w, V + 1, Hd, ctx->V1pad, ctx->scr_Kp, ctx->scr_w, ctx->scr_wnorm, s));
+  for (const auto& e : ctx->planes)
+    if (e.planes != nullptr && (e.W == ctx->fc6_w || e.W == ctx->fc7_w || e.W == ctx->dec_w)) KCHK(launch_split_planes(e.W, e.planes, e.rows, e.K, s));
+  ctx->grad_epoch = ctx->recog_epoch = ctx->rpn_epoch = 0;     // (weights_epoch >= 1 once weights are loaded)
+  return DC_OK;
+}
+}  // namespace
+
+int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts) {
+  const char* who = "dc_train_begin";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (ctx->training) return ctx->fail(DC_E_STATE, "%s: already training; dc_train_end first", who);
+  DCCHK(check_train_opts(ctx, opts, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  auto body = [&]() -> int {
+    const size_t wn = (size_t)ctx->R * 512 * 9;
+    HIPCHK(ctx->train_master.grow(wn * 4, s));
+    KCHK(launch_unpack_conv3x3(ctx->rpn_w, static_cast<float*>(ctx->train_master.get()), ctx->R, 512, s));
+    std::vector<TrainSeg> segs;
+    train_segments(ctx, segs);
+    TrainArena g, m, v;
+    const size_t bytes = train_arena_carve(segs, g, nullptr);
+    HIPCHK(ctx->train_g.grow(bytes, s));
+    HIPCHK(ctx->train_m.grow(bytes, s));
+    HIPCHK(ctx->train_v.grow(bytes, s));
+    HIPCHK(hipMemsetAsync(ctx->train_m.get(), 0, bytes, s));
+    HIPCHK(hipMemsetAsync(ctx->train_v.get(), 0, bytes, s));
+    train_arena_carve(segs, g, ctx->train_g.get());
+    train_arena_carve(segs, m, ctx->train_m.get());
+    train_arena_carve(segs, v, ctx->train_v.get());
+    std::vector<AdamSeg> tab;
+    for (const TrainSeg& sg : segs) tab.push_back({sg.p, g.*(sg.slot), m.*(sg.slot), v.*(sg.slot), sg.n, 0});
+    DCCHK(upload_adam_table(ctx, ctx->train_tab, s, tab, &ctx->train_chunks));
+    ctx->train_nseg = (int)segs.size();
+    for (hipEvent_t& e : ctx->train_ev)
+      if (e == nullptr) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipStreamSynchronize(s));
+    return DC_OK;
+  };
+  const int rc = body();
+  if (rc != DC_OK) { (void)hipStreamSynchronize(s); train_release(ctx); return rc; }
+  ctx->train_opts = *opts;
+  ctx->train_t = 0;
+  ctx->training = true;
+  return DC_OK;
+}
+
+int dc_train_end(dc_ctx* ctx) {
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "dc_train_end: not training");
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  train_release(ctx);
+  return DC_OK;
+}
+
+int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                  const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                  dc_losses* out, const dc_loss_dump* dump, float box_reg_decay) {
+  const char* who = "dc_train_step";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: dc_train_begin first", who);
+  const TrainCall c = TRAIN_ARGS(who);
+  // what sizes the outputs below is checked here; train_call then checks everything, in dc_forward_backward's order
+  DCCHK(check_forward_args(ctx, c));
+  int fh = 1, fw = 1;
+  feature_size(H, W, &fh, &fw);
+  DCCHK(check_rpn_grad_shape(ctx, fh, fw, box_reg_decay, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  std::vector<TrainSeg> segs;
+  train_segments(ctx, segs);
+  TrainArena g;
+  train_arena_carve(segs, g, ctx->train_g.get());
+  float *feat_rg = nullptr, *feat_pg = nullptr, *roi = nullptr;
+  const std::vector<Carve> cv = {{(void**)&feat_rg, (size_t)fh * fw * 512 * 4}, {(void**)&feat_pg, (size_t)fh * fw * 512 * 4},
+                                 {(void**)&roi, (size_t)c.o.batch_size * 16}};
+  HIPCHK(ctx->train_out.grow(carve(cv, nullptr), s));
+  carve(cv, ctx->train_out.get());
+  const size_t k = ctx->k, R = ctx->R, D = ctx->D;
+  const dc_recog_grads rg = {g.fc6_w, g.fc6_b, g.fc7_w, g.fc7_b, g.head5_w, g.head5_b, g.head5_w + D, g.head5_b + 1, feat_rg, roi};
+  const dc_lm_grads lg = {g.enc_w, g.enc_b, g.emb, g.lstm_w, g.lstm_b, g.out_w, g.out_b, nullptr};
+  const dc_rpn_grads pg = {g.rpn_conv_w, g.rpn_conv_b, g.heads_w, g.heads_b, g.heads_w + 4 * k * R, g.heads_b + 4 * k, feat_pg};
+  hipEvent_t* ev = ctx->train_ev;
+  HIPCHK(hipEventRecord(ev[0], s));
+  ctx->fc6_grad_engine = true;
+  const int rc = train_call(ctx, c, 3, &rg, &lg, box_reg_decay, &pg);
+  ctx->fc6_grad_engine = false;
+  if (rc != DC_OK) return rc;                      // no weight and no t has changed
+  const AdamScalars k1 = adam_scalars(ctx->train_opts, ctx->train_t + 1);
+  auto body = [&]() -> int {
+    HIPCHK(hipEventRecord(ev[1], s));
+    KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_tab.get()), ctx->train_nseg, ctx->train_chunks, k1, 0, s));
+    HIPCHK(hipEventRecord(ev[2], s));
+    DCCHK(train_refresh(ctx, s));
+    HIPCHK(hipEventRecord(ev[3], s));
+    return DC_OK;
+  };
+  ctx->train_t += 1;                               // (from the launch on the weights are step t's, whatever fails after it)
+  const int rc2 = call_finish(ctx, s, body(), who, true);
+  if (rc2 != DC_OK) return rc2;
+  for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ctx->train_ms[i], ev[i], ev[i + 1]);
+  return DC_OK;
+}
+
+int dc_get_weights(dc_ctx* ctx, const dc_weights* out) {
+  const char* who = "dc_get_weights";
+  if (!ctx || !out) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  const size_t k = ctx->k, R = ctx->R, D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
+  auto d2h = [&](const float* dst, const float* dev, size_t n) -> int {
+    if (dst != nullptr) HIPCHK(hipMemcpy(const_cast<float*>(dst), dev, n * 4, hipMemcpyDeviceToHost));
+    return DC_OK;
+  };
+  // a packed convolution through a call's scratch: unpack, then copy
+  auto conv_out = [&](const float* dst, const float* packed, int Cout, int Cin) -> int {
+    if (dst == nullptr) return DC_OK;
+    Scratch tmp(ctx->scratch, s);
+    HIPCHK(tmp.alloc((size_t)Cout * Cin * 9 * 4));
+    KCHK(launch_unpack_conv3x3(packed, static_cast<float*>(tmp.get()), Cout, Cin, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return d2h(dst, static_cast<const float*>(tmp.get()), (size_t)Cout * Cin * 9);
+  };
+  DCCHK(d2h(out->conv_w[0], ctx->conv_w[0], (size_t)64 * 27));
+  for (int i = 0; i < DC_NUM_VGG_CONVS; ++i) {
+    if (i > 0) DCCHK(conv_out(out->conv_w[i], ctx->conv_w[i], kVgg[i].cout, kVgg[i].cin));
+    DCCHK(d2h(out->conv_b[i], ctx->conv_b[i], kVgg[i].cout));
+  }
+  DCCHK(conv_out(out->rpn_conv_w, ctx->rpn_w, (int)R, 512));
+  DCCHK(d2h(out->rpn_conv_b, ctx->rpn_b, R));
+  DCCHK(d2h(out->rpn_box_w, ctx->heads_w, 4 * k * R));
+  DCCHK(d2h(out->rpn_score_w, ctx->heads_w + 4 * k * R, 2 * k * R));
+  DCCHK(d2h(out->rpn_box_b, ctx->heads_b, 4 * k));
+  DCCHK(d2h(out->rpn_score_b, ctx->heads_b + 4 * k, 2 * k));
+  if (out->fc6_w != nullptr) {
+    if (D > 65535) return ctx->fail(DC_E_UNSUPPORTED, "%s: fc_dim = %d: the fc6 permutation takes at most 65535 rows", who, (int)D);
+    Scratch tmp(ctx->scratch, s);
+    HIPCHK(tmp.alloc(D * kRecogK6 * 4));
+    KCHK(launch_permute_fc6_back(ctx->fc6_w, static_cast<float*>(tmp.get()), (int)D, 512, 49, s));
+    HIPCHK(hipStreamSynchronize(s));
+    DCCHK(d2h(out->fc6_w, static_cast<const float*>(tmp.get()), D * kRecogK6));
+  }
+  DCCHK(d2h(out->fc6_b, ctx->fc6_b, D));
+  DCCHK(d2h(out->fc7_w, ctx->fc7_w, D * D));
+  DCCHK(d2h(out->fc7_b, ctx->fc7_b, D));
+  DCCHK(d2h(out->obj_w, ctx->head5_w, D));
+  DCCHK(d2h(out->obj_b, ctx->head5_b, 1));
+  DCCHK(d2h(out->boxreg_w, ctx->head5_w + D, 4 * D));
+  DCCHK(d2h(out->boxreg_b, ctx->head5_b + 1, 4));
+  DCCHK(d2h(out->lm_enc_w, ctx->enc_w, E * D));
+  DCCHK(d2h(out->lm_enc_b, ctx->enc_b, E));
+  DCCHK(d2h(out->lm_emb, ctx->emb, (V + 2) * E));
+  DCCHK(d2h(out->lstm_w, ctx->lstm_w_ck, (E + Hd) * 4 * Hd));
+  DCCHK(d2h(out->lstm_b, ctx->lstm_b, 4 * Hd));
+  DCCHK(d2h(out->lm_out_w, ctx->dec_w, (V + 1) * Hd));
+  DCCHK(d2h(out->lm_out_b, ctx->out_b, V + 1));
+  DCCHK(d2h(out->anchors, ctx->anchors, 2 * k));
+  return DC_OK;
+}
+
+static int adam_segments_run(dc_ctx* ctx, const char* who, std::vector<AdamSeg>& tab, int t, const dc_train_opts* opts, int grid) {
+  DCCHK(check_train_opts(ctx, opts, who));
+  if (t < 1) return ctx->fail(DC_E_INVALID, "%s: t counts from 1 (got %d)", who, t);
+  for (const AdamSeg& e : tab)
+    if (!e.p || !e.g || !e.m || !e.v || e.n < 1) return ctx->fail(DC_E_INVALID, "%s: a segment needs four buffers and n >= 1", who);
+  if (grid < 0 || grid > 65535) return ctx->fail(DC_E_INVALID, "%s: grid must be in 0..65535", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  const int nseg = (int)tab.size();
+  unsigned long long chunks = 0;
+  DCCHK(upload_adam_table(ctx, ctx->optim_tab, s, tab, &chunks));
+  auto body = [&]() -> int {
+    KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->optim_tab.get()), nseg, chunks, adam_scalars(*opts, t), grid, s));
+    return DC_OK;
+  };
+  return call_finish(ctx, s, body(), who);
+}
+
+int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, int t, const dc_train_opts* opts) {
+  if (!ctx) return DC_E_INVALID;
+  std::vector<AdamSeg> tab = {{p, g, m, v, n, 0}};
+  return adam_segments_run(ctx, "dc_op_adam", tab, t, opts, 0);
+}
+
+// ---- test hooks of the optimiser's kernels (densecap_debug_optim.h) ----------------------------------------------------------------
+int dc_debug_adam_multi(dc_ctx* ctx, float* const* p, const float* const* g, float* const* m, float* const* v, const size_t* n,
+                        int nseg, int t, const dc_train_opts* opts, int grid) {
+  const char* who = "dc_debug_adam_multi";
+  if (!ctx) return DC_E_INVALID;
+  if (!p || !g || !m || !v || !n || nseg < 1 || nseg > 4096) return ctx->fail(DC_E_INVALID, "%s: 1..4096 segments, five lists", who);
+  std::vector<AdamSeg> tab;
+  for (int i = 0; i < nseg; ++i) tab.push_back({p[i], g[i], m[i], v[i], n[i], 0});
+  return adam_segments_run(ctx, who, tab, t, opts, grid);
+}
+int dc_debug_screen_operands(dc_ctx* ctx, const float* W, int V1, int Hd, int V1pad, int Kp, uint16_t* wb, uint16_t* wn) {
+  const char* who = "dc_debug_screen_operands";
+  if (!ctx) return DC_E_INVALID;
+  if (!W || !wb || !wn || V1 < 1 || Hd < 1 || V1pad < V1 || Kp < Hd) return ctx->fail(DC_E_INVALID, "%s: bad argument", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  auto body = [&]() -> int { KCHK(launch_screen_operands(W, V1, Hd, V1pad, Kp, wb, wn, s)); return DC_OK; };
+  return call_finish(ctx, s, body(), who);
+}
+int dc_debug_unpack_conv3x3(dc_ctx* ctx, const float* w_packed, float* w_oihw, int Cout, int Cin) {
+  const char* who = "dc_debug_unpack_conv3x3";
+  if (!ctx) return DC_E_INVALID;
+  if (!w_packed || !w_oihw || Cout < 1 || Cin < 1) return ctx->fail(DC_E_INVALID, "%s: bad argument", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  auto body = [&]() -> int { KCHK(launch_unpack_conv3x3(w_packed, w_oihw, Cout, Cin, s)); return DC_OK; };
+  return call_finish(ctx, s, body(), who);
 }
 #undef TRAIN_ARGS
 

@@ -133,7 +133,7 @@ def read_dataset(data_h5, data_json, split, max_images):
     d = read_hdf5(data_h5, names=("boxes", "labels", "img_to_first_box", "img_to_last_box", "split"))
     with open(data_json) as f:
         info = json.load(f)
-    want = {"val": 1, "test": 2}[split]
+    want = {"train": 0, "val": 1, "test": 2}[split]
     out = []
     for ix in np.flatnonzero(np.asarray(d["split"]).reshape(-1) == want):
         r0, r1 = int(d["img_to_first_box"][ix]), int(d["img_to_last_box"][ix])          # 1-based, inclusive

@@ -175,6 +175,15 @@ class DenseCapModel:
         self.ctx.lm_dims = dict(E=int(w.enc_size), Hd=int(w.rnn_size), D=int(w.fc_dim), V=self.vocab_size, k=int(w.num_anchors),
                                 R=int(w.rpn_hidden))   # ops.lm_grad, ops.recog_grad, ops.rpn_grad: their buffers
         self._keep = []
+        # what get_weights needs to hand the weights back in the shapes they came in, and the keys it passes through
+        self._weight_shapes = {n: tuple(_np32(weights[n]).shape) for n in
+                               ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "fc6_w", "fc6_b",
+                                "fc7_w", "fc7_b", "obj_w", "obj_b", "boxreg_w", "boxreg_b", "lm_enc_w", "lm_enc_b", "lm_emb", "lstm_w",
+                                "lstm_b", "lm_out_w", "lm_out_b", "anchors")}
+        self._weight_shapes["conv_w"] = [tuple(_np32(a).shape) for a in weights["conv_w"]]
+        self._weight_shapes["conv_b"] = [tuple(_np32(a).shape) for a in weights["conv_b"]]
+        self._weight_meta = {"field_centers": tuple(float(v) for v in weights["field_centers"]), "vocab_size": self.vocab_size,
+                             "seq_length": self.seq_length, "idx_to_token": self.idx_to_token}
         self._push_test_args()
 
     # ---- reference API ---------------------------------------------------------------------
@@ -582,7 +591,7 @@ class DenseCapModel:
         the six losses and the counts, the eight recognition tensors (fc6_w, fc6_b, fc7_w, fc7_b, obj_w, obj_b, boxreg_w,
         boxreg_b) and the seven language-model tensors in checkpoint layouts, `feat` (512, h, w) -- RoI pooling's share of the
         feature map's gradient, the reference's layout --, `roi_boxes` (num_pos + num_neg, 4) and `codes` (num_pos, fc_dim), the
-        language model's gradient of the positive codes.  The CNN backward and an optimiser are not built; the loaded weights do not
+        language model's gradient of the positive codes.  The CNN backward is not built; the loaded weights do not
         change."""
         from . import ops
         return ops.loss_gradients(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
@@ -594,9 +603,46 @@ class DenseCapModel:
         checkpoint layouts -- the two mid criteria and box_reg_decay (train_opts.lua:42) through the sampler's backward, the
         heads and the RPN's convolution.  `feat` (512, h, w) is now the complete grad_cnn_features, `feat_roi` and `feat_rpn`
         its two shares.  Together: the gradient of all five criteria with respect to all 21 tensors outside the CNN.  The CNN
-        backward and an optimiser are not built; the loaded weights do not change."""
+        backward is not built; the loaded weights do not change (train_step is the call that updates them)."""
         from . import ops
         return ops.forward_backward(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, **opts)
+
+    # ---- training (docs/SEMANTICS.md, "Training step") ----------------------------------------------------------------------
+    def train_begin(self, **opts):
+        """dc_train_begin: Adam's moments (zero) and the gradient arena for the 21 tensors outside the CNN; the step count
+        starts at 0.  opts: learning_rate 1e-5, beta1 0.9, beta2 0.999, epsilon 1e-8, weight_decay 1e-6 (train_opts.lua)."""
+        from . import ops
+        ops.train_begin(self.ctx, **opts)
+
+    def train_step(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, **opts):
+        """One iteration of train.lua's loop body (train.lua:163-185) on one image: forward_backward (same arguments; the dict
+        returned holds its six losses and the counts, for the weights as they were), grad_params:add(weight_decay, params), adam
+        (optim_updates.lua:56-84) on the device, and the refresh of everything derived from a trained weight.  Dropout is the
+        identity; the CNN is not trained."""
+        from . import ops
+        return ops.train_step(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, **opts)
+
+    def train_end(self):
+        """dc_train_end: frees the moments and the arena; the weights stay as trained."""
+        from . import ops
+        ops.train_end(self.ctx)
+
+    def get_weights(self, conv=True):
+        """The current weights as a dict in the keys of densecap_amd/weights.py (dc_get_weights), float32 numpy arrays in the
+        shapes the model was built from; conv=False leaves the 13 CNN layers out (they are not trained)."""
+        from . import ops
+        W = ops.get_weights(self.ctx, self._weight_shapes, conv=conv)
+        W.update(self._weight_meta)
+        W["test_args"] = dict(test_clip_boxes=bool(self.nets.localization_layer.test_clip_boxes),
+                              test_nms_thresh=float(self.nets.localization_layer.test_nms_thresh),
+                              test_max_proposals=int(self.nets.localization_layer.test_max_proposals),
+                              final_nms_thresh=float(self.opt["final_nms_thresh"]))
+        return W
+
+    def save_checkpoint(self, path):
+        """torch.save(path, {model = ...}) of the current weights (t7.checkpoint_from_weights, t7.save)."""
+        from . import t7
+        t7.save(path, t7.checkpoint_from_weights(self.get_weights()))
 
     def lm_gradients(self, codes, labels, weight=1.0):
         """The captioning loss of n (fc7 code, caption) pairs and its gradients with respect to the seven language-model tensors

@@ -872,6 +872,122 @@ def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY,
     res["feat_rpn"] = np.ascontiguousarray(share.reshape(h, w, 512).transpose(2, 0, 1))
     return res
 
+# ---- the training step (docs/SEMANTICS.md, "Training step") -----------------------------------------------------------------------
+TRAIN_DEFAULTS = dict(learning_rate=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=1e-6)      # train_opts.lua
+
+
+def train_opts(**kw):
+    """A filled DcTrainOpts (train_opts.lua's defaults).  Unknown keys raise; the library checks the values."""
+    unknown = set(kw) - set(TRAIN_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown training option(s): %s" % ", ".join(sorted(unknown)))
+    o = dict(TRAIN_DEFAULTS, **kw)
+    return _lib.DcTrainOpts(*[float(o[k]) for k in ("learning_rate", "beta1", "beta2", "epsilon", "weight_decay")])
+
+
+def adam(ctx, p, g, m, v, t, offset=0, guard=8, **opts):
+    """The Adam kernel alone (dc_op_adam) on copies of the float32 vectors p, g, m, v: step t >= 1.  offset: floats by which
+    every buffer is shifted off its 16-byte aligned allocation; guard: floats of a known pattern kept on both sides of every
+    buffer.  Returns (p, m, v, g_after, guards_intact)."""
+    arrs = [_f32(a).reshape(-1) for a in (p, g, m, v)]
+    n = len(arrs[0])
+    if any(len(a) != n for a in arrs):
+        raise ValueError("adam: p, g, m, v differ in length")
+    o = train_opts(**opts)
+    pad = np.float32(-7.25)
+    bufs = []
+    for a in arrs:
+        host = np.full(offset + guard + n + guard, pad, np.float32)
+        host[offset + guard:offset + guard + n] = a
+        bufs.append(ctx.to_device(host))
+    at = lambda b: C.c_void_p(b.ptr.value + 4 * (offset + guard))
+    check(ctx.h, ctx.lib.dc_op_adam(ctx.h, at(bufs[0]), at(bufs[1]), at(bufs[2]), at(bufs[3]), n, int(t), C.byref(o)), "dc_op_adam")
+    outs = [b.numpy() for b in bufs]
+    body = lambda h: h[offset + guard:offset + guard + n].copy()
+    intact = all((h[:offset + guard] == pad).all() and (h[offset + guard + n:] == pad).all() for h in outs)
+    return body(outs[0]), body(outs[2]), body(outs[3]), body(outs[1]), intact
+
+
+def adam_multi(ctx, segments, t, grid=0, **opts):
+    """dc_debug_adam_multi: `segments` is a list of (p, g, m, v) float32 vectors, updated in ONE launch as dc_train_step issues
+    it.  Returns the list of (p, m, v) after the step."""
+    o = train_opts(**opts)
+    dev = [[ctx.to_device(_f32(a).reshape(-1)) for a in seg] for seg in segments]
+    ns = len(dev)
+    cols = [(C.c_void_p * ns)(*[d[j].ptr for d in dev]) for j in range(4)]
+    sizes = (C.c_size_t * ns)(*[d[0].shape[0] for d in dev])
+    check(ctx.h, ctx.lib.dc_debug_adam_multi(ctx.h, cols[0], cols[1], cols[2], cols[3], sizes, ns, int(t), C.byref(o), int(grid)),
+          "dc_debug_adam_multi")
+    return [(d[0].numpy(), d[2].numpy(), d[3].numpy()) for d in dev]
+
+
+def screen_operands(ctx, W):
+    """dc_debug_screen_operands on W (V1, Hd) float32: (wb (V1pad, Kp) uint16 bf16 bits, wn (V1pad) uint16 fp16 bits) with the
+    padding the library uses (screen_pads)."""
+    W = _f32(W)
+    V1, Hd = W.shape
+    V1pad, Kp = (V1 + 63) // 64 * 64, (Hd + 63) // 64 * 64
+    wd = ctx.to_device(W)
+    wb = ctx.to_device(np.full((V1pad, Kp), 0xAAAA, np.uint16)); wn = ctx.to_device(np.full((V1pad,), 0xAAAA, np.uint16))
+    check(ctx.h, ctx.lib.dc_debug_screen_operands(ctx.h, wd.ptr, V1, Hd, V1pad, Kp, wb.ptr, wn.ptr), "dc_debug_screen_operands")
+    return wb.numpy(), wn.numpy()
+
+
+def unpack_conv3x3(ctx, w_packed, Cout, Cin):
+    """dc_debug_unpack_conv3x3: (Cout, 9 Cin) packed -> (Cout, Cin, 3, 3)."""
+    wd = ctx.to_device(_f32(w_packed).reshape(Cout, 9 * Cin))
+    out = ctx.empty((Cout, Cin, 3, 3))
+    check(ctx.h, ctx.lib.dc_debug_unpack_conv3x3(ctx.h, wd.ptr, out.ptr, int(Cout), int(Cin)), "dc_debug_unpack_conv3x3")
+    return out.numpy()
+
+
+def train_begin(ctx, **opts):
+    """dc_train_begin: allocate the moments and the gradient arena, t = 0.  opts: the keys of TRAIN_DEFAULTS."""
+    o = train_opts(**opts)
+    check(ctx.h, ctx.lib.dc_train_begin(ctx.h, C.byref(o)), "dc_train_begin")
+
+
+def train_step(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY, forced_pos=None, forced_neg=None, dump=False,
+               on_device=False, **opts):
+    """dc_train_step: forward_backward's losses for the weights as they were (same arguments, the same numbers; no gradient
+    leaves the device), then the Adam update of the 21 tensors outside the CNN and the refresh of what is derived from them."""
+    args, out, lists, _hw, _cap, _keep = _train_args("train_step", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
+                                                    on_device, opts)
+    check(ctx.h, ctx.lib.dc_train_step(*args, float(box_reg_decay)), "dc_train_step")
+    return _train_result(out, lists)
+
+
+def train_end(ctx):
+    check(ctx.h, ctx.lib.dc_train_end(ctx.h), "dc_train_end")
+
+
+def train_step_ms(ctx):
+    """The library's event split of the last train_step in ms: backward (the three stages), the Adam launch, the refresh."""
+    ms = np.zeros(3, np.float32)
+    check(ctx.h, ctx.lib.dc_debug_fetch(ctx.h, b"train_step_ms", ms.ctypes.data, ms.nbytes), "dc_debug_fetch")
+    return dict(zip(("backward", "adam", "refresh"), (float(x) for x in ms)))
+
+
+WEIGHT_KEYS = ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b",
+               "obj_w", "obj_b", "boxreg_w", "boxreg_b", "lm_enc_w", "lm_enc_b", "lm_emb", "lstm_w", "lstm_b", "lm_out_w", "lm_out_b")
+
+
+def get_weights(ctx, shapes, conv=True):
+    """dc_get_weights: the ctx's current weights in checkpoint layouts.  shapes: {name: shape} for WEIGHT_KEYS and "anchors",
+    "conv_w" / "conv_b" lists of 13 shapes (read only with conv).  Returns a dict of float32 arrays (conv_w / conv_b: lists)."""
+    w = _lib.DcWeights()
+    out = {}
+    for name in WEIGHT_KEYS + ("anchors",):
+        out[name] = np.empty(tuple(shapes[name]), np.float32)
+        setattr(w, name, out[name].ctypes.data_as(_lib.c_float_p))
+    if conv:
+        out["conv_w"] = [np.empty(tuple(sh), np.float32) for sh in shapes["conv_w"]]
+        out["conv_b"] = [np.empty(tuple(sh), np.float32) for sh in shapes["conv_b"]]
+        for i in range(_lib.DC_NUM_VGG_CONVS):
+            w.conv_w[i] = out["conv_w"][i].ctypes.data_as(_lib.c_float_p)
+            w.conv_b[i] = out["conv_b"][i].ctypes.data_as(_lib.c_float_p)
+    check(ctx.h, ctx.lib.dc_get_weights(ctx.h, C.byref(w)), "dc_get_weights")
+    return out
 
 
 def rpn_dheads(ctx, trans, scores, anchors, boxes, h, w, k, pos_input_idx, pos_target_idx, neg_input_idx, gt, droi=None,

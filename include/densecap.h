@@ -567,8 +567,7 @@ int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C,
  * feat buffers are indexed by them (the lane's buffers are sized from img_h, img_w and batch_size).  DC_E_INVALID before any
  * launch: n outside 1..1024, num_pos outside 0..n, n > batch_size, a null output, positive rows without target boxes, an image
  * side below 32 px, bad sampler options; DC_E_UNSUPPORTED: h * w > 65536, or scratch above 8 GiB.  The scratch (0.45 GB at the
- * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the CNN backward,
- * any optimiser. */
+ * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the CNN backward. */
 typedef struct dc_recog_grads {
   float* fc6_w; float* fc6_b; float* fc7_w; float* fc7_b; float* obj_w; float* obj_b; float* boxreg_w; float* boxreg_b; float* feat; float* roi_boxes;
 } dc_recog_grads;
@@ -628,11 +627,41 @@ int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32
  * grad_cnn_features = rg->feat + the RPN's share, one fp32 add per element (LocalizationLayer.lua:550,581,601); rg->feat keeps RoI
  * pooling's share.  box_reg_decay: train_opts.lua's -box_reg_decay (5e-5 there).  With no sampled row the RPN gradients are the
  * decay term's alone.  Together the three structs hold the gradient of all five criteria and the decay with respect to all 21
- * tensors outside the CNN.  Not here: the CNN's backward, any optimiser.  Synchronous. */
+ * tensors outside the CNN.  Not here: the CNN's backward (the optimiser: dc_train_step).  Synchronous. */
 int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                         const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg);
+/* ---- training step (docs/SEMANTICS.md, "Training step") ----
+ * The other half of train.lua's loop body (train.lua:163-185) on the device: grad_params:add(weight_decay, params), then
+ * adam(params, grad_params, learning_rate, beta1, beta2, epsilon) (optim_updates.lua:56-84) on the 21 tensors outside the CNN, in
+ * place, in one launch.  train_opts.lua's defaults: 1e-5, 0.9, 0.999, 1e-8, weight_decay 1e-6. */
+typedef struct dc_train_opts { double learning_rate, beta1, beta2, epsilon, weight_decay; } dc_train_opts;
+/* Needs loaded weights (DC_E_STATE).  Allocates the two moments, zeroed, and a gradient arena for the 21 tensors (three times the
+ * trained parameters' bytes; fc6's three live in the engine's (i, j, c) input order), makes an OIHW master of the RPN convolution,
+ * sets t = 0.  DC_E_INVALID before anything is allocated: a negative or non-finite learning_rate, beta1 or beta2 outside [0, 1),
+ * epsilon <= 0 or non-finite, a negative or non-finite weight_decay.  A second begin without dc_train_end: DC_E_STATE. */
+int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts);
+/* One iteration on one image: dc_forward_backward into the arena (same arguments, checked by the same checker; out and dump are
+ * that call's bits for the weights as they were BEFORE the step), t += 1, the Adam launch, then every operand the library derives
+ * from a trained weight is remade on the device (the list: DESIGN.md section 19), so that every later call -- forward, scoring,
+ * sampling, either math mode, a captured graph: weight pointers do not move -- computes what a fresh ctx loaded with
+ * dc_get_weights' arrays computes.  A refused step changes no weight and no t.  Before dc_train_begin: DC_E_STATE.  Dropout is
+ * the identity, as in dc_forward_backward; the CNN is not trained.  Eager on lane 0, synchronous. */
+int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                  const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                  dc_losses* out, const dc_loss_dump* dump, float box_reg_decay);
+/* Frees the moments, the arena and the master; the weights stay as trained.  Without a begin: DC_E_STATE. */
+int dc_train_end(dc_ctx* ctx);
+/* The current weights in the checkpoint's layouts: every non-null tensor pointer of `out` (HOST memory, the sizes of
+ * dc_load_weights) is filled -- fc6 permuted back, the fused heads split, the packed convolutions unpacked; a null pointer is
+ * skipped (conv_w[i] / conv_b[i] may be: the CNN is not trained).  The dimension fields and field_centers of `out` are ignored.
+ * Straight after dc_load_weights it returns the loaded arrays bit for bit. */
+int dc_get_weights(dc_ctx* ctx, const dc_weights* out);
+/* The Adam kernel alone on caller-supplied DEVICE buffers of n floats as one segment: step t >= 1 of the update above; p, m and
+ * v are updated in place, g is read only.  Any alignment (4-byte).  The same refusals for opts as dc_train_begin; n < 1 or
+ * t < 1: DC_E_INVALID.  Synchronous. */
+int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, int t, const dc_train_opts* opts);
 /* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
  * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */

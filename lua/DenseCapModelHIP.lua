@@ -302,7 +302,7 @@ end
 -- of the RPN (dc_loss_gradients; docs/SEMANTICS.md, "Recognition-net gradients").  data and opts as forward_losses.  Returns
 -- forward_backward's loss keys, num_pos and num_neg, and `grads`: FloatTensors in the checkpoint's layouts for fc6_w, fc6_b, fc7_w,
 -- fc7_b, obj_w, obj_b, boxreg_w, boxreg_b and the seven language-model tensors, feat (512, h, w) -- RoI pooling's share of
--- grad_cnn_features --, roi_boxes (num_pos + num_neg, 4) and codes (num_pos, fc_dim).  The CNN backward and an optimiser are not
+-- grad_cnn_features --, roi_boxes (num_pos + num_neg, 4) and codes (num_pos, fc_dim).  The CNN backward is not
 -- built.
 function Model:loss_gradients(data, opts)
   opts = opts or {}
@@ -377,8 +377,8 @@ end
 -- (dc_forward_backward; docs/SEMANTICS.md, "RPN gradients").  data and opts as forward_losses, plus opts.box_reg_decay
 -- (train_opts.lua:42: 5e-5).  Returns the reference's loss keys, num_pos and num_neg, and `grads`: loss_gradients' tensors plus
 -- rpn_conv_w, rpn_conv_b, rpn_box_w, rpn_box_b, rpn_score_w, rpn_score_b in the checkpoint's layouts -- all 21 tensors outside the
--- CNN --, feat (512, h, w), now the complete grad_cnn_features, and feat_roi, RoI pooling's share of it.  The CNN backward and an
--- optimiser are not built; the loaded weights do not change.
+-- CNN --, feat (512, h, w), now the complete grad_cnn_features, and feat_roi, RoI pooling's share of it.  The CNN backward is
+-- not built; the loaded weights do not change (train_step is the call that updates them).
 function Model:forward_backward(data, opts)
   opts = opts or {}
   local input = data.image
@@ -455,6 +455,60 @@ function Model:forward_backward(data, opts)
     captioning_loss = out.captioning_loss, total_loss = out.total_loss,
     num_pos = out.num_pos, num_neg = out.num_neg, grads = grads,
   }
+end
+
+-- The training step (docs/SEMANTICS.md, "Training step"): train.lua's loop body for the default -finetune_cnn_after -1 on the
+-- device.  train_begin(opts): opts.learning_rate, optim_beta1, optim_beta2, optim_epsilon, weight_decay (train_opts.lua's names
+-- and defaults: 1e-5, 0.9, 0.999, 1e-8, 1e-6); Adam's moments start at zero, the step count at 0.
+function Model:train_begin(opts)
+  opts = opts or {}
+  local function get(k, d) if opts[k] == nil then return d end return opts[k] end
+  local o = ffi.new('dc_train_opts')
+  o.learning_rate = get('learning_rate', 1e-5)
+  o.beta1, o.beta2 = get('optim_beta1', 0.9), get('optim_beta2', 0.999)
+  o.epsilon = get('optim_epsilon', 1e-8)
+  o.weight_decay = get('weight_decay', 1e-6)
+  hip.check(self.ctx, C.dc_train_begin(self.ctx, o), 'dc_train_begin')
+end
+
+-- One iteration (dc_train_step): forward_backward on `data` (data and opts as forward_losses, plus opts.box_reg_decay), then
+-- grad_params:add(weight_decay, params) and adam(params, grad_params, ...) on the 21 tensors outside the CNN, in place on the
+-- device, and the refresh of everything the library derives from them.  Returns forward_backward's loss keys, num_pos and
+-- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is the identity; the CNN is
+-- not trained.
+function Model:train_step(data, opts)
+  opts = opts or {}
+  local input = data.image
+  assert(input:dim() == 4 and input:size(1) == 1 and input:size(2) == 3)
+  local img = input:float():contiguous()
+  local gb, gl = data.gt_boxes, data.gt_labels
+  if gb:dim() == 3 then gb = gb[1] end
+  if gl:dim() == 3 then gl = gl[1] end
+  gb, gl = gb:float():contiguous(), gl:int():contiguous()
+  assert(gb:dim() == 2 and gb:size(2) == 4 and gl:dim() == 2 and gl:size(1) == gb:size(1), 'gt_boxes (G,4), gt_labels (G,L)')
+  local function get(k, d) if opts[k] == nil then return d end return opts[k] end
+  local o = ffi.new('dc_loss_opts')
+  o.batch_size = get('sampler_batch_size', 256)
+  o.high_thresh, o.low_thresh = get('sampler_high_thresh', 0.7), get('sampler_low_thresh', 0.3)
+  o.remove_outbounds = get('train_remove_outbounds_boxes', 1)
+  o.mid_box_reg_weight, o.mid_objectness_weight = get('mid_box_reg_weight', 0.05), get('mid_objectness_weight', 0.1)
+  o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
+  o.captioning_weight = get('captioning_weight', 1.0)
+  o.seed = get('loss_seed', 0)
+  local out = ffi.new('dc_losses')
+  hip.check(self.ctx, C.dc_train_step(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),
+                                      gb:size(1), gl:size(2), o, nil, out, nil, get('box_reg_decay', 5e-5)), 'dc_train_step')
+  return {
+    mid_objectness_loss = out.mid_objectness_loss, mid_box_reg_loss = out.mid_box_reg_loss,
+    end_objectness_loss = out.end_objectness_loss, end_box_reg_loss = out.end_box_reg_loss,
+    captioning_loss = out.captioning_loss, total_loss = out.total_loss,
+    num_pos = out.num_pos, num_neg = out.num_neg,
+  }
+end
+
+-- dc_train_end: frees the moments and the gradient arena; the weights stay as trained.
+function Model:train_end()
+  hip.check(self.ctx, C.dc_train_end(self.ctx), 'dc_train_end')
 end
 
 -- Language-model gradients (dc_op_lm_grad; docs/SEMANTICS.md, "Language-model gradients"): codes FloatTensor (n, fc_dim), labels

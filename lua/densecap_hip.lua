@@ -108,6 +108,14 @@ int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img
                         const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg);
+typedef struct dc_train_opts { double learning_rate, beta1, beta2, epsilon, weight_decay; } dc_train_opts;
+int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts);
+int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                  const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                  dc_losses* out, const dc_loss_dump* dump, float box_reg_decay);
+int dc_train_end(dc_ctx* ctx);
+int dc_get_weights(dc_ctx* ctx, const dc_weights* out);
+int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, int t, const dc_train_opts* opts);
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
                       const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
                       int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,
