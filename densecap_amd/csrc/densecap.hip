@@ -180,6 +180,26 @@ struct TrainFwd {
   float stage_ms[5] = {0, 0, 0, 0, 0};
 };
 
+// The event split of a driver's last call: N events around its N - 1 stages, each made on first use and recorded on the call's
+// stream; read() once the stream has drained.  The events die with the clock, that is with the ctx.
+template <int N>
+struct StageClock {
+  hipEvent_t ev[N] = {};
+  float ms[N - 1] = {};
+  bool ran = false;              // read() has run: ms holds a call's times
+  StageClock() = default;  StageClock(const StageClock&) = delete;     // (it owns its events)
+  ~StageClock() { for (hipEvent_t e : ev) if (e != nullptr) (void)hipEventDestroy(e); }
+  hipError_t record(int i, hipStream_t s) {
+    if (ev[i] == nullptr)
+      if (const hipError_t e = hipEventCreate(&ev[i]); e != hipSuccess) return e;
+    return hipEventRecord(ev[i], s);
+  }
+  void read() {
+    for (int i = 0; i + 1 < N; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+    ran = true;
+  }
+};
+
 }  // namespace
 
 struct dc_ctx {
@@ -215,26 +235,22 @@ struct dc_ctx {
   int V1pad = 0;
   // language-model gradients (lm_grad): the checkpoint-layout lstm_w (E+Hd, 4Hd) and lm_emb (V+2, E) as uploaded, and the two
   // transposed copies the data gradients need, made on the first gradient call after a dc_load_weights: out_wT (Hd, V1pad; zero
-  // columns past V+1) and enc_wT (D, E).  lm_grad_ms: the event split of the last call (dc_debug_lm_grad_stage_ms).
+  // columns past V+1) and enc_wT (D, E).  lm_grad_clock: the event split of the last call (dc_debug_lm_grad_stage_ms).
   float *lstm_w_ck = nullptr, *emb = nullptr, *out_wT = nullptr, *enc_wT = nullptr;
   uint64_t grad_epoch = 0;
-  float lm_grad_ms[4] = {0, 0, 0, 0};
-  bool lm_grad_ran = false;
+  StageClock<5> lm_grad_clock;
   // recognition-net gradients (recog_backward): fc7_wT (D, D) and fc6_wT (49*512, D), the transposed copies the data gradients
   // need, made on the first call after a dc_load_weights; the RoI index's scratch (grow only); the event split of the last call
   float *fc7_wT = nullptr, *fc6_wT = nullptr;
   uint64_t recog_epoch = 0;
   KeptBuf roi_grad_ws{scratch}, recog_ws{scratch}, recog_aux_ws{scratch};   // (recog_ws: the backward's scratch; recog_aux_ws: the callers' few rows)
-  hipEvent_t recog_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  float recog_grad_ms[4] = {0, 0, 0, 0};
-  bool recog_grad_ran = false;
+  StageClock<5> recog_clock;
   // RPN gradients (rpn_backward): the RPN convolution's flipped, transposed weights, OIHW and in the engine's packed form (512,
   // 9R), made on first need and again when weights_epoch moves; the backward's scratch and the op's forward rows (grow only);
   // what the last backward left there for the hooks: its event split and the RPN's share of the feature map's gradient
   KeptBuf rpn_wf{scratch}, rpn_ws{scratch}, rpn_aux_ws{scratch};
   uint64_t rpn_epoch = 0;
-  hipEvent_t rpn_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  float rpn_grad_ms[4] = {0, 0, 0, 0};
+  StageClock<5> rpn_clock;
   const float* rpn_dfeat = nullptr;
   int rpn_dfeat_pixels = 0;
   // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
@@ -274,8 +290,7 @@ struct dc_ctx {
   KeptBuf optim_tab{scratch};
   int train_nseg = 0;
   unsigned long long train_chunks = 0;
-  hipEvent_t train_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float train_ms[3] = {0, 0, 0};
+  StageClock<4> train_clock;
   // MFMA profile
   bool prof = false;
   std::vector<ProfEvt> prof_pending;
@@ -1199,14 +1214,13 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
   const int plan = std::min(n, kScorePlanRows);
   Scratch base(ctx->scratch, s);
   HIPCHK(base.alloc(cv));
-  hipEvent_t ev[5] = {};
+  auto& clock = ctx->lm_grad_clock;
   std::vector<double> acc_host(n);
   auto slot = [&](float* b, int q, int width) { return b + (size_t)off[q] * width; };
   auto body = [&]() -> int {
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
     const int32_t *d_tgt = ints, *d_fed = ints + o_fed;
     HIPCHK(hipMemcpyAsync(ints, ih.data(), ih.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev[0], s));
+    HIPCHK(clock.record(0, s));
     // ---- forward ----
     KCHK(launch_gather_rows(codes, ints + o_ord, ints + o_n, n, D, gcodes, s));
     DCCHK(lm_start_state(ctx, s, gcodes, n, slot(Xb, 0, E), slot(Gb, 1, 4 * Hd), slot(Cb, 2, Hd), slot(Hb, 2, Hd), plan, nullptr, Ws()));
@@ -1230,7 +1244,7 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
                                 slot(Hb, 2 + j, Hd), acc, alive[j], Hd, s));
     }
     HIPCHK(hipMemcpyAsync(acc_host.data(), acc, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipEventRecord(ev[1], s));
+    HIPCHK(clock.record(1, s));
     // ---- backward: projections, then the steps ----
     const float scale = (float)((double)weight / ((double)n * (double)(L + 2)));
     {
@@ -1254,7 +1268,7 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
     }
     KCHK(launch_lstm_cell_bwd(slot(Gb, 0, 4 * Hd), nullptr, nullptr, nullptr, slot(Cb, 1, Hd), nullptr, dhc, dcc, slot(DGb, 0, 4 * Hd), dcc, n,
                               Hd, s));
-    HIPCHK(hipEventRecord(ev[2], s));
+    HIPCHK(clock.record(2, s));
     // ---- stacked gradients ----
     KCHK(launch_embed_rows(ctx->emb, d_fed + n, P - n, E, slot(Xb, 1, E), s));
     KCHK(launch_wgrad(logits, V1pad, slot(Hb, 2, Hd), Hd, Mp, V1, Hd, out.lm_out_w, Hd, ws, s));
@@ -1275,15 +1289,14 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
       g.A = dXb; g.W = ctx->enc_wT; g.C = dcodes; g.M = n; g.N = D; g.K = E; g.ldc = D;
       DCCHK(run_gemm(ctx, g, s));
     }
-    HIPCHK(hipEventRecord(ev[3], s));
+    HIPCHK(clock.record(3, s));
     // ---- rows ----
     HIPCHK(hipMemsetAsync(out.lm_emb, 0, (size_t)(V + 2) * E * 4, s));
     KCHK(launch_embed_segsum(dXb, E, ints + o_erow, ints + o_eseg, ints + o_eid, ntok, out.lm_emb, s));
     if (out.codes != nullptr) KCHK(launch_scatter_rows(dcodes, ints + o_ord, n, D, out.codes, s));
-    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(clock.record(4, s));
     HIPCHK(hipStreamSynchronize(s));
-    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->lm_grad_ms[i], ev[i], ev[i + 1]);
-    ctx->lm_grad_ran = true;
+    clock.read();
     double sum = 0.0;
     for (int r = 0; r < n; ++r) sum += acc_host[r];           // (permuted order: longest caption first)
     *loss = (double)weight * (-sum) / ((double)n * (double)(L + 2));
@@ -1291,10 +1304,7 @@ int lm_grad(dc_ctx* ctx, hipStream_t s, const float* codes, int n, const int32_t
       for (int i = 0; i < n; ++i) rowlik[order[i]] = acc_host[i];
     return DC_OK;
   };
-  const int rc = call_finish(ctx, s, body(), "dc_op_lm_grad");
-  for (auto& evt : ev)
-    if (evt != nullptr) hipEventDestroy(evt);
-  return rc;
+  return call_finish(ctx, s, body(), "dc_op_lm_grad");
 }
 
 // the rules of docs/SEMANTICS.md ("Sampling captions") for a dc_sample_opts; nothing is enqueued before they hold
@@ -1806,11 +1816,8 @@ void dc_destroy(dc_ctx* ctx) {
   hipDeviceSynchronize();
   for (auto& lp : ctx->lanes) lane_release(*lp);
   for (void* p : ctx->owned) hipFree(p);
-  for (hipEvent_t e : ctx->recog_ev) if (e) hipEventDestroy(e);
-  for (hipEvent_t e : ctx->rpn_ev) if (e) hipEventDestroy(e);
-  for (hipEvent_t e : ctx->train_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
-  delete ctx;                 // (the kept buffers free themselves here)
+  delete ctx;                 // (the kept buffers and the stage clocks' events free themselves here)
 }
 
 const char* dc_last_error(const dc_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
@@ -2408,7 +2415,7 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
   }
   if (strcmp(name, "train_step_ms") == 0) {          // the last dc_train_step: backward (the three stages), Adam launch, refresh
     if (capacity_bytes < 12) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
-    memcpy(host_buf, ctx->train_ms, 12);
+    memcpy(host_buf, ctx->train_clock.ms, 12);
     return 3;
   }
   if (strcmp(name, "train_t") == 0) {
@@ -3432,8 +3439,8 @@ int dc_debug_lstm_cell_bwd(dc_ctx* ctx, const float* gates_pre, const float* c_p
 int dc_debug_lm_grad_stage_ms(dc_ctx* ctx, float* ms) {
   if (!ctx) return DC_E_INVALID;
   if (!ms) return ctx->fail(DC_E_INVALID, "dc_debug_lm_grad_stage_ms: null pointer");
-  if (!ctx->lm_grad_ran) return ctx->fail(DC_E_STATE, "dc_debug_lm_grad_stage_ms: no dc_op_lm_grad call has completed");
-  memcpy(ms, ctx->lm_grad_ms, 16);
+  if (!ctx->lm_grad_clock.ran) return ctx->fail(DC_E_STATE, "dc_debug_lm_grad_stage_ms: no dc_op_lm_grad call has completed");
+  memcpy(ms, ctx->lm_grad_clock.ms, 16);
   return 4;
 }
 
@@ -3480,15 +3487,15 @@ int dc_feature_size(int H, int W, int* h, int* w) {
 }
 
 // The backward of bilinear RoI pooling on stream s (not synchronised): the tap index in the ctx's own scratch (grow only), the
-// scatter sum, the box gradient.  ev (optional): an event recorded between the scatter sum and the box gradient.
+// scatter sum, the box gradient.  clock (optional): its event `mark` is recorded between the scatter sum and the box gradient.
 static int roi_pool_grad(dc_ctx* ctx, hipStream_t s, const float* feat, int h, int w, int C, const float* boxes, int B, int img_h,
-                         int img_w, int HH, int WW, const float* dout, float* dfeat, float* dboxes, hipEvent_t ev = nullptr) {
+                         int img_w, int HH, int WW, const float* dout, float* dfeat, float* dboxes, StageClock<5>* clock = nullptr, int mark = 0) {
   const size_t bytes = roi_grad_ws_bytes(B, HH * WW, h * w, C);
   HIPCHK(ctx->roi_grad_ws.grow(bytes, s));
   const RoiGradWs ws = roi_grad_carve(ctx->roi_grad_ws.get(), B, HH * WW, h * w, C);
   KCHK(launch_roi_tap_index(boxes, B, h, w, img_h, img_w, HH, WW, ws, s));
   KCHK(launch_roi_scatter_sum(dout, B, h, w, C, HH, WW, ws, dfeat, s));
-  if (ev != nullptr) HIPCHK(hipEventRecord(ev, s));
+  if (clock != nullptr) HIPCHK(clock->record(mark, s));
   if (dboxes != nullptr) KCHK(launch_roi_box_grad(feat, h, w, C, boxes, B, img_h, img_w, HH, WW, dout, dboxes, s));
   return DC_OK;
 }
@@ -3575,11 +3582,9 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
   const std::vector<Carve> cv = recog_carve(ctx, n, r);
   HIPCHK(ctx->recog_ws.grow(carve(cv, nullptr), s));               // kept by the context: 0.45 GB at the real model
   carve(cv, ctx->recog_ws.get());
-  hipEvent_t* ev = ctx->recog_ev;
+  auto& clock = ctx->recog_clock;
   auto body = [&]() -> int {
-    for (int i = 0; i < 5; ++i)
-      if (ev[i] == nullptr) HIPCHK(hipEventCreate(&ev[i]));
-    HIPCHK(hipEventRecord(ev[0], s));
+    HIPCHK(clock.record(0, s));
     KCHK(launch_end_crit_grad(in.obj, in.final_trans, in.roi_boxes, in.target, n, np, in.w_obj, in.w_box, r.dobj, r.dtrans, r.danchor, r.masked, s));
     KCHK(launch_heads_bwd(in.codes, ctx->head5_w, r.dobj, r.dtrans, in.g, n, np, D, r.dcodes, r.dw5, r.db5, s));
     HIPCHK(hipMemcpyAsync(out.obj_w, r.dw5, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
@@ -3603,19 +3608,18 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
       KCHK(launch_permute_fc6_back(r.dw6, out.fc6_w, D, 512, 49, s));
     }
     KCHK(launch_colsum(r.dx7, D, n, D, out.fc6_b, s));
-    HIPCHK(hipEventRecord(ev[1], s));
+    HIPCHK(clock.record(1, s));
     {
       GemmDesc g;              // dpool = d(fc6 pre-activation).W6, point-major
       g.A = r.dx7; g.W = ctx->fc6_wT; g.C = r.dpool; g.M = n; g.N = kRecogK6; g.K = D; g.ldc = kRecogK6;
       DCCHK(run_gemm(ctx, g, s));
     }
-    HIPCHK(hipEventRecord(ev[2], s));
-    DCCHK(roi_pool_grad(ctx, s, in.feat, in.h, in.w, 512, in.roi_boxes, n, in.img_h, in.img_w, 7, 7, r.dpool, out.feat, r.dbox, ev[3]));
+    HIPCHK(clock.record(2, s));
+    DCCHK(roi_pool_grad(ctx, s, in.feat, in.h, in.w, 512, in.roi_boxes, n, in.img_h, in.img_w, 7, 7, r.dpool, out.feat, r.dbox, &clock, 3));
     KCHK(launch_add_pos_rows4(r.dbox, r.danchor, n, np, out.roi_boxes, s));
-    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(clock.record(4, s));
     HIPCHK(hipStreamSynchronize(s));
-    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->recog_grad_ms[i], ev[i], ev[i + 1]);
-    ctx->recog_grad_ran = true;
+    clock.read();
     return DC_OK;
   };
   return call_finish(ctx, s, body(), "recognition backward");
@@ -3789,8 +3793,8 @@ int dc_debug_permute_fc6_back(dc_ctx* ctx, const float* in, float* out, int N, i
 int dc_debug_recog_grad_stage_ms(dc_ctx* ctx, float* ms) {
   if (!ctx) return DC_E_INVALID;
   if (!ms) return ctx->fail(DC_E_INVALID, "dc_debug_recog_grad_stage_ms: null pointer");
-  if (!ctx->recog_grad_ran) return ctx->fail(DC_E_STATE, "dc_debug_recog_grad_stage_ms: no recognition backward has completed");
-  memcpy(ms, ctx->recog_grad_ms, 16);
+  if (!ctx->recog_clock.ran) return ctx->fail(DC_E_STATE, "dc_debug_recog_grad_stage_ms: no recognition backward has completed");
+  memcpy(ms, ctx->recog_clock.ms, 16);
   return 4;
 }
 
@@ -4151,11 +4155,9 @@ static int rpn_backward(dc_ctx* ctx, hipStream_t s, const RpnKept& in, const dc_
   HIPCHK(ctx->rpn_ws.grow(carve(cv, nullptr), s));
   carve(cv, ctx->rpn_ws.get());
   ctx->rpn_dfeat = nullptr;
-  hipEvent_t* ev = ctx->rpn_ev;
+  auto& clock = ctx->rpn_clock;
   auto body = [&]() -> int {
-    for (int i = 0; i < 5; ++i)
-      if (ev[i] == nullptr) HIPCHK(hipEventCreate(&ev[i]));
-    HIPCHK(hipEventRecord(ev[0], s));
+    HIPCHK(clock.record(0, s));
     RpnDheadsArgs a{};
     a.trans = in.trans; a.scores = in.scores; a.anchors = in.anchors; a.boxes = in.boxes; a.gt = in.gt; a.droi = in.droi;
     a.pos_input_idx = in.pos_idx; a.pos_target_idx = in.pos_tgt; a.neg_input_idx = in.neg_idx;
@@ -4163,7 +4165,7 @@ static int rpn_backward(dc_ctx* ctx, hipStream_t s, const RpnKept& in, const dc_
     a.w_mid_obj = in.w_mid_obj; a.w_mid_box = in.w_mid_box; a.decay = in.decay;
     a.win_all = r.win_all; a.win_pos = r.win_pos; a.dheads = r.dheads;
     KCHK(launch_rpn_dheads(a, s));
-    HIPCHK(hipEventRecord(ev[1], s));
+    HIPCHK(clock.record(1, s));
     KCHK(launch_wgrad(r.dheads, K6, in.hidden, R, hw, K6, R, r.dw6, R, r.ws, s));
     KCHK(launch_colsum(r.dheads, K6, hw, K6, r.db6, s));
     HIPCHK(hipMemcpyAsync(out.rpn_box_w, r.dw6, (size_t)4 * k * R * 4, hipMemcpyDeviceToDevice, s));
@@ -4171,16 +4173,16 @@ static int rpn_backward(dc_ctx* ctx, hipStream_t s, const RpnKept& in, const dc_
     HIPCHK(hipMemcpyAsync(out.rpn_box_b, r.db6, (size_t)4 * k * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(out.rpn_score_b, r.db6 + 4 * k, (size_t)2 * k * 4, hipMemcpyDeviceToDevice, s));
     KCHK(launch_rpn_heads_bwd(r.dheads, ctx->heads_w, in.hidden, hw, K6, R, r.dhidden, s));
-    HIPCHK(hipEventRecord(ev[2], s));
+    HIPCHK(clock.record(2, s));
     KCHK(launch_conv3x3_wgrad(in.feat, r.dhidden, h, w, 512, R, S, out.rpn_conv_w, r.part, s));
     KCHK(launch_colsum(r.dhidden, R, hw, R, out.rpn_conv_b, s));
-    HIPCHK(hipEventRecord(ev[3], s));
+    HIPCHK(clock.record(3, s));
     DCCHK(conv3x3(ctx, s, r.dhidden, static_cast<const float*>(ctx->rpn_wf.get()), nullptr, r.dfeat, 1, h, w, R, 512, 0, ws));
     if (feat_add != nullptr) KCHK(launch_add_pos_rows4(feat_add, r.dfeat, hw * 128, hw * 128, out.feat, s));
     else HIPCHK(hipMemcpyAsync(out.feat, r.dfeat, (size_t)hw * 512 * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(clock.record(4, s));
     HIPCHK(hipStreamSynchronize(s));
-    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->rpn_grad_ms[i], ev[i], ev[i + 1]);
+    clock.read();
     ctx->rpn_dfeat = r.dfeat; ctx->rpn_dfeat_pixels = hw;
     return DC_OK;
   };
@@ -4434,8 +4436,6 @@ int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts) {
     for (const TrainSeg& sg : segs) tab.push_back({sg.p, g.*(sg.slot), m.*(sg.slot), v.*(sg.slot), sg.n, 0});
     DCCHK(upload_adam_table(ctx, ctx->train_tab, s, tab, &ctx->train_chunks));
     ctx->train_nseg = (int)segs.size();
-    for (hipEvent_t& e : ctx->train_ev)
-      if (e == nullptr) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipStreamSynchronize(s));
     return DC_OK;
   };
@@ -4485,25 +4485,25 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
   const dc_recog_grads rg = {g.fc6_w, g.fc6_b, g.fc7_w, g.fc7_b, g.head5_w, g.head5_b, g.head5_w + D, g.head5_b + 1, feat_rg, roi};
   const dc_lm_grads lg = {g.enc_w, g.enc_b, g.emb, g.lstm_w, g.lstm_b, g.out_w, g.out_b, nullptr};
   const dc_rpn_grads pg = {g.rpn_conv_w, g.rpn_conv_b, g.heads_w, g.heads_b, g.heads_w + 4 * k * R, g.heads_b + 4 * k, feat_pg};
-  hipEvent_t* ev = ctx->train_ev;
-  HIPCHK(hipEventRecord(ev[0], s));
+  auto& clock = ctx->train_clock;
+  HIPCHK(clock.record(0, s));
   ctx->fc6_grad_engine = true;
   const int rc = train_call(ctx, c, 3, &rg, &lg, box_reg_decay, &pg);
   ctx->fc6_grad_engine = false;
   if (rc != DC_OK) return rc;                      // no weight and no t has changed
   const AdamScalars k1 = adam_scalars(ctx->train_opts, ctx->train_t + 1);
   auto body = [&]() -> int {
-    HIPCHK(hipEventRecord(ev[1], s));
+    HIPCHK(clock.record(1, s));
     KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_tab.get()), ctx->train_nseg, ctx->train_chunks, k1, 0, s));
-    HIPCHK(hipEventRecord(ev[2], s));
+    HIPCHK(clock.record(2, s));
     DCCHK(train_refresh(ctx, s));
-    HIPCHK(hipEventRecord(ev[3], s));
+    HIPCHK(clock.record(3, s));
     return DC_OK;
   };
   ctx->train_t += 1;                               // (from the launch on the weights are step t's, whatever fails after it)
   const int rc2 = call_finish(ctx, s, body(), who, true);
   if (rc2 != DC_OK) return rc2;
-  for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ctx->train_ms[i], ev[i], ev[i + 1]);
+  clock.read();
   return DC_OK;
 }
 
@@ -4673,7 +4673,7 @@ int dc_debug_rpn_grad_kept(dc_ctx* ctx, float* feat_rpn, int pixels, float* ms) 
     if (pixels != ctx->rpn_dfeat_pixels) return ctx->fail(DC_E_INVALID, "%s: the kept map has %d pixels (got %d)", who, ctx->rpn_dfeat_pixels, pixels);
     HIPCHK(hipMemcpyAsync(feat_rpn, ctx->rpn_dfeat, (size_t)pixels * 512 * 4, hipMemcpyDeviceToDevice, s));
   }
-  memcpy(ms, ctx->rpn_grad_ms, 16);
+  memcpy(ms, ctx->rpn_clock.ms, 16);
   OP_EPILOGUE();
 }
 
