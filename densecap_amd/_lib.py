@@ -107,6 +107,16 @@ class DcRpnGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "feat")]
 
 
+class DcCnnGrads(C.Structure):
+    """dc_cnn_grads: device buffers for the gradients of conv3_1 .. conv5_3 (OIHW) and their biases; x may be null."""
+    _fields_ = [("conv_w", C.c_void_p * 9), ("conv_b", C.c_void_p * 9), ("x", C.c_void_p)]
+
+
+class DcCnnDump(C.Structure):
+    """dc_cnn_dump: optional device buffers for what dc_op_cnn_grad's forward kept and the masked gradients."""
+    _fields_ = [("act", C.c_void_p * 9), ("prepool", C.c_void_p * 2), ("feat", C.c_void_p), ("dy", C.c_void_p * 9)]
+
+
 class DcTrainOpts(C.Structure):
     """dc_train_opts: Adam's settings and the L2 weight decay (train_opts.lua's defaults: 1e-5, 0.9, 0.999, 1e-8, 1e-6)."""
     _fields_ = [(n, C.c_double) for n in ("learning_rate", "beta1", "beta2", "epsilon", "weight_decay")]
@@ -240,15 +250,23 @@ _SIGS = {
                                     C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads)]),
     "dc_feature_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dc_op_conv3x3_grad": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "dc_op_maxpool2x2_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "dc_op_relu_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]),
+    "dc_op_cnn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DcCnnGrads), C.POINTER(DcCnnDump)]),
     "dc_op_rpn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(DcLossOpts), C.c_float,
                                  C.POINTER(DcRpnGrads), C.POINTER(C.c_double), C.POINTER(C.c_double), c_int32_p]),
     "dc_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
                                       C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads), C.c_float, C.POINTER(DcRpnGrads)]),
+    "dc_forward_backward_cnn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump),
+                                          C.POINTER(DcRecogGrads), C.POINTER(DcLmGrads), C.c_float, C.POINTER(DcRpnGrads),
+                                          C.POINTER(DcCnnGrads)]),
     "dc_train_begin": (C.c_int, [C.c_void_p, C.POINTER(DcTrainOpts)]),
     "dc_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                 C.POINTER(DcLossOpts), C.POINTER(DcSamplerForced), C.POINTER(DcLosses), C.POINTER(DcLossDump), C.c_float]),
+    "dc_train_set_cnn": (C.c_int, [C.c_void_p, C.c_int]),
     "dc_train_end": (C.c_int, [C.c_void_p]),
     "dc_get_weights": (C.c_int, [C.c_void_p, C.POINTER(DcWeights)]),
     "dc_op_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(DcTrainOpts)]),

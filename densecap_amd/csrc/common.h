@@ -500,7 +500,6 @@ hipError_t launch_softmax_grad(float* x, int ld, int V1, const int32_t* tgt, flo
 hipError_t launch_lstm_cell_bwd(const float* gates_pre, const int32_t* tok, const float* xg, const float* c_prev, const float* c,
                                 const float* dh_a, const float* dh_b, const float* dc_in, float* dgates, float* dc_prev, int rows,
                                 int Hd, hipStream_t s);
-hipError_t launch_relu_mask(float* d, const float* y, size_t len, hipStream_t s);
 hipError_t launch_embed_rows(const float* emb, const int32_t* tok, int rows, int E, float* out, hipStream_t s);
 hipError_t launch_scatter_rows(const float* src, const int32_t* perm, int rows, int width, float* out, hipStream_t s);
 // demb[ids[t] - 1] = sum of dx[rows[i]] for i in [seg[t], seg[t + 1]), in that order, for t < ntok
@@ -577,6 +576,14 @@ hipError_t launch_conv3x3_wgrad(const float* x, const float* dy, int h, int w, i
                                 hipStream_t s);
 // wf (Cin, Cout, 3, 3) with wf[c][o][tap] = w[o][c][8 - tap]: dx = conv3x3(dy, wf).  w: OIHW, or (packed) launch_pack_conv3x3's form
 hipError_t launch_conv3x3_flip(const float* w, int Cout, int Cin, int packed, float* wf, hipStream_t s);
+
+// ---- CNN gradients (cnn_grad.hip; docs/SEMANTICS.md, "CNN gradients") ----
+// dy (n, H, W, C), every element written: dpool (n, ceil(H/2), ceil(W/2), C) routed to the first maximum of each clipped 2x2
+// window of y (n, H, W, C) where that maximum is > 0, +0.0 elsewhere.  C % 4 == 0; 16-byte aligned pointers.
+hipError_t launch_maxpool2x2_ceil_relu_grad(const float* y, const float* dpool, float* dy, int nimg, int H, int W, int C,
+                                            hipStream_t s);
+// dy[i] = y[i] > 0 ? dy[i] : +0.0 in place, n floats; any 4-byte alignment (16-byte accesses where both pointers allow them)
+hipError_t launch_relu_mask(float* dy, const float* y, size_t n, hipStream_t s);
 
 // ---- RPN gradients (rpn_grad.hip; docs/SEMANTICS.md, "RPN gradients") ----
 // The gradient at the RPN's head outputs, dheads (h * w, 6k) in the layout of the heads: the two mid criteria on the sampled rows,

@@ -178,6 +178,7 @@ struct TrainFwd {
   int A = 0, G = 0, np = 0, nn = 0, h = 0, w = 0, H = 0, W = 0;
   dc_loss_opts opts{};                                              // resolved (the defaults for a null pointer)
   float stage_ms[5] = {0, 0, 0, 0, 0};
+  bool kept_feat = false;      // feat is ctx->cnn_feat (dc_forward_backward_cnn's trunk), not lane 0's
 };
 
 // The event split of a driver's last call: N events around its N - 1 stages, each made on first use and recorded on the call's
@@ -253,6 +254,18 @@ struct dc_ctx {
   StageClock<5> rpn_clock;
   const float* rpn_dfeat = nullptr;
   int rpn_dfeat_pixels = 0;
+  // CNN gradients (dc_op_cnn_grad): the activations the forward keeps for the backward and the backward's scratch (grow only);
+  // the event split of the last call (kept forward, dump copies, backward; dc_debug_fetch "cnn_grad_ms")
+  KeptBuf cnn_kept{scratch}, cnn_ws{scratch};
+  KeptBuf train_cnn_kept{scratch};      // ... and the training forward's own kept activations (dc_forward_backward_cnn, the step)
+  // the CNN's share of the training step (dc_train_set_cnn): mode, its own step count, the OIHW masters of the nine convolutions,
+  // gradient arena and moments of the 18 tensors, the second Adam launch's segment table
+  int train_cnn_mode = 0, train_cnn_t = 0, train_cnn_nseg = 0;
+  unsigned long long train_cnn_chunks = 0;
+  KeptBuf train_cnn_master{scratch}, train_cnn_g{scratch}, train_cnn_m{scratch}, train_cnn_v{scratch}, train_cnn_tab{scratch};
+  const float *cnn_x4 = nullptr, *cnn_feat = nullptr;   // the last dc_forward_backward_cnn's kept pool2 map and conv5_3 map (dc_debug_fetch "cnn_x4" / "cnn_feat")
+  int cnn_h4 = 0, cnn_w4 = 0;
+  StageClock<4> cnn_clock;
   // screened greedy decode (Settings::decode_screen): bf16 copy of Wout (V1pad rows of scr_Kp, zero padded), the rows' 2-norms
   // rounded up to fp16 (V1pad of them), the constant c of the bound.  Part of the weights, made with dec_w.
   uint16_t* scr_w = nullptr;
@@ -1475,11 +1488,13 @@ int lm_sample_two_streams(dc_ctx* ctx, Lane& L, const float* codes, int n, int p
 
 // The VGG-16 trunk (DenseCapModel.lua:73-76) of the g images at L.img, on the lane's stream: L.feat = conv5_3's map, (*fh, *fw)
 // its size.  Shared by the test-time forward (enqueue_body) and the training forward of dc_forward_losses.
-int enqueue_trunk(dc_ctx* ctx, Lane& L, int g, int* fh, int* fw) {
+// nconv: only the first nconv convolutions (the training forward with kept activations stops behind pool2 and goes on in
+// cnn_forward_kept); L.feat is then that layer's map.
+int enqueue_trunk(dc_ctx* ctx, Lane& L, int g, int* fh, int* fw, int nconv = DC_NUM_VGG_CONVS) {
   hipStream_t s = L.stream;
   int h = L.H, w = L.W, cur = 0;
   KCHK(launch_conv3x3_c3(L.img, ctx->conv_w[0], ctx->conv_b[0], L.act[0], g, h, w, 64, 1, s));
-  for (int i = 1; i < DC_NUM_VGG_CONVS; ++i) {
+  for (int i = 1; i < nconv; ++i) {
     if (kVgg[i].pool_after) {
       // conv + ReLU + ceil-mode 2x2 pool in one launch
       DCCHK(conv3x3_pool(ctx, s, L.act[cur], ctx->conv_w[i], ctx->conv_b[i], L.act[cur ^ 1], g, h, w, kVgg[i].cin,
@@ -2418,6 +2433,30 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
     memcpy(host_buf, ctx->train_clock.ms, 12);
     return 3;
   }
+  if (strcmp(name, "cnn_grad_ms") == 0) {            // the last dc_op_cnn_grad: the kept-activation forward, the backward
+    if (capacity_bytes < 8) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    if (!ctx->cnn_clock.ran) return ctx->fail(DC_E_STATE, "dc_debug_fetch: no dc_op_cnn_grad has run");
+    static_cast<float*>(host_buf)[0] = ctx->cnn_clock.ms[0];
+    static_cast<float*>(host_buf)[1] = ctx->cnn_clock.ms[2];
+    return 2;
+  }
+  if (strcmp(name, "cnn_x4") == 0 || strcmp(name, "cnn_feat") == 0) {      // what the last dc_forward_backward_cnn kept
+    const bool x4 = name[4] == 'x';
+    if (ctx->cnn_x4 == nullptr) return ctx->fail(DC_E_STATE, "dc_debug_fetch: no dc_forward_backward_cnn has run");
+    int fh = ctx->cnn_h4, fw = ctx->cnn_w4;
+    if (!x4) { fh = ((fh + 1) / 2 + 1) / 2; fw = ((fw + 1) / 2 + 1) / 2; }
+    const int64_t elems = (int64_t)fh * fw * (x4 ? 128 : 512);
+    if (elems * 4 > capacity_bytes) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small (%lld needed)", (long long)elems * 4);
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(host_buf, x4 ? ctx->cnn_x4 : ctx->cnn_feat, elems * 4, hipMemcpyDeviceToHost));
+    return elems;
+  }
+  if (strcmp(name, "train_cnn_t") == 0) {          // the CNN's own step count; -1 before the first non-zero dc_train_set_cnn
+    if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
+    *static_cast<int32_t*>(host_buf) = ctx->training && ctx->train_cnn_nseg > 0 ? ctx->train_cnn_t : -1;
+    return 1;
+  }
   if (strcmp(name, "train_t") == 0) {
     if (capacity_bytes < 4) return ctx->fail(DC_E_INVALID, "dc_debug_fetch: buffer too small");
     *static_cast<int32_t*>(host_buf) = ctx->training ? ctx->train_t : -1;
@@ -2459,7 +2498,7 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
         {"loss_rpn_trans", k.trans, (int64_t)k.A * 4, 4},     {"loss_rpn_scores", k.scores, (int64_t)k.A * 2, 4},
         {"loss_obj", L.obj, kn, 4},                           {"loss_final_trans", L.final_trans, kn * 4, 4},
         {"loss_roi_boxes", L.roi_boxes, kn * 4, 4},           {"loss_codes", L.codes, kn * ctx->D, 4},
-        {"loss_rowlik", k.rowlik, (int64_t)k.np, 8}};
+        {"loss_rowlik", k.rowlik, (int64_t)k.np, 8},         {"loss_feat", k.kept_feat ? ctx->cnn_feat : L.feat, (int64_t)k.h * k.w * 512, 4}};
     for (const auto& e : kept) {
       if (strcmp(name, e.n) != 0) continue;
       const int64_t bytes = e.elems * e.esize;
@@ -3049,6 +3088,7 @@ int dc_localize_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int im
 // The settings a losses call runs under, whatever the ctx holds: fp32 MFMA and multi-lane planning (single-image planning shares a
 // layer's last tile round along K, another summation order), so that the numbers depend on neither dc_set_math_mode nor
 // dc_set_lanes.  The ctx's own settings come back when the guard dies.
+static int train_trunk_kept(dc_ctx* ctx, Lane& L, int* fh, int* fw);      // (with the CNN gradients, below)
 struct LossCfgGuard {
   Settings& c; Settings saved;
   explicit LossCfgGuard(Settings& cfg) : c(cfg), saved(cfg) { c.math_mode = 0; c.serial_mode = 0; c.plan_mode = 0; }
@@ -3063,6 +3103,7 @@ namespace {
 struct TrainCall {             // the arguments the three entry points share, as the entry point got them (o: resolved)
   const char* who; const float* img; int H, W, on_device; const float* gt_boxes; const int32_t* gt_labels; int G, Lw;
   dc_loss_opts o; const dc_sampler_forced* forced; dc_losses* out; const dc_loss_dump* dump;
+  bool cnn = false;            // the trunk keeps conv_net2's activations (dc_forward_backward_cnn)
 };
 void feature_size(int H, int W, int* h, int* w) {
   for (int i = 0; i < DC_NUM_VGG_CONVS; ++i)
@@ -3187,7 +3228,9 @@ int train_forward(dc_ctx* ctx, const TrainCall& c, Lane& L, TrainFwd& f) {
   auto body = [&]() -> int {
     HIPCHK(hipEventRecord(L.ev[0], s));
     HIPCHK(hipMemcpyAsync(L.img, c.img, (size_t)3 * H * W * 4, c.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    DCCHK(enqueue_trunk(ctx, L, 1, &f.h, &f.w));
+    f.kept_feat = c.cnn;
+    if (c.cnn) DCCHK(train_trunk_kept(ctx, L, &f.h, &f.w));
+    else DCCHK(enqueue_trunk(ctx, L, 1, &f.h, &f.w));
     const int h = f.h, w = f.w;
     ensure_fault_word(ctx);
     DCCHK(rpn_train_forward(ctx, L, L.feat, h, w, H, W, L.rpn_hidden, L.heads, f.boxes, f.anchors, f.trans, f.scores));
@@ -4068,12 +4111,13 @@ static std::vector<Carve> conv3x3_grad_carve(int Cin, int Cout, int S, bool dw, 
 }
 // Launch list (stream s, eager, not synchronised; the caller holds LossCfgGuard):
 //   conv3x3_wgrad + conv3x3_wgrad_finish (dw); colsum (db); conv3x3_flip + pack_conv3x3 + the engine's conv (dx)
+// w_packed: w is in launch_pack_conv3x3's form (the ctx's own convolutions), not OIHW
 static int conv3x3_grad(dc_ctx* ctx, hipStream_t s, const float* x, const float* w, const float* dy, int h, int wd, int Cin, int Cout,
-                        int S, float* dw, float* db, float* dx, const ConvGradScratch& r) {
+                        int S, float* dw, float* db, float* dx, const ConvGradScratch& r, int w_packed = 0) {
   if (dw != nullptr) KCHK(launch_conv3x3_wgrad(x, dy, h, wd, Cin, Cout, S, dw, r.part, s));
   if (db != nullptr) KCHK(launch_colsum(dy, Cout, h * wd, Cout, db, s));
   if (dx != nullptr) {
-    KCHK(launch_conv3x3_flip(w, Cout, Cin, 0, r.wf, s));
+    KCHK(launch_conv3x3_flip(w, Cout, Cin, w_packed, r.wf, s));
     KCHK(launch_pack_conv3x3(r.wf, r.wfp, Cin, Cout, s));
     DCCHK(conv3x3(ctx, s, dy, r.wfp, nullptr, dx, 1, h, wd, Cout, Cin, 0, Ws{r.splitk, kSplitkWsFloats}));
   }
@@ -4093,6 +4137,206 @@ int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float*
   Scratch block(ctx->scratch, s);
   HIPCHK(block.alloc(conv3x3_grad_carve(Cin, Cout, S, dw != nullptr, dx != nullptr, r)));
   return call_finish(ctx, s, conv3x3_grad(ctx, s, x, w, dy, h, w_px, Cin, Cout, S, dw, db, dx, r), who, dx != nullptr);
+}
+
+// ---- CNN gradients (docs/SEMANTICS.md, "CNN gradients") -------------------------------------------------------------
+int dc_op_maxpool2x2_grad(dc_ctx* ctx, const float* y, const float* dpool, int n, int H, int W, int C, float* dy) {
+  OP_PROLOGUE();
+  if (!y || !dpool || !dy) return ctx->fail(DC_E_INVALID, "dc_op_maxpool2x2_grad: null pointer");
+  if (n < 1 || H < 1 || W < 1 || C < 1 || C % 4) return ctx->fail(DC_E_INVALID, "dc_op_maxpool2x2_grad: need C %% 4 == 0 and positive sizes");
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dpool) | reinterpret_cast<uintptr_t>(dy)) & 15)
+    return ctx->fail(DC_E_INVALID, "dc_op_maxpool2x2_grad: y, dpool and dy must be 16-byte aligned");
+  KCHK(launch_maxpool2x2_ceil_relu_grad(y, dpool, dy, n, H, W, C, s));
+  OP_EPILOGUE();
+}
+int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats) {
+  OP_PROLOGUE();
+  if (!y || !dy) return ctx->fail(DC_E_INVALID, "dc_op_relu_grad: null pointer");
+  if (n_floats < 1) return ctx->fail(DC_E_INVALID, "dc_op_relu_grad: need n_floats >= 1");
+  KCHK(launch_relu_mask(dy, y, (size_t)n_floats, s));
+  OP_EPILOGUE();
+}
+
+// conv_net2: convolutions kCnnFirst .. 12 of kVgg.  Layer j = 0..8 is convolution kCnnFirst + j on a map of (h[j], w[j]) pixels.
+constexpr int kCnnFirst = DC_NUM_VGG_CONVS - DC_NUM_CNN_GRAD_CONVS;
+struct CnnShape {
+  int h[DC_NUM_CNN_GRAD_CONVS], w[DC_NUM_CNN_GRAD_CONVS], fh, fw;
+  CnnShape(int h4, int w4) {
+    for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+      h[j] = h4; w[j] = w4;
+      if (kVgg[kCnnFirst + j].pool_after) { h4 = (h4 + 1) / 2; w4 = (w4 + 1) / 2; }
+    }
+    fh = h4; fw = w4;
+  }
+  size_t in_floats(int j) const { return (size_t)h[j] * w[j] * kVgg[kCnnFirst + j].cin; }
+  size_t out_floats(int j) const { return (size_t)h[j] * w[j] * kVgg[kCnnFirst + j].cout; }
+};
+// What the forward keeps: out[j] convolution j's output after its ReLU (the mask of layer j; the input of layer j + 1 where no
+// pool follows), pooled[j] the pool's output where one does.  in(j): the input of layer j, x4 for the first.
+struct CnnKept {
+  const float* x4 = nullptr;
+  float *out[DC_NUM_CNN_GRAD_CONVS] = {}, *pooled[DC_NUM_CNN_GRAD_CONVS] = {};
+  const float* in(int j) const { return j == 0 ? x4 : pooled[j - 1] != nullptr ? pooled[j - 1] : out[j - 1]; }
+};
+// own_x4: a piece for the pool2 map itself (the training forward's, which the lane's ping-pong buffers would overwrite)
+static std::vector<Carve> cnn_kept_carve(const CnnShape& sh, CnnKept& k, float** own_x4 = nullptr) {
+  std::vector<Carve> cv;
+  if (own_x4 != nullptr) cv.push_back({(void**)own_x4, sh.in_floats(0) * 4});
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+    cv.push_back({(void**)&k.out[j], sh.out_floats(j) * 4});
+    if (kVgg[kCnnFirst + j].pool_after) cv.push_back({(void**)&k.pooled[j], sh.in_floats(j + 1) * 4});
+  }
+  return cv;
+}
+// The backward's scratch, sized once for the largest layer: two gradient maps (ga, gb) and conv3x3_grad's own pieces
+struct CnnScratch { float *ga = nullptr, *gb = nullptr; ConvGradScratch r; int S[DC_NUM_CNN_GRAD_CONVS] = {}; };
+static std::vector<Carve> cnn_scratch_carve(const CnnShape& sh, CnnScratch& c) {
+  size_t map = 0, part = 0, wn = 0;
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+    const VggItem& v = kVgg[kCnnFirst + j];
+    c.S[j] = conv3x3_wgrad_slices(sh.h[j] * sh.w[j], v.cout, v.cin);
+    map = std::max(map, std::max(sh.in_floats(j), sh.out_floats(j)));
+    part = std::max(part, conv3x3_wgrad_ws_floats(c.S[j], v.cout, v.cin));
+    wn = std::max(wn, (size_t)v.cout * v.cin * 9);
+  }
+  return {{(void**)&c.ga, map * 4},        {(void**)&c.gb, map * 4},        {(void**)&c.r.part, part * 4},
+          {(void**)&c.r.wf, wn * 4},       {(void**)&c.r.wfp, wn * 4},      {(void**)&c.r.splitk, kSplitkWsFloats * 4}};
+}
+static int check_cnn_grad_args(dc_ctx* ctx, int h4, int w4, const dc_cnn_grads* out, const char* who) {
+  if (!out) return ctx->fail(DC_E_INVALID, "%s: null CNN gradient struct", who);
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j)
+    if (!out->conv_w[j] || !out->conv_b[j]) return ctx->fail(DC_E_INVALID, "%s: null CNN gradient buffer", who);
+  if (h4 < 1 || w4 < 1) return ctx->fail(DC_E_INVALID, "%s: need positive sizes", who);
+  const CnnShape sh(h4, w4);
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j)
+    DCCHK(check_conv3x3_grad_shape(ctx, sh.h[j], sh.w[j], kVgg[kCnnFirst + j].cin, kVgg[kCnnFirst + j].cout, j > 0 || out->x != nullptr, who));
+  return DC_OK;
+}
+// Launch list (stream s, eager, not synchronised; the caller holds LossCfgGuard), per layer: the engine's conv with ReLU
+// [+ maxpool2x2_ceil]; every output stays in `k`
+static int cnn_forward_kept(dc_ctx* ctx, hipStream_t s, const CnnShape& sh, const CnnKept& k, const Ws& ws) {
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+    const int i = kCnnFirst + j;
+    DCCHK(conv3x3(ctx, s, k.in(j), ctx->conv_w[i], ctx->conv_b[i], k.out[j], 1, sh.h[j], sh.w[j], kVgg[i].cin, kVgg[i].cout, 1, ws));
+    if (kVgg[i].pool_after) KCHK(launch_maxpool2x2_ceil(k.out[j], k.pooled[j], 1, sh.h[j], sh.w[j], kVgg[i].cout, s));
+  }
+  return DC_OK;
+}
+// Launch list, from conv5_3 down: relu_mask in place (maxpool2x2_ceil_relu_grad into the other map where a pool follows the
+// layer), then conv3x3_grad's launches; the first layer's dx only where out.x asks for it.  dfeat is copied first: it is read only.
+static int cnn_backward(dc_ctx* ctx, hipStream_t s, const CnnShape& sh, const CnnKept& k, const float* dfeat, const dc_cnn_grads& out,
+                        const dc_cnn_dump* dump, const CnnScratch& c) {
+  const int last = DC_NUM_CNN_GRAD_CONVS - 1;
+  float *cur = c.ga, *other = c.gb;            // cur: the gradient at the layer's output map (after the pool, where one follows)
+  HIPCHK(hipMemcpyAsync(cur, dfeat, sh.out_floats(last) * 4, hipMemcpyDeviceToDevice, s));
+  for (int j = last; j >= 0; --j) {
+    const VggItem& v = kVgg[kCnnFirst + j];
+    float* dy = cur;
+    if (v.pool_after) {
+      KCHK(launch_maxpool2x2_ceil_relu_grad(k.out[j], cur, other, 1, sh.h[j], sh.w[j], v.cout, s));
+      dy = other;
+    } else {
+      KCHK(launch_relu_mask(cur, k.out[j], sh.out_floats(j), s));
+    }
+    if (dump != nullptr && dump->dy[j] != nullptr)
+      HIPCHK(hipMemcpyAsync(dump->dy[j], dy, sh.out_floats(j) * 4, hipMemcpyDeviceToDevice, s));
+    float* dx = j > 0 ? (dy == cur ? other : cur) : out.x;
+    DCCHK(conv3x3_grad(ctx, s, k.in(j), ctx->conv_w[kCnnFirst + j], dy, sh.h[j], sh.w[j], v.cin, v.cout, c.S[j], out.conv_w[j],
+                       out.conv_b[j], dx, c.r, 1));
+    if (j > 0) { other = dy; cur = dx; }
+  }
+  return DC_OK;
+}
+// The training forward's trunk with kept activations (dc_forward_backward_cnn): conv1_1 .. pool2 as enqueue_trunk runs them, the
+// pool2 map copied into ctx->train_cnn_kept (only this function grows it: cnn_x4 / cnn_feat stay valid), then cnn_forward_kept on the lane's split-K scratch; L.feat = conv5_3's kept map.
+static int train_trunk_kept(dc_ctx* ctx, Lane& L, int* fh, int* fw) {
+  hipStream_t s = L.stream;
+  int h4 = 0, w4 = 0;
+  DCCHK(enqueue_trunk(ctx, L, 1, &h4, &w4, kCnnFirst));
+  const CnnShape sh(h4, w4);
+  CnnKept k;
+  float* x4 = nullptr;
+  const std::vector<Carve> kc = cnn_kept_carve(sh, k, &x4);
+  HIPCHK(ctx->train_cnn_kept.grow(carve(kc, nullptr), s));
+  carve(kc, ctx->train_cnn_kept.get());
+  HIPCHK(hipMemcpyAsync(x4, L.feat, sh.in_floats(0) * 4, hipMemcpyDeviceToDevice, s));
+  k.x4 = x4;
+  DCCHK(cnn_forward_kept(ctx, s, sh, k, lane_ws(L)));
+  L.feat = k.out[DC_NUM_CNN_GRAD_CONVS - 1];
+  ctx->cnn_x4 = x4; ctx->cnn_feat = L.feat; ctx->cnn_h4 = h4; ctx->cnn_w4 = w4;
+  *fh = sh.fh; *fw = sh.fw;
+  return DC_OK;
+}
+// The fourth stage of dc_forward_backward_cnn: the chain on what train_trunk_kept left in ctx->cnn_kept, dfeat = pg->feat
+static int train_cnn_backward(dc_ctx* ctx, Lane& L, const float* dfeat, const dc_cnn_grads& cg) {
+  hipStream_t s = L.stream;
+  const CnnShape sh(ctx->cnn_h4, ctx->cnn_w4);
+  CnnKept k;
+  CnnScratch c;
+  float* x4 = nullptr;
+  carve(cnn_kept_carve(sh, k, &x4), ctx->train_cnn_kept.get());
+  k.x4 = x4;
+  const std::vector<Carve> sc = cnn_scratch_carve(sh, c);
+  HIPCHK(ctx->cnn_ws.grow(carve(sc, nullptr), s));
+  carve(sc, ctx->cnn_ws.get());
+  auto& clock = ctx->cnn_clock;
+  auto body = [&]() -> int {
+    for (int i = 0; i < 3; ++i) HIPCHK(clock.record(i, s));          // (the forward ran inside train_forward: its time is the trunk stage's)
+    DCCHK(cnn_backward(ctx, s, sh, k, dfeat, cg, nullptr, c));
+    HIPCHK(clock.record(3, s));
+    HIPCHK(hipStreamSynchronize(s));
+    clock.read();
+    return DC_OK;
+  };
+  return call_finish(ctx, s, body(), "CNN backward", true);
+}
+int dc_op_cnn_grad(dc_ctx* ctx, const float* x4_hwc, int h4, int w4, const float* dfeat_hwc, const dc_cnn_grads* out,
+                   const dc_cnn_dump* dump) {
+  const char* who = "dc_op_cnn_grad";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", who);
+  if (!x4_hwc || !dfeat_hwc) return ctx->fail(DC_E_INVALID, "%s: null input", who);
+  DCCHK(check_cnn_grad_args(ctx, h4, w4, out, who));
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  drain_lanes(ctx);
+  LossCfgGuard guard(ctx->cfg);
+  const CnnShape sh(h4, w4);
+  CnnKept k;
+  CnnScratch c;
+  k.x4 = x4_hwc;
+  const std::vector<Carve> kc = cnn_kept_carve(sh, k), sc = cnn_scratch_carve(sh, c);
+  HIPCHK(ctx->cnn_kept.grow(carve(kc, nullptr), s));
+  HIPCHK(ctx->cnn_ws.grow(carve(sc, nullptr), s));
+  carve(kc, ctx->cnn_kept.get());
+  carve(sc, ctx->cnn_ws.get());
+  auto& clock = ctx->cnn_clock;
+  auto body = [&]() -> int {
+    ensure_fault_word(ctx);
+    HIPCHK(clock.record(0, s));
+    DCCHK(cnn_forward_kept(ctx, s, sh, k, Ws{c.r.splitk, kSplitkWsFloats}));
+    HIPCHK(clock.record(1, s));
+    if (dump != nullptr) {
+      const int last = DC_NUM_CNN_GRAD_CONVS - 1;
+      for (int j = 0; j <= last; ++j)
+        if (dump->act[j] != nullptr) HIPCHK(hipMemcpyAsync(dump->act[j], k.in(j), sh.in_floats(j) * 4, hipMemcpyDeviceToDevice, s));
+      for (int j = 0, p = 0; j <= last; ++j)
+        if (kVgg[kCnnFirst + j].pool_after) {
+          if (p < 2 && dump->prepool[p] != nullptr)
+            HIPCHK(hipMemcpyAsync(dump->prepool[p], k.out[j], sh.out_floats(j) * 4, hipMemcpyDeviceToDevice, s));
+          ++p;
+        }
+      if (dump->feat != nullptr) HIPCHK(hipMemcpyAsync(dump->feat, k.out[last], sh.out_floats(last) * 4, hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(clock.record(2, s));
+    DCCHK(cnn_backward(ctx, s, sh, k, dfeat_hwc, *out, dump, c));
+    HIPCHK(clock.record(3, s));
+    HIPCHK(hipStreamSynchronize(s));
+    clock.read();
+    return DC_OK;
+  };
+  return call_finish(ctx, s, body(), who, true);
 }
 
 // ---- RPN gradients (docs/SEMANTICS.md, "RPN gradients") -------------------------------------------------------------
@@ -4279,9 +4523,13 @@ int train_rpn_backward(dc_ctx* ctx, Lane& L, const TrainFwd& f, float box_reg_de
 // launched, in the order the refusals have always come in (RPN, recognition / language model, forward; every family ends with
 // the dump's); one LossCfgGuard, one drain, one lane_prepare; the stages on ctx->train; dc_losses and the dump from it.
 int train_call(dc_ctx* ctx, const TrainCall& c, int stages, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
-               const dc_rpn_grads* pg) {
+               const dc_rpn_grads* pg, const dc_cnn_grads* cg = nullptr) {
   if (!ctx) return DC_E_INVALID;
   if (!ctx->have_weights) return ctx->fail(DC_E_STATE, "%s: weights not loaded", c.who);
+  if (stages > 3) {
+    const int H = std::max(c.H, 1), W = std::max(c.W, 1);
+    DCCHK(check_cnn_grad_args(ctx, ((H + 1) / 2 + 1) / 2, ((W + 1) / 2 + 1) / 2, cg, c.who));
+  }
   if (stages > 2) DCCHK(check_rpn_args(ctx, c, pg, box_reg_decay));
   if (stages > 1) DCCHK(check_recog_lm_args(ctx, c, rg, lg));
   DCCHK(check_forward_args(ctx, c));
@@ -4290,10 +4538,15 @@ int train_call(dc_ctx* ctx, const TrainCall& c, int stages, const dc_recog_grads
   LossCfgGuard guard(ctx->cfg);
   Lane& L = lane0(ctx);
   DCCHK(lane_prepare(ctx, L, c.H, c.W, c.o.batch_size, 1));
+  struct FeatGuard {           // the kept-activation trunk points L.feat into ctx->train_cnn_kept for the stages of this call
+    Lane& L; bool on; float* feat;        // only: afterwards the lane's pointer is what it was
+    ~FeatGuard() { if (on) L.feat = feat; }
+  } feat_guard{L, c.cnn, L.feat};
   DCCHK(train_forward(ctx, c, L, ctx->train));
   fill_losses(ctx->train, c.out, c.dump);
   if (stages > 1) DCCHK(train_recog_lm_backward(ctx, c, L, ctx->train, *rg, *lg));
   if (stages > 2) DCCHK(train_rpn_backward(ctx, L, ctx->train, box_reg_decay, rg->roi_boxes, rg->feat, *pg));
+  if (stages > 3) DCCHK(train_cnn_backward(ctx, L, pg->feat, *cg));
   return DC_OK;
 }
 }  // namespace
@@ -4314,6 +4567,14 @@ int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg) {
   return train_call(ctx, TRAIN_ARGS("dc_forward_backward"), 3, rg, lg, box_reg_decay, pg);
+}
+int dc_forward_backward_cnn(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                            const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                            dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg,
+                            float box_reg_decay, const dc_rpn_grads* pg, const dc_cnn_grads* cg) {
+  TrainCall c = TRAIN_ARGS("dc_forward_backward_cnn");
+  c.cnn = true;
+  return train_call(ctx, c, 4, rg, lg, box_reg_decay, pg, cg);
 }
 // ---- the training step (docs/SEMANTICS.md, "Training step") ----------------------------------------------------------
 namespace {
@@ -4378,7 +4639,10 @@ int upload_adam_table(dc_ctx* ctx, KeptBuf& tab, hipStream_t s, std::vector<Adam
   return DC_OK;
 }
 void train_release(dc_ctx* ctx) {
-  for (KeptBuf* b : {&ctx->train_g, &ctx->train_m, &ctx->train_v, &ctx->train_master, &ctx->train_out, &ctx->train_tab}) b->reset();
+  for (KeptBuf* b : {&ctx->train_g, &ctx->train_m, &ctx->train_v, &ctx->train_master, &ctx->train_out, &ctx->train_tab,
+                     &ctx->train_cnn_master, &ctx->train_cnn_g, &ctx->train_cnn_m, &ctx->train_cnn_v, &ctx->train_cnn_tab}) b->reset();
+  ctx->train_cnn_mode = ctx->train_cnn_t = ctx->train_cnn_nseg = 0;
+  ctx->train_cnn_chunks = 0;
   ctx->training = false;
   ctx->train_t = 0;
   ctx->train_nseg = 0;
@@ -4404,7 +4668,79 @@ int train_refresh(dc_ctx* ctx, hipStream_t s) {
   ctx->grad_epoch = ctx->recog_epoch = ctx->rpn_epoch = 0;     // (weights_epoch >= 1 once weights are loaded)
   return DC_OK;
 }
+// The CNN's 18 trained tensors: per convolution kCnnFirst + j the OIHW master (w) and the ctx's own bias.  One carve list serves
+// the masters (biases: zero bytes), the gradient arena and the two moments.
+struct CnnTrain { float *w[DC_NUM_CNN_GRAD_CONVS] = {}, *b[DC_NUM_CNN_GRAD_CONVS] = {}; };
+size_t cnn_train_carve(CnnTrain& a, void* base, bool biases) {
+  std::vector<Carve> cv;
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+    const VggItem& v = kVgg[kCnnFirst + j];
+    cv.push_back({(void**)&a.w[j], (size_t)v.cout * v.cin * 9 * 4});
+    if (biases) cv.push_back({(void**)&a.b[j], (size_t)v.cout * 4});
+  }
+  return carve(cv, base);
+}
+// ... and what the library derives from them: the engine's packed convolutions and, where they exist, their split-bf16 planes
+int train_refresh_cnn(dc_ctx* ctx, hipStream_t s) {
+  CnnTrain p;
+  cnn_train_carve(p, ctx->train_cnn_master.get(), false);
+  for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+    const int i = kCnnFirst + j;
+    KCHK(launch_pack_conv3x3(p.w[j], ctx->conv_w[i], kVgg[i].cout, kVgg[i].cin, s));
+    for (const auto& e : ctx->planes)
+      if (e.planes != nullptr && e.W == ctx->conv_w[i]) KCHK(launch_split_planes(e.W, e.planes, e.rows, e.K, s));
+  }
+  return DC_OK;
+}
 }  // namespace
+
+int dc_train_set_cnn(dc_ctx* ctx, int mode) {
+  const char* who = "dc_train_set_cnn";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
+  if (mode < 0 || mode > 2) return ctx->fail(DC_E_INVALID, "%s: mode must be 0, 1 or 2 (got %d)", who, mode);
+  if (mode != 0 && ctx->train_cnn_nseg == 0) {       // the first non-zero mode: masters, zeroed moments and arena, t = 0
+    HIPCHK(hipSetDevice(ctx->device));
+    drain_lanes(ctx);
+    hipStream_t s;
+    DCCHK(lane0_stream(ctx, &s));
+    auto body = [&]() -> int {
+      CnnTrain p, g, m, v;
+      HIPCHK(ctx->train_cnn_master.grow(cnn_train_carve(p, nullptr, false), s));
+      cnn_train_carve(p, ctx->train_cnn_master.get(), false);
+      const size_t bytes = cnn_train_carve(g, nullptr, true);
+      for (KeptBuf* b : {&ctx->train_cnn_g, &ctx->train_cnn_m, &ctx->train_cnn_v}) {
+        HIPCHK(b->grow(bytes, s));
+        HIPCHK(hipMemsetAsync(b->get(), 0, bytes, s));
+      }
+      cnn_train_carve(g, ctx->train_cnn_g.get(), true);
+      cnn_train_carve(m, ctx->train_cnn_m.get(), true);
+      cnn_train_carve(v, ctx->train_cnn_v.get(), true);
+      std::vector<AdamSeg> tab;
+      for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+        const int i = kCnnFirst + j;
+        KCHK(launch_unpack_conv3x3(ctx->conv_w[i], p.w[j], kVgg[i].cout, kVgg[i].cin, s));
+        tab.push_back({p.w[j], g.w[j], m.w[j], v.w[j], (size_t)kVgg[i].cout * kVgg[i].cin * 9, 0});
+        tab.push_back({ctx->conv_b[i], g.b[j], m.b[j], v.b[j], (size_t)kVgg[i].cout, 0});
+      }
+      const int nseg = (int)tab.size();
+      DCCHK(upload_adam_table(ctx, ctx->train_cnn_tab, s, tab, &ctx->train_cnn_chunks));
+      HIPCHK(hipStreamSynchronize(s));
+      ctx->train_cnn_nseg = nseg;
+      ctx->train_cnn_t = 0;
+      return DC_OK;
+    };
+    const int rc = body();
+    if (rc != DC_OK) {
+      (void)hipStreamSynchronize(s);
+      for (KeptBuf* b : {&ctx->train_cnn_master, &ctx->train_cnn_g, &ctx->train_cnn_m, &ctx->train_cnn_v, &ctx->train_cnn_tab}) b->reset();
+      ctx->train_cnn_nseg = 0;
+      return rc;
+    }
+  }
+  ctx->train_cnn_mode = mode;
+  return DC_OK;
+}
 
 int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts) {
   const char* who = "dc_train_begin";
@@ -4462,7 +4798,9 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
   const char* who = "dc_train_step";
   if (!ctx) return DC_E_INVALID;
   if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: dc_train_begin first", who);
-  const TrainCall c = TRAIN_ARGS(who);
+  TrainCall c = TRAIN_ARGS(who);
+  const int cnn_mode = ctx->train_cnn_mode;
+  c.cnn = cnn_mode == 2;
   // what sizes the outputs below is checked here; train_call then checks everything, in dc_forward_backward's order
   DCCHK(check_forward_args(ctx, c));
   int fh = 1, fw = 1;
@@ -4487,20 +4825,35 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
   const dc_rpn_grads pg = {g.rpn_conv_w, g.rpn_conv_b, g.heads_w, g.heads_b, g.heads_w + 4 * k * R, g.heads_b + 4 * k, feat_pg};
   auto& clock = ctx->train_clock;
   HIPCHK(clock.record(0, s));
+  // the CNN's gradients: mode 2 the chain's, into the CNN's arena; mode 1 zero (train.lua:64-66, 83-85: at iter == finetune_cnn_after
+  // cnn_grad_params is zeroed and model.finetune_cnn is still false), so that step is weight decay and Adam alone
+  dc_cnn_grads cg{};
+  if (cnn_mode != 0) {
+    CnnTrain ga;
+    cnn_train_carve(ga, ctx->train_cnn_g.get(), true);
+    for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) { cg.conv_w[j] = ga.w[j]; cg.conv_b[j] = ga.b[j]; }
+  }
   ctx->fc6_grad_engine = true;
-  const int rc = train_call(ctx, c, 3, &rg, &lg, box_reg_decay, &pg);
+  const int rc = train_call(ctx, c, cnn_mode == 2 ? 4 : 3, &rg, &lg, box_reg_decay, &pg, cnn_mode == 2 ? &cg : nullptr);
   ctx->fc6_grad_engine = false;
   if (rc != DC_OK) return rc;                      // no weight and no t has changed
   const AdamScalars k1 = adam_scalars(ctx->train_opts, ctx->train_t + 1);
+  const AdamScalars kc = adam_scalars(ctx->train_opts, ctx->train_cnn_t + 1);      // (the CNN's own t: it counts CNN steps only)
   auto body = [&]() -> int {
     HIPCHK(clock.record(1, s));
     KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_tab.get()), ctx->train_nseg, ctx->train_chunks, k1, 0, s));
+    if (cnn_mode != 0) {
+      if (cnn_mode == 1) HIPCHK(hipMemsetAsync(ctx->train_cnn_g.get(), 0, ctx->train_cnn_g.bytes(), s));
+      KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_cnn_tab.get()), ctx->train_cnn_nseg, ctx->train_cnn_chunks, kc, 0, s));
+    }
     HIPCHK(clock.record(2, s));
     DCCHK(train_refresh(ctx, s));
+    if (cnn_mode != 0) DCCHK(train_refresh_cnn(ctx, s));
     HIPCHK(clock.record(3, s));
     return DC_OK;
   };
   ctx->train_t += 1;                               // (from the launch on the weights are step t's, whatever fails after it)
+  if (cnn_mode != 0) ctx->train_cnn_t += 1;
   const int rc2 = call_finish(ctx, s, body(), who, true);
   if (rc2 != DC_OK) return rc2;
   clock.read();

@@ -187,12 +187,6 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
   }
 }
 
-// d[i] = y[i] > 0 ? d[i] : 0 (the image encoder's ReLU)
-__global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ d, const float* __restrict__ y, size_t len) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < len) d[i] = y[i] > 0.f ? d[i] : 0.f;
-}
-
 // out[r] = tok[r] > 0 ? emb[tok[r] - 1] : 0, rows of E floats (the inputs the token cells were fed)
 __global__ __launch_bounds__(256) void embed_rows_kernel(const float* __restrict__ emb, const int32_t* __restrict__ tok, int E,
                                                          float* __restrict__ out) {
@@ -262,10 +256,6 @@ hipError_t launch_lstm_cell_bwd(const float* gates_pre, const int32_t* tok, cons
                                 int Hd, hipStream_t s) {
   hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(rows), dim3(256), 0, s, gates_pre, tok, xg, c_prev, c, dh_a, dh_b, dc_in, dgates,
                      dc_prev, Hd);
-  return hipGetLastError();
-}
-hipError_t launch_relu_mask(float* d, const float* y, size_t len, hipStream_t s) {
-  hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, d, y, len);
   return hipGetLastError();
 }
 hipError_t launch_embed_rows(const float* emb, const int32_t* tok, int rows, int E, float* out, hipStream_t s) {

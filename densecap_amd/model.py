@@ -591,21 +591,23 @@ class DenseCapModel:
         the six losses and the counts, the eight recognition tensors (fc6_w, fc6_b, fc7_w, fc7_b, obj_w, obj_b, boxreg_w,
         boxreg_b) and the seven language-model tensors in checkpoint layouts, `feat` (512, h, w) -- RoI pooling's share of the
         feature map's gradient, the reference's layout --, `roi_boxes` (num_pos + num_neg, 4) and `codes` (num_pos, fc_dim), the
-        language model's gradient of the positive codes.  The CNN backward is not built; the loaded weights do not
+        language model's gradient of the positive codes.  The CNN backward is not run here (ops.cnn_grad is a call of its own); the loaded weights do not
         change."""
         from . import ops
         return ops.loss_gradients(self.ctx, self._check_input(img), gt_boxes, gt_labels, **opts)
 
-    def forward_backward(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, **opts):
+    def forward_backward(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, cnn=False, **opts):
         """DenseCapModel:forward_backward (DenseCapModel.lua:401-474) with the reference's default -finetune_cnn_after -1
         (dc_forward_backward; docs/SEMANTICS.md, "RPN gradients"): loss_gradients' dict (same arguments, the same numbers) plus
         the gradients of the RPN's six tensors (rpn_conv_w, rpn_conv_b, rpn_box_w, rpn_box_b, rpn_score_w, rpn_score_b) in
         checkpoint layouts -- the two mid criteria and box_reg_decay (train_opts.lua:42) through the sampler's backward, the
         heads and the RPN's convolution.  `feat` (512, h, w) is now the complete grad_cnn_features, `feat_roi` and `feat_rpn`
-        its two shares.  Together: the gradient of all five criteria with respect to all 21 tensors outside the CNN.  The CNN
-        backward is not built; the loaded weights do not change (train_step is the call that updates them)."""
+        its two shares.  Together: the gradient of all five criteria with respect to all 21 tensors outside the CNN.  cnn=True
+        (dc_forward_backward_cnn, the reference with model.finetune_cnn; "CNN gradients"): the same dict bit for bit plus
+        conv_w4 .. conv_w12 and conv_b4 .. conv_b12, the gradients of conv3_1 .. conv5_3.  The loaded weights do not change
+        (train_step is the call that updates them; it does not train the CNN)."""
         from . import ops
-        return ops.forward_backward(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, **opts)
+        return ops.forward_backward(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, cnn=cnn, **opts)
 
     # ---- training (docs/SEMANTICS.md, "Training step") ----------------------------------------------------------------------
     def train_begin(self, **opts):
@@ -613,6 +615,12 @@ class DenseCapModel:
         starts at 0.  opts: learning_rate 1e-5, beta1 0.9, beta2 0.999, epsilon 1e-8, weight_decay 1e-6 (train_opts.lua)."""
         from . import ops
         ops.train_begin(self.ctx, **opts)
+
+    def train_set_cnn(self, mode):
+        """dc_train_set_cnn (train.lua's -finetune_cnn_after): 0 = the CNN is left alone, 1 = decay and Adam on conv3_1 .. conv5_3
+        with a zero gradient, 2 = the full CNN backward, decay and Adam; the CNN keeps an Adam step count of its own."""
+        from . import ops
+        ops.train_set_cnn(self.ctx, mode)
 
     def train_step(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, **opts):
         """One iteration of train.lua's loop body (train.lua:163-185) on one image: forward_backward (same arguments; the dict

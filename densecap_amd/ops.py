@@ -786,6 +786,83 @@ def conv3x3_wgrad(ctx, x_chw, dy_chw, slices=0):
     return o.numpy()
 
 
+# ---- CNN gradients (docs/SEMANTICS.md, "CNN gradients") -----------------------------------------------------------------------------
+CNN_GRAD_CONVS = tuple(range(4, 13))          # conv3_1 .. conv5_3 as indices of the thirteen convolutions (weights.VGG16_CONVS)
+CNN_GRAD_KEYS = tuple("conv_w%d" % i for i in CNN_GRAD_CONVS) + tuple("conv_b%d" % i for i in CNN_GRAD_CONVS)
+
+
+def maxpool2x2_grad(ctx, y_nchw, dpool_nchw):
+    """The backward of the ceil-mode 2x2/2 max pool fused with the mask of the ReLU in front of it (dc_op_maxpool2x2_grad):
+    y (N,C,H,W) the map the pool read, dpool (N,C,ceil(H/2),ceil(W/2)) -> dy (N,C,H,W)."""
+    y = _f32(y_nchw); g = _f32(dpool_nchw)
+    N, C_, H, W = y.shape
+    if g.shape != (N, C_, (H + 1) // 2, (W + 1) // 2):
+        raise ValueError("maxpool2x2_grad: dpool has shape %s" % (g.shape,))
+    yd = ctx.to_device(np.ascontiguousarray(y.transpose(0, 2, 3, 1))); gd = ctx.to_device(np.ascontiguousarray(g.transpose(0, 2, 3, 1)))
+    o = ctx.empty((N, H, W, C_))
+    check(ctx.h, ctx.lib.dc_op_maxpool2x2_grad(ctx.h, yd.ptr, gd.ptr, N, H, W, C_, o.ptr), "dc_op_maxpool2x2_grad")
+    return np.ascontiguousarray(o.numpy().transpose(0, 3, 1, 2))
+
+
+def relu_grad(ctx, y, dy):
+    """dy where y > 0, +0.0 elsewhere (dc_op_relu_grad; the library works in place on its copy of dy): arrays of one shape."""
+    y = _f32(y); dy = _f32(dy)
+    if y.shape != dy.shape:
+        raise ValueError("relu_grad: shapes %s and %s" % (y.shape, dy.shape))
+    yd = ctx.to_device(y); dd = ctx.to_device(dy)
+    check(ctx.h, ctx.lib.dc_op_relu_grad(ctx.h, yd.ptr, dd.ptr, int(y.size)), "dc_op_relu_grad")
+    return dd.numpy()
+
+
+def cnn_shapes(h4, w4):
+    """[(index of the convolution, h, w, Cin, Cout)] of conv3_1 .. conv5_3 on an (h4, w4) pool2 map, and conv5_3's map size."""
+    from .weights import VGG16_CONVS
+    out, h, w = [], int(h4), int(w4)
+    for i in CNN_GRAD_CONVS:
+        out.append((i, h, w) + tuple(VGG16_CONVS[i]))
+        if i in (6, 9):                       # pool3 behind conv3_3, pool4 behind conv4_3
+            h, w = (h + 1) // 2, (w + 1) // 2
+    return out, (h, w)
+
+
+def cnn_grad(ctx, x4_chw, dfeat_chw, want_x=True, dump=False):
+    """The backward through conv3_1 .. conv5_3 with the ctx's loaded weights (dc_op_cnn_grad): x4 (128,h4,w4) the pool2 map,
+    dfeat (512,h6,w6) the gradient at conv5_3's output -> {"conv_w4" .. "conv_w12" (Cout,Cin,3,3), "conv_b4" .. "conv_b12", "x"
+    (128,h4,w4) if want_x}.  dump: also "act4" .. "act12" (the layers' inputs), "prepool6", "prepool9", "feat" and "dy4" .. "dy12"
+    (the gradients at the convolutions' outputs after the mask), all CHW."""
+    x = _f32(x4_chw); g = _f32(dfeat_chw)
+    _, h4, w4 = x.shape
+    layers, (fh, fw) = cnn_shapes(h4, w4)
+    if x.shape[0] != 128 or g.shape != (512, fh, fw):
+        raise ValueError("cnn_grad: x4 %s, dfeat %s (want (128, h4, w4) and (512, %d, %d))" % (x.shape, g.shape, fh, fw))
+    xd = ctx.to_device(np.ascontiguousarray(x.transpose(1, 2, 0))); gd = ctx.to_device(np.ascontiguousarray(g.transpose(1, 2, 0)))
+    bufs, cg, cd = {}, _lib.DcCnnGrads(), _lib.DcCnnDump()
+    for j, (i, h, w, cin, cout) in enumerate(layers):
+        bufs["conv_w%d" % i] = ctx.empty((cout, cin, 3, 3)); bufs["conv_b%d" % i] = ctx.empty((cout,))
+        cg.conv_w[j] = bufs["conv_w%d" % i].ptr.value; cg.conv_b[j] = bufs["conv_b%d" % i].ptr.value
+        if dump:
+            bufs["act%d" % i] = ctx.empty((h, w, cin)); bufs["dy%d" % i] = ctx.empty((h, w, cout))
+            cd.act[j] = bufs["act%d" % i].ptr.value; cd.dy[j] = bufs["dy%d" % i].ptr.value
+            if i in (6, 9):
+                bufs["prepool%d" % i] = ctx.empty((h, w, cout))
+                cd.prepool[0 if i == 6 else 1] = bufs["prepool%d" % i].ptr.value
+    if dump:
+        bufs["feat"] = ctx.empty((fh, fw, 512)); cd.feat = bufs["feat"].ptr.value
+    if want_x:
+        bufs["x"] = ctx.empty((h4, w4, 128)); cg.x = bufs["x"].ptr.value
+    check(ctx.h, ctx.lib.dc_op_cnn_grad(ctx.h, xd.ptr, h4, w4, gd.ptr, C.byref(cg), C.byref(cd) if dump else None), "dc_op_cnn_grad")
+    out = {k: b.numpy() for k, b in bufs.items()}
+    return {k: (np.ascontiguousarray(a.transpose(2, 0, 1)) if a.ndim == 3 else a) for k, a in out.items()}
+
+
+def cnn_grad_ms(ctx):
+    """(kept-activation forward, backward) in ms of the last dc_op_cnn_grad, from the library's own events."""
+    ms = np.zeros(2, np.float32)
+    n = ctx.lib.dc_debug_fetch(ctx.h, b"cnn_grad_ms", ms.ctypes.data, ms.nbytes)
+    check(ctx.h, int(n), "dc_debug_fetch cnn_grad_ms")
+    return float(ms[0]), float(ms[1])
+
+
 # ---- RPN gradients (docs/SEMANTICS.md, "RPN gradients") -----------------------------------------------------------------------------
 RPN_GRAD_KEYS = ("rpn_conv_w", "rpn_conv_b", "rpn_box_w", "rpn_box_b", "rpn_score_w", "rpn_score_b", "feat")
 BOX_REG_DECAY = 5e-5               # train_opts.lua:42
@@ -849,10 +926,11 @@ def rpn_grad(ctx, feat_chw, pos_input_idx, pos_target_idx, neg_input_idx, gt_box
 
 
 def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY, forced_pos=None, forced_neg=None, dump=False,
-                     on_device=False, **opts):
+                     on_device=False, cnn=False, **opts):
     """dc_forward_backward: loss_gradients (same arguments, the same numbers) and the RPN's gradients.  Returns loss_gradients'
     dict plus the six RPN tensors, `feat_rpn` and `feat_roi` (512,h,w) -- the RPN's and RoI pooling's shares of the feature map's
-    gradient -- with `feat` now their sum, the complete grad_cnn_features."""
+    gradient -- with `feat` now their sum, the complete grad_cnn_features.  cnn=True (dc_forward_backward_cnn): the same dict bit
+    for bit, plus CNN_GRAD_KEYS, the backward of `feat` through conv5_3 .. conv3_1 on activations the forward kept."""
     dims = getattr(ctx, "lm_dims", None)
     k, R = _rpn_dims(ctx, "forward_backward")
     args, out, lists, (H, W), cap, _keep = _train_args("forward_backward", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
@@ -861,8 +939,18 @@ def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY,
     rbufs, lbufs, rg, lg = _grad_bufs(ctx, dims, h, w, cap)
     pbufs = _rpn_bufs(ctx, k, R, h, w)
     pg = _lib.DcRpnGrads(**{n: v.ptr for n, v in pbufs.items()})
-    check(ctx.h, ctx.lib.dc_forward_backward(*args, C.byref(rg), C.byref(lg), float(box_reg_decay), C.byref(pg)),
-          "dc_forward_backward")
+    cbufs = {}
+    if cnn:
+        layers, _ = cnn_shapes(*cnn_input_size(H, W))
+        cg = _lib.DcCnnGrads()
+        for j, (i, _h, _w, cin, cout) in enumerate(layers):
+            cbufs["conv_w%d" % i] = ctx.empty((cout, cin, 3, 3)); cbufs["conv_b%d" % i] = ctx.empty((cout,))
+            cg.conv_w[j] = cbufs["conv_w%d" % i].ptr.value; cg.conv_b[j] = cbufs["conv_b%d" % i].ptr.value
+        check(ctx.h, ctx.lib.dc_forward_backward_cnn(*args, C.byref(rg), C.byref(lg), float(box_reg_decay), C.byref(pg), C.byref(cg)),
+              "dc_forward_backward_cnn")
+    else:
+        check(ctx.h, ctx.lib.dc_forward_backward(*args, C.byref(rg), C.byref(lg), float(box_reg_decay), C.byref(pg)),
+              "dc_forward_backward")
     res = _train_result(out, lists)
     res.update(_grad_out(ctx, out, rbufs, lbufs, dims["D"]))
     res["feat_roi"] = res["feat"]
@@ -870,7 +958,26 @@ def forward_backward(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY,
     res["feat"] = np.ascontiguousarray(pbufs["feat"].numpy().transpose(2, 0, 1))
     share, _ms = rpn_grad_kept(ctx, h * w)
     res["feat_rpn"] = np.ascontiguousarray(share.reshape(h, w, 512).transpose(2, 0, 1))
+    res.update({n: b.numpy() for n, b in cbufs.items()})
     return res
+
+
+def cnn_input_size(H, W):
+    """(h4, w4) of the pool2 map of an H x W image (two ceil-mode 2x2 pools)."""
+    return ((H + 1) // 2 + 1) // 2, ((W + 1) // 2 + 1) // 2
+
+
+def cnn_kept(ctx, H, W):
+    """What the last forward_backward(cnn=True) of an H x W image kept (dc_debug_fetch "cnn_x4" / "cnn_feat"): the pool2 map
+    (128, h4, w4) and conv5_3's map (512, h, w)."""
+    h4, w4 = cnn_input_size(H, W)
+    _, (fh, fw) = cnn_shapes(h4, w4)
+    out = []
+    for key, shape in ((b"cnn_x4", (h4, w4, 128)), (b"cnn_feat", (fh, fw, 512))):
+        a = np.zeros(shape, np.float32)
+        check(ctx.h, int(ctx.lib.dc_debug_fetch(ctx.h, key, a.ctypes.data, a.nbytes)), "dc_debug_fetch %s" % key.decode())
+        out.append(np.ascontiguousarray(a.transpose(2, 0, 1)))
+    return tuple(out)
 
 # ---- the training step (docs/SEMANTICS.md, "Training step") -----------------------------------------------------------------------
 TRAIN_DEFAULTS = dict(learning_rate=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=1e-6)      # train_opts.lua
@@ -945,6 +1052,21 @@ def train_begin(ctx, **opts):
     """dc_train_begin: allocate the moments and the gradient arena, t = 0.  opts: the keys of TRAIN_DEFAULTS."""
     o = train_opts(**opts)
     check(ctx.h, ctx.lib.dc_train_begin(ctx.h, C.byref(o)), "dc_train_begin")
+
+
+def train_set_cnn(ctx, mode):
+    """dc_train_set_cnn: 0 = the CNN is left alone (the default), 1 = weight decay and Adam on conv3_1 .. conv5_3 with a zero
+    gradient (train.lua's step at iter == finetune_cnn_after), 2 = the full backward, decay and Adam."""
+    check(ctx.h, ctx.lib.dc_train_set_cnn(ctx.h, int(mode)), "dc_train_set_cnn")
+
+
+def finetune_cnn_mode(finetune_cnn_after, it):
+    """The CNN mode of 1-based iteration `it` under train.lua's -finetune_cnn_after N (its iter is 0-based: k = it - 1 before the
+    step): 0 if N < 0 or k < N, 1 if k == N, 2 if k > N."""
+    N, k = int(finetune_cnn_after), int(it) - 1
+    if N < 0 or k < N:
+        return 0
+    return 1 if k == N else 2
 
 
 def train_step(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY, forced_pos=None, forced_neg=None, dump=False,

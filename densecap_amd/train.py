@@ -1,4 +1,4 @@
-"""train.lua's loop on the MI355X path, for the reference's default -finetune_cnn_after -1 (the CNN stays as loaded):
+"""train.lua's loop on the MI355X path (-finetune_cnn_after N trains conv3_1 .. conv5_3 too, from iteration N on; default -1):
 
     python -m densecap_amd.train -checkpoint_start_from model.t7 -data_h5 VG.h5 -data_json VG.json -image_dir imgs \\
         -max_iters 1000 -checkpoint_path out.t7
@@ -10,7 +10,7 @@ Prints `iter %d:` lines with the six losses every -losses_log_every iterations; 
 end writes -checkpoint_path (a .t7 that run_model and evaluate_model load) and, beside it, a .json with the loss history.
 
 Not here: Dropout (the identity, where the reference trains with -drop_prob 0.5), the validation mAP inside the loop (run
-evaluate_model on the saved checkpoint), saving Adam's moments and step count, the CNN backward.  There is no CPU mode: without a
+evaluate_model on the saved checkpoint), saving Adam's moments and step count.  There is no CPU mode: without a
 HIP device the tool stops with the library's error.
 """
 from __future__ import annotations
@@ -51,6 +51,8 @@ def build_parser():
     a("-captioning_weight", type=float, default=1.0)
     # ---- the loop: train_opts.lua:61-92 ----
     a("-max_iters", type=int, default=-1, help="iterations to run; -1 = until interrupted")
+    a("-finetune_cnn_after", type=int, default=-1,
+      help="train conv3_1 .. conv5_3 too from this (0-based) iteration on; -1 = never (train_opts.lua:64)")
     a("-checkpoint_start_from", default="", help="the .t7 to start from")
     a("-checkpoint_path", default="checkpoint.t7")
     a("-save_checkpoint_every", type=int, default=10000)
@@ -82,8 +84,8 @@ def main(argv=None):
     from .evaluate_model import read_dataset
     from .run_model import load_image_caffe, load_weights
     if not opt.synthetic_weights and not opt.checkpoint_start_from:
-        raise SystemExit("-checkpoint_start_from FILE.t7 (or -synthetic_weights 1) must be given: this path trains the 21 tensors "
-                         "outside the CNN of an existing model")
+        raise SystemExit("-checkpoint_start_from FILE.t7 (or -synthetic_weights 1) must be given: this path trains "
+                         "an existing model")
     opt.checkpoint = opt.checkpoint_start_from
     weights = load_weights(opt)
     model = DenseCapModel(weights, device=opt.gpu)                      # no HIP device: DenseCapError, no CPU fallback
@@ -99,6 +101,7 @@ def main(argv=None):
             name, boxes, labels = data[it % len(data)]
             img = load_image_caffe(os.path.join(opt.image_dir, name), opt.image_size)[0][0]
             it += 1
+            model.train_set_cnn(ops.finetune_cnn_mode(opt.finetune_cnn_after, it))
             lo = model.train_step(img, boxes, np.asarray(labels)[:, :model.seq_length], box_reg_decay=opt.box_reg_decay,
                                   **loss_options(opt, it))
             if it % max(1, opt.losses_log_every) == 0 or it == opt.max_iters:

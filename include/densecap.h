@@ -567,7 +567,7 @@ int dc_op_roi_pool_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, int C,
  * feat buffers are indexed by them (the lane's buffers are sized from img_h, img_w and batch_size).  DC_E_INVALID before any
  * launch: n outside 1..1024, num_pos outside 0..n, n > batch_size, a null output, positive rows without target boxes, an image
  * side below 32 px, bad sampler options; DC_E_UNSUPPORTED: h * w > 65536, or scratch above 8 GiB.  The scratch (0.45 GB at the
- * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the CNN backward. */
+ * real model) and the two transposed weights (0.48 GB) are kept by the ctx after the first call.  Not here: the CNN's backward (dc_op_cnn_grad, a call of its own). */
 typedef struct dc_recog_grads {
   float* fc6_w; float* fc6_b; float* fc7_w; float* fc7_b; float* obj_w; float* obj_b; float* boxreg_w; float* boxreg_b; float* feat; float* roi_boxes;
 } dc_recog_grads;
@@ -598,6 +598,40 @@ int dc_feature_size(int H, int W, int* h, int* w);
  * operand offsets do not take (Cout > 2048).  Device pointers; synchronous. */
 int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float* dy, int h, int w_px, int Cin, int Cout, float* dw,
                        float* db, float* dx);
+/* ---- CNN gradients (docs/SEMANTICS.md, "CNN gradients") ----
+ * The two point-wise kernels of the CNN's backward, alone, on DEVICE pointers; synchronous.
+ * dc_op_maxpool2x2_grad: the backward of nn.SpatialMaxPooling(2,2,2,2):ceil() fused with the mask of the in-place nn.ReLU in
+ * front of it.  y (n, H, W, C): the map the pool read (the ReLU's output); dpool (n, ceil(H/2), ceil(W/2), C) -> dy (n, H, W, C),
+ * every element written: a window is clipped at the map's edge, its gradient goes to its first maximum in scan order (row, then
+ * column; `>` is strict) and only if that value is > 0; every other element is +0.0.  No atomics.  C % 4 != 0 or a non-positive
+ * size, or a pointer that is not 16-byte aligned (the kernel moves four channels at a time): DC_E_INVALID before any launch.  A NaN
+ * in y is never a maximum (every comparison with it is false): y is a ReLU's output, where the forward would have put the NaN
+ * into every later map; THNN, which takes a NaN as the maximum, is not followed there. */
+int dc_op_maxpool2x2_grad(dc_ctx* ctx, const float* y, const float* dpool, int n, int H, int W, int C, float* dy);
+/* dc_op_relu_grad: dy[i] = y[i] > 0 ? dy[i] : +0.0 in place, n_floats of them, any 4-byte alignment.  n_floats < 1: DC_E_INVALID. */
+int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats);
+/* The backward through conv_net2 (DenseCapModel.lua:338-376 with model.finetune_cnn): VGG layers 11..30, that is the nine
+ * convolutions conv3_1 .. conv5_3 (index 4..12 of the thirteen; entry i here is convolution 4 + i), their in-place ReLUs, pool3
+ * and pool4.  dc_cnn_grads: DEVICE buffers, all overwritten -- conv_w[i] (Cout, Cin, 3, 3) in the checkpoint's OIHW order,
+ * conv_b[i] (Cout), all eighteen required; x (h4, w4, 128), the gradient at conv3_1's input, or NULL (conv_net1 is never trained:
+ * that product is then not computed).  dc_cnn_dump: optional DEVICE buffers, each filled if not NULL -- act[i] the input of
+ * convolution 4 + i, prepool[0] / prepool[1] conv3_3's / conv4_3's output after its ReLU (what pool3 / pool4 read), feat conv5_3's
+ * output after its ReLU, dy[i] the gradient at convolution 4 + i's own output, after the mask. */
+#define DC_NUM_CNN_GRAD_CONVS 9
+typedef struct dc_cnn_grads { float* conv_w[9]; float* conv_b[9]; float* x; } dc_cnn_grads;
+typedef struct dc_cnn_dump { float* act[9]; float* prepool[2]; float* feat; float* dy[9]; } dc_cnn_dump;
+/* conv_net2's forward from a caller-supplied pool2 map x4_hwc (h4, w4, 128) with the loaded weights, keeping the nine layer
+ * inputs and the two pre-pool maps on the device (the ctx keeps them between calls, grow only: 145 MB at 720 x 600, and 0.5 GB
+ * of scratch, 400 MiB of it the engine's split-K scratch), then the backward
+ * of dfeat_hwc (h6, w6, 512), h6 = ceil(ceil(h4 / 2) / 2): per layer, from conv5_3 down, the ReLU's mask (dc_op_relu_grad; at
+ * conv4_3 and conv3_3 dc_op_maxpool2x2_grad), then dc_op_conv3x3_grad's launches for dw, db and dx.  The forward is
+ * dc_op_conv3x3 with relu = 1 and dc_op_maxpool2x2_ceil, layer by layer.  fp32 whatever dc_set_math_mode says, eager on lane 0,
+ * no float atomics: two identical calls give identical bits; settings and weights are left as they were.  Device pointers;
+ * synchronous.  Without weights: DC_E_STATE.  DC_E_INVALID before any launch: a null input or gradient buffer, a non-positive
+ * size; DC_E_UNSUPPORTED: h4 * w4 > 65536, in dc_op_conv3x3_grad's words.  Not here: Dropout (the identity), the optimiser
+ * (dc_train_step trains the 21 tensors outside the CNN only). */
+int dc_op_cnn_grad(dc_ctx* ctx, const float* x4_hwc, int h4, int w4, const float* dfeat_hwc, const dc_cnn_grads* out,
+                   const dc_cnn_dump* dump_or_null);
 /* RPN gradients (docs/SEMANTICS.md, "RPN gradients"): DEVICE buffers for the gradients of the RPN's six tensors in checkpoint
  * layouts -- rpn_conv_w (rpn_hidden, 512, 3, 3), rpn_conv_b, rpn_box_w (4k, rpn_hidden), rpn_box_b, rpn_score_w (2k, rpn_hidden),
  * rpn_score_b -- and feat (h, w, 512), a gradient of the feature map.  All required, all overwritten. */
@@ -627,11 +661,22 @@ int dc_op_rpn_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const int32
  * grad_cnn_features = rg->feat + the RPN's share, one fp32 add per element (LocalizationLayer.lua:550,581,601); rg->feat keeps RoI
  * pooling's share.  box_reg_decay: train_opts.lua's -box_reg_decay (5e-5 there).  With no sampled row the RPN gradients are the
  * decay term's alone.  Together the three structs hold the gradient of all five criteria and the decay with respect to all 21
- * tensors outside the CNN.  Not here: the CNN's backward (the optimiser: dc_train_step).  Synchronous. */
+ * tensors outside the CNN.  Not here: the CNN's backward (dc_forward_backward_cnn) and the optimiser (dc_train_step).
+ * Synchronous. */
 int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                         const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg);
+/* dc_forward_backward (same arguments; out, dump, rg, lg and pg are that call's bits) with conv_net2's activations kept by the
+ * forward -- conv1_1 .. pool2 as ever, then dc_op_cnn_grad's forward on the pool2 map, whose conv5_3 map is the fused trunk's bit
+ * for bit --, and then dc_op_cnn_grad's backward of pg->feat, the complete grad_cnn_features: cg, the 18 gradients of conv3_1 ..
+ * conv5_3 (cg->x may be NULL).  DenseCapModel:forward_backward with model.finetune_cnn.  The refusals of dc_forward_backward and
+ * of dc_op_cnn_grad, before anything is allocated or launched.  Not here: the optimiser (dc_train_step, dc_train_set_cnn).
+ * Synchronous. */
+int dc_forward_backward_cnn(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                            const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                            dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg,
+                            float box_reg_decay, const dc_rpn_grads* pg, const dc_cnn_grads* cg);
 /* ---- training step (docs/SEMANTICS.md, "Training step") ----
  * The other half of train.lua's loop body (train.lua:163-185) on the device: grad_params:add(weight_decay, params), then
  * adam(params, grad_params, learning_rate, beta1, beta2, epsilon) (optim_updates.lua:56-84) on the 21 tensors outside the CNN, in
@@ -647,10 +692,21 @@ int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts);
  * from a trained weight is remade on the device (the list: DESIGN.md section 19), so that every later call -- forward, scoring,
  * sampling, either math mode, a captured graph: weight pointers do not move -- computes what a fresh ctx loaded with
  * dc_get_weights' arrays computes.  A refused step changes no weight and no t.  Before dc_train_begin: DC_E_STATE.  Dropout is
- * the identity, as in dc_forward_backward; the CNN is not trained.  Eager on lane 0, synchronous. */
+ * the identity, as in dc_forward_backward; the CNN is trained only after dc_train_set_cnn.  Eager on lane 0, synchronous. */
 int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                   const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                   dc_losses* out, const dc_loss_dump* dump, float box_reg_decay);
+/* The CNN's share of the step, train.lua's -finetune_cnn_after (docs/SEMANTICS.md, "CNN gradients").  Valid between dc_train_begin
+ * and dc_train_end (else DC_E_STATE); a mode outside 0..2: DC_E_INVALID.  mode 0, the default: dc_train_step is the step above,
+ * bit for bit.  mode 1, the step train.lua takes at iter == finetune_cnn_after: the CNN's gradient is zero (model.finetune_cnn is
+ * still false there), weight_decay * cnn_params is added and Adam steps on conv3_1 .. conv5_3 and their biases.  mode 2: the
+ * step runs dc_forward_backward_cnn, then decay and Adam on those 18 tensors too.  The first non-zero mode allocates the OIHW
+ * masters of the nine convolutions, zeroed moments and a gradient arena; the CNN has its own Adam step count, from 0, which
+ * counts the steps taken in mode 1 or 2 only (cnn_optim_state, train.lua:115), with dc_train_begin's learning rate and betas, in
+ * a second launch of the Adam kernel; the 21 other tensors' update is the same launch with the same bits in every mode.  After a
+ * CNN step the nine packed convolutions and their split-bf16 planes are remade from the masters (pointers do not move).
+ * conv1_1 .. conv2_2 are never trained.  dc_train_end frees this state too. */
+int dc_train_set_cnn(dc_ctx* ctx, int mode);
 /* Frees the moments, the arena and the master; the weights stay as trained.  Without a begin: DC_E_STATE. */
 int dc_train_end(dc_ctx* ctx);
 /* The current weights in the checkpoint's layouts: every non-null tensor pointer of `out` (HOST memory, the sizes of

@@ -303,7 +303,7 @@ end
 -- forward_backward's loss keys, num_pos and num_neg, and `grads`: FloatTensors in the checkpoint's layouts for fc6_w, fc6_b, fc7_w,
 -- fc7_b, obj_w, obj_b, boxreg_w, boxreg_b and the seven language-model tensors, feat (512, h, w) -- RoI pooling's share of
 -- grad_cnn_features --, roi_boxes (num_pos + num_neg, 4) and codes (num_pos, fc_dim).  The CNN backward is not
--- built.
+-- run here (dc_op_cnn_grad is a call of its own).
 function Model:loss_gradients(data, opts)
   opts = opts or {}
   local input = data.image
@@ -377,8 +377,9 @@ end
 -- (dc_forward_backward; docs/SEMANTICS.md, "RPN gradients").  data and opts as forward_losses, plus opts.box_reg_decay
 -- (train_opts.lua:42: 5e-5).  Returns the reference's loss keys, num_pos and num_neg, and `grads`: loss_gradients' tensors plus
 -- rpn_conv_w, rpn_conv_b, rpn_box_w, rpn_box_b, rpn_score_w, rpn_score_b in the checkpoint's layouts -- all 21 tensors outside the
--- CNN --, feat (512, h, w), now the complete grad_cnn_features, and feat_roi, RoI pooling's share of it.  The CNN backward is
--- not built; the loaded weights do not change (train_step is the call that updates them).
+-- CNN --, feat (512, h, w), now the complete grad_cnn_features, and feat_roi, RoI pooling's share of it.  With model.finetune_cnn
+-- set (DenseCapModel.lua:338-376) the call is dc_forward_backward_cnn and grads also holds conv_w4 .. conv_w12 (Cout, Cin, 3, 3)
+-- and conv_b4 .. conv_b12, the gradients of conv3_1 .. conv5_3.  The loaded weights do not change (train_step updates them).
 function Model:forward_backward(data, opts)
   opts = opts or {}
   local input = data.image
@@ -436,9 +437,28 @@ function Model:forward_backward(data, opts)
   bind(rg, rnames, {feat = 'feat_roi'})
   bind(lg, lnames)
   bind(pg, pnames)
+  local cg = nil
+  if self.finetune_cnn then                           -- conv3_1 .. conv5_3: entry j of dc_cnn_grads is convolution 4 + j
+    local chans = {{128, 256}, {256, 256}, {256, 256}, {256, 512}, {512, 512}, {512, 512}, {512, 512}, {512, 512}, {512, 512}}
+    cg = ffi.new('dc_cnn_grads')
+    for j, c in ipairs(chans) do
+      local tw, tb = torch.FloatTensor(c[2], c[1], 3, 3), torch.FloatTensor(c[2])
+      cg.conv_w[j - 1] = ffi.cast('float*', alloc(tw:nElement() * 4))
+      cg.conv_b[j - 1] = ffi.cast('float*', alloc(tb:nElement() * 4))
+      grads['conv_w' .. (j + 3)], grads['conv_b' .. (j + 3)] = tw, tb
+      host[#host + 1] = {cg.conv_w, j - 1, tw}
+      host[#host + 1] = {cg.conv_b, j - 1, tb}
+    end
+  end
   local out = ffi.new('dc_losses')
-  local rc = C.dc_forward_backward(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl), gb:size(1),
-                                   gl:size(2), o, nil, out, nil, rg, lg, decay, pg)
+  local rc
+  if cg then
+    rc = C.dc_forward_backward_cnn(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl), gb:size(1),
+                                   gl:size(2), o, nil, out, nil, rg, lg, decay, pg, cg)
+  else
+    rc = C.dc_forward_backward(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl), gb:size(1),
+                               gl:size(2), o, nil, out, nil, rg, lg, decay, pg)
+  end
   for _, e in ipairs(host) do
     if rc == 0 then rc = C.dc_memcpy_d2h(self.ctx, torch.data(e[3]), e[1][e[2]], e[3]:nElement() * 4) end
   end
@@ -474,8 +494,9 @@ end
 -- One iteration (dc_train_step): forward_backward on `data` (data and opts as forward_losses, plus opts.box_reg_decay), then
 -- grad_params:add(weight_decay, params) and adam(params, grad_params, ...) on the 21 tensors outside the CNN, in place on the
 -- device, and the refresh of everything the library derives from them.  Returns forward_backward's loss keys, num_pos and
--- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is the identity; the CNN is
--- not trained.
+-- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is the identity.  The CNN:
+-- opts.cnn_mode (dc_train_set_cnn: 0, 1, 2), by default 2 where model.finetune_cnn is set (train.lua:83-85) and 0 where not;
+-- train.lua's step at iter == finetune_cnn_after, decay and Adam on a zero gradient, is cnn_mode = 1.
 function Model:train_step(data, opts)
   opts = opts or {}
   local input = data.image
@@ -495,6 +516,7 @@ function Model:train_step(data, opts)
   o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
   o.captioning_weight = get('captioning_weight', 1.0)
   o.seed = get('loss_seed', 0)
+  hip.check(self.ctx, C.dc_train_set_cnn(self.ctx, get('cnn_mode', self.finetune_cnn and 2 or 0)), 'dc_train_set_cnn')
   local out = ffi.new('dc_losses')
   hip.check(self.ctx, C.dc_train_step(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),
                                       gb:size(1), gl:size(2), o, nil, out, nil, get('box_reg_decay', 5e-5)), 'dc_train_step')
@@ -506,7 +528,7 @@ function Model:train_step(data, opts)
   }
 end
 
--- dc_train_end: frees the moments and the gradient arena; the weights stay as trained.
+-- dc_train_end: frees the moments and the gradient arenas (the CNN's too); the weights stay as trained.
 function Model:train_end()
   hip.check(self.ctx, C.dc_train_end(self.ctx), 'dc_train_end')
 end

@@ -97,6 +97,12 @@ int dc_loss_gradients(dc_ctx* ctx, const float* img_chw, int H, int W, int img_o
 int dc_feature_size(int H, int W, int* h, int* w);
 int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float* dy, int h, int w_px, int Cin, int Cout, float* dw,
                        float* db, float* dx);
+int dc_op_maxpool2x2_grad(dc_ctx* ctx, const float* y, const float* dpool, int n, int H, int W, int C, float* dy);
+int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats);
+typedef struct dc_cnn_grads { float* conv_w[9]; float* conv_b[9]; float* x; } dc_cnn_grads;
+typedef struct dc_cnn_dump { float* act[9]; float* prepool[2]; float* feat; float* dy[9]; } dc_cnn_dump;
+int dc_op_cnn_grad(dc_ctx* ctx, const float* x4_hwc, int h4, int w4, const float* dfeat_hwc, const dc_cnn_grads* out,
+                   const dc_cnn_dump* dump_or_null);
 typedef struct dc_rpn_grads {
   float* rpn_conv_w; float* rpn_conv_b; float* rpn_box_w; float* rpn_box_b; float* rpn_score_w; float* rpn_score_b; float* feat;
 } dc_rpn_grads;
@@ -108,8 +114,13 @@ int dc_forward_backward(dc_ctx* ctx, const float* img_chw, int H, int W, int img
                         const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                         dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg, float box_reg_decay,
                         const dc_rpn_grads* pg);
+int dc_forward_backward_cnn(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
+                            const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
+                            dc_losses* out, const dc_loss_dump* dump, const dc_recog_grads* rg, const dc_lm_grads* lg,
+                            float box_reg_decay, const dc_rpn_grads* pg, const dc_cnn_grads* cg);
 typedef struct dc_train_opts { double learning_rate, beta1, beta2, epsilon, weight_decay; } dc_train_opts;
 int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts);
+int dc_train_set_cnn(dc_ctx* ctx, int mode);
 int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                   const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                   dc_losses* out, const dc_loss_dump* dump, float box_reg_decay);

@@ -12,8 +12,9 @@ minimum.
                      written, g read), and hipMemcpy device to device of the same byte count split as a copy moves it (half read,
                      half written), both timed by the host around a synchronous call in the same loop
 
---tree DIR: time forward_backward alone with the package of another checkout (the parent commit's, built), for the A/B of
-"forward_backward must not slow": run it alternating with this tree's in one job.
+--tree DIR: time forward_backward and train_step with the package of another checkout (the parent commit's, built), for the A/B
+of "must not slow": run it alternating with this tree's in one job.  --cnn_mode M: dc_train_set_cnn(M) before the timed steps
+(2: the step with the CNN's backward, decay and Adam; its backward stage from dc_debug_fetch "cnn_grad_ms").
 usage: python tools/train_step_bench.py [--reps 30] [--warmup 5] [--tree DIR] [--out profiles/train_step_bench.json]"""
 import argparse
 import ctypes as C
@@ -47,6 +48,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--tree", default="")
+    ap.add_argument("--cnn_mode", type=int, default=0, help="dc_train_set_cnn before the timed steps (0: the CNN is left alone)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
@@ -91,27 +93,34 @@ def main():
                tree=os.path.abspath(a.tree) if a.tree else "this tree")
     doc["forward_backward"] = stats(timed(fb, a.warmup, a.reps))
     doc["num_pos"], doc["num_neg"] = int(out_b.num_pos), int(out_b.num_neg)
-    if a.tree:
-        print(json.dumps(doc))
-        if a.out:
-            with open(a.out, "w") as f:
-                json.dump(doc, f, indent=1)
-        return
     for b in list(rb.values()) + list(lb.values()) + list(pb.values()):      # the step keeps its gradients in an arena of its own
         b.free()
     ops.train_begin(ctx)
-    split = []
+    if a.cnn_mode:
+        ops.train_set_cnn(ctx, a.cnn_mode)
+    doc["cnn_mode"] = a.cnn_mode
+    split, cnn_ms = [], []
 
     def ts():
         _lib.check(ctx.h, lib.dc_train_step(ctx.h, *args, C.byref(out_t), None, ops.BOX_REG_DECAY), "dc_train_step")
         split.append(list(ops.train_step_ms(ctx).values()))
+        if a.cnn_mode == 2:
+            cnn_ms.append(ops.cnn_grad_ms(ctx)[1])
 
     doc["train_step"] = stats(timed(ts, a.warmup, a.reps))
     sp = np.asarray(split[a.warmup:], np.float64)
     doc["train_step_split_ms"] = {n: dict(median=float(np.median(sp[:, i])), p10=float(np.percentile(sp[:, i], 10)),
                                           p90=float(np.percentile(sp[:, i], 90))) for i, n in enumerate(("backward", "adam", "refresh"))}
     doc["loss_before_the_first_step"], doc["loss_before_the_last_step"] = float(out_b.total_loss), float(out_t.total_loss)
+    if cnn_ms:
+        doc["cnn_backward_ms"] = float(np.median(cnn_ms[a.warmup:]))
     ops.train_end(ctx)
+    if a.tree or a.cnn_mode:
+        print(json.dumps(doc))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+        return
     # ---- the Adam kernel against a device-to-device copy of the same bytes ----
     n = int(sum(int(np.prod(s)) for name, s in list(lshapes.items()) if name != "codes") + D * 49 * 512 + D + D * D + D + 5 * D + 5 +
             R * 512 * 9 + R + 6 * k * R + 6 * k)
