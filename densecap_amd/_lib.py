@@ -252,6 +252,10 @@ _SIGS = {
     "dc_op_conv3x3_grad": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
     "dc_op_maxpool2x2_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "dc_op_relu_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]),
+    "dc_set_dropout": (C.c_int, [C.c_void_p, C.c_float]),
+    "dc_get_dropout": (C.c_int, [C.c_void_p, c_float_p]),
+    "dc_op_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64]),
+    "dc_op_relu_dropout_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float]),
     "dc_op_cnn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DcCnnGrads), C.POINTER(DcCnnDump)]),
     "dc_op_rpn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(DcLossOpts), C.c_float,

@@ -585,6 +585,17 @@ hipError_t launch_maxpool2x2_ceil_relu_grad(const float* y, const float* dpool, 
 // dy[i] = y[i] > 0 ? dy[i] : +0.0 in place, n floats; any 4-byte alignment (16-byte accesses where both pointers allow them)
 hipError_t launch_relu_mask(float* dy, const float* y, size_t n, hipStream_t s);
 
+// ---- Dropout of the training forward (dropout.hip; docs/SEMANTICS.md, "Dropout") ----
+// T = floor((1 - p) 2^32) in double (2^32 where 1 - p rounds to 1); s = 1 / (1 - p) in fp32
+unsigned long long dropout_threshold(float p);
+float dropout_scale(float p);
+// In place on x (rows, cols), row stride ld >= cols floats: element (row, col) is kept, as x * s, iff word col & 3 of
+// philox4x32_10(col >> 2, row, layer, 1, seed) < T, and is +0.0 otherwise.  0 < p < 1, layer in 0..255; any 4-byte alignment
+// (16-byte accesses where x is 16-byte aligned and ld % 4 == 0).
+hipError_t launch_dropout_rows(float* x, int rows, int cols, size_t ld, int layer, float p, uint64_t seed, hipStream_t s);
+// dy[i] = y[i] > 0 ? dy[i] * s : +0.0 in place, n floats, y the dropped activation; 0 < p < 1; alignment as launch_relu_mask
+hipError_t launch_relu_dropout_mask(float* dy, const float* y, size_t n, float p, hipStream_t s);
+
 // ---- RPN gradients (rpn_grad.hip; docs/SEMANTICS.md, "RPN gradients") ----
 // The gradient at the RPN's head outputs, dheads (h * w, 6k) in the layout of the heads: the two mid criteria on the sampled rows,
 // ApplyBoxTransform:backward of droi (n, 4) or null, scattered by the sampler's copy rule (the last sampled row that names an

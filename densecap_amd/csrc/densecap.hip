@@ -64,10 +64,12 @@ struct Settings {
                                     // hook: small and ragged problems then exercise the split-bf16 kernels)
   int nms_band = 1;                 // launch_nms `band`; dc_create reads the default from DC_NMS_BAND
   int decode_screen = -1;           // greedy decode step: 0 = fused fp32 step, 1 = bf16 screen + exact re-score, -1 = by row count (screen_pays)
+  float dropout_p = 0.f;            // dc_set_dropout: the two nn.Dropout layers of the training forward (0 = none; never NaN, so bytewise
+                                    // comparison holds); inference never reads it
   // contractions planned for one image alone (stream-K / tail plans over partial last rounds): images then travel alone
   bool serial_planning() const { return plan_mode < 0 ? serial_mode != 0 : plan_mode == 1; }
 };
-static_assert(sizeof(Settings) == 19 * 4, "Settings has 4-byte fields only (GraphKey compares it bytewise); a new field updates this count");
+static_assert(sizeof(Settings) == 20 * 4, "Settings has 4-byte fields only (GraphKey compares it bytewise); a new field updates this count");
 
 // Everything a captured forward bakes in: workspace pointers (carve epoch, arena, staging), weights, shape and the settings.
 // Bytewise equality up to the end of `set`: 8-byte fields first, then 4-byte ones, so nothing in between is padding.
@@ -1917,6 +1919,20 @@ int dc_set_math_mode(dc_ctx* ctx, int mode) {
   return DC_OK;
 }
 
+// nn.Dropout's own check (Dropout.lua: "p must be in range [0, 1)"); NaN fails the comparison
+int dc_set_dropout(dc_ctx* ctx, float p) {
+  if (!ctx) return DC_E_INVALID;
+  if (!(p >= 0.f && p < 1.f)) return ctx->fail(DC_E_INVALID, "dc_set_dropout: p must be in [0, 1), got %g", (double)p);
+  ctx->cfg.dropout_p = p;
+  return DC_OK;
+}
+int dc_get_dropout(dc_ctx* ctx, float* p) {
+  if (!ctx) return DC_E_INVALID;
+  if (!p) return ctx->fail(DC_E_INVALID, "dc_get_dropout: null pointer");
+  *p = ctx->cfg.dropout_p;
+  return DC_OK;
+}
+
 int dc_set_graph_replay(dc_ctx* ctx, int on) {
   if (!ctx) return DC_E_INVALID;
   ctx->graphs = on != 0;
@@ -2498,6 +2514,7 @@ int64_t dc_debug_fetch(dc_ctx* ctx, const char* name, void* host_buf, int64_t ca
         {"loss_rpn_trans", k.trans, (int64_t)k.A * 4, 4},     {"loss_rpn_scores", k.scores, (int64_t)k.A * 2, 4},
         {"loss_obj", L.obj, kn, 4},                           {"loss_final_trans", L.final_trans, kn * 4, 4},
         {"loss_roi_boxes", L.roi_boxes, kn * 4, 4},           {"loss_codes", L.codes, kn * ctx->D, 4},
+        {"loss_fc6_out", L.fc6_out, kn * ctx->D, 4},
         {"loss_rowlik", k.rowlik, (int64_t)k.np, 8},         {"loss_feat", k.kept_feat ? ctx->cnn_feat : L.feat, (int64_t)k.h * k.w * 512, 4}};
     for (const auto& e : kept) {
       if (strcmp(name, e.n) != 0) continue;
@@ -3168,12 +3185,17 @@ int rpn_train_forward(dc_ctx* ctx, Lane& L, const float* feat, int h, int w, int
   KCHK(launch_rpn_score_rows(heads, h, w, k, scores, s));
   return DC_OK;
 }
-// fc6, fc7 and the recognition heads on the n pooled rows of L.roi_feats (their boxes in L.roi_boxes), planned for `batch` rows
-int recog_rows_forward(dc_ctx* ctx, Lane& L, int n, int batch) {
+// fc6, fc7 and the recognition heads on the n pooled rows of L.roi_feats (their boxes in L.roi_boxes), planned for `batch` rows.
+// With dc_set_dropout's p > 0: Dropout layer 1 in place on fc6_out and layer 2 on codes, masks by `seed` (docs/SEMANTICS.md,
+// "Dropout"); at p = 0 no launch is added.
+int recog_rows_forward(dc_ctx* ctx, Lane& L, int n, int batch, uint64_t seed) {
   hipStream_t s = L.stream;
   const int D = ctx->D;
+  const float p = ctx->cfg.dropout_p;
   DCCHK(linear(ctx, s, L.roi_feats, ctx->fc6_w, ctx->fc6_b, L.fc6_out, n, D, 49 * 512, 1, lane_ws(L), batch));
+  if (p > 0.f) KCHK(launch_dropout_rows(L.fc6_out, n, D, (size_t)D, 1, p, seed, s));
   DCCHK(linear(ctx, s, L.fc6_out, ctx->fc7_w, ctx->fc7_b, L.codes, n, D, D, 1, lane_ws(L), batch));
+  if (p > 0.f) KCHK(launch_dropout_rows(L.codes, n, D, (size_t)D, 2, p, seed, s));
   KCHK(launch_recog_heads(L.codes, ctx->head5_w, ctx->head5_b, L.roi_boxes, L.obj, L.final_trans, L.final_boxes, L.final_xyxy, n, D, s));
   return DC_OK;
 }
@@ -3260,7 +3282,7 @@ int train_forward(dc_ctx* ctx, const TrainCall& c, Lane& L, TrainFwd& f) {
       HIPCHK(hipMemcpyAsync(sel, f.pos_idx, (size_t)np * 4, hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemcpyAsync(sel + np, f.neg_idx, (size_t)nn * 4, hipMemcpyDeviceToDevice, s));
       KCHK(launch_bilinear_roi_pool_group(L.feat, 0, 1, h, w, 512, L.roi_boxes, n, nullptr, 0, sel, f.boxes, 0, H, W, 7, 7, L.roi_feats, 1, s));
-      DCCHK(recog_rows_forward(ctx, L, n, batch));
+      DCCHK(recog_rows_forward(ctx, L, n, batch, o.seed));
     }
     HIPCHK(hipEventRecord(L.ev[3], s));
     // ---- captioning: every positive row against the labels of its ground-truth box ----
@@ -3607,11 +3629,13 @@ static int check_recog_out(dc_ctx* ctx, const dc_recog_grads* o, const char* who
 // Launch list (lane 0's stream, eager; the caller holds LossCfgGuard):
 //   end_crit_grad; heads_bwd; five small copies into the head outputs
 //   relu_mask (fc7); wgrad + colsum (fc7); GEMM on fc7_wT; relu_mask (fc6); wgrad + permute_fc6_back + colsum (fc6)
+//   (with dc_set_dropout's p > 0 the two relu_mask launches are relu_dropout_mask: in.codes and in.fc6_out carry the masks)
 //   GEMM on fc6_wT: dpool (n, 7, 7, 512)
 //   memset + roi_taps + roi_index_scan + roi_place + roi_sort_lists; roi_scatter_sum + roi_chunk_reduce
 //   roi_box_grad; add_pos_rows4
 static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const dc_recog_grads& out, int32_t* masked_end) {
   const int D = ctx->D, n = in.n, np = in.np;
+  const float drop_p = ctx->cfg.dropout_p;
   if (ctx->fc7_wT == nullptr || ctx->recog_epoch != ctx->weights_epoch) {
     if (ctx->fc7_wT == nullptr) {
       DCCHK(dev_alloc(ctx, (void**)&ctx->fc7_wT, (size_t)D * D * 4));
@@ -3635,7 +3659,8 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
     HIPCHK(hipMemcpyAsync(out.obj_b, r.db5, 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(out.boxreg_b, r.db5 + 1, 16, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(masked_end, r.masked, 4, hipMemcpyDeviceToHost, s));
-    KCHK(launch_relu_mask(r.dcodes, in.codes, (size_t)n * D, s));
+    if (drop_p > 0.f) KCHK(launch_relu_dropout_mask(r.dcodes, in.codes, (size_t)n * D, drop_p, s));
+    else KCHK(launch_relu_mask(r.dcodes, in.codes, (size_t)n * D, s));
     KCHK(launch_wgrad(r.dcodes, D, in.fc6_out, D, n, D, D, out.fc7_w, D, r.ws, s));
     KCHK(launch_colsum(r.dcodes, D, n, D, out.fc7_b, s));
     {
@@ -3643,7 +3668,8 @@ static int recog_backward(dc_ctx* ctx, hipStream_t s, const RecogKept& in, const
       g.A = r.dcodes; g.W = ctx->fc7_wT; g.C = r.dx7; g.M = n; g.N = D; g.K = D; g.ldc = D;
       DCCHK(run_gemm(ctx, g, s));
     }
-    KCHK(launch_relu_mask(r.dx7, in.fc6_out, (size_t)n * D, s));
+    if (drop_p > 0.f) KCHK(launch_relu_dropout_mask(r.dx7, in.fc6_out, (size_t)n * D, drop_p, s));
+    else KCHK(launch_relu_mask(r.dx7, in.fc6_out, (size_t)n * D, s));
     if (ctx->fc6_grad_engine) {        // the training step updates fc6 where it lives: its gradient stays in the engine's order
       KCHK(launch_wgrad(r.dx7, D, in.roi_feats, kRecogK6, n, D, kRecogK6, out.fc6_w, kRecogK6, r.ws, s));
     } else {
@@ -3716,7 +3742,7 @@ int dc_op_recog_grad(dc_ctx* ctx, const float* feat_hwc, int h, int w, const flo
   auto fwd = [&]() -> int {
     HIPCHK(hipMemcpyAsync(L.roi_boxes, roi_boxes, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
     KCHK(launch_bilinear_roi_pool(feat_hwc, h, w, 512, L.roi_boxes, n, nullptr, img_h, img_w, 7, 7, L.roi_feats, 1, s));
-    DCCHK(recog_rows_forward(ctx, L, n, o.batch_size));
+    DCCHK(recog_rows_forward(ctx, L, n, o.batch_size, o.seed));
     DCCHK(enqueue_loss_terms(ctx, s, f, L.roi_boxes, L.final_trans, L.obj, 1, terms, masked));
     HIPCHK(hipStreamSynchronize(s));
     return DC_OK;
@@ -4154,6 +4180,28 @@ int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats) 
   if (!y || !dy) return ctx->fail(DC_E_INVALID, "dc_op_relu_grad: null pointer");
   if (n_floats < 1) return ctx->fail(DC_E_INVALID, "dc_op_relu_grad: need n_floats >= 1");
   KCHK(launch_relu_mask(dy, y, (size_t)n_floats, s));
+  OP_EPILOGUE();
+}
+
+// ---- Dropout (docs/SEMANTICS.md, "Dropout") ---------------------------------------------------------------------------------------
+int dc_op_dropout(dc_ctx* ctx, float* x, int rows, int cols, int layer, float p, uint64_t seed) {
+  OP_PROLOGUE();
+  const char* who = "dc_op_dropout";
+  if (!x) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (rows < 1 || cols < 1) return ctx->fail(DC_E_INVALID, "%s: need rows >= 1 and cols >= 1 (got %d, %d)", who, rows, cols);
+  if (layer < 0 || layer > 255) return ctx->fail(DC_E_INVALID, "%s: layer must be in 0..255 (got %d)", who, layer);
+  if (!(p >= 0.f && p < 1.f)) return ctx->fail(DC_E_INVALID, "%s: p must be in [0, 1), got %g", who, (double)p);
+  if (p > 0.f) KCHK(launch_dropout_rows(x, rows, cols, (size_t)cols, layer, p, seed, s));     // (p = 0: the identity, no launch)
+  OP_EPILOGUE();
+}
+int dc_op_relu_dropout_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats, float p) {
+  OP_PROLOGUE();
+  const char* who = "dc_op_relu_dropout_grad";
+  if (!y || !dy) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n_floats < 1) return ctx->fail(DC_E_INVALID, "%s: need n_floats >= 1", who);
+  if (!(p >= 0.f && p < 1.f)) return ctx->fail(DC_E_INVALID, "%s: p must be in [0, 1), got %g", who, (double)p);
+  if (p > 0.f) KCHK(launch_relu_dropout_mask(dy, y, (size_t)n_floats, p, s));
+  else KCHK(launch_relu_mask(dy, y, (size_t)n_floats, s));
   OP_EPILOGUE();
 }
 

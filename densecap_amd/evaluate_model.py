@@ -20,7 +20,9 @@ hdf5_min.write_hdf5's layout (classic superblock, contiguous datasets); files wr
 they are with -data_h5, the -gt_json captions tokenised like query_regions' queries (unknown words become <UNK>), cut to the
 model's seq_length and zero-padded -- and the six losses, averaged over the images, are printed as `loss_results`, added to the
 result under that key and kept in eval_state.json, so that the second phase reports them again.  The sampler's settings and the
-five weights are train_opts.lua's, with its defaults; -loss_seed selects the sampler's draws.
+five weights are train_opts.lua's, with its defaults; -loss_seed selects the sampler's draws.  -drop_prob P runs that forward
+under Dropout (docs/SEMANTICS.md, "Dropout"; default 0, none; the reference's eval_split measures under 0.5); the detections
+never drop.
 """
 from __future__ import annotations
 
@@ -72,7 +74,10 @@ def build_parser():
     a("-end_box_reg_weight", type=float, default=0.1)
     a("-end_objectness_weight", type=float, default=0.1)
     a("-captioning_weight", type=float, default=1.0)
-    a("-loss_seed", type=int, default=0, help="seed of the box sampler's draws")
+    a("-loss_seed", type=int, default=0, help="seed of the box sampler's draws (and of the Dropout masks)")
+    a("-drop_prob", type=float, default=0.0,
+      help="with -losses 1: Dropout after fc6 and fc7 in the training forward, a number in [0, 1); 0 (default) = none, 0.5 = what "
+           "the reference's eval_split measures its losses under")
     return p
 
 
@@ -216,6 +221,7 @@ def main(argv=None):
     if opt.losses:
         from . import ops
         from .evaluate import dict_average
+        model.set_dropout(opt.drop_prob)
         try:
             gt_labels = labels if labels is not None else {n: encode_gt_captions(gt_caps[n], model.idx_to_token, model.seq_length) for n in names}
         except ValueError as e:

@@ -578,8 +578,8 @@ class DenseCapModel:
     def forward_losses(self, img, gt_boxes, gt_labels, **opts):
         """The validation losses of one image: what DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474) and
         eval_utils.eval_split averages -- mid_objectness_loss, mid_box_reg_loss, end_objectness_loss, end_box_reg_loss,
-        captioning_loss, total_loss -- from the forward half alone, every Dropout the identity (docs/SEMANTICS.md, "Validation
-        losses").  gt_boxes (G,4) xcycwh in the frame of the image passed, gt_labels (G,L) word ids padded with zeros.  opts: the
+        captioning_loss, total_loss -- from the forward half alone, Dropout as set_dropout says (none by default; docs/SEMANTICS.md,
+        "Validation losses", "Dropout").  gt_boxes (G,4) xcycwh in the frame of the image passed, gt_labels (G,L) word ids padded with zeros.  opts: the
         sampler's settings and the five weights (ops.LOSS_DEFAULTS), forced_pos / forced_neg, dump.  The test arguments
         (setTestArgs) play no part."""
         from . import ops
@@ -609,7 +609,21 @@ class DenseCapModel:
         from . import ops
         return ops.forward_backward(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, cnn=cnn, **opts)
 
-    # ---- training (docs/SEMANTICS.md, "Training step") ----------------------------------------------------------------------
+    # ---- training (docs/SEMANTICS.md, "Dropout", "Training step") -----------------------------------------------------------
+    def set_dropout(self, p):
+        """dc_set_dropout: p of the two Dropout layers of the training forward (after fc6's ReLU and after fc7's; models.lua's
+        drop_prob, 0.5 in train_opts.lua).  0, the default: none.  A float in [0, 1).  Read by forward_losses, loss_gradients,
+        forward_backward, train_step and ops.recog_grad, whose masks follow their `seed`; inference never drops."""
+        check(self.ctx.h, self.lib.dc_set_dropout(self.ctx.h, float(p)), "dc_set_dropout")
+        return self
+
+    @property
+    def dropout(self):
+        """dc_get_dropout: the p in force."""
+        p = C.c_float(0.0)
+        check(self.ctx.h, self.lib.dc_get_dropout(self.ctx.h, C.byref(p)), "dc_get_dropout")
+        return float(p.value)
+
     def train_begin(self, **opts):
         """dc_train_begin: Adam's moments (zero) and the gradient arena for the 21 tensors outside the CNN; the step count
         starts at 0.  opts: learning_rate 1e-5, beta1 0.9, beta2 0.999, epsilon 1e-8, weight_decay 1e-6 (train_opts.lua)."""
@@ -625,8 +639,8 @@ class DenseCapModel:
     def train_step(self, img, gt_boxes, gt_labels, box_reg_decay=5e-5, **opts):
         """One iteration of train.lua's loop body (train.lua:163-185) on one image: forward_backward (same arguments; the dict
         returned holds its six losses and the counts, for the weights as they were), grad_params:add(weight_decay, params), adam
-        (optim_updates.lua:56-84) on the device, and the refresh of everything derived from a trained weight.  Dropout is the
-        identity; the CNN is not trained."""
+        (optim_updates.lua:56-84) on the device, and the refresh of everything derived from a trained weight.  Dropout is
+        set_dropout's (none by default); the CNN is trained only after train_set_cnn."""
         from . import ops
         return ops.train_step(self.ctx, self._check_input(img), gt_boxes, gt_labels, box_reg_decay=box_reg_decay, **opts)
 

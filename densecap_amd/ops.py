@@ -814,6 +814,31 @@ def relu_grad(ctx, y, dy):
     return dd.numpy()
 
 
+# ---- Dropout (docs/SEMANTICS.md, "Dropout") ------------------------------------------------------------------------------------------
+def dropout(ctx, x, layer, p, seed):
+    """nn.Dropout's forward on a (rows, cols) matrix (dc_op_dropout; the library works in place on its copy of x): element
+    (row, col) is kept, as x * (1 / (1 - p)), iff its Philox word of (seed, layer, row, col) is below floor((1 - p) 2^32), and
+    is +0.0 otherwise."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise ValueError("dropout: x has shape %s, a (rows, cols) matrix is needed" % (x.shape,))
+    xd = ctx.to_device(x)
+    check(ctx.h, ctx.lib.dc_op_dropout(ctx.h, xd.ptr, x.shape[0], x.shape[1], int(layer), float(p), int(seed) & (2 ** 64 - 1)),
+          "dc_op_dropout")
+    return xd.numpy()
+
+
+def relu_dropout_grad(ctx, y, dy, p):
+    """The backward of ReLU followed by an in-place Dropout, from the dropped activation y: dy * (1 / (1 - p)) where y > 0, +0.0
+    elsewhere (dc_op_relu_dropout_grad; the library works in place on its copy of dy): arrays of one shape."""
+    y = _f32(y); dy = _f32(dy)
+    if y.shape != dy.shape:
+        raise ValueError("relu_dropout_grad: shapes %s and %s" % (y.shape, dy.shape))
+    yd = ctx.to_device(y); dd = ctx.to_device(dy)
+    check(ctx.h, ctx.lib.dc_op_relu_dropout_grad(ctx.h, yd.ptr, dd.ptr, int(y.size), float(p)), "dc_op_relu_dropout_grad")
+    return dd.numpy()
+
+
 def cnn_shapes(h4, w4):
     """[(index of the convolution, h, w, Cin, Cout)] of conv3_1 .. conv5_3 on an (h4, w4) pool2 map, and conv5_3's map size."""
     from .weights import VGG16_CONVS

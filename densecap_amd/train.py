@@ -9,8 +9,10 @@ are train.lua's (train_opts.lua) with its defaults, as far as this path reads th
 Prints `iter %d:` lines with the six losses every -losses_log_every iterations; every -save_checkpoint_every iterations and at the
 end writes -checkpoint_path (a .t7 that run_model and evaluate_model load) and, beside it, a .json with the loss history.
 
-Not here: Dropout (the identity, where the reference trains with -drop_prob 0.5), the validation mAP inside the loop (run
-evaluate_model on the saved checkpoint), saving Adam's moments and step count.  There is no CPU mode: without a
+-drop_prob P is the Dropout of recog_base (after fc6 and after fc7; docs/SEMANTICS.md, "Dropout"), its masks drawn on the device
+from the iteration's seed.  The default is 0.0, no Dropout: -drop_prob 0.5 is the reference's training (train_opts.lua:60).
+
+Not here: the validation mAP inside the loop (run evaluate_model on the saved checkpoint), saving Adam's moments and step count.  There is no CPU mode: without a
 HIP device the tool stops with the library's error.
 """
 from __future__ import annotations
@@ -49,6 +51,8 @@ def build_parser():
     a("-end_box_reg_weight", type=float, default=0.1)
     a("-end_objectness_weight", type=float, default=0.1)
     a("-captioning_weight", type=float, default=1.0)
+    a("-drop_prob", type=float, default=0.0,
+      help="Dropout after fc6 and fc7, a number in [0, 1); 0 (default) = none, 0.5 = the reference's training (train_opts.lua:60)")
     # ---- the loop: train_opts.lua:61-92 ----
     a("-max_iters", type=int, default=-1, help="iterations to run; -1 = until interrupted")
     a("-finetune_cnn_after", type=int, default=-1,
@@ -89,6 +93,7 @@ def main(argv=None):
     opt.checkpoint = opt.checkpoint_start_from
     weights = load_weights(opt)
     model = DenseCapModel(weights, device=opt.gpu)                      # no HIP device: DenseCapError, no CPU fallback
+    model.set_dropout(opt.drop_prob)
     data = read_dataset(opt.data_h5, opt.data_json, "train", opt.debug_max_train_images)
     data = [d for d in data if len(d[1]) > 0]
     if not data:

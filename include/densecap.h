@@ -204,8 +204,8 @@ int dc_beam_captions(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on
                      int32_t* captions, float* logprob);
 /* ---- validation losses (docs/SEMANTICS.md, "Validation losses") ----
  * The six numbers DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474, LocalizationLayer.lua:383-527) and
- * eval_utils.eval_split averages (eval/eval_utils.lua:54-59,78-81): the forward half only, every Dropout the identity.
- * The sampler's rules: see dc_op_box_sampler. */
+ * eval_utils.eval_split averages (eval/eval_utils.lua:54-59,78-81): the forward half only, the two Dropout layers of
+ * recog_base by dc_set_dropout (0, the default: the identity).  The sampler's rules: see dc_op_box_sampler. */
 /* Settings of the training forward (train_opts.lua:18-40).  The sampler reads batch_size (even, 2..1024), high_thresh and
  * low_thresh (numbers in [0, 1], low <= high), remove_outbounds (0 / 1) and seed; the five weights belong to the loss terms.
  * Defaults of the reference: 256, 0.7, 0.3, 1, mid_box_reg 0.05, mid_objectness 0.1, end_box_reg 0.1, end_objectness 0.1,
@@ -246,8 +246,8 @@ typedef struct dc_loss_dump { int32_t* pos_input_idx; int32_t* pos_target_idx; i
  * enqueued; forced lists that give more than batch_size rows in all are DC_E_INVALID.
  * Stage-wise test hooks, read with dc_debug_fetch after a call that completed its forward (dc_loss_gradients and
  * dc_forward_backward run the same one and leave the same): "loss_rpn_boxes", "loss_rpn_anchors", "loss_rpn_trans" (A,4),
- * "loss_rpn_scores" (A,2) float; "loss_obj" (n), "loss_final_trans" (n,4), "loss_roi_boxes" (n,4), "loss_codes" (n,fc_dim)
- * float of the n sampled rows; "loss_rowlik" (num_pos) double, every positive row's caption log-likelihood; "loss_stage_ms" 5 float: trunk + RPN, match + assign + draw,
+ * "loss_rpn_scores" (A,2) float; "loss_obj" (n), "loss_final_trans" (n,4), "loss_roi_boxes" (n,4), "loss_codes" (n,fc_dim),
+ * "loss_fc6_out" (n,fc_dim) float of the n sampled rows (the last two as fc7 and the heads read them: after Dropout); "loss_rowlik" (num_pos) double, every positive row's caption log-likelihood; "loss_stage_ms" 5 float: trunk + RPN, match + assign + draw,
  * RoI pool + fc, paired scoring, loss terms. */
 int dc_forward_losses(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                       const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts_or_null,
@@ -283,6 +283,14 @@ int dc_set_group(dc_ctx* ctx, int images);
  * first and decode only the K surviving rows: LSTM rows are independent, so boxes, scores and tokens
  * are bit-identical, with ~K/num_proposals of the decode work. */
 int dc_set_caption_order(dc_ctx* ctx, int after_final_nms);
+/* Dropout of the training forward (docs/SEMANTICS.md, "Dropout"): p of the two nn.Dropout layers of recog_base, after fc6's
+ * ReLU (layer 1) and after fc7's (layer 2); models.lua's drop_prob, 0.5 in train_opts.lua.  0 (the default) = none: every call
+ * issues the launches and gives the bits it gives without the setting.  A float in [0, 1); NaN, p < 0 and p >= 1 are
+ * DC_E_INVALID, as nn.Dropout refuses them.  Read by dc_forward_losses, dc_loss_gradients, dc_forward_backward,
+ * dc_forward_backward_cnn, dc_train_step and dc_op_recog_grad, whose masks follow dc_loss_opts.seed; by nothing else:
+ * dc_forward_test, scoring, sampling, beam search, dc_forward_boxes and feature extraction never drop. */
+int dc_set_dropout(dc_ctx* ctx, float p);
+int dc_get_dropout(dc_ctx* ctx, float* p);
 /* Arithmetic of the dense contractions (convolutions, nn.Linear, LSTM / vocabulary products).
  *   DC_MATH_FP32 (0, the default): fp32 MFMA, v_mfma_f32_32x32x2_f32 -- an exact fp32 multiply-add chain, the arithmetic the
  *     reference computes in (DenseCapModel.lua:73-76,133) and the only mode whose results are compared bit for bit.
@@ -610,6 +618,15 @@ int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float*
 int dc_op_maxpool2x2_grad(dc_ctx* ctx, const float* y, const float* dpool, int n, int H, int W, int C, float* dy);
 /* dc_op_relu_grad: dy[i] = y[i] > 0 ? dy[i] : +0.0 in place, n_floats of them, any 4-byte alignment.  n_floats < 1: DC_E_INVALID. */
 int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats);
+/* dc_op_dropout: nn.Dropout's forward in place on the DEVICE matrix x (rows, cols), any 4-byte alignment.  Element (row, col) is
+ * kept iff (uint64) philox4x32_10(col >> 2, row, layer, 1, seed_lo, seed_hi).w[col & 3] < floor((1 - (double)p) * 2^32); a
+ * kept element becomes x * s, s = 1.0f / (1.0f - p) in fp32, one fp32 multiply; a dropped one becomes +0.0 whatever x was (the
+ * reference multiplies by 0: a dropped inf or NaN stays NaN there).  p = 0: the identity, nothing is launched.  rows < 1,
+ * cols < 1, layer outside 0..255, p outside [0, 1) or NaN: DC_E_INVALID, x untouched. */
+int dc_op_dropout(dc_ctx* ctx, float* x, int rows, int cols, int layer, float p, uint64_t seed);
+/* dc_op_relu_dropout_grad: the backward of nn.ReLU(true) followed by an in-place nn.Dropout, on the dropped activation y:
+ * dy[i] = y[i] > 0 ? dy[i] * s : +0.0 in place (NaN y: 0), n_floats of them, any 4-byte alignment.  p = 0: dc_op_relu_grad. */
+int dc_op_relu_dropout_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats, float p);
 /* The backward through conv_net2 (DenseCapModel.lua:338-376 with model.finetune_cnn): VGG layers 11..30, that is the nine
  * convolutions conv3_1 .. conv5_3 (index 4..12 of the thirteen; entry i here is convolution 4 + i), their in-place ReLUs, pool3
  * and pool4.  dc_cnn_grads: DEVICE buffers, all overwritten -- conv_w[i] (Cout, Cin, 3, 3) in the checkpoint's OIHW order,
@@ -628,8 +645,8 @@ typedef struct dc_cnn_dump { float* act[9]; float* prepool[2]; float* feat; floa
  * dc_op_conv3x3 with relu = 1 and dc_op_maxpool2x2_ceil, layer by layer.  fp32 whatever dc_set_math_mode says, eager on lane 0,
  * no float atomics: two identical calls give identical bits; settings and weights are left as they were.  Device pointers;
  * synchronous.  Without weights: DC_E_STATE.  DC_E_INVALID before any launch: a null input or gradient buffer, a non-positive
- * size; DC_E_UNSUPPORTED: h4 * w4 > 65536, in dc_op_conv3x3_grad's words.  Not here: Dropout (the identity), the optimiser
- * (dc_train_step trains the 21 tensors outside the CNN only). */
+ * size; DC_E_UNSUPPORTED: h4 * w4 > 65536, in dc_op_conv3x3_grad's words.  Not here: Dropout (conv_net2 has none; the recognition net's is
+ * dc_set_dropout), the optimiser (dc_train_step trains the 21 tensors outside the CNN only). */
 int dc_op_cnn_grad(dc_ctx* ctx, const float* x4_hwc, int h4, int w4, const float* dfeat_hwc, const dc_cnn_grads* out,
                    const dc_cnn_dump* dump_or_null);
 /* RPN gradients (docs/SEMANTICS.md, "RPN gradients"): DEVICE buffers for the gradients of the RPN's six tensors in checkpoint
@@ -692,7 +709,7 @@ int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts);
  * from a trained weight is remade on the device (the list: DESIGN.md section 19), so that every later call -- forward, scoring,
  * sampling, either math mode, a captured graph: weight pointers do not move -- computes what a fresh ctx loaded with
  * dc_get_weights' arrays computes.  A refused step changes no weight and no t.  Before dc_train_begin: DC_E_STATE.  Dropout is
- * the identity, as in dc_forward_backward; the CNN is trained only after dc_train_set_cnn.  Eager on lane 0, synchronous. */
+ * dc_set_dropout's, as in dc_forward_backward; the CNN is trained only after dc_train_set_cnn.  Eager on lane 0, synchronous. */
 int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_device, const float* gt_boxes,
                   const int32_t* gt_labels, int G, int L, const dc_loss_opts* opts, const dc_sampler_forced* forced,
                   dc_losses* out, const dc_loss_dump* dump, float box_reg_decay);

@@ -264,7 +264,8 @@ function Model:forward_test(input)
 end
 
 -- The validation losses of one image: what DenseCapModel:forward_backward returns (DenseCapModel.lua:401-474) and
--- eval_utils.eval_split averages, from the forward half alone, every Dropout the identity (docs/SEMANTICS.md, "Validation losses").
+-- eval_utils.eval_split averages, from the forward half alone (docs/SEMANTICS.md, "Validation losses").  model.drop_prob (a number in
+-- [0, 1); nil or 0: none) is the Dropout after fc6 and fc7 in this and the other training calls ("Dropout"), masks by loss_seed.
 -- data.image (1, 3, H, W), data.gt_boxes (1, G, 4) or (G, 4) xcycwh in the frame of the image, data.gt_labels (1, G, L) or (G, L) word
 -- ids padded with zeros.  opts (optional): sampler_batch_size, sampler_high_thresh, sampler_low_thresh,
 -- train_remove_outbounds_boxes, the five *_weight keys of train_opts.lua and loss_seed; absent keys take train_opts' defaults.
@@ -288,6 +289,7 @@ function Model:forward_losses(data, opts)
   o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
   o.captioning_weight = get('captioning_weight', 1.0)
   o.seed = get('loss_seed', 0)
+  hip.check(self.ctx, C.dc_set_dropout(self.ctx, self.drop_prob or 0), 'dc_set_dropout')   -- models.lua's drop_prob; nil: none
   local out = ffi.new('dc_losses')
   hip.check(self.ctx, C.dc_forward_losses(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),
                                           gb:size(1), gl:size(2), o, nil, out, nil), 'dc_forward_losses')
@@ -323,6 +325,7 @@ function Model:loss_gradients(data, opts)
   o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
   o.captioning_weight = get('captioning_weight', 1.0)
   o.seed = get('loss_seed', 0)
+  hip.check(self.ctx, C.dc_set_dropout(self.ctx, self.drop_prob or 0), 'dc_set_dropout')   -- models.lua's drop_prob; nil: none
   local hw = ffi.new('int[2]')
   hip.check(self.ctx, C.dc_feature_size(img:size(3), img:size(4), hw, hw + 1), 'dc_feature_size')
   local h, w, cap = hw[0], hw[1], o.batch_size
@@ -399,6 +402,7 @@ function Model:forward_backward(data, opts)
   o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
   o.captioning_weight = get('captioning_weight', 1.0)
   o.seed = get('loss_seed', 0)
+  hip.check(self.ctx, C.dc_set_dropout(self.ctx, self.drop_prob or 0), 'dc_set_dropout')   -- models.lua's drop_prob; nil: none
   local decay = get('box_reg_decay', 5e-5)
   local hw = ffi.new('int[2]')
   hip.check(self.ctx, C.dc_feature_size(img:size(3), img:size(4), hw, hw + 1), 'dc_feature_size')
@@ -494,7 +498,7 @@ end
 -- One iteration (dc_train_step): forward_backward on `data` (data and opts as forward_losses, plus opts.box_reg_decay), then
 -- grad_params:add(weight_decay, params) and adam(params, grad_params, ...) on the 21 tensors outside the CNN, in place on the
 -- device, and the refresh of everything the library derives from them.  Returns forward_backward's loss keys, num_pos and
--- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is the identity.  The CNN:
+-- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is model.drop_prob's.  The CNN:
 -- opts.cnn_mode (dc_train_set_cnn: 0, 1, 2), by default 2 where model.finetune_cnn is set (train.lua:83-85) and 0 where not;
 -- train.lua's step at iter == finetune_cnn_after, decay and Adam on a zero gradient, is cnn_mode = 1.
 function Model:train_step(data, opts)
@@ -516,6 +520,7 @@ function Model:train_step(data, opts)
   o.end_box_reg_weight, o.end_objectness_weight = get('end_box_reg_weight', 0.1), get('end_objectness_weight', 0.1)
   o.captioning_weight = get('captioning_weight', 1.0)
   o.seed = get('loss_seed', 0)
+  hip.check(self.ctx, C.dc_set_dropout(self.ctx, self.drop_prob or 0), 'dc_set_dropout')   -- models.lua's drop_prob; nil: none
   hip.check(self.ctx, C.dc_train_set_cnn(self.ctx, get('cnn_mode', self.finetune_cnn and 2 or 0)), 'dc_train_set_cnn')
   local out = ffi.new('dc_losses')
   hip.check(self.ctx, C.dc_train_step(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),

@@ -99,6 +99,10 @@ int dc_op_conv3x3_grad(dc_ctx* ctx, const float* x, const float* w, const float*
                        float* db, float* dx);
 int dc_op_maxpool2x2_grad(dc_ctx* ctx, const float* y, const float* dpool, int n, int H, int W, int C, float* dy);
 int dc_op_relu_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats);
+int dc_set_dropout(dc_ctx* ctx, float p);
+int dc_get_dropout(dc_ctx* ctx, float* p);
+int dc_op_dropout(dc_ctx* ctx, float* x, int rows, int cols, int layer, float p, uint64_t seed);
+int dc_op_relu_dropout_grad(dc_ctx* ctx, const float* y, float* dy, long long n_floats, float p);
 typedef struct dc_cnn_grads { float* conv_w[9]; float* conv_b[9]; float* x; } dc_cnn_grads;
 typedef struct dc_cnn_dump { float* act[9]; float* prepool[2]; float* feat; float* dy[9]; } dc_cnn_dump;
 int dc_op_cnn_grad(dc_ctx* ctx, const float* x4_hwc, int h4, int w4, const float* dfeat_hwc, const dc_cnn_grads* out,

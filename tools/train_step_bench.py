@@ -14,8 +14,9 @@ minimum.
 
 --tree DIR: time forward_backward and train_step with the package of another checkout (the parent commit's, built), for the A/B
 of "must not slow": run it alternating with this tree's in one job.  --cnn_mode M: dc_train_set_cnn(M) before the timed steps
-(2: the step with the CNN's backward, decay and Adam; its backward stage from dc_debug_fetch "cnn_grad_ms").
-usage: python tools/train_step_bench.py [--reps 30] [--warmup 5] [--tree DIR] [--out profiles/train_step_bench.json]"""
+(2: the step with the CNN's backward, decay and Adam; its backward stage from dc_debug_fetch "cnn_grad_ms").  --drop_prob P:
+dc_set_dropout(P) before the timed calls (docs/SEMANTICS.md, "Dropout").
+usage: python tools/train_step_bench.py [--reps 30] [--warmup 5] [--tree DIR] [--drop_prob P] [--out profiles/train_step_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--tree", default="")
     ap.add_argument("--cnn_mode", type=int, default=0, help="dc_train_set_cnn before the timed steps (0: the CNN is left alone)")
+    ap.add_argument("--drop_prob", type=float, default=0.0,
+                    help="dc_set_dropout before the timed calls (0: never called, so that --tree may name a library without it)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
@@ -74,6 +77,8 @@ def main():
     ok = np.nonzero((boxes[:, 2] > 30) & (boxes[:, 3] > 30) & (boxes[:, 0] > 60) & (boxes[:, 0] < W - 60) & (boxes[:, 1] > 60) & (boxes[:, 1] < H - 60))[0]
     gt = (boxes[ok[np.linspace(0, len(ok) - 1, G).astype(int)]] * (1 + 0.02 * rng.uniform(-1, 1, (G, 4)))).astype(np.float32)
     idev = ctx.to_device(img)
+    if a.drop_prob:
+        m.set_dropout(a.drop_prob)
     rb = ops._recog_bufs(ctx, D, h, w, batch)
     lshapes = {"lm_enc_w": (E, D), "lm_enc_b": (E,), "lm_emb": (V + 2, E), "lstm_w": (E + Hd, 4 * Hd), "lstm_b": (4 * Hd,),
                "lm_out_w": (V + 1, Hd), "lm_out_b": (V + 1,), "codes": (batch, D)}
@@ -90,7 +95,7 @@ def main():
                                                   C.byref(pg)), "dc_forward_backward")
 
     doc = dict(image=[H, W], gt_boxes=G, batch_size=batch, dims=dict(E=E, Hd=Hd, D=D, V=V, L=L, k=k, R=R), reps=a.reps, warmup=a.warmup,
-               tree=os.path.abspath(a.tree) if a.tree else "this tree")
+               tree=os.path.abspath(a.tree) if a.tree else "this tree", drop_prob=a.drop_prob)
     doc["forward_backward"] = stats(timed(fb, a.warmup, a.reps))
     doc["num_pos"], doc["num_neg"] = int(out_b.num_pos), int(out_b.num_neg)
     for b in list(rb.values()) + list(lb.values()) + list(pb.values()):      # the step keeps its gradients in an arena of its own
@@ -115,7 +120,7 @@ def main():
     if cnn_ms:
         doc["cnn_backward_ms"] = float(np.median(cnn_ms[a.warmup:]))
     ops.train_end(ctx)
-    if a.tree or a.cnn_mode:
+    if a.tree or a.cnn_mode or a.drop_prob:
         print(json.dumps(doc))
         if a.out:
             with open(a.out, "w") as f:
