@@ -127,6 +127,24 @@ class DcBeamStdState(C.Structure):
     _fields_ = DcBeamState._fields_ + [("len", C.c_void_p)]
 
 
+class DcStepGemm(C.Structure):
+    """dc_step_gemm (include/densecap_debug_step.h): one GEMM of a decode step on the caller's device operands."""
+    _fields_ = [("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("plan_M", C.c_int32), ("epilogue", C.c_int32), ("relu", C.c_int32), ("C", C.c_void_p), ("ldc", C.c_int32),
+                ("part_ld", C.c_int32), ("part", C.c_void_p), ("part_idx", C.c_void_p), ("rowidx", C.c_void_p), ("t", C.c_int32),
+                ("inv_temp", C.c_float), ("seed", C.c_uint64), ("amax_cols", C.c_int32), ("amax_n", C.c_int32),
+                ("m_dev_or_null", C.c_void_p)]
+
+
+class DcStepTail(C.Structure):
+    """dc_step_tail (include/densecap_debug_step.h): one launch of one row tail on the caller's partials and state."""
+    _fields_ = [("kind", C.c_int32), ("nslots", C.c_int32), ("ld", C.c_int32), ("xg_rows", C.c_int32), ("part", C.c_void_p),
+                ("part_idx", C.c_void_p), ("xg", C.c_void_p), ("gates_pre", C.c_void_p), ("c", C.c_void_p), ("h", C.c_void_p),
+                ("n", C.c_int32), ("Hd", C.c_int32), ("n_dev_or_null", C.c_void_p), ("zero_c", C.c_int32), ("fixed_tok", C.c_int32),
+                ("tgt", C.c_void_p), ("end_tok", C.c_int32), ("T", C.c_int32), ("t", C.c_int32), ("acc", C.c_void_p),
+                ("fin", C.c_void_p), ("seq", C.c_void_p)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -284,6 +302,11 @@ _SAMPLE_HOOK_SIGS = {
                                              C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
 }
+# the hooks of include/densecap_debug_step.h (the classic decode step's GEMM epilogues and row tails; bound like the others)
+_STEP_HOOK_SIGS = {
+    "dc_debug_step_gemm": (C.c_int, [C.c_void_p, C.POINTER(DcStepGemm)]),
+    "dc_debug_step_tail": (C.c_int, [C.c_void_p, C.POINTER(DcStepTail)]),
+}
 # the hooks of include/densecap_debug_beam.h (the standard beam search; bound like the others)
 _BEAM_STD_HOOK_SIGS = {
     "dc_debug_beam_std_merge": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 6),
@@ -348,7 +371,8 @@ def lib():
                 "libdensecap_hip.so not built at %s -- run `make -C densecap_amd/csrc` "
                 "(there is no CPU fallback)" % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_BEAM_STD_HOOK_SIGS.items()) +
+        for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_STEP_HOOK_SIGS.items()) +
+                                  list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
                                   list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported

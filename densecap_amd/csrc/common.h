@@ -9,6 +9,7 @@
 #include "../../include/densecap.h"
 #include "../../include/densecap_debug.h"
 #include "../../include/densecap_debug_sample.h"
+#include "../../include/densecap_debug_step.h"
 #include "../../include/densecap_debug_beam.h"
 #include "../../include/densecap_debug_grad.h"
 #include "../../include/densecap_debug_recog.h"

@@ -3893,6 +3893,132 @@ int dc_debug_sample_trunc_rows(dc_ctx* ctx, const float* logits, int rows, int V
   OP_EPILOGUE();
 }
 
+// ---- the classic decode step's test hooks (densecap_debug_step.h) -----------------------------------------------------------------
+// One GEMM of a step on the caller's operands: the descriptor of decode_step_desc and of its three callers (lm_sample_parts,
+// lm_score, lm_sample_n), field for field, through run_gemm without scratch, as a step runs it.
+int dc_debug_step_gemm(dc_ctx* ctx, const dc_step_gemm* g) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_step_gemm";
+  if (!g || !g->A || !g->W) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (g->M < 1 || g->N < 1 || g->K < 1 || g->K % 32 || g->plan_M < 0 || g->plan_M > g->M)
+    return ctx->fail(DC_E_INVALID, "%s: M, N, K >= 1, K %% 32 == 0 and plan_M in [0, M] wanted", who);
+  const int epi = g->epilogue;
+  if (epi < DC_STEP_STORE || epi > DC_STEP_SAMPLE) return ctx->fail(DC_E_INVALID, "%s: unknown epilogue %d", who, epi);
+  if (g->amax_cols < 0 || g->amax_n < 0) return ctx->fail(DC_E_INVALID, "%s: amax_cols, amax_n >= 0 wanted", who);
+  const bool prefix = g->amax_cols > 0;
+  if (epi == DC_STEP_STORE) {
+    if (prefix || !g->C || g->ldc < g->N) return ctx->fail(DC_E_INVALID, "%s: a store wants C, ldc >= N and no prefix", who);
+  } else {
+    if (!g->part || (epi == DC_STEP_ARGMAX && !g->part_idx) || (epi != DC_STEP_ARGMAX && !g->rowidx))
+      return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+    if (epi == DC_STEP_SAMPLE && g->t < 1) return ctx->fail(DC_E_INVALID, "%s: t >= 1 wanted", who);
+    // the stored half's row length is nothing a launcher can judge; a prefix the launchers refuse never gets as far as a store
+    if (prefix && g->C != nullptr && g->amax_cols <= g->N && g->ldc < g->N - g->amax_cols)
+      return ctx->fail(DC_E_INVALID, "%s: ldc = %d is below the %d stored columns", who, g->ldc, g->N - g->amax_cols);
+    // (the log-sum-exp and sampling launches check their part_ld; the arg-max launch trusts its caller)
+    const long cols = prefix ? g->amax_cols : g->N;
+    if (epi == DC_STEP_ARGMAX && g->part_ld < 2 * ((cols + 63) / 64))
+      return ctx->fail(DC_E_INVALID, "%s: part_ld = %d is below the arg-max's 2 x %ld slots", who, g->part_ld, (cols + 63) / 64);
+  }
+  if (g->m_dev_or_null) {
+    int32_t live = 0;
+    HIPCHK(hipMemcpy(&live, g->m_dev_or_null, 4, hipMemcpyDeviceToHost));
+    if (live < 0) return ctx->fail(DC_E_INVALID, "%s: *m_dev = %d", who, (int)live);
+  }
+  GemmDesc v;
+  v.A = g->A; v.W = g->W; v.bias = g->bias; v.M = g->M; v.K = g->K; v.plan_M = g->plan_M;
+  if (!prefix) {
+    v.N = g->N; v.ldc = g->N;
+  } else {
+    v.N = g->N; v.amax_cols = g->amax_cols; v.amax_n = g->amax_n; v.C = g->C; v.ldc = g->ldc;
+  }
+  switch (epi) {
+    case DC_STEP_STORE:
+      v.C = g->C; v.ldc = g->ldc; v.relu = g->relu ? 1 : 0;
+      break;
+    case DC_STEP_ARGMAX:
+      v.amax_val = g->part; v.amax_idx = g->part_idx; v.amax_ld = g->part_ld;
+      break;
+    case DC_STEP_LSE:
+      v.amax_val = g->part; v.amax_ld = g->part_ld; v.rowidx = g->rowidx;
+      break;
+    default:
+      v.amax_val = g->part; v.amax_ld = g->part_ld; v.rowidx = g->rowidx;
+      v.samp_t = g->t; v.samp_seed_lo = (uint32_t)(g->seed & 0xffffffffu); v.samp_seed_hi = (uint32_t)(g->seed >> 32);
+      v.samp_inv_temp = g->inv_temp;
+  }
+  v.m_dev = g->m_dev_or_null;
+  DCCHK(run_gemm(ctx, v, s));
+  OP_EPILOGUE();
+}
+
+// One launch of one row tail on the caller's partials.  Every value the tail would turn into an address of xg is checked on the
+// host first (the greedy tail does not bound its column: densecap_debug_step.h).
+int dc_debug_step_tail(dc_ctx* ctx, const dc_step_tail* a) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_step_tail";
+  constexpr int32_t kSentinel = 0x7fffffff;
+  if (!a) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  const int kind = a->kind;
+  if (kind < DC_STEP_TAIL_GREEDY || kind > DC_STEP_TAIL_SAMPLE) return ctx->fail(DC_E_INVALID, "%s: unknown kind %d", who, kind);
+  if (a->n < 1 || a->Hd < 1 || a->nslots < 0 || a->xg_rows < 0 || a->T < 1 || a->t < 0 || a->t >= a->T)
+    return ctx->fail(DC_E_INVALID, "%s: n, Hd, T >= 1, nslots, xg_rows >= 0 and t in [0, T) wanted", who);
+  const bool step = a->gates_pre != nullptr;
+  if (step && (!a->c || !a->h)) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  const size_t n = a->n, ns = a->nslots;
+  const bool has_part = kind != DC_STEP_TAIL_GREEDY || a->part != nullptr || a->part_idx != nullptr;
+  const int per = kind == DC_STEP_TAIL_GREEDY ? 1 : kind == DC_STEP_TAIL_SCORE ? 2 : 5;
+  if (has_part && (!a->part || a->ld < per * a->nslots + (kind == DC_STEP_TAIL_SCORE ? 1 : 0)))
+    return ctx->fail(DC_E_INVALID, "%s: partials wanted, ld >= %d floats a slot%s", who, per, kind == DC_STEP_TAIL_SCORE ? " + 1" : "");
+  auto column_ok = [&](int32_t col) { return col == kSentinel || (col >= 0 && col < a->xg_rows); };
+  std::vector<int32_t> host;
+  if (kind == DC_STEP_TAIL_GREEDY) {
+    if (has_part && (!a->part_idx || !a->seq)) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+    if (a->fixed_tok < 0 || a->fixed_tok > a->xg_rows)
+      return ctx->fail(DC_E_INVALID, "%s: fixed_tok = %d is not 0 or a word id in [1, %d]", who, a->fixed_tok, a->xg_rows);
+    if (step && !a->xg && (has_part || a->fixed_tok > 0)) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+    if (has_part && ns > 0) {
+      host.resize(n * a->ld);
+      HIPCHK(hipMemcpy(host.data(), a->part_idx, host.size() * 4, hipMemcpyDeviceToHost));
+      for (size_t m = 0; m < n; ++m)
+        for (size_t j = 0; j < ns; ++j)
+          if (!column_ok(host[m * a->ld + j]))
+            return ctx->fail(DC_E_INVALID, "%s: part_idx[%zu][%zu] = %d is not a column in [0, %d) or the sentinel", who, m, j,
+                             (int)host[m * a->ld + j], a->xg_rows);
+    }
+  } else if (kind == DC_STEP_TAIL_SCORE) {
+    if (!a->tgt || !a->acc || (step && !a->xg)) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+    host.resize(n);
+    HIPCHK(hipMemcpy(host.data(), a->tgt, n * 4, hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < n; ++m)
+      if (host[m] != a->end_tok && (host[m] < 1 || host[m] > a->xg_rows))
+        return ctx->fail(DC_E_INVALID, "%s: tgt[%zu] = %d is not a word id in [1, %d] or end_tok", who, m, (int)host[m], a->xg_rows);
+  } else {
+    if (!a->acc || !a->fin || !a->seq || (step && !a->xg)) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+    if (a->end_tok < 1 || a->end_tok > a->xg_rows)
+      return ctx->fail(DC_E_INVALID, "%s: end_tok = %d is not a word id in [1, %d]", who, a->end_tok, a->xg_rows);
+    if (ns > 0) {
+      host.resize(n * a->ld);
+      HIPCHK(hipMemcpy(host.data(), a->part, host.size() * 4, hipMemcpyDeviceToHost));      // the column travels as a float's bits
+      for (size_t m = 0; m < n; ++m)
+        for (size_t j = 0; j < ns; ++j)
+          if (!column_ok(host[m * a->ld + 5 * j + 3]))
+            return ctx->fail(DC_E_INVALID, "%s: the column of part[%zu], slot %zu, = %d is not in [0, %d) or the sentinel", who, m, j,
+                             (int)host[m * a->ld + 5 * j + 3], a->xg_rows);
+    }
+  }
+  if (kind == DC_STEP_TAIL_GREEDY) {
+    KCHK(launch_lstm_step_tail(has_part ? a->part : nullptr, has_part ? a->part_idx : nullptr, a->nslots, a->ld, a->fixed_tok, a->xg,
+                               a->gates_pre, a->c, a->h, a->n, a->n_dev_or_null, a->Hd, a->zero_c ? 1 : 0, a->seq, a->T, a->t, s));
+  } else if (kind == DC_STEP_TAIL_SCORE) {
+    KCHK(launch_lse_step_tail(a->part, a->nslots, a->ld, a->tgt, a->end_tok, a->xg, a->gates_pre, a->c, a->h, a->acc, a->n, a->Hd, s));
+  } else {
+    KCHK(launch_sample_step_tail(a->part, a->nslots, a->ld, a->end_tok, a->xg, a->gates_pre, a->c, a->h, a->acc, a->fin, a->seq, a->T,
+                                 a->t, a->n, a->Hd, s));
+  }
+  OP_EPILOGUE();
+}
+
 // ---- beam search test hooks, both rules (densecap_debug.h, densecap_debug_beam.h) ----------------------------------------------
 int dc_debug_beam_topk(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const uint8_t* finished_or_null, int k,
                        float* top_lp, int32_t* top_idx) {

@@ -175,6 +175,17 @@ __device__ __forceinline__ float pool_window(const GemmDesc& d, int win, float v
 // at load: three bf16 planes in HBM (GemmDesc::sk_slots carries the pointer in this mode), fetched by LDS-DMA as they are
 // LSE (with AMAX): 1 = the fused row log-sum-exp epilogue of teacher-forced scoring instead of the arg-max (see GemmDesc::rowidx);
 // 2 = the fused row sampling epilogue (Gumbel-max draw + the same log-sum-exp partials, see GemmDesc::samp_t).
+// a * b + c as TWO rounded fp32 operations (the perturbed score of the sampling epilogue: docs/SEMANTICS.md, "Sampling captions",
+// 3).  This file is built with FMA contraction on, and under it __fmul_rn / __fadd_rn are a plain * and + that fuse into one
+// v_fmac (one rounding: every score whose product is inexact could differ by a unit from the rule, the truncated sampler's build
+// and the restatement); the pragma takes the contract flag off these two operations wherever they are inlined.  It is honoured
+// under hipcc's default -ffp-contract=fast-honor-pragmas; a plain -ffp-contract=fast on this file's command line would fuse them
+// again (the Makefile says so too; tests/test_gpu_step_gemm.py::test_sampling_entries would show it).
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
 template <int TM, int TN, bool CONV, int NS, bool AMAX, int BF3 = 0, int LSE = 0>
 __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const int n0, const int tile_n, const int Meff,
                                         float* const smem) {
@@ -754,7 +765,7 @@ __device__ __forceinline__ void v2_tile(const GemmDesc& d, const int m0, const i
             v[q4 * 4 + c] = nb + c < an ? acc[i][0][q4 * 4 + c] + bv[c] : -INFINITY;
             mx = v[q4 * 4 + c] > mx ? v[q4 * 4 + c] : mx;
             float pv = v[q4 * 4 + c];
-            if (inv_temp != 0.f && nb + c < an) pv = __fadd_rn(__fmul_rn(pv, inv_temp), gumbel_from_bits(nz.w[c]));
+            if (inv_temp != 0.f && nb + c < an) pv = mul_then_add(pv, inv_temp, gumbel_from_bits(nz.w[c]));
             if (pv > best) { best = pv; bi = nb + c; bl = v[q4 * 4 + c]; }
           }
         }
@@ -1087,8 +1098,13 @@ __global__ __launch_bounds__(256) void mfma_gemm_v2_mixed_kernel(GemmDesc d, int
     if (nbig + 2 * tail <= G) {
       nwalk = nbig;                                     // one workgroup per live tile
     } else {
-      // fewer workgroups than live tiles: the host launched a tile WALK (dc_debug_set "walk": nwalk slots + the split round) --
-      // the live tiles are walked by as many workgroups as there are, a multiple of 8 so that a workgroup stays on its XCD
+      // the rebuilt map does not fit the grid: the live tiles run whole, walked by as many workgroups as there are, a multiple
+      // of 8 so that a workgroup stays on its XCD.  Two launches get here.  A tile WALK (dc_debug_set "walk": the host sized
+      // the grid as nwalk slots + its own split round) with more live tiles than workgroups: each takes several.  And an
+      // ordinary launch whose d.M rows had no split round (the host sized one workgroup per tile) while the live count has
+      // one that is longer than the dead tiles' workgroups can hold -- 2048 x 6144, 1536 tiles on 768 slots, at 13 or 14 live
+      // row tiles: 768 + 2 x 480 / 576 > 1536 -- : nwalk >= the live tiles, one tile per workgroup, nothing is walked
+      // (tests/test_gpu_step_gemm.py::test_device_row_count).
       nbig = total; tail = 0;
       nwalk = G >= 8 ? (G & ~7) : G;
     }

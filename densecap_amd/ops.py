@@ -1536,3 +1536,90 @@ def rescore_tail(ctx, scores, h, hnorm, c=None, gates_pre=None, n_dev=None, guar
                                                o["tok"].ptr, o["cand"].ptr, o["best"].ptr, ptr("h"), ptr("c"), ptr("hb"),
                                                ptr("hnorm")), "dc_debug_rescore_tail")
     return {k: v.numpy() for k, v in o.items()}
+
+
+# ---- the classic decode step's test hooks (include/densecap_debug_step.h) -----------------------------------------------------
+STEP_STORE, STEP_ARGMAX, STEP_LSE, STEP_SAMPLE = 0, 1, 2, 3
+STEP_TAIL_GREEDY, STEP_TAIL_SCORE, STEP_TAIL_SAMPLE = 0, 1, 2
+STEP_NO_COLUMN = 0x7fffffff      # the column of a partial without an entry
+STEP_FLOATS_PER_SLOT = {STEP_ARGMAX: 1, STEP_LSE: 2, STEP_SAMPLE: 5}
+
+
+def step_slots(columns):
+    """32-column slots of an epilogue over `columns` columns (amax_cols with a prefix, N without): two per 64-column tile."""
+    return 2 * ((int(columns) + 63) // 64)
+
+
+def step_part_ld(epilogue, columns):
+    """The least row length of an epilogue's partials, as include/densecap_debug_step.h documents it."""
+    return STEP_FLOATS_PER_SLOT[epilogue] * step_slots(columns) + (1 if epilogue == STEP_LSE else 0)
+
+
+def _on_device(ctx, a, dtype):
+    """a as a DeviceArray: kept if it is one (operands a test uploads once), uploaded otherwise; None stays None."""
+    if a is None or isinstance(a, DeviceArray):
+        return a
+    return ctx.to_device(np.ascontiguousarray(a, dtype=dtype))
+
+
+def _ptr(buf):
+    return buf.ptr if buf is not None else None
+
+
+def step_gemm(ctx, A, W, bias, epilogue, M, N, K, plan_M=0, relu=False, amax_cols=0, amax_n=0, part_ld=None, ldc=None,
+              rowidx=None, t=0, seed=0, inv_temp=0.0, m_dev=None, guard_rows=2, want_C=True, raise_errors=True):
+    """dc_debug_step_gemm.  A (M, K), W (N, K), bias (N) or None: numpy arrays or DeviceArrays.  Returns a dict of the outputs the
+    epilogue has, each with guard_rows rows after the M the call may write and every byte DEBUG_FILL before the call:
+    C (M + g, ldc) float32 (a store, or the raw half of a prefix; want_C=False passes null), part (M + g, part_ld) float32,
+    idx (M + g, part_ld) int32 (arg-max).  rc = the call's return code; raise_errors=False returns it with the (untouched)
+    buffers instead of raising.  m_dev: a device-side row count."""
+    g = int(guard_rows)
+    Ad, Wd, bd = _on_device(ctx, A, np.float32), _on_device(ctx, W, np.float32), _on_device(ctx, bias, np.float32)
+    rd = _on_device(ctx, rowidx, np.int32)
+    nd = _count(ctx, m_dev)
+    out = {}
+    stored = N if epilogue == STEP_STORE else max(N - amax_cols, 0) if amax_cols > 0 else 0
+    if ldc is None:
+        ldc = stored
+    if want_C and (epilogue == STEP_STORE or amax_cols > 0):
+        out["C"] = _filled(ctx, (M + g, 4 * max(ldc, 1)), np.float32)
+    if epilogue != STEP_STORE:
+        if part_ld is None:
+            part_ld = step_part_ld(epilogue, amax_cols if amax_cols > 0 else N)
+        out["part"] = _filled(ctx, (M + g, 4 * max(part_ld, 1)), np.float32)
+        if epilogue == STEP_ARGMAX:
+            out["idx"] = _filled(ctx, (M + g, 4 * max(part_ld, 1)), np.int32)
+    a = _lib.DcStepGemm(A=Ad.ptr, W=Wd.ptr, bias=_ptr(bd), M=M, N=N, K=K, plan_M=plan_M, epilogue=epilogue, relu=int(relu),
+                        C=_ptr(out.get("C")), ldc=ldc, part_ld=part_ld or 0, part=_ptr(out.get("part")), part_idx=_ptr(out.get("idx")),
+                        rowidx=_ptr(rd), t=int(t), inv_temp=float(inv_temp), seed=int(seed), amax_cols=amax_cols, amax_n=amax_n,
+                        m_dev_or_null=_ptr(nd))
+    rc = ctx.lib.dc_debug_step_gemm(ctx.h, C.byref(a))
+    if raise_errors:
+        check(ctx.h, rc, "dc_debug_step_gemm")
+    res = {k: v.numpy() for k, v in out.items()}
+    res["rc"] = rc
+    return res
+
+
+def step_tail(ctx, kind, n, Hd, part=None, idx=None, nslots=0, ld=0, xg=None, gates_pre=None, c=None, h=None, n_dev=None,
+              zero_c=False, fixed_tok=0, tgt=None, end_tok=0, acc=None, fin=None, T=1, t=0, raise_errors=True):
+    """dc_debug_step_tail: one launch of the greedy / scoring / sampling row tail on n rows.  part (n, ld) float32 (the sampling
+    partials' column travels as a float's bits), idx (n, ld) int32 (greedy), xg (xg_rows, 4 Hd), gates_pre (n, 4 Hd) or None,
+    c, h (n, Hd), tgt (n,) int32, acc (n,) float64 and fin (n,) uint8 as they stand before the launch.  Returns dict(rc, c, h,
+    acc, fin, seq) of what the kind has, after the launch; seq (n, T) int32 with every byte DEBUG_FILL before it."""
+    f = lambda a_: _on_device(ctx, a_, np.float32)
+    pd, xd, gd, cd, hd = f(part), f(xg), f(gates_pre), f(c), f(h)
+    idd, td = _on_device(ctx, idx, np.int32), _on_device(ctx, tgt, np.int32)
+    ad, fd = _on_device(ctx, acc, np.float64), _on_device(ctx, fin, np.uint8)
+    nd = _count(ctx, n_dev)
+    seq = _filled(ctx, (n, 4 * T), np.int32) if kind != STEP_TAIL_SCORE else None
+    a = _lib.DcStepTail(kind=kind, nslots=nslots, ld=ld, xg_rows=xd.shape[0] if xd is not None else 0, part=_ptr(pd),
+                        part_idx=_ptr(idd), xg=_ptr(xd), gates_pre=_ptr(gd), c=_ptr(cd), h=_ptr(hd), n=n, Hd=Hd,
+                        n_dev_or_null=_ptr(nd), zero_c=int(zero_c), fixed_tok=int(fixed_tok), tgt=_ptr(td), end_tok=int(end_tok),
+                        T=T, t=t, acc=_ptr(ad), fin=_ptr(fd), seq=_ptr(seq))
+    rc = ctx.lib.dc_debug_step_tail(ctx.h, C.byref(a))
+    if raise_errors:
+        check(ctx.h, rc, "dc_debug_step_tail")
+    res = {k: v.numpy() for k, v in (("c", cd), ("h", hd), ("acc", ad), ("fin", fd), ("seq", seq)) if v is not None}
+    res["rc"] = rc
+    return res

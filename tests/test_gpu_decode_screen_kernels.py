@@ -409,6 +409,15 @@ def test_non_finite_scores(name):
 
 
 # ---- the tail with the LSTM update -----------------------------------------------------------------------------------------------
+def tail_update_tol(t, cmax):
+    """(tol_c, tol_h): how far the device's c' and h' of tail_update (common.h) may be from the float64 cell when every gate
+    pre-activation is off by at most t and |c| <= cmax.  Sigmoid and tanh move by at most a quarter of / exactly what their
+    argument moves by, so c' = f c + i g moves by at most (cmax / 4 + 1 / 4 + 1) t and h' = o tanh(c') by t / 4 more; 2e-6 for the
+    roundings and the device's exp of values <= 1.  (tests/test_gpu_step_tails.py holds the other tails to the same model.)"""
+    tol_c = (cmax / 4 + 1.25) * t + 2e-6
+    return tol_c, tol_c + t / 4 + 2e-6
+
+
 @pytest.mark.parametrize("name", ["default", "e_lt_h", "odd32"])
 def test_tail_with_gates_writes_the_next_operands(name):
     """With gates the tail also takes the LSTM step and writes the next screen's operands: hb = bf16 of the h it wrote, bit for
@@ -435,9 +444,8 @@ def test_tail_with_gates_writes_the_next_operands(name):
     for k, a in o.items():
         _untouched(a[live:], "%s past the device-side count" % k)
     # the LSTM update itself against float64 (the route tests hold it bit for bit against the fused step).  The word's gate row
-    # xg = b + emb.Wx is an fp32 chain of E terms: off by at most (E + 2) 2^-24 of its sum of magnitudes, t at worst.  Sigmoid and
-    # tanh move by at most a quarter of / exactly what their argument moves by, and |c| <= cmax, so c' = f c + i g moves by at
-    # most (cmax / 4 + 1 / 4 + 1) t and h' = o tanh(c') by t / 4 more; 2e-6 for the roundings and the device's exp of values <= 1.
+    # xg = b + emb.Wx is an fp32 chain of E terms: off by at most (E + 2) 2^-24 of its sum of magnitudes, t at worst; from there
+    # tail_update_tol.
     W = s.W
     E = W["lstm_w"].shape[0] - s.Hd
     tok = torch.from_numpy(o["tok"][:live].astype(np.int64))
@@ -447,5 +455,5 @@ def test_tail_with_gates_writes_the_next_operands(name):
     i, f, og, g = pre.split(s.Hd, 1)
     c_ref = torch.sigmoid(f) * torch.from_numpy(c[:live]).double() + torch.sigmoid(i) * torch.tanh(g)
     h_ref = torch.sigmoid(og) * torch.tanh(c_ref)
-    tol_c = (float(np.abs(c).max()) / 4 + 1.25) * t + 2e-6
-    assert np.abs(c1 - c_ref.numpy()).max() <= tol_c and np.abs(h1 - h_ref.numpy()).max() <= tol_c + t / 4 + 2e-6
+    tol_c, tol_h = tail_update_tol(t, float(np.abs(c).max()))
+    assert np.abs(c1 - c_ref.numpy()).max() <= tol_c and np.abs(h1 - h_ref.numpy()).max() <= tol_h
