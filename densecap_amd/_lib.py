@@ -145,6 +145,23 @@ class DcStepTail(C.Structure):
                 ("fin", C.c_void_p), ("seq", C.c_void_p)]
 
 
+class DcGlueRoiPool(C.Structure):
+    """dc_glue_roi_pool (include/densecap_debug_glue.h): one launch of the group form of bilinear RoI pooling."""
+    _fields_ = [("feat_hwc", C.c_void_p), ("feat_stride", C.c_size_t), ("nimg", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("C", C.c_int32), ("boxes", C.c_void_p), ("B", C.c_int32), ("B_dev", C.c_void_p), ("bdev_stride", C.c_int32),
+                ("pick", C.c_void_p), ("src_boxes", C.c_void_p), ("src_stride", C.c_size_t), ("src_rows", C.c_int32),
+                ("img_h", C.c_int32), ("img_w", C.c_int32), ("HH", C.c_int32), ("WW", C.c_int32), ("out", C.c_void_p),
+                ("out_layout", C.c_int32)]
+
+
+class DcGlueFinalPack(C.Structure):
+    """dc_glue_final_pack (include/densecap_debug_glue.h): one launch of the group's result records."""
+    _fields_ = [("final_boxes", C.c_void_p), ("obj", C.c_void_p), ("tokens", C.c_void_p), ("tok_gather", C.c_int32),
+                ("codes", C.c_void_p), ("picks", C.c_void_p), ("count", C.c_void_p), ("count_stride", C.c_int32),
+                ("fault", C.c_void_p), ("nimg", C.c_int32), ("P", C.c_int32), ("T", C.c_int32), ("D", C.c_int32),
+                ("pack", C.c_void_p), ("stride", C.c_size_t), ("box_src", C.c_void_p)]
+
+
 class DenseCapError(RuntimeError):
     pass
 
@@ -357,6 +374,17 @@ _OPTIM_HOOK_SIGS = {
     "dc_debug_screen_operands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_debug_unpack_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
 }
+# the hooks of include/densecap_debug_glue.h (the forward path's glue kernels, one launch each; bound like the others)
+_GLUE_HOOK_SIGS = {
+    "dc_debug_boxes_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int]),
+    "dc_debug_roi_pool_group": (C.c_int, [C.c_void_p, C.POINTER(DcGlueRoiPool)]),
+    "dc_debug_recog_heads": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int]),
+    "dc_debug_iota_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "dc_debug_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_int]),
+    "dc_debug_survivor_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "dc_debug_final_pack": (C.c_int, [C.c_void_p, C.POINTER(DcGlueFinalPack)]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -374,7 +402,8 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SAMPLE_HOOK_SIGS.items()) + list(_STEP_HOOK_SIGS.items()) +
                                   list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
-                                  list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items())):
+                                  list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items()) +
+                                  list(_GLUE_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -4019,6 +4019,142 @@ int dc_debug_step_tail(dc_ctx* ctx, const dc_step_tail* a) {
   OP_EPILOGUE();
 }
 
+// ---- the forward path's glue kernels, one launch each (densecap_debug_glue.h) -------------------------------------------------------
+// These kernels trust picks, indices and counts; the hooks read them back and check every value that would become a row index.
+// live[i] = max(0, min(count[i * stride], cap)) of nimg images, read from the device.  who: the kernel sums min(count, cap) into
+// row offsets without a lower clamp (the NMS that writes the counts never goes below 0), so a negative count is refused.
+static int glue_live_counts(dc_ctx* ctx, const int32_t* count, int stride, int nimg, int cap, std::vector<int32_t>& live,
+                            const char* who = nullptr) {
+  std::vector<int32_t> host((size_t)(nimg - 1) * stride + 1);
+  HIPCHK(hipMemcpy(host.data(), count, host.size() * 4, hipMemcpyDeviceToHost));
+  live.resize(nimg);
+  for (int i = 0; i < nimg; ++i) {
+    const int32_t c = host[(size_t)i * stride];
+    if (who != nullptr && c < 0) return ctx->fail(DC_E_INVALID, "%s: count[%d] = %d is below 0", who, i, (int)c);
+    live[i] = std::max(0, std::min(c, (int32_t)cap));
+  }
+  return DC_OK;
+}
+// idx (nimg blocks of `rows` values): block i's first live[i] values must lie in [0, bound)
+static int glue_check_rows(dc_ctx* ctx, const int32_t* idx, int nimg, int rows, const std::vector<int32_t>& live, int bound,
+                           const char* who, const char* what) {
+  std::vector<int32_t> host((size_t)nimg * rows);
+  HIPCHK(hipMemcpy(host.data(), idx, host.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < nimg; ++i)
+    for (int r = 0; r < live[i]; ++r) {
+      const int32_t v = host[(size_t)i * rows + r];
+      if (v < 0 || v >= bound) return ctx->fail(DC_E_INVALID, "%s: %s[%d][%d] = %d is not a row in [0, %d)", who, what, i, r, (int)v, bound);
+    }
+  return DC_OK;
+}
+
+int dc_debug_boxes_ingest(dc_ctx* ctx, const float* in_boxes, const int32_t* in_n, int nimg, int P, int clip, int img_h, int img_w,
+                          float* roi_boxes, int32_t* box_src, int32_t* count, int count_stride) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_boxes_ingest";
+  if (!in_boxes || !in_n || !roi_boxes || !box_src || !count) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (nimg < 1 || nimg > 65535 || P < 1 || (long long)nimg * P > (1 << 28) || img_h < 1 || img_w < 1 || count_stride < 1)
+    return ctx->fail(DC_E_INVALID, "%s: nimg in [1, 65535], P, img_h, img_w, count_stride >= 1 wanted", who);
+  KCHK(launch_boxes_ingest(in_boxes, in_n, nimg, P, clip ? 1 : 0, img_h, img_w, roi_boxes, box_src, count, count_stride, s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_roi_pool_group(dc_ctx* ctx, const dc_glue_roi_pool* a) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_roi_pool_group";
+  if (!a || !a->feat_hwc || !a->boxes || !a->out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (a->nimg < 1 || a->B < 1 || a->h < 1 || a->w < 1 || a->C < 1 || a->HH < 2 || a->WW < 2 || a->img_h < 2 || a->img_w < 2 ||
+      (a->out_layout != 0 && a->out_layout != 1))
+    return ctx->fail(DC_E_INVALID, "%s: nimg, B, h, w, C >= 1, HH, WW, img_h, img_w >= 2 and out_layout 0 or 1 wanted", who);
+  const long long map = (long long)a->h * a->w * a->C;
+  if (map >= (1ll << 31) || (long long)a->nimg * a->B > (1 << 24) || (long long)a->HH * a->WW * a->C >= (1ll << 31))
+    return ctx->fail(DC_E_INVALID, "%s: the shape is past the kernel's 32-bit indices", who);
+  if (a->nimg > 1 && a->feat_stride < (size_t)map)
+    return ctx->fail(DC_E_INVALID, "%s: feat_stride = %zu is below the %lld floats of a map", who, a->feat_stride, map);
+  if (a->B_dev != nullptr && a->bdev_stride < 1) return ctx->fail(DC_E_INVALID, "%s: bdev_stride >= 1 wanted", who);
+  // a pick list without source boxes is the launcher's to refuse; with them, every pick of a live row is checked here
+  if (a->pick != nullptr && a->src_boxes != nullptr) {
+    if (a->src_rows < 1) return ctx->fail(DC_E_INVALID, "%s: src_rows >= 1 wanted", who);
+    if (a->nimg > 1 && a->src_stride < (size_t)a->src_rows * 4)
+      return ctx->fail(DC_E_INVALID, "%s: src_stride = %zu is below the %d source rows", who, a->src_stride, a->src_rows);
+    std::vector<int32_t> live(a->nimg, a->B);
+    if (a->B_dev != nullptr) DCCHK(glue_live_counts(ctx, a->B_dev, a->bdev_stride, a->nimg, a->B, live));
+    DCCHK(glue_check_rows(ctx, a->pick, a->nimg, a->B, live, a->src_rows, who, "pick"));
+  }
+  KCHK(launch_bilinear_roi_pool_group(a->feat_hwc, a->feat_stride, a->nimg, a->h, a->w, a->C, a->boxes, a->B, a->B_dev, a->bdev_stride,
+                                      a->pick, a->src_boxes, a->src_stride, a->img_h, a->img_w, a->HH, a->WW, a->out, a->out_layout, s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_recog_heads(dc_ctx* ctx, const float* codes, const float* w5, const float* b5, const float* roi, float* obj,
+                         float* trans, float* fin, float* fin_xyxy_or_null, int n, int D) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_recog_heads";
+  if (!codes || !w5 || !b5 || !roi || !obj || !trans || !fin) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n < 1 || n > (1 << 28) || D < 1) return ctx->fail(DC_E_INVALID, "%s: n in [1, 2^28] and D >= 1 wanted", who);
+  KCHK(launch_recog_heads(codes, w5, b5, roi, obj, trans, fin, fin_xyxy_or_null, n, D, s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_iota_count(dc_ctx* ctx, int32_t* idx, int32_t* count_out, const int32_t* count_in, int cap) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_iota_count";
+  if (!idx || !count_out || !count_in) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (cap < 1) return ctx->fail(DC_E_INVALID, "%s: cap >= 1 wanted", who);
+  KCHK(launch_iota_count(idx, count_out, count_in, cap, s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_gather_rows(dc_ctx* ctx, const void* src, int src_rows, const int32_t* idx, const int32_t* count, int cap, int width,
+                         void* out, int is_i32) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_gather_rows";
+  if (!src || !idx || !count || !out) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (src_rows < 1 || cap < 1 || width < 1 || (long long)cap * width >= (1ll << 31))
+    return ctx->fail(DC_E_INVALID, "%s: src_rows, cap, width >= 1 and cap * width < 2^31 wanted", who);
+  std::vector<int32_t> live;
+  DCCHK(glue_live_counts(ctx, count, 1, 1, cap, live));
+  DCCHK(glue_check_rows(ctx, idx, 1, cap, live, src_rows, who, "idx"));
+  if (is_i32) KCHK(launch_gather_rows_i32(static_cast<const int32_t*>(src), idx, count, cap, width, static_cast<int32_t*>(out), s));
+  else KCHK(launch_gather_rows(static_cast<const float*>(src), idx, count, cap, width, static_cast<float*>(out), s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_survivor_compact(dc_ctx* ctx, const float* codes, const int32_t* picks, const int32_t* count, int count_stride,
+                              int nimg, int P, int D, float* out, int32_t* total) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_survivor_compact";
+  if (!codes || !picks || !count || !out || !total) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (nimg < 1 || nimg > 65535 || P < 1 || D < 1 || count_stride < 1 || (long long)nimg * P > (1 << 28))
+    return ctx->fail(DC_E_INVALID, "%s: nimg in [1, 65535], P, D, count_stride >= 1 wanted", who);
+  std::vector<int32_t> live;
+  DCCHK(glue_live_counts(ctx, count, count_stride, nimg, P, live, who));
+  DCCHK(glue_check_rows(ctx, picks, nimg, P, live, P, who, "picks"));
+  KCHK(launch_survivor_compact(codes, picks, count, count_stride, nimg, P, D, out, total, s));
+  OP_EPILOGUE();
+}
+
+int dc_debug_final_pack(dc_ctx* ctx, const dc_glue_final_pack* a) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_final_pack";
+  if (!a || !a->final_boxes || !a->obj || !a->picks || !a->count || !a->pack) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if ((a->tokens != nullptr) == (a->codes != nullptr)) return ctx->fail(DC_E_INVALID, "%s: exactly one of tokens and codes wanted", who);
+  const int words = a->codes != nullptr ? a->D : a->T;
+  if (a->nimg < 1 || a->nimg > 65535 || a->P < 1 || words < 1 || a->count_stride < 1 || (long long)a->nimg * a->P > (1 << 28))
+    return ctx->fail(DC_E_INVALID, "%s: nimg in [1, 65535], P, count_stride and the row's T or D >= 1 wanted", who);
+  if (a->tokens != nullptr && (a->tok_gather < 0 || a->tok_gather > 2))
+    return ctx->fail(DC_E_INVALID, "%s: tok_gather = %d is not 0, 1 or 2", who, a->tok_gather);
+  const size_t need = (a->box_src != nullptr ? rec_src(a->P, words) + (size_t)a->P * 4 : rec_src(a->P, words));
+  if (a->stride < need || a->stride % 4)
+    return ctx->fail(DC_E_INVALID, "%s: stride = %zu is below the record's %zu bytes or no multiple of 4", who, a->stride, need);
+  std::vector<int32_t> live;
+  DCCHK(glue_live_counts(ctx, a->count, a->count_stride, a->nimg, a->P, live, who));
+  DCCHK(glue_check_rows(ctx, a->picks, a->nimg, a->P, live, a->P, who, "picks"));
+  KCHK(launch_final_pack(a->final_boxes, a->obj, a->tokens, a->tok_gather, a->codes, a->picks, a->count, a->count_stride, a->fault,
+                         a->nimg, a->P, a->T, a->D, a->pack, a->stride, s, a->box_src));
+  OP_EPILOGUE();
+}
+
 // ---- beam search test hooks, both rules (densecap_debug.h, densecap_debug_beam.h) ----------------------------------------------
 int dc_debug_beam_topk(dc_ctx* ctx, const float* logits, int rows, int V1, int ld, const uint8_t* finished_or_null, int k,
                        float* top_lp, int32_t* top_idx) {

@@ -1623,3 +1623,166 @@ def step_tail(ctx, kind, n, Hd, part=None, idx=None, nslots=0, ld=0, xg=None, ga
     res = {k: v.numpy() for k, v in (("c", cd), ("h", hd), ("acc", ad), ("fin", fd), ("seq", seq)) if v is not None}
     res["rc"] = rc
     return res
+
+
+# ---- the forward path's glue kernels, one launch each (include/densecap_debug_glue.h) -------------------------------------------
+# Every output buffer holds a sentinel before the call -- a fixed NaN pattern in float32 buffers, 0x5a5a5a5a in int32 buffers, 0x5a
+# in the byte records -- and carries guard rows after its end; the wrappers return the whole buffers, guards included, with
+# rc = the call's return code (raise_errors=False: returned with the untouched buffers instead of raising).
+GLUE_F32_FILL = 0x7fc5a5a5
+GLUE_I32_FILL = 0x5a5a5a5a
+GLUE_BYTE_FILL = 0x5a
+
+
+def _glue_filled(ctx, shape, dtype):
+    dtype = np.dtype(dtype)
+    if dtype == np.float32:
+        return ctx.to_device(np.full(shape, GLUE_F32_FILL, np.uint32).view(np.float32))
+    return ctx.to_device(np.full(shape, GLUE_I32_FILL if dtype == np.int32 else GLUE_BYTE_FILL, dtype))
+
+
+def _glue_guarded(ctx, a, dtype, guard_rows):
+    """a on the device with guard_rows sentinel rows after it (a buffer a kernel reads AND writes)."""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    buf = _glue_filled(ctx, (a.shape[0] + guard_rows,) + a.shape[1:], dtype).numpy()
+    buf[:a.shape[0]] = a
+    return ctx.to_device(buf)
+
+
+def _glue_counts(ctx, count, stride):
+    """Per-image counts `stride` int32 apart; the slots between them hold the int32 sentinel (a large count)."""
+    count = np.asarray(count, np.int32).reshape(-1)
+    step = max(int(stride), 1)                       # (a stride below 1 is for the hook to refuse)
+    a = np.full((len(count) * step,), GLUE_I32_FILL, np.int32)
+    a[::step] = count
+    return ctx.to_device(a)
+
+
+def _glue_result(ctx, rc, who, out, raise_errors):
+    if raise_errors:
+        check(ctx.h, rc, who)
+    res = {k: v.numpy() for k, v in out.items() if v is not None}
+    res["rc"] = rc
+    return res
+
+
+def glue_boxes_ingest(ctx, in_boxes, in_n, P, clip, img_h, img_w, count_stride=1, guard_rows=2, raise_errors=True):
+    """dc_debug_boxes_ingest: in_boxes (nimg * P, 4), in_n (nimg,) -> roi_boxes (nimg * P + g, 4), box_src (nimg * P + g,),
+    count (nimg * count_stride + g,)."""
+    nimg = len(in_n)
+    g = int(guard_rows)
+    bd, nd = ctx.to_device(_f32(in_boxes)), ctx.to_device(np.asarray(in_n, np.int32))
+    out = dict(roi_boxes=_glue_filled(ctx, (nimg * P + g, 4), np.float32), box_src=_glue_filled(ctx, (nimg * P + g,), np.int32),
+               count=_glue_filled(ctx, (nimg * count_stride + g,), np.int32))
+    rc = ctx.lib.dc_debug_boxes_ingest(ctx.h, bd.ptr, nd.ptr, nimg, int(P), int(clip), int(img_h), int(img_w), out["roi_boxes"].ptr,
+                                       out["box_src"].ptr, out["count"].ptr, int(count_stride))
+    return _glue_result(ctx, rc, "dc_debug_boxes_ingest", out, raise_errors)
+
+
+def glue_roi_pool_group(ctx, feats, B, img_h, img_w, HH, WW, out_layout, boxes=None, B_dev=None, bdev_stride=1, pick=None,
+                        src_boxes=None, src_pad_rows=3, feat_pad=8, guard_rows=2, raise_errors=True):
+    """dc_debug_roi_pool_group.  feats (nimg, C, h, w), uploaded channels last with feat_pad floats between two maps; boxes
+    (nimg * B, 4) (without pick); B_dev (nimg,) or None; pick (nimg * B,) into src_boxes (nimg, S, 4), uploaded with
+    src_pad_rows rows between two images' lists.  Returns out (nimg * B + g, ...) in the layout asked for and boxes
+    (nimg * B + g, 4) as they stand after the call."""
+    f = _f32(feats)
+    nimg, C_, h, w = f.shape
+    g = int(guard_rows)
+    fs = h * w * C_ + int(feat_pad)
+    fh = np.zeros((nimg, fs), np.float32)
+    fh[:, :h * w * C_] = f.transpose(0, 2, 3, 1).reshape(nimg, -1)
+    fd = ctx.to_device(fh)
+    bd = _glue_guarded(ctx, _f32(boxes).reshape(nimg * B, 4), np.float32, g) if boxes is not None else _glue_filled(ctx, (nimg * B + g, 4), np.float32)
+    cd = _glue_counts(ctx, B_dev, bdev_stride) if B_dev is not None else None
+    pd = ctx.to_device(np.asarray(pick, np.int32).reshape(-1)) if pick is not None else None
+    sd, S, ss = None, 0, 0
+    if src_boxes is not None:
+        sb = _f32(src_boxes)
+        S = sb.shape[1]
+        ss = (S + int(src_pad_rows)) * 4
+        sh = np.full((nimg, ss), 1e30, np.float32)
+        sh[:, :S * 4] = sb.reshape(nimg, -1)
+        sd = ctx.to_device(sh)
+    out = dict(out=_glue_filled(ctx, (nimg * B + g, C_, HH, WW) if out_layout == 0 else (nimg * B + g, HH, WW, C_), np.float32), boxes=bd)
+    a = _lib.DcGlueRoiPool(feat_hwc=fd.ptr, feat_stride=fs, nimg=nimg, h=h, w=w, C=C_, boxes=bd.ptr, B=int(B), B_dev=_ptr(cd),
+                           bdev_stride=int(bdev_stride), pick=_ptr(pd), src_boxes=_ptr(sd), src_stride=ss, src_rows=S,
+                           img_h=int(img_h), img_w=int(img_w), HH=int(HH), WW=int(WW), out=out["out"].ptr, out_layout=int(out_layout))
+    rc = ctx.lib.dc_debug_roi_pool_group(ctx.h, C.byref(a))
+    return _glue_result(ctx, rc, "dc_debug_roi_pool_group", out, raise_errors)
+
+
+def glue_recog_heads(ctx, codes, w5, b5, roi, with_xyxy=True, guard_rows=2, raise_errors=True):
+    """dc_debug_recog_heads: codes (n, D), w5 (5, D), b5 (5,), roi (n, 4) -> obj (n + g,), trans, fin, fin_xyxy (n + g, 4)."""
+    x = _f32(codes)
+    n, D = x.shape
+    g = int(guard_rows)
+    xd, wd, bd, rd = ctx.to_device(x), ctx.to_device(_f32(w5)), ctx.to_device(_f32(b5)), ctx.to_device(_f32(roi))
+    out = dict(obj=_glue_filled(ctx, (n + g,), np.float32), trans=_glue_filled(ctx, (n + g, 4), np.float32),
+               fin=_glue_filled(ctx, (n + g, 4), np.float32), fin_xyxy=_glue_filled(ctx, (n + g, 4), np.float32) if with_xyxy else None)
+    rc = ctx.lib.dc_debug_recog_heads(ctx.h, xd.ptr, wd.ptr, bd.ptr, rd.ptr, out["obj"].ptr, out["trans"].ptr, out["fin"].ptr,
+                                      _ptr(out["fin_xyxy"]), n, D)
+    return _glue_result(ctx, rc, "dc_debug_recog_heads", out, raise_errors)
+
+
+def glue_iota_count(ctx, cap, count_in, guard_rows=2, raise_errors=True):
+    """dc_debug_iota_count -> idx (cap + g,), count_out (1 + g,)."""
+    g = int(guard_rows)
+    cd = _count(ctx, int(count_in))
+    out = dict(idx=_glue_filled(ctx, (max(cap, 0) + g,), np.int32), count_out=_glue_filled(ctx, (1 + g,), np.int32))
+    rc = ctx.lib.dc_debug_iota_count(ctx.h, out["idx"].ptr, out["count_out"].ptr, cd.ptr, int(cap))
+    return _glue_result(ctx, rc, "dc_debug_iota_count", out, raise_errors)
+
+
+def glue_gather_rows(ctx, src, idx, count, cap, guard_rows=2, raise_errors=True):
+    """dc_debug_gather_rows: src (src_rows, width) float32 or int32 (the dtype selects the kernel), idx (cap,) -> out (cap + g, width)."""
+    src = np.ascontiguousarray(src)
+    is_i32 = src.dtype == np.int32
+    if not is_i32:
+        src = _f32(src)
+    g = int(guard_rows)
+    sd, idd, cd = ctx.to_device(src), ctx.to_device(np.asarray(idx, np.int32)), _count(ctx, int(count))
+    out = dict(out=_glue_filled(ctx, (max(cap, 0) + g, src.shape[1]), src.dtype))
+    rc = ctx.lib.dc_debug_gather_rows(ctx.h, sd.ptr, src.shape[0], idd.ptr, cd.ptr, int(cap), src.shape[1], out["out"].ptr, int(is_i32))
+    return _glue_result(ctx, rc, "dc_debug_gather_rows", out, raise_errors)
+
+
+def glue_survivor_compact(ctx, codes, picks, count, P, count_stride=1, guard_rows=2, raise_errors=True):
+    """dc_debug_survivor_compact: codes (nimg * P, D), picks (nimg * P,), count (nimg,) -> out (nimg * P + g, D), total (1 + g,)."""
+    x = _f32(codes)
+    nimg = len(count)
+    g = int(guard_rows)
+    xd, pd, cd = ctx.to_device(x), ctx.to_device(np.asarray(picks, np.int32)), _glue_counts(ctx, count, count_stride)
+    out = dict(out=_glue_filled(ctx, (nimg * P + g, x.shape[1]), np.float32), total=_glue_filled(ctx, (1 + g,), np.int32))
+    rc = ctx.lib.dc_debug_survivor_compact(ctx.h, xd.ptr, pd.ptr, cd.ptr, int(count_stride), nimg, int(P), x.shape[1], out["out"].ptr,
+                                           out["total"].ptr)
+    return _glue_result(ctx, rc, "dc_debug_survivor_compact", out, raise_errors)
+
+
+def glue_record_bytes(P, words, with_src):
+    """Bytes of one image's record: the header's 256, boxes, scores, `words` values a row and, with_src, one int32 a row."""
+    return 256 + 4 * int(P) * (5 + int(words) + (1 if with_src else 0))
+
+
+def glue_final_pack(ctx, final_boxes, obj, picks, count, P, tokens=None, tok_gather=0, codes=None, fault=None, box_src=None,
+                    count_stride=1, stride=None, guard_bytes=256, raise_errors=True):
+    """dc_debug_final_pack: final_boxes (nimg * P, 4), obj (nimg * P,), picks (nimg * P,), count (nimg,), tokens (nimg * P, T)
+    int32 or codes (nimg * P, D), fault: the word the fault pointer points at (None: a null pointer), box_src (nimg * P,) or
+    None.  stride: bytes between two records (default: the record, rounded up to 256, plus 256).  Returns pack (nimg * stride +
+    guard_bytes,) uint8."""
+    nimg = len(count)
+    td = ctx.to_device(np.ascontiguousarray(tokens, dtype=np.int32)) if tokens is not None else None
+    xd = ctx.to_device(_f32(codes)) if codes is not None else None
+    T = td.shape[1] if td is not None else 0
+    D = xd.shape[1] if xd is not None else 0
+    if stride is None:
+        stride = (glue_record_bytes(P, D if xd is not None else T, box_src is not None) + 255) // 256 * 256 + 256
+    bd, od = ctx.to_device(_f32(final_boxes)), ctx.to_device(_f32(obj))
+    pd, cd = ctx.to_device(np.asarray(picks, np.int32)), _glue_counts(ctx, count, count_stride)
+    fd = ctx.to_device(np.array([fault], np.uint32)) if fault is not None else None
+    sd = ctx.to_device(np.asarray(box_src, np.int32)) if box_src is not None else None
+    out = dict(pack=_glue_filled(ctx, (nimg * int(stride) + int(guard_bytes),), np.uint8))
+    a = _lib.DcGlueFinalPack(final_boxes=bd.ptr, obj=od.ptr, tokens=_ptr(td), tok_gather=int(tok_gather), codes=_ptr(xd), picks=pd.ptr,
+                             count=cd.ptr, count_stride=int(count_stride), fault=_ptr(fd), nimg=nimg, P=int(P), T=T, D=D,
+                             pack=out["pack"].ptr, stride=int(stride), box_src=_ptr(sd))
+    rc = ctx.lib.dc_debug_final_pack(ctx.h, C.byref(a))
+    return _glue_result(ctx, rc, "dc_debug_final_pack", out, raise_errors)
