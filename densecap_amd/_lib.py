@@ -385,6 +385,13 @@ _GLUE_HOOK_SIGS = {
     "dc_debug_survivor_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "dc_debug_final_pack": (C.c_int, [C.c_void_p, C.POINTER(DcGlueFinalPack)]),
 }
+# the hooks of include/densecap_debug_nms.h (the two NMS launchers with a device-side row count; bound like the others)
+_NMS_HOOK_SIGS = {
+    "dc_debug_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_debug_nms_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
@@ -403,7 +410,7 @@ def lib():
                                   list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
                                   list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items()) +
-                                  list(_GLUE_HOOK_SIGS.items())):
+                                  list(_GLUE_HOOK_SIGS.items()) + list(_NMS_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -17,6 +17,7 @@
 #include "../../include/densecap_debug_rpn.h"
 #include "../../include/densecap_debug_optim.h"
 #include "../../include/densecap_debug_glue.h"
+#include "../../include/densecap_debug_nms.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -303,6 +303,7 @@ struct dc_ctx {
   int train_t = 0;
   KeptBuf train_g{scratch}, train_m{scratch}, train_v{scratch}, train_master{scratch}, train_out{scratch}, train_tab{scratch};
   KeptBuf optim_tab{scratch};
+  KeptBuf nms_debug_ws{scratch};         // dc_debug_nms's workspace (grow only: a call finds what the larger one before it left)
   int train_nseg = 0;
   unsigned long long train_chunks = 0;
   StageClock<4> train_clock;
@@ -4153,6 +4154,46 @@ int dc_debug_final_pack(dc_ctx* ctx, const dc_glue_final_pack* a) {
   KCHK(launch_final_pack(a->final_boxes, a->obj, a->tokens, a->tok_gather, a->codes, a->picks, a->count, a->count_stride, a->fault,
                          a->nimg, a->P, a->T, a->D, a->pack, a->stride, s, a->box_src));
   OP_EPILOGUE();
+}
+
+// ---- the two NMS launchers with a device-side row count (densecap_debug_nms.h) -----------------------------------------------------
+// dc_op_nms binds a workspace of its own for exactly n rows; the forward binds one for the RPN list and runs the final NMS in it.
+// The hook's workspace is a buffer the ctx keeps, bound for ws_rows: a small call after a large one reads the large one's leftovers.
+int dc_debug_nms(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n,
+                 const int32_t* n_dev_or_null, int ws_rows, float thresh, int max_boxes, int32_t* picks, int32_t* count,
+                 int32_t* order_or_null, int32_t* nvalid_or_null) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_nms";
+  if (!boxes || !scores || !picks || !count) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n < 1) return ctx->fail(DC_E_INVALID, "%s: n must be >= 1 (got %d)", who, n);
+  if (ws_rows < n) return ctx->fail(DC_E_INVALID, "%s: ws_rows = %d is below the %d rows of the call", who, ws_rows, n);
+  if (max_boxes < -1) return ctx->fail(DC_E_INVALID, "%s: max_boxes must be >= -1 (got %d)", who, max_boxes);
+  HIPCHK(ctx->nms_debug_ws.grow(nms_workspace_bytes(ws_rows), s));
+  NmsWorkspace ws;
+  nms_workspace_bind(ws, ctx->nms_debug_ws.get(), ws_rows);
+  ensure_fault_word(ctx);
+  KCHK(launch_nms(ws, boxes, scores, valid_or_null, n, n_dev_or_null, thresh, max_boxes, picks, count, ctx->cfg.nms_band, s,
+                  ctx->fault_dev));
+  if (order_or_null != nullptr) HIPCHK(hipMemcpyAsync(order_or_null, ws.order, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (nvalid_or_null != nullptr) HIPCHK(hipMemcpyAsync(nvalid_or_null, ws.nvalid, 4, hipMemcpyDeviceToDevice, s));
+  return call_finish(ctx, s, DC_OK, who, true);
+}
+
+int dc_debug_nms_multi(dc_ctx* ctx, const float* boxes, const float* scores, const uint8_t* valid_or_null, int n,
+                       const int32_t* n_dev_or_null, int Q, float thresh, int max_picks, int32_t* picks, int32_t* counts) {
+  OP_PROLOGUE();
+  const char* who = "dc_debug_nms_multi";
+  if (!boxes || !scores || !picks || !counts) return ctx->fail(DC_E_INVALID, "%s: null pointer", who);
+  if (n < 1) return ctx->fail(DC_E_INVALID, "%s: n must be >= 1 (got %d)", who, n);
+  if (Q < 1) return ctx->fail(DC_E_INVALID, "%s: Q must be >= 1 (got %d)", who, Q);
+  if (max_picks < 1 || max_picks > kNmsMultiMax)
+    return ctx->fail(DC_E_INVALID, "%s: max_picks must be in 1..%d (got %d)", who, kNmsMultiMax, max_picks);
+  if (n > kNmsMultiMax)
+    return ctx->fail(DC_E_UNSUPPORTED, "%s: %d boxes exceed the %d the per-query scan holds", who, n, kNmsMultiMax);
+  Scratch ws(ctx->scratch, s);
+  HIPCHK(ws.alloc(nms_multi_workspace_bytes(n)));
+  KCHK(launch_nms_multi(ws.get(), boxes, scores, valid_or_null, n, n_dev_or_null, Q, thresh, max_picks, picks, counts, s));
+  return call_finish(ctx, s, DC_OK, who);
 }
 
 // ---- beam search test hooks, both rules (densecap_debug.h, densecap_debug_beam.h) ----------------------------------------------

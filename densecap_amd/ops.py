@@ -1786,3 +1786,53 @@ def glue_final_pack(ctx, final_boxes, obj, picks, count, P, tokens=None, tok_gat
                              pack=out["pack"].ptr, stride=int(stride), box_src=_ptr(sd))
     rc = ctx.lib.dc_debug_final_pack(ctx.h, C.byref(a))
     return _glue_result(ctx, rc, "dc_debug_final_pack", out, raise_errors)
+
+
+# ---- the two NMS launchers with a device-side row count (include/densecap_debug_nms.h) -------------------------------------------
+# Output buffers are sentinel-filled and guarded as the glue wrappers' are; `null` names arguments to pass as null pointers.
+def nms_debug(ctx, boxes5, thresh, max_boxes=None, valid=None, n_dev=None, ws_rows=None, n=None, guard_rows=2, null=(),
+              raise_errors=True):
+    """dc_debug_nms: launch_nms on boxes5 (N, 5) x1 y1 x2 y2 score.  max_boxes None: -1; valid (N,) bytes or None; n_dev: the
+    value of the device-side row count or None (a null pointer); ws_rows: rows the workspace is bound for (default n); n: the
+    row count passed (default N).  Returns dict(rc, picks (cap + g,), count (1 + g,), order (N + g,), nvalid (1 + g,)), all
+    int32, cap = N or min(N, max_boxes)."""
+    b = _f32(boxes5)
+    N = b.shape[0]
+    n = N if n is None else int(n)
+    g = int(guard_rows)
+    bd = ctx.to_device(np.ascontiguousarray(b[:, :4])) if "boxes" not in null else None
+    sd = ctx.to_device(np.ascontiguousarray(b[:, 4])) if "scores" not in null else None
+    vd = ctx.to_device(np.ascontiguousarray(valid, dtype=np.uint8)) if valid is not None else None
+    nd = ctx.to_device(np.array([n_dev], np.int32)) if n_dev is not None else None
+    mb = -1 if max_boxes is None else int(max_boxes)
+    cap = N if mb < 0 else min(N, mb)
+    out = dict(picks=_glue_filled(ctx, (cap + g,), np.int32), count=_glue_filled(ctx, (1 + g,), np.int32),
+               order=_glue_filled(ctx, (N + g,), np.int32), nvalid=_glue_filled(ctx, (1 + g,), np.int32))
+    rc = ctx.lib.dc_debug_nms(ctx.h, _ptr(bd), _ptr(sd), _ptr(vd), n, _ptr(nd), n if ws_rows is None else int(ws_rows),
+                              C.c_float(float(np.float32(thresh))), mb, None if "picks" in null else out["picks"].ptr,
+                              None if "count" in null else out["count"].ptr, out["order"].ptr, out["nvalid"].ptr)
+    return _glue_result(ctx, rc, "dc_debug_nms", out, raise_errors)
+
+
+def nms_multi_debug(ctx, boxes, scores, thresh, max_picks, valid=None, n_dev=None, n=None, Q=None, guard_rows=2, null=(),
+                    raise_errors=True):
+    """dc_debug_nms_multi: launch_nms_multi on boxes (N, 4), scores (N, Q) with the device-side row count n_dev (None: a null
+    pointer).  Returns dict(rc, picks (Q + g, M) int32, counts (Q + g,) int32), M = max_picks clamped to 1..4096."""
+    b = _f32(boxes).reshape(-1, 4)
+    s = _f32(scores)
+    if s.ndim == 1:
+        s = s[:, None]
+    N, Qs = s.shape
+    n = N if n is None else int(n)
+    Q = Qs if Q is None else int(Q)
+    g = int(guard_rows)
+    bd = ctx.to_device(b) if "boxes" not in null else None
+    sd = ctx.to_device(s) if "scores" not in null else None
+    vd = ctx.to_device(np.ascontiguousarray(valid, dtype=np.uint8)) if valid is not None else None
+    nd = ctx.to_device(np.array([n_dev], np.int32)) if n_dev is not None else None
+    M = min(max(int(max_picks), 1), 4096)
+    out = dict(picks=_glue_filled(ctx, (Qs + g, M), np.int32), counts=_glue_filled(ctx, (Qs + g,), np.int32))
+    rc = ctx.lib.dc_debug_nms_multi(ctx.h, _ptr(bd), _ptr(sd), _ptr(vd), n, _ptr(nd), Q, C.c_float(float(np.float32(thresh))),
+                                    int(max_picks), None if "picks" in null else out["picks"].ptr,
+                                    None if "counts" in null else out["counts"].ptr)
+    return _glue_result(ctx, rc, "dc_debug_nms_multi", out, raise_errors)
