@@ -309,6 +309,12 @@ _SIGS = {
     "dc_train_end": (C.c_int, [C.c_void_p]),
     "dc_get_weights": (C.c_int, [C.c_void_p, C.POINTER(DcWeights)]),
     "dc_op_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(DcTrainOpts)]),
+    "dc_train_set_grad_clip": (C.c_int, [C.c_void_p, C.c_double]),
+    "dc_train_grad_norm": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_float_p]),
+    "dc_op_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  c_float_p]),
+    "dc_train_get_state": (C.c_int, [C.c_void_p, C.POINTER(DcWeights), C.POINTER(DcWeights), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dc_train_set_state": (C.c_int, [C.c_void_p, C.POINTER(DcWeights), C.POINTER(DcWeights), C.c_int, C.c_int]),
     "dc_localize_captions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(DcLocalizeOpts), C.POINTER(DcResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -374,6 +380,12 @@ _OPTIM_HOOK_SIGS = {
     "dc_debug_screen_operands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_debug_unpack_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
 }
+# the hook of include/densecap_debug_clip.h (gradient clipping: the norm pass and the scaled Adam launch; bound like the others)
+_CLIP_HOOK_SIGS = {
+    "dc_debug_adam_multi_clip": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 +
+                                 [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DcTrainOpts), C.c_int, C.c_double,
+                                  C.POINTER(C.c_double), c_float_p]),
+}
 # the hooks of include/densecap_debug_glue.h (the forward path's glue kernels, one launch each; bound like the others)
 _GLUE_HOOK_SIGS = {
     "dc_debug_boxes_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int]),
@@ -410,6 +422,7 @@ def lib():
                                   list(_BEAM_STD_HOOK_SIGS.items()) +
                                   list(_GRAD_HOOK_SIGS.items()) + list(_RECOG_HOOK_SIGS.items()) +
                                   list(_BWD_HOOK_SIGS.items()) + list(_RPN_HOOK_SIGS.items()) + list(_OPTIM_HOOK_SIGS.items()) +
+                                  list(_CLIP_HOOK_SIGS.items()) +
                                   list(_GLUE_HOOK_SIGS.items()) + list(_NMS_HOOK_SIGS.items())):
             fn = getattr(l, name)  # AttributeError if the symbol is not exported
             fn.restype = res

@@ -16,6 +16,7 @@
 #include "../../include/densecap_debug_bwd.h"
 #include "../../include/densecap_debug_rpn.h"
 #include "../../include/densecap_debug_optim.h"
+#include "../../include/densecap_debug_clip.h"
 #include "../../include/densecap_debug_glue.h"
 #include "../../include/densecap_debug_nms.h"
 
@@ -632,6 +633,19 @@ unsigned long long adam_chunks(size_t n);
 // grid_or_0: 0 = the production grid (min(chunks, 2048) workgroups); > 0: that many (a test hook: the result does not depend on it)
 hipError_t launch_adam_multi(const AdamSeg* seg_dev, int nseg, unsigned long long chunks, const AdamScalars& k, int grid_or_0,
                              hipStream_t s);
+// ---- the global gradient norm (docs/SEMANTICS.md, "Gradient clipping") ----
+// What grad_norm_finish_kernel leaves on the device: the sum of squares, its root, and the factor the scaled Adam launch reads
+struct GradNormRec { double sumsq, norm; float scale, pad_; };
+// partial[c] = the sum of squares of chunk c of the table's gradients (one double per chunk of the launch_adam_multi list,
+// `chunks` of them, whatever the grid); only the g pointers and n of the table are read
+hipError_t launch_grad_sumsq(const AdamSeg* seg_dev, int nseg, unsigned long long chunks, double* partial, int grid_or_0,
+                             hipStream_t s);
+// One workgroup: the `total` partials (of one table, or of two laid end to end) in a fixed order -> *rec.  max_norm >= 0 or +inf;
+// 0 reports the norm and leaves scale = 1
+hipError_t launch_grad_norm_finish(const double* partial, unsigned long long total, double max_norm, GradNormRec* rec, hipStream_t s);
+// launch_adam_multi with every gradient element multiplied by *scale_dev (a device float, read by the kernel) first
+hipError_t launch_adam_multi_scaled(const AdamSeg* seg_dev, int nseg, unsigned long long chunks, const AdamScalars& k,
+                                    const float* scale_dev, int grid_or_0, hipStream_t s);
 // The decode screen's operands from W (V1, Hd) fp32: wb (V1pad, Kp) bf16 bits, zero padded; wn (V1pad) the rows' 2-norms rounded
 // up to fp16, zero past V1
 hipError_t launch_screen_operands(const float* W, int V1, int Hd, int V1pad, int Kp, uint16_t* wb, uint16_t* wn, hipStream_t s);

@@ -306,6 +306,12 @@ struct dc_ctx {
   KeptBuf nms_debug_ws{scratch};         // dc_debug_nms's workspace (grow only: a call finds what the larger one before it left)
   int train_nseg = 0;
   unsigned long long train_chunks = 0;
+  // gradient clipping (dc_train_set_grad_clip): max_norm (0 = off), the device block of the step's norm pass (the
+  // record, then one double per chunk of the two tables), the last completed clipped step's record on the host
+  double train_clip = 0;
+  bool train_clip_have = false;
+  GradNormRec train_clip_rec{};
+  KeptBuf train_clip_buf{scratch};
   StageClock<4> train_clock;
   // MFMA profile
   bool prof = false;
@@ -4991,9 +4997,12 @@ int upload_adam_table(dc_ctx* ctx, KeptBuf& tab, hipStream_t s, std::vector<Adam
 }
 void train_release(dc_ctx* ctx) {
   for (KeptBuf* b : {&ctx->train_g, &ctx->train_m, &ctx->train_v, &ctx->train_master, &ctx->train_out, &ctx->train_tab,
-                     &ctx->train_cnn_master, &ctx->train_cnn_g, &ctx->train_cnn_m, &ctx->train_cnn_v, &ctx->train_cnn_tab}) b->reset();
+                     &ctx->train_cnn_master, &ctx->train_cnn_g, &ctx->train_cnn_m, &ctx->train_cnn_v, &ctx->train_cnn_tab,
+                     &ctx->train_clip_buf}) b->reset();
   ctx->train_cnn_mode = ctx->train_cnn_t = ctx->train_cnn_nseg = 0;
   ctx->train_cnn_chunks = 0;
+  ctx->train_clip = 0;
+  ctx->train_clip_have = false;
   ctx->training = false;
   ctx->train_t = 0;
   ctx->train_nseg = 0;
@@ -5043,14 +5052,9 @@ int train_refresh_cnn(dc_ctx* ctx, hipStream_t s) {
   }
   return DC_OK;
 }
-}  // namespace
-
-int dc_train_set_cnn(dc_ctx* ctx, int mode) {
-  const char* who = "dc_train_set_cnn";
-  if (!ctx) return DC_E_INVALID;
-  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
-  if (mode < 0 || mode > 2) return ctx->fail(DC_E_INVALID, "%s: mode must be 0, 1 or 2 (got %d)", who, mode);
-  if (mode != 0 && ctx->train_cnn_nseg == 0) {       // the first non-zero mode: masters, zeroed moments and arena, t = 0
+// The CNN's training state as the first non-zero dc_train_set_cnn makes it: masters, zeroed moments and arena, t = 0
+int train_cnn_alloc(dc_ctx* ctx) {
+  {
     HIPCHK(hipSetDevice(ctx->device));
     drain_lanes(ctx);
     hipStream_t s;
@@ -5089,6 +5093,16 @@ int dc_train_set_cnn(dc_ctx* ctx, int mode) {
       return rc;
     }
   }
+  return DC_OK;
+}
+}  // namespace
+
+int dc_train_set_cnn(dc_ctx* ctx, int mode) {
+  const char* who = "dc_train_set_cnn";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
+  if (mode < 0 || mode > 2) return ctx->fail(DC_E_INVALID, "%s: mode must be 0, 1 or 2 (got %d)", who, mode);
+  if (mode != 0 && ctx->train_cnn_nseg == 0) DCCHK(train_cnn_alloc(ctx));
   ctx->train_cnn_mode = mode;
   return DC_OK;
 }
@@ -5130,6 +5144,8 @@ int dc_train_begin(dc_ctx* ctx, const dc_train_opts* opts) {
   if (rc != DC_OK) { (void)hipStreamSynchronize(s); train_release(ctx); return rc; }
   ctx->train_opts = *opts;
   ctx->train_t = 0;
+  ctx->train_clip = 0;
+  ctx->train_clip_have = false;
   ctx->training = true;
   return DC_OK;
 }
@@ -5190,12 +5206,35 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
   if (rc != DC_OK) return rc;                      // no weight and no t has changed
   const AdamScalars k1 = adam_scalars(ctx->train_opts, ctx->train_t + 1);
   const AdamScalars kc = adam_scalars(ctx->train_opts, ctx->train_cnn_t + 1);      // (the CNN's own t: it counts CNN steps only)
+  // clipping (docs/SEMANTICS.md, "Gradient clipping"): one norm over the table(s) whose gradients the backward filled, its two
+  // launches in front of the Adam launch(es), which then read the scale from the device
+  const bool clip = ctx->train_clip > 0;
+  const AdamSeg* const tab1 = static_cast<const AdamSeg*>(ctx->train_tab.get());
+  const AdamSeg* const tabc = static_cast<const AdamSeg*>(ctx->train_cnn_tab.get());
+  GradNormRec* rec = nullptr;
+  if (clip) {
+    HIPCHK(ctx->train_clip_buf.grow(256 + (ctx->train_chunks + ctx->train_cnn_chunks) * sizeof(double), s));
+    rec = static_cast<GradNormRec*>(ctx->train_clip_buf.get());
+  }
   auto body = [&]() -> int {
     HIPCHK(clock.record(1, s));
-    KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_tab.get()), ctx->train_nseg, ctx->train_chunks, k1, 0, s));
+    if (clip) {
+      double* const partial = reinterpret_cast<double*>(reinterpret_cast<char*>(rec) + 256);
+      unsigned long long total = ctx->train_chunks;
+      KCHK(launch_grad_sumsq(tab1, ctx->train_nseg, ctx->train_chunks, partial, 0, s));
+      if (cnn_mode == 2) {
+        KCHK(launch_grad_sumsq(tabc, ctx->train_cnn_nseg, ctx->train_cnn_chunks, partial + total, 0, s));
+        total += ctx->train_cnn_chunks;
+      }
+      KCHK(launch_grad_norm_finish(partial, total, ctx->train_clip, rec, s));
+      KCHK(launch_adam_multi_scaled(tab1, ctx->train_nseg, ctx->train_chunks, k1, &rec->scale, 0, s));
+    } else {
+      KCHK(launch_adam_multi(tab1, ctx->train_nseg, ctx->train_chunks, k1, 0, s));
+    }
     if (cnn_mode != 0) {
       if (cnn_mode == 1) HIPCHK(hipMemsetAsync(ctx->train_cnn_g.get(), 0, ctx->train_cnn_g.bytes(), s));
-      KCHK(launch_adam_multi(static_cast<const AdamSeg*>(ctx->train_cnn_tab.get()), ctx->train_cnn_nseg, ctx->train_cnn_chunks, kc, 0, s));
+      if (clip && cnn_mode == 2) KCHK(launch_adam_multi_scaled(tabc, ctx->train_cnn_nseg, ctx->train_cnn_chunks, kc, &rec->scale, 0, s));
+      else KCHK(launch_adam_multi(tabc, ctx->train_cnn_nseg, ctx->train_cnn_chunks, kc, 0, s));
     }
     HIPCHK(clock.record(2, s));
     DCCHK(train_refresh(ctx, s));
@@ -5208,6 +5247,28 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
   const int rc2 = call_finish(ctx, s, body(), who, true);
   if (rc2 != DC_OK) return rc2;
   clock.read();
+  if (clip) {                                      // (the stream has drained: this copy waits for nothing)
+    HIPCHK(hipMemcpy(&ctx->train_clip_rec, rec, sizeof(GradNormRec), hipMemcpyDeviceToHost));
+    ctx->train_clip_have = true;
+  }
+  return DC_OK;
+}
+
+int dc_train_set_grad_clip(dc_ctx* ctx, double max_norm) {
+  const char* who = "dc_train_set_grad_clip";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
+  if (!(max_norm >= 0)) return ctx->fail(DC_E_INVALID, "%s: max_norm must be >= 0 or +inf (0: off)", who);
+  ctx->train_clip = max_norm;
+  return DC_OK;
+}
+
+int dc_train_grad_norm(dc_ctx* ctx, double* norm, float* scale) {
+  const char* who = "dc_train_grad_norm";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training || !ctx->train_clip_have) return ctx->fail(DC_E_STATE, "%s: no step has run with clipping on since dc_train_begin", who);
+  if (norm) *norm = ctx->train_clip_rec.norm;
+  if (scale) *scale = ctx->train_clip_rec.scale;
   return DC_OK;
 }
 
@@ -5293,6 +5354,201 @@ int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t
   if (!ctx) return DC_E_INVALID;
   std::vector<AdamSeg> tab = {{p, g, m, v, n, 0}};
   return adam_segments_run(ctx, "dc_op_adam", tab, t, opts, 0);
+}
+
+// The norm pass over `tab` (uploaded into ctx->optim_tab), then, with `adam`, the scaled Adam launch; the record comes back to *out
+static int grad_norm_run(dc_ctx* ctx, const char* who, std::vector<AdamSeg>& tab, double max_norm, int grid, const AdamScalars* adam,
+                         GradNormRec* out) {
+  if (!(max_norm >= 0)) return ctx->fail(DC_E_INVALID, "%s: max_norm must be >= 0 or +inf", who);
+  if (grid < 0 || grid > 65535) return ctx->fail(DC_E_INVALID, "%s: grid must be in 0..65535", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  const int nseg = (int)tab.size();
+  unsigned long long chunks = 0;
+  DCCHK(upload_adam_table(ctx, ctx->optim_tab, s, tab, &chunks));
+  Scratch block(ctx->scratch, s);
+  GradNormRec* rec = nullptr;
+  double* partial = nullptr;
+  HIPCHK(block.alloc(std::vector<Carve>{{(void**)&rec, sizeof(GradNormRec)}, {(void**)&partial, (size_t)chunks * sizeof(double)}}));
+  const AdamSeg* const dev = static_cast<const AdamSeg*>(ctx->optim_tab.get());
+  auto body = [&]() -> int {
+    KCHK(launch_grad_sumsq(dev, nseg, chunks, partial, grid, s));
+    KCHK(launch_grad_norm_finish(partial, chunks, max_norm, rec, s));
+    if (adam) KCHK(launch_adam_multi_scaled(dev, nseg, chunks, *adam, &rec->scale, grid, s));
+    return DC_OK;
+  };
+  DCCHK(call_finish(ctx, s, body(), who));
+  HIPCHK(hipMemcpy(out, rec, sizeof(GradNormRec), hipMemcpyDeviceToHost));
+  return DC_OK;
+}
+
+int dc_op_grad_norm(dc_ctx* ctx, const float* g, size_t n, double max_norm, double* sumsq, double* norm, float* scale) {
+  const char* who = "dc_op_grad_norm";
+  if (!ctx) return DC_E_INVALID;
+  if (!g || n < 1) return ctx->fail(DC_E_INVALID, "%s: a segment needs a buffer and n >= 1", who);
+  std::vector<AdamSeg> tab = {{nullptr, g, nullptr, nullptr, n, 0}};
+  GradNormRec r{};
+  DCCHK(grad_norm_run(ctx, who, tab, max_norm, 0, nullptr, &r));
+  if (sumsq) *sumsq = r.sumsq;
+  if (norm) *norm = r.norm;
+  if (scale) *scale = r.scale;
+  return DC_OK;
+}
+
+// ---- Adam's state out and in (docs/SEMANTICS.md, "Training step") ------------------------------------------------------------------
+namespace {
+// What both directions check first: the pointers of the untrained tensors must be null; *cnn = how many of the CNN's 18 are given
+int train_state_shape(dc_ctx* ctx, const dc_weights* w, const char* who, int* cnn) {
+  *cnn = 0;
+  if (!w) return DC_OK;
+  for (int i = 0; i < DC_NUM_VGG_CONVS; ++i) {
+    if (i < kCnnFirst) {
+      if (w->conv_w[i] || w->conv_b[i]) return ctx->fail(DC_E_INVALID, "%s: conv_w[%d] / conv_b[%d] are never trained: must be null", who, i, i);
+    } else {
+      *cnn += (w->conv_w[i] != nullptr) + (w->conv_b[i] != nullptr);
+    }
+  }
+  if (w->anchors) return ctx->fail(DC_E_INVALID, "%s: anchors are not trained: must be null", who);
+  return DC_OK;
+}
+bool train_state_complete(const dc_weights* w) {          // the 21 trained tensors outside the CNN
+  for (const float* f : {w->rpn_conv_w, w->rpn_conv_b, w->rpn_box_w, w->rpn_box_b, w->rpn_score_w, w->rpn_score_b, w->fc6_w, w->fc6_b,
+                         w->fc7_w, w->fc7_b, w->obj_w, w->obj_b, w->boxreg_w, w->boxreg_b, w->lm_enc_w, w->lm_enc_b, w->lm_emb,
+                         w->lstm_w, w->lstm_b, w->lm_out_w, w->lm_out_b})
+    if (f == nullptr) return false;
+  return true;
+}
+// One moment block (the arena `base` of the 21 tensors, `cnn_base` of the CNN's or null) <-> w's host tensors, in checkpoint layouts
+int train_state_move(dc_ctx* ctx, hipStream_t s, const dc_weights* w, void* base, void* cnn_base, bool to_host, const char* who) {
+  const size_t k = ctx->k, R = ctx->R, D = ctx->D, E = ctx->E, Hd = ctx->Hd, V = ctx->V;
+  std::vector<TrainSeg> segs;
+  train_segments(ctx, segs);
+  TrainArena a;
+  train_arena_carve(segs, a, base);
+  auto mv = [&](const float* host, float* dev, size_t n) -> int {
+    if (host == nullptr) return DC_OK;
+    if (to_host) HIPCHK(hipMemcpy(const_cast<float*>(host), dev, n * 4, hipMemcpyDeviceToHost));
+    else HIPCHK(hipMemcpy(dev, host, n * 4, hipMemcpyHostToDevice));
+    return DC_OK;
+  };
+  DCCHK(mv(w->rpn_conv_w, a.rpn_conv_w, R * 512 * 9));
+  DCCHK(mv(w->rpn_conv_b, a.rpn_conv_b, R));
+  DCCHK(mv(w->rpn_box_w, a.heads_w, 4 * k * R));
+  DCCHK(mv(w->rpn_score_w, a.heads_w + 4 * k * R, 2 * k * R));
+  DCCHK(mv(w->rpn_box_b, a.heads_b, 4 * k));
+  DCCHK(mv(w->rpn_score_b, a.heads_b + 4 * k, 2 * k));
+  if (w->fc6_w != nullptr) {                      // the arena holds fc6 in the engine's (i, j, c) input order
+    if (D > 65535) return ctx->fail(DC_E_UNSUPPORTED, "%s: fc_dim = %d: the fc6 permutation takes at most 65535 rows", who, (int)D);
+    Scratch tmp(ctx->scratch, s);
+    HIPCHK(tmp.alloc(D * kRecogK6 * 4));
+    float* const t = static_cast<float*>(tmp.get());
+    if (to_host) {
+      KCHK(launch_permute_fc6_back(a.fc6_w, t, (int)D, 512, 49, s));
+      HIPCHK(hipStreamSynchronize(s));
+      DCCHK(mv(w->fc6_w, t, D * kRecogK6));
+    } else {
+      DCCHK(mv(w->fc6_w, t, D * kRecogK6));
+      KCHK(launch_permute_fc6(t, a.fc6_w, (int)D, 512, 49, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+  }
+  DCCHK(mv(w->fc6_b, a.fc6_b, D));
+  DCCHK(mv(w->fc7_w, a.fc7_w, D * D));
+  DCCHK(mv(w->fc7_b, a.fc7_b, D));
+  DCCHK(mv(w->obj_w, a.head5_w, D));
+  DCCHK(mv(w->obj_b, a.head5_b, 1));
+  DCCHK(mv(w->boxreg_w, a.head5_w + D, 4 * D));
+  DCCHK(mv(w->boxreg_b, a.head5_b + 1, 4));
+  DCCHK(mv(w->lm_enc_w, a.enc_w, E * D));
+  DCCHK(mv(w->lm_enc_b, a.enc_b, E));
+  DCCHK(mv(w->lm_emb, a.emb, (V + 2) * E));
+  DCCHK(mv(w->lstm_w, a.lstm_w, (E + Hd) * 4 * Hd));
+  DCCHK(mv(w->lstm_b, a.lstm_b, 4 * Hd));
+  DCCHK(mv(w->lm_out_w, a.out_w, (V + 1) * Hd));
+  DCCHK(mv(w->lm_out_b, a.out_b, V + 1));
+  if (cnn_base != nullptr) {
+    CnnTrain c;
+    cnn_train_carve(c, cnn_base, true);
+    for (int j = 0; j < DC_NUM_CNN_GRAD_CONVS; ++j) {
+      const VggItem& vg = kVgg[kCnnFirst + j];
+      DCCHK(mv(w->conv_w[kCnnFirst + j], c.w[j], (size_t)vg.cout * vg.cin * 9));
+      DCCHK(mv(w->conv_b[kCnnFirst + j], c.b[j], (size_t)vg.cout));
+    }
+  }
+  return DC_OK;
+}
+}  // namespace
+
+int dc_train_get_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int* t, int* cnn_t) {
+  const char* who = "dc_train_get_state";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
+  int cm = 0, cv = 0;
+  DCCHK(train_state_shape(ctx, m, who, &cm));
+  DCCHK(train_state_shape(ctx, v, who, &cv));
+  const bool have_cnn = ctx->train_cnn_nseg > 0;
+  if ((cm > 0 || cv > 0) && !have_cnn) return ctx->fail(DC_E_STATE, "%s: the CNN has no training state (no non-zero dc_train_set_cnn yet)", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (m) DCCHK(train_state_move(ctx, s, m, ctx->train_m.get(), have_cnn ? ctx->train_cnn_m.get() : nullptr, true, who));
+  if (v) DCCHK(train_state_move(ctx, s, v, ctx->train_v.get(), have_cnn ? ctx->train_cnn_v.get() : nullptr, true, who));
+  if (t) *t = ctx->train_t;
+  if (cnn_t) *cnn_t = have_cnn ? ctx->train_cnn_t : 0;
+  return DC_OK;
+}
+
+int dc_train_set_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int t, int cnn_t) {
+  const char* who = "dc_train_set_state";
+  if (!ctx) return DC_E_INVALID;
+  if (!ctx->training) return ctx->fail(DC_E_STATE, "%s: only between dc_train_begin and dc_train_end", who);
+  if (!m || !v) return ctx->fail(DC_E_INVALID, "%s: both moments are required", who);
+  if (t < 0 || cnn_t < 0) return ctx->fail(DC_E_INVALID, "%s: t and cnn_t must be >= 0 (got %d, %d)", who, t, cnn_t);
+  int cm = 0, cv = 0;
+  DCCHK(train_state_shape(ctx, m, who, &cm));
+  DCCHK(train_state_shape(ctx, v, who, &cv));
+  if (!train_state_complete(m) || !train_state_complete(v))
+    return ctx->fail(DC_E_INVALID, "%s: all 21 trained tensors are required in m and in v", who);
+  const int all = 2 * DC_NUM_CNN_GRAD_CONVS;
+  if (cm != cv || (cm != 0 && cm != all)) return ctx->fail(DC_E_INVALID, "%s: the CNN's 18 tensors are given in both moments or in neither", who);
+  if (cm == 0 && cnn_t != 0) return ctx->fail(DC_E_INVALID, "%s: cnn_t = %d without the CNN's moments", who, cnn_t);
+  if (ctx->D > 65535) return ctx->fail(DC_E_UNSUPPORTED, "%s: fc_dim = %d: the fc6 permutation takes at most 65535 rows", who, (int)ctx->D);
+  if (cm == all && ctx->train_cnn_nseg == 0) DCCHK(train_cnn_alloc(ctx));
+  HIPCHK(hipSetDevice(ctx->device));
+  drain_lanes(ctx);
+  hipStream_t s;
+  DCCHK(lane0_stream(ctx, &s));
+  HIPCHK(hipStreamSynchronize(s));
+  const bool cnn = cm == all;
+  DCCHK(train_state_move(ctx, s, m, ctx->train_m.get(), cnn ? ctx->train_cnn_m.get() : nullptr, false, who));
+  DCCHK(train_state_move(ctx, s, v, ctx->train_v.get(), cnn ? ctx->train_cnn_v.get() : nullptr, false, who));
+  ctx->train_t = t;
+  if (cnn) ctx->train_cnn_t = cnn_t;
+  return DC_OK;
+}
+
+// ---- test hook of gradient clipping (densecap_debug_clip.h) ---------------------------------------------------------------------------
+int dc_debug_adam_multi_clip(dc_ctx* ctx, float* const* p, const float* const* g, float* const* m, float* const* v, const size_t* n,
+                             int nseg, int t, const dc_train_opts* opts, int grid, double max_norm, double* sumsq, float* scale) {
+  const char* who = "dc_debug_adam_multi_clip";
+  if (!ctx) return DC_E_INVALID;
+  if (!p || !g || !m || !v || !n || nseg < 1 || nseg > 4096) return ctx->fail(DC_E_INVALID, "%s: 1..4096 segments, five lists", who);
+  DCCHK(check_train_opts(ctx, opts, who));
+  if (t < 1) return ctx->fail(DC_E_INVALID, "%s: t counts from 1 (got %d)", who, t);
+  std::vector<AdamSeg> tab;
+  for (int i = 0; i < nseg; ++i) {
+    if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 1) return ctx->fail(DC_E_INVALID, "%s: a segment needs four buffers and n >= 1", who);
+    tab.push_back({p[i], g[i], m[i], v[i], n[i], 0});
+  }
+  const AdamScalars k = adam_scalars(*opts, t);
+  GradNormRec r{};
+  DCCHK(grad_norm_run(ctx, who, tab, max_norm, grid, &k, &r));
+  if (sumsq) *sumsq = r.sumsq;
+  if (scale) *scale = r.scale;
+  return DC_OK;
 }
 
 // ---- test hooks of the optimiser's kernels (densecap_debug_optim.h) ----------------------------------------------------------------

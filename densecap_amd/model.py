@@ -90,6 +90,28 @@ def encode_captions(texts, idx_to_token, max_len):
     return out
 
 
+def flatten_train_state(state):
+    """train_state()'s dict -> the flat .npz keys m/<name>, v/<name>, t, cnn_t"""
+    flat = {"t": np.int64(state["t"]), "cnn_t": np.int64(state["cnn_t"])}
+    for mom in ("m", "v"):
+        for k, a in state[mom].items():
+            flat["%s/%s" % (mom, k)] = np.ascontiguousarray(a, dtype=np.float32)
+    return flat
+
+
+def unflatten_train_state(flat):
+    """the inverse of flatten_train_state on a mapping (an open .npz file serves); a key outside the scheme raises"""
+    state = {"m": {}, "v": {}, "t": int(flat["t"]), "cnn_t": int(flat["cnn_t"])}
+    for key in (flat.files if hasattr(flat, "files") else flat):
+        if key in ("t", "cnn_t"):
+            continue
+        mom, _, name = key.partition("/")
+        if mom not in ("m", "v") or not name:
+            raise ValueError("training state: unknown key %r" % key)
+        state[mom][name] = np.ascontiguousarray(flat[key], dtype=np.float32)
+    return state
+
+
 def getopt(opt, key, default_value=None):
     """utils.getopt (densecap/utils.lua:67-75): opt[key], or the default when the key is absent / nil (None here);
     a missing key without a default is an error, as in the reference."""
@@ -648,6 +670,35 @@ class DenseCapModel:
         """dc_train_end: frees the moments and the arena; the weights stay as trained."""
         from . import ops
         ops.train_end(self.ctx)
+
+    def train_set_grad_clip(self, max_norm):
+        """dc_train_set_grad_clip (docs/SEMANTICS.md, "Gradient clipping"): every later train_step clips its gradient by the
+        global L2 norm -- scale = min(1, max_norm / (norm + 1e-6)) on all trained tensors at once -- and its dict gains
+        `grad_norm` and `grad_scale`.  0 (the default after train_begin): off; inf: the norm is reported, nothing is scaled."""
+        from . import ops
+        ops.train_set_grad_clip(self.ctx, max_norm)
+
+    def train_state(self):
+        """Adam's state (dc_train_get_state): {"m": {name: array}, "v": {name: array}, "t": int, "cnn_t": int}, numpy arrays in
+        the checkpoint's layouts under get_weights' names; the CNN's moments (conv_w4 .. conv_b12) once train_set_cnn made them."""
+        from . import ops
+        return ops.train_get_state(self.ctx, self._weight_shapes)
+
+    def train_load_state(self, state):
+        """dc_train_set_state: continue from train_state()'s dict (after train_begin on the weights saved with it)."""
+        from . import ops
+        ops.train_set_state(self.ctx, state, self._weight_shapes)
+
+    def save_train_state(self, path):
+        """train_state() as an uncompressed .npz with the flat keys m/<name>, v/<name>, t, cnn_t (1.1 GB at the real model)."""
+        np.savez(path, **flatten_train_state(self.train_state()))
+
+    def load_train_state(self, path):
+        """train_load_state of a file save_train_state wrote; returns (t, cnn_t)."""
+        with np.load(path) as z:
+            state = unflatten_train_state(z)
+        self.train_load_state(state)
+        return state["t"], state["cnn_t"]
 
     def get_weights(self, conv=True):
         """The current weights as a dict in the keys of densecap_amd/weights.py (dc_get_weights), float32 numpy arrays in the

@@ -1077,6 +1077,7 @@ def train_begin(ctx, **opts):
     """dc_train_begin: allocate the moments and the gradient arena, t = 0.  opts: the keys of TRAIN_DEFAULTS."""
     o = train_opts(**opts)
     check(ctx.h, ctx.lib.dc_train_begin(ctx.h, C.byref(o)), "dc_train_begin")
+    ctx.grad_clip = 0.0
 
 
 def train_set_cnn(ctx, mode):
@@ -1097,15 +1098,63 @@ def finetune_cnn_mode(finetune_cnn_after, it):
 def train_step(ctx, img, gt_boxes, gt_labels, box_reg_decay=BOX_REG_DECAY, forced_pos=None, forced_neg=None, dump=False,
                on_device=False, **opts):
     """dc_train_step: forward_backward's losses for the weights as they were (same arguments, the same numbers; no gradient
-    leaves the device), then the Adam update of the 21 tensors outside the CNN and the refresh of what is derived from them."""
+    leaves the device), then the Adam update of the 21 tensors outside the CNN and the refresh of what is derived from them.
+    While train_set_grad_clip is on, the dict also holds `grad_norm` and `grad_scale` of this step."""
     args, out, lists, _hw, _cap, _keep = _train_args("train_step", ctx, img, gt_boxes, gt_labels, forced_pos, forced_neg, dump,
                                                     on_device, opts)
     check(ctx.h, ctx.lib.dc_train_step(*args, float(box_reg_decay)), "dc_train_step")
-    return _train_result(out, lists)
+    res = _train_result(out, lists)
+    if getattr(ctx, "grad_clip", 0.0) > 0:                   # (train_set_grad_clip's; the dict is the unclipped one otherwise)
+        res["grad_norm"], res["grad_scale"] = train_grad_norm(ctx)
+    return res
+
+
+def train_set_grad_clip(ctx, max_norm):
+    """dc_train_set_grad_clip: clip the step's gradient by its global L2 norm (docs/SEMANTICS.md, "Gradient clipping").  0: off
+    (the default after train_begin); inf: the norm is computed and reported, nothing is scaled."""
+    check(ctx.h, ctx.lib.dc_train_set_grad_clip(ctx.h, float(max_norm)), "dc_train_set_grad_clip")
+    ctx.grad_clip = float(max_norm)
+
+
+def train_grad_norm(ctx):
+    """dc_train_grad_norm: (norm, scale) of the last completed clipped step."""
+    norm, scale = C.c_double(0.0), C.c_float(0.0)
+    check(ctx.h, ctx.lib.dc_train_grad_norm(ctx.h, C.byref(norm), C.byref(scale)), "dc_train_grad_norm")
+    return float(norm.value), float(np.float32(scale.value))
+
+
+def grad_norm(ctx, g, max_norm, offset=0, guard=8):
+    """The two norm kernels alone (dc_op_grad_norm) on a copy of the float32 vector g.  offset: floats by which the buffer is
+    shifted off its 16-byte aligned allocation; guard: floats on both sides of it, filled with NaN (a read outside g turns the
+    sum into NaN).  Returns (sumsq, norm, scale): two floats and an np.float32."""
+    a = _f32(g).reshape(-1)
+    n = len(a)
+    host = np.full(offset + guard + n + guard, np.nan, np.float32)
+    host[offset + guard:offset + guard + n] = a
+    buf = ctx.to_device(host)
+    sumsq, norm, scale = C.c_double(0.0), C.c_double(0.0), C.c_float(0.0)
+    check(ctx.h, ctx.lib.dc_op_grad_norm(ctx.h, C.c_void_p(buf.ptr.value + 4 * (offset + guard)), n, float(max_norm), C.byref(sumsq),
+                                         C.byref(norm), C.byref(scale)), "dc_op_grad_norm")
+    return float(sumsq.value), float(norm.value), np.float32(scale.value)
+
+
+def adam_multi_clip(ctx, segments, t, max_norm, grid=0, **opts):
+    """dc_debug_adam_multi_clip: adam_multi's segments through the sequence a clipped train_step issues (the norm over all the
+    g, then the scaled Adam launch).  Returns (list of (p, m, v), sumsq, scale)."""
+    o = train_opts(**opts)
+    dev = [[ctx.to_device(_f32(a).reshape(-1)) for a in seg] for seg in segments]
+    ns = len(dev)
+    cols = [(C.c_void_p * ns)(*[d[j].ptr for d in dev]) for j in range(4)]
+    sizes = (C.c_size_t * ns)(*[d[0].shape[0] for d in dev])
+    sumsq, scale = C.c_double(0.0), C.c_float(0.0)
+    check(ctx.h, ctx.lib.dc_debug_adam_multi_clip(ctx.h, cols[0], cols[1], cols[2], cols[3], sizes, ns, int(t), C.byref(o), int(grid),
+                                                  float(max_norm), C.byref(sumsq), C.byref(scale)), "dc_debug_adam_multi_clip")
+    return [(d[0].numpy(), d[2].numpy(), d[3].numpy()) for d in dev], float(sumsq.value), np.float32(scale.value)
 
 
 def train_end(ctx):
     check(ctx.h, ctx.lib.dc_train_end(ctx.h), "dc_train_end")
+    ctx.grad_clip = 0.0
 
 
 def train_step_ms(ctx):
@@ -1135,6 +1184,68 @@ def get_weights(ctx, shapes, conv=True):
             w.conv_b[i] = out["conv_b"][i].ctypes.data_as(_lib.c_float_p)
     check(ctx.h, ctx.lib.dc_get_weights(ctx.h, C.byref(w)), "dc_get_weights")
     return out
+
+
+CNN_STATE_CONVS = tuple(range(4, 13))                       # conv3_1 .. conv5_3: the convolutions dc_train_set_cnn trains
+
+
+def cnn_state_keys():
+    """The names of the CNN's 18 trained tensors in a training state: conv_w4, conv_b4, .., conv_w12, conv_b12."""
+    return tuple("conv_%s%d" % (wb, i) for i in CNN_STATE_CONVS for wb in "wb")
+
+
+def _state_struct(arrs, cnn):
+    w = _lib.DcWeights()
+    for name in WEIGHT_KEYS:
+        setattr(w, name, arrs[name].ctypes.data_as(_lib.c_float_p))
+    if cnn:
+        for i in CNN_STATE_CONVS:
+            w.conv_w[i] = arrs["conv_w%d" % i].ctypes.data_as(_lib.c_float_p)
+            w.conv_b[i] = arrs["conv_b%d" % i].ctypes.data_as(_lib.c_float_p)
+    return w
+
+
+def _state_shapes(shapes, cnn):
+    out = {name: tuple(shapes[name]) for name in WEIGHT_KEYS}
+    if cnn:
+        for i in CNN_STATE_CONVS:
+            out["conv_w%d" % i] = tuple(shapes["conv_w"][i])
+            out["conv_b%d" % i] = tuple(shapes["conv_b"][i])
+    return out
+
+
+def train_get_state(ctx, shapes):
+    """dc_train_get_state: {"m": {name: array}, "v": {...}, "t": int, "cnn_t": int} in checkpoint layouts; shapes as get_weights
+    takes them.  The CNN's 18 moments (cnn_state_keys) are there once a non-zero train_set_cnn has made them."""
+    t7 = np.zeros(1, np.int32)
+    check(ctx.h, int(ctx.lib.dc_debug_fetch(ctx.h, b"train_cnn_t", t7.ctypes.data, t7.nbytes)), "dc_debug_fetch train_cnn_t")
+    cnn = int(t7[0]) >= 0
+    sh = _state_shapes(shapes, cnn)
+    m = {k: np.empty(s, np.float32) for k, s in sh.items()}
+    v = {k: np.empty(s, np.float32) for k, s in sh.items()}
+    wm, wv = _state_struct(m, cnn), _state_struct(v, cnn)
+    t, ct = C.c_int(0), C.c_int(0)
+    check(ctx.h, ctx.lib.dc_train_get_state(ctx.h, C.byref(wm), C.byref(wv), C.byref(t), C.byref(ct)), "dc_train_get_state")
+    return {"m": m, "v": v, "t": int(t.value), "cnn_t": int(ct.value)}
+
+
+def train_set_state(ctx, state, shapes):
+    """dc_train_set_state: load what train_get_state returned (the CNN's moments if the state holds them)."""
+    cnn = "conv_w4" in state["m"]
+    sh = _state_shapes(shapes, cnn)
+    keep = []
+    for mom in ("m", "v"):
+        arrs = {}
+        for k, s in sh.items():
+            if k not in state[mom]:
+                raise ValueError("training state: %s/%s is missing" % (mom, k))
+            a = _f32(state[mom][k])
+            if a.size != int(np.prod(s)):
+                raise ValueError("training state: %s/%s has %d elements, the model %d" % (mom, k, a.size, int(np.prod(s))))
+            arrs[k] = a
+        keep.append(arrs)
+    wm, wv = _state_struct(keep[0], cnn), _state_struct(keep[1], cnn)
+    check(ctx.h, ctx.lib.dc_train_set_state(ctx.h, C.byref(wm), C.byref(wv), int(state["t"]), int(state["cnn_t"])), "dc_train_set_state")
 
 
 def rpn_dheads(ctx, trans, scores, anchors, boxes, h, w, k, pos_input_idx, pos_target_idx, neg_input_idx, gt, droi=None,

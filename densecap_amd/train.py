@@ -12,7 +12,13 @@ end writes -checkpoint_path (a .t7 that run_model and evaluate_model load) and, 
 -drop_prob P is the Dropout of recog_base (after fc6 and after fc7; docs/SEMANTICS.md, "Dropout"), its masks drawn on the device
 from the iteration's seed.  The default is 0.0, no Dropout: -drop_prob 0.5 is the reference's training (train_opts.lua:60).
 
-Not here: the validation mAP inside the loop (run evaluate_model on the saved checkpoint), saving Adam's moments and step count.  There is no CPU mode: without a
+-grad_clip X clips every step's gradient by its global L2 norm (docs/SEMANTICS.md, "Gradient clipping"; inf: log only); the
+`iter %d:` lines and the loss history then carry grad_norm.  -save_optim_state 1 writes Adam's moments and step counts beside
+every checkpoint (<checkpoint_path stem>.optim.npz); -resume_optim_state FILE loads such a file after train_begin and continues
+at its iteration t + 1 with that iteration's image and seed, so that the run is the uninterrupted one -- start it from the
+checkpoint written with the file.
+
+Not here: the validation mAP inside the loop (run evaluate_model on the saved checkpoint).  There is no CPU mode: without a
 HIP device the tool stops with the library's error.
 """
 from __future__ import annotations
@@ -65,6 +71,12 @@ def build_parser():
     a("-gpu", type=int, default=0)
     # ---- not reference flags ----
     a("-synthetic_weights", type=int, default=0, help="1: random weights in checkpoint shapes instead of -checkpoint_start_from")
+    a("-grad_clip", type=float, default=0.0,
+      help="clip the gradient by its global L2 norm to this value; 0 (default) = off, inf = compute and log the norm only")
+    a("-save_optim_state", type=int, default=0, choices=[0, 1],
+      help="1: write Adam's moments and step counts to <checkpoint_path stem>.optim.npz beside every checkpoint "
+           "(about 1.1 GB at the real model)")
+    a("-resume_optim_state", default="", help="an .optim.npz to load after train_begin; the loop continues at its iteration t + 1")
     return p
 
 
@@ -80,6 +92,14 @@ def save(model, opt, history, it):
     with open(os.path.splitext(opt.checkpoint_path)[0] + ".json", "w") as f:
         json.dump({"iter": it, "loss_history": history, "opt": {k: v for k, v in vars(opt).items()}}, f)
     print("wrote %s after %d iterations" % (opt.checkpoint_path, it))
+    if opt.save_optim_state:
+        path = optim_state_path(opt.checkpoint_path)
+        model.save_train_state(path)
+        print("wrote %s" % path)
+
+
+def optim_state_path(checkpoint_path):
+    return os.path.splitext(checkpoint_path)[0] + ".optim.npz"
 
 
 def main(argv=None):
@@ -100,7 +120,11 @@ def main(argv=None):
         raise SystemExit("the train split of %s holds no image with ground truth" % opt.data_h5)
     model.train_begin(learning_rate=opt.learning_rate, beta1=opt.optim_beta1, beta2=opt.optim_beta2, epsilon=opt.optim_epsilon,
                       weight_decay=opt.weight_decay)
+    model.train_set_grad_clip(opt.grad_clip)
     history, it = {}, 0
+    if opt.resume_optim_state:
+        it, cnn_t = model.load_train_state(opt.resume_optim_state)      # iteration `it` was the last one of the saved run
+        print("resumed Adam's state of %s: t = %d, cnn_t = %d" % (opt.resume_optim_state, it, cnn_t))
     try:
         while opt.max_iters < 0 or it < opt.max_iters:
             name, boxes, labels = data[it % len(data)]
@@ -110,8 +134,9 @@ def main(argv=None):
             lo = model.train_step(img, boxes, np.asarray(labels)[:, :model.seq_length], box_reg_decay=opt.box_reg_decay,
                                   **loss_options(opt, it))
             if it % max(1, opt.losses_log_every) == 0 or it == opt.max_iters:
-                history[str(it)] = {k: lo[k] for k in ops.LOSS_KEYS}
-                print("iter %d: %s" % (it, ", ".join("%s: %.6f" % (k, lo[k]) for k in ops.LOSS_KEYS)))
+                keys = ops.LOSS_KEYS + (("grad_norm",) if "grad_norm" in lo else ())
+                history[str(it)] = {k: lo[k] for k in keys}
+                print("iter %d: %s" % (it, ", ".join("%s: %.6f" % (k, lo[k]) for k in keys)))
             if it % max(1, opt.save_checkpoint_every) == 0 and it != opt.max_iters:
                 save(model, opt, history, it)
     except KeyboardInterrupt:

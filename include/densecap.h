@@ -735,6 +735,36 @@ int dc_get_weights(dc_ctx* ctx, const dc_weights* out);
  * v are updated in place, g is read only.  Any alignment (4-byte).  The same refusals for opts as dc_train_begin; n < 1 or
  * t < 1: DC_E_INVALID.  Synchronous. */
 int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, int t, const dc_train_opts* opts);
+/* ---- gradient clipping (docs/SEMANTICS.md, "Gradient clipping") ----
+ * Clipping by the global L2 norm of the gradient, between the backward and grad_params:add(weight_decay, params): sumsq = the sum
+ * of (double)g * (double)g over every element the step's Adam launches read (the 21 tensors; in CNN mode 2 the CNN's 18 too: one
+ * norm), norm = sqrt(sumsq), c = max_norm / (norm + 1e-6), scale = c < 1 ? (float)c : 1, and Adam reads g * scale (one rounded
+ * fp32 multiply) in place of g; the arena is not rewritten and the scale never visits the host.  A sumsq that is not finite
+ * gives scale = 1 and is reported as it is.  max_norm = +inf: the norm is computed and reported, scale is exactly 1.
+ * max_norm = 0, the default (dc_train_begin resets it): off -- dc_train_step issues the launches and gives the bits it gives
+ * without this call.  A negative or NaN max_norm: DC_E_INVALID.  Valid between dc_train_begin and dc_train_end, else DC_E_STATE. */
+int dc_train_set_grad_clip(dc_ctx* ctx, double max_norm);
+/* The norm and the scale of the last completed dc_train_step that ran with clipping on (either pointer may be null); a refused
+ * step leaves them as they were.  No such step since dc_train_begin: DC_E_STATE. */
+int dc_train_grad_norm(dc_ctx* ctx, double* norm, float* scale);
+/* The two norm kernels alone on one caller-supplied DEVICE segment g of n floats, any alignment (4-byte): *sumsq, *norm and
+ * *scale (HOST pointers, each may be null) by the rule above; max_norm = 0 leaves scale = 1.  n < 1, a null g, a negative or NaN
+ * max_norm: DC_E_INVALID.  Two identical calls give identical bits.  Synchronous. */
+int dc_op_grad_norm(dc_ctx* ctx, const float* g, size_t n, double max_norm, double* sumsq, double* norm, float* scale);
+/* ---- Adam's state out and in (docs/SEMANTICS.md, "Training step") ----
+ * dc_weights as dc_get_weights uses it: HOST pointers, tensors in the checkpoint's layouts (fc6 permuted back, the fused heads
+ * split, lm_out_w the first V + 1 rows, rpn_conv_w OIHW), dimension fields ignored.  Both valid only between dc_train_begin and
+ * dc_train_end (else DC_E_STATE).
+ * get: every non-null pointer among the 21 trained tensors of m / v is filled with the first / second moment (m, v themselves
+ * may be null); conv_w[4..12] / conv_b[4..12] with the CNN's moments -- non-null while no CNN state exists (no non-zero
+ * dc_train_set_cnn yet): DC_E_STATE; conv_w[0..3], conv_b[0..3] and anchors must be null: DC_E_INVALID.  *t, *cnn_t (may be
+ * null): the two step counts (cnn_t = 0 without CNN state). */
+int dc_train_get_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int* t, int* cnn_t);
+/* set: all 21 tensors are required in both m and v; conv_w[4..12] / conv_b[4..12] are given all 18 in both or not at all --
+ * given, the CNN's state is allocated if need be as the first non-zero dc_train_set_cnn allocates it (the mode stays as it is);
+ * not given, cnn_t must be 0.  conv_w[0..3], conv_b[0..3] and anchors must be null.  t >= 0, cnn_t >= 0.  Any breach:
+ * DC_E_INVALID, and nothing is changed. */
+int dc_train_set_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int t, int cnn_t);
 /* The sampling of dc_sample_captions on given fc7 codes (n, fc_dim): samples (n, S, T), logprob (n, S).  row_ids (n) int32
  * >= 0 or NULL (= 0..n-1): the region row r of the noise counter for every code row, so that a subset of regions draws what
  * it draws in the full call.  Device pointers throughout (codes, row_ids, samples, logprob); synchronous. */

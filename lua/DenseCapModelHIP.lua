@@ -500,7 +500,8 @@ end
 -- device, and the refresh of everything the library derives from them.  Returns forward_backward's loss keys, num_pos and
 -- num_neg, for the weights as they were before the step; no gradient leaves the device.  Dropout is model.drop_prob's.  The CNN:
 -- opts.cnn_mode (dc_train_set_cnn: 0, 1, 2), by default 2 where model.finetune_cnn is set (train.lua:83-85) and 0 where not;
--- train.lua's step at iter == finetune_cnn_after, decay and Adam on a zero gradient, is cnn_mode = 1.
+-- train.lua's step at iter == finetune_cnn_after, decay and Adam on a zero gradient, is cnn_mode = 1.  With model.grad_clip > 0
+-- the gradient is clipped by its global norm and the result carries grad_norm and grad_scale.
 function Model:train_step(data, opts)
   opts = opts or {}
   local input = data.image
@@ -522,15 +523,24 @@ function Model:train_step(data, opts)
   o.seed = get('loss_seed', 0)
   hip.check(self.ctx, C.dc_set_dropout(self.ctx, self.drop_prob or 0), 'dc_set_dropout')   -- models.lua's drop_prob; nil: none
   hip.check(self.ctx, C.dc_train_set_cnn(self.ctx, get('cnn_mode', self.finetune_cnn and 2 or 0)), 'dc_train_set_cnn')
+  -- gradient clipping (docs/SEMANTICS.md, "Gradient clipping"): model.grad_clip = max_norm of the global L2 norm; nil or 0: off
+  local clip = self.grad_clip or 0
+  hip.check(self.ctx, C.dc_train_set_grad_clip(self.ctx, clip), 'dc_train_set_grad_clip')
   local out = ffi.new('dc_losses')
   hip.check(self.ctx, C.dc_train_step(self.ctx, fptr(img), img:size(3), img:size(4), 0, torch.data(gb), torch.data(gl),
                                       gb:size(1), gl:size(2), o, nil, out, nil, get('box_reg_decay', 5e-5)), 'dc_train_step')
-  return {
+  local res = {
     mid_objectness_loss = out.mid_objectness_loss, mid_box_reg_loss = out.mid_box_reg_loss,
     end_objectness_loss = out.end_objectness_loss, end_box_reg_loss = out.end_box_reg_loss,
     captioning_loss = out.captioning_loss, total_loss = out.total_loss,
     num_pos = out.num_pos, num_neg = out.num_neg,
   }
+  if clip > 0 then
+    local norm, scale = ffi.new('double[1]'), ffi.new('float[1]')
+    hip.check(self.ctx, C.dc_train_grad_norm(self.ctx, norm, scale), 'dc_train_grad_norm')
+    res.grad_norm, res.grad_scale = norm[0], scale[0]
+  end
+  return res
 end
 
 -- dc_train_end: frees the moments and the gradient arenas (the CNN's too); the weights stay as trained.

@@ -131,6 +131,11 @@ int dc_train_step(dc_ctx* ctx, const float* img_chw, int H, int W, int img_on_de
 int dc_train_end(dc_ctx* ctx);
 int dc_get_weights(dc_ctx* ctx, const dc_weights* out);
 int dc_op_adam(dc_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, int t, const dc_train_opts* opts);
+int dc_train_set_grad_clip(dc_ctx* ctx, double max_norm);
+int dc_train_grad_norm(dc_ctx* ctx, double* norm, float* scale);
+int dc_op_grad_norm(dc_ctx* ctx, const float* g, size_t n, double max_norm, double* sumsq, double* norm, float* scale);
+int dc_train_get_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int* t, int* cnn_t);
+int dc_train_set_state(dc_ctx* ctx, const dc_weights* m, const dc_weights* v, int t, int cnn_t);
 int dc_op_box_sampler(dc_ctx* ctx, const float* boxes, const float* gt, int A, int G, int img_h, int img_w,
                       const dc_loss_opts* opts, const dc_sampler_forced* forced_or_null, int32_t* pos_input_idx,
                       int32_t* pos_target_idx, int32_t* neg_input_idx, int32_t* counts, float* max_iou_or_null,

@@ -15,8 +15,10 @@ minimum.
 --tree DIR: time forward_backward and train_step with the package of another checkout (the parent commit's, built), for the A/B
 of "must not slow": run it alternating with this tree's in one job.  --cnn_mode M: dc_train_set_cnn(M) before the timed steps
 (2: the step with the CNN's backward, decay and Adam; its backward stage from dc_debug_fetch "cnn_grad_ms").  --drop_prob P:
-dc_set_dropout(P) before the timed calls (docs/SEMANTICS.md, "Dropout").
-usage: python tools/train_step_bench.py [--reps 30] [--warmup 5] [--tree DIR] [--drop_prob P] [--out profiles/train_step_bench.json]"""
+dc_set_dropout(P) before the timed calls (docs/SEMANTICS.md, "Dropout").  --grad_clip X: dc_train_set_grad_clip(X) before the
+timed steps (docs/SEMANTICS.md, "Gradient clipping"; the norm pass counts in the "adam" stage of the split).
+usage: python tools/train_step_bench.py [--reps 30] [--warmup 5] [--tree DIR] [--drop_prob P] [--grad_clip X]
+                                        [--out profiles/train_step_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -52,6 +54,8 @@ def main():
     ap.add_argument("--cnn_mode", type=int, default=0, help="dc_train_set_cnn before the timed steps (0: the CNN is left alone)")
     ap.add_argument("--drop_prob", type=float, default=0.0,
                     help="dc_set_dropout before the timed calls (0: never called, so that --tree may name a library without it)")
+    ap.add_argument("--grad_clip", type=float, default=0.0,
+                    help="dc_train_set_grad_clip before the timed steps (0: never called, so that --tree may name a library without it)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
@@ -103,7 +107,9 @@ def main():
     ops.train_begin(ctx)
     if a.cnn_mode:
         ops.train_set_cnn(ctx, a.cnn_mode)
-    doc["cnn_mode"] = a.cnn_mode
+    if a.grad_clip:
+        ops.train_set_grad_clip(ctx, a.grad_clip)
+    doc["cnn_mode"], doc["grad_clip"] = a.cnn_mode, a.grad_clip
     split, cnn_ms = [], []
 
     def ts():
@@ -119,8 +125,10 @@ def main():
     doc["loss_before_the_first_step"], doc["loss_before_the_last_step"] = float(out_b.total_loss), float(out_t.total_loss)
     if cnn_ms:
         doc["cnn_backward_ms"] = float(np.median(cnn_ms[a.warmup:]))
+    if a.grad_clip:
+        doc["grad_norm"], doc["grad_scale"] = ops.train_grad_norm(ctx)
     ops.train_end(ctx)
-    if a.tree or a.cnn_mode or a.drop_prob:
+    if a.tree or a.cnn_mode or a.drop_prob or a.grad_clip:
         print(json.dumps(doc))
         if a.out:
             with open(a.out, "w") as f:
